@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: piano-roll frames/s for a 200-step reverse-diffusion sample.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1..5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1..7}] [--dump-outputs DIR]
 
 ``--gpus N`` with N > 1 starts the N ranks itself (re-executes under ``python -m torch.distributed.run``, one
 process per GPU, RCCL); the same script also runs under an external launcher:
@@ -23,6 +23,12 @@ CPU fp32) timed on this box's host cores on a bounded sample.  `launch_mode` / `
 `fused_fallbacks` say what every rank's engine launched inside the timed region: a region in which any rank yielded to
 per-phase launches or healed a fused time-out is discarded by all ranks and repeated (`attempts`, `discarded_attempts`), at
 most twice - then there is no line and the exit code is not 0.
+
+``--dump-outputs DIR`` writes what the timed path returned in its last timed step, as float32 ``DIR/<name>.npy``:
+``roll`` = the gathered rolls (n_gpus * B, 1, T, 88) one_step() hands to its caller, ``spec`` = rank 0's spectrogram
+(B, n_mels, T) that model.sample() returns with them.  Inputs, weights and noise are seeded, so two builds run with the
+same arguments can be compared array for array.  At most 64 MB in all: an array that does not fit is replaced by a
+seeded sample of its elements (``DIR/<name>_sample.npy``, same indices in every run).
 """
 import argparse
 import hashlib
@@ -306,6 +312,33 @@ def degraded_ranks(states, share_gpu):
     return [(r, sx) for r, sx in enumerate(states) if sx[0] or sx[1] or not sx[3]]
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy (float32), at most `cap` bytes of data in all; an array that does
+    not fit into what is left becomes path/<name>_sample.npy, a sample of its flattened elements at indices drawn by a
+    generator seeded with 0 (sorted, the same in every run).  Returns the record for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = cap - 4096 * len(arrays)              # .npy headers
+    rec = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        entry = {"shape": list(a.shape), "dtype": "float32"}
+        if a.nbytes > left:
+            n = max(0, left // a.itemsize)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+            name = name + "_sample"
+            entry["sampled_elements"] = int(n)
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        entry["file"] = name + ".npy"
+        rec[name] = entry
+    return rec
+
+
 def _modes():
     from diffroll_amd import _cabi
     return dict(_cabi.MODES)
@@ -330,6 +363,9 @@ def main():
     ap.add_argument("--no-cold-start", action="store_true", help="skip the time-to-first-roll subprocesses (configs 1 and 2)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-split", action="store_true", help="skip the extra bf16x3 split-precision measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned (roll, spec) to DIR/<name>.npy "
+                         "in float32 (rank 0; at most 64 MB, larger arrays as a seeded sample; bench_outputs/ is git-ignored)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="PLUMBING TEST of the N > 1 path on a 1-GPU box: all ranks bind device 0 over a gloo group with one "
                          "launch per phase (no persistent kernels); the line carries dist.share_gpu = true and is no measurement")
@@ -343,6 +379,8 @@ def main():
     from diffroll_amd import launch
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if not launch.under_launcher() and args.gpus > 1:
         # `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU over RCCL)
         sys.exit(launch.spawn_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:]))
@@ -382,11 +420,14 @@ def main():
         model.engine.set_option("fused_stack", 0)
         model.engine.set_option("fused_tail", 0)
 
+    last = {}                                                  # rank 0: the spectrogram of the latest step (--dump-outputs)
+
     def one_step():
         model._fe_key = None                                   # front-end is part of every sample
-        roll, _ = model.sample(x_T, wav, seed=0, first_sample=rank * B)   # on-device Philox noise
+        roll, spec = model.sample(x_T, wav, seed=0, first_sample=rank * B)   # on-device Philox noise
         full = gather_rolls(roll)                              # RCCL all-gather (no-op without a process group)
         if rank == 0:
+            last["spec"] = spec                                # a fresh tensor per sample: no copy here
             return full.cpu()
         return None
 
@@ -435,6 +476,7 @@ def main():
             one_step()
         st1 = model.engine.launch_state()
         dt, out = timed(args.steps)
+        spec_out = last.get("spec")                            # the last timed step's spectrogram (later steps allocate anew)
         st = model.engine.launch_state()
         mine = torch.tensor(rank_state(st1, st, expect_fused, mode_code), device=cdev, dtype=torch.int64)
         if dist is not None:
@@ -594,6 +636,9 @@ def main():
         result["cpu_baseline"] = cpu_baseline(model, cfg, hp)
     if rank == 0 and world == 1 and not args.no_cold_start:
         result["cold_start"] = cold_start()
+    if rank == 0 and args.dump_outputs:
+        result["dumped_outputs"] = {"dir": args.dump_outputs,
+                                    "arrays": dump_outputs(args.dump_outputs, {"roll": out, "spec": spec_out})}
     seen = result["dist"]["ranks_seen"]
     if rank == 0:
         print(json.dumps(result), flush=True)
