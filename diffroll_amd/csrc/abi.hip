@@ -61,18 +61,10 @@ void forget_fused_slot(dr_engine* e) {
     }
     s.cv.notify_all();
 }
-// this engine stops fusing (another process is computing on the device): per-phase launches from the next launch on
-int yield_fused(dr_engine* e, const char* why) {
-    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));      // its captured chain may still be running
+// the launch mode changed (a FusedMode transition returned true) or a tuning knob did: the captured chain is stale
+int drop_chain(dr_engine* e) {
+    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));      // it may still be running
     drop_graph(e);
-    e->yielded_from = e->opt_stack;     // (restored by dr_sample after two clean looks)
-    e->yield_clean = 0;
-    e->opt_stack = 0;
-    e->stack_yields += 1;
-    if (e->stack_yields <= 3)           // per engine (a measurement reads the counter: dr_launch_state); not a log flood
-        fprintf(stderr, "[diffroll_amd] engine %p: %s on device %d - one launch per phase from now on (same results, no co-residency "
-                        "assumption; yield #%lld of this engine; fused launches come back after two clean looks)\n",
-                (void*)e, why, e->cfg.device, (long long)e->stack_yields);
     return DR_OK;
 }
 // Another process on this GPU (tenants.h)?  Asked at creation and in front of a chain, at most every 250 ms (a scan is
@@ -104,6 +96,20 @@ int shared_with_another_process(dr_engine* e, bool force = false, bool may_sync 
     t = scan_tenants(root, e->kfd_gpu_id);
     return (t.holders >= 2 && t.busy_cus > 0) ? 1 : 0;
 }
+// What a look found goes into the engine's FusedMode: another process computing yields (per-phase launches from the next
+// launch on); while yielded, two looks in a row that find the GPU exclusive again switch the fused launches back on.
+int fused_look(dr_engine* e, int shared) {
+    const bool yielded = e->fused.state == FusedMode::YIELDED;
+    if (!e->fused.look(shared)) return DR_OK;
+    if (int rc = drop_chain(e)) return rc;
+    if (!yielded && e->fused.yields <= 3)       // per engine (a measurement reads the counter: dr_launch_state); not a log flood
+        fprintf(stderr, "[diffroll_amd] engine %p: another process is computing on device %d - one launch per phase from now on (same "
+                        "results, no co-residency assumption; yield #%lld of this engine; fused launches come back after two clean looks)\n",
+                (void*)e, e->cfg.device, (long long)e->fused.yields);
+    if (yielded && e->fused.rearms <= 3)
+        fprintf(stderr, "[diffroll_amd] engine %p: device %d is this process's own again - fused launches back on\n", (void*)e, e->cfg.device);
+    return DR_OK;
+}
 
 // the engine's turn on the slot for the duration of one API call that may issue fused launches
 struct FusedTurn {
@@ -112,7 +118,7 @@ struct FusedTurn {
     bool held = false;
     int rc = DR_OK;
     FusedTurn(dr_engine* e_, hipStream_t st_) : e(e_), st(st_) {
-        if (!e->opt_stack) return;
+        if (!e->fused.active()) return;
         if (claim_fused_slot(e, st)) held = true;
         else rc = fail(e, DR_EHIP, "hipStreamWaitEvent behind another engine's fused work failed");
     }
@@ -157,13 +163,8 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         (void)hipDeviceSynchronize();
         drop_graph(e);
     };
-    if (n == "fused_stack") {
-        if (e->opt_stack != value) drop();
-        e->opt_stack = value;
-        e->yielded_from = 0; e->healed_from = 0;      // the caller's word replaces any pending re-arm
-        return DR_OK;
-    }
-    if (n == "fused_rearm") { e->opt_rearm = value; return DR_OK; }
+    if (n == "fused_stack") { if (e->fused.set_option(value)) drop(); return DR_OK; }      // (forgets a pending yield or heal)
+    if (n == "fused_rearm") { e->fused.rearm_after = value; return DR_OK; }
     if (n == "blocked_accumulation") {
         if (value != 1 && value != 2) return fail(e, DR_EINVAL, "blocked_accumulation is 1 or 2");
         if (e->opt_blocked != value) drop();
@@ -273,8 +274,7 @@ int dr_create(dr_engine** out, const dr_config* cfg) {
             e->kfd_gpu_id = kfd_gpu_id(kfd_root(), prop.pciDomainID, prop.pciBusID, prop.pciDeviceID);
         // (only the FIRST engine of the process on this device may wait for the device in a doubtful look: later ones would
         // wait for their siblings' chains - and if those are what is busy, the fused slot already handles it)
-        if (shared_with_another_process(e, false, g_engines[cfg->device].load() == 1) == 1)
-            (void)yield_fused(e, "another process is computing");
+        (void)fused_look(e, shared_with_another_process(e, false, g_engines[cfg->device].load() == 1));
     }
     *out = e;
     return DR_OK;
@@ -382,9 +382,7 @@ int dr_frontend(dr_engine* e, const float* d_wav, int B, int L, int T_roll, int 
     if (cond_need > e->cond_cap) { if ((rc = dev_alloc(e, &e->cond, cond_need))) return rc; e->cond_cap = cond_need; cond_moved = true; }
     if (cond_moved || B != e->fe_B || T != e->fe_T) {
         // a captured chain bakes the conditioner pointers / strides: drop it when they change
-        if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
-        if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-        e->gkey = GraphKey{};
+        drop_graph(e);
     }
 
     // 1. center / reflect padding
@@ -497,28 +495,11 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (e->tuning_epoch != tuning_epoch().load()) {      // a tune.* knob changed (any engine, any thread): the cached chain is stale
-        if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
-        drop_graph(e);
+        if ((rc = drop_chain(e))) return rc;
         e->tuning_epoch = tuning_epoch().load();
     }
-    if (e->opt_stack) {
-        if (shared_with_another_process(e) == 1 && (rc = yield_fused(e, "another process is computing"))) return rc;
-    } else if (e->yielded_from) {
-        // a yield is a precaution, not a verdict: two looks in a row (>= 250 ms apart, in front of later chains) that find
-        // the GPU exclusive again switch the fused launches back on
-        const int shared = shared_with_another_process(e);
-        if (shared == 1) e->yield_clean = 0;
-        else if (shared == 0 && ++e->yield_clean >= 2) {
-            if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
-            drop_graph(e);
-            e->opt_stack = e->yielded_from;
-            e->yielded_from = 0;
-            e->yield_clean = 0;
-            e->stack_rearms += 1;
-            if (e->stack_rearms <= 3)
-                fprintf(stderr, "[diffroll_amd] engine %p: device %d is this process's own again - fused launches back on\n", (void*)e, e->cfg.device);
-        }
-    }
+    // (a yield is a precaution, not a verdict: the looks in front of later chains, >= 250 ms apart, may re-arm)
+    if (e->fused.may_fuse() && (rc = fused_look(e, shared_with_another_process(e)))) return rc;
     FusedTurn turn(e, st);      // (released - event recorded on `st` - when this call returns, behind the chain's launches)
     if (turn.rc) return turn.rc;
     const size_t per = (size_t)B * T * 88;
@@ -555,8 +536,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     GraphKey key;
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
-        if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
-        if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
+        drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
         hipStream_t user = st;
         st = e->cap_stream;   // chain() launches on `st`
@@ -577,10 +557,8 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         e->gkey = key;
         e->tuning_epoch = tuning_epoch().load();
         // capture + instantiation took tens of milliseconds: look again before a chain of persistent launches goes out
-        if (attempt == 0 && e->opt_stack && turn.held) {
-            if (shared_with_another_process(e, true) == 1) {
-                if ((rc = yield_fused(e, "another process is computing"))) return rc;      // (drops the graph: captured again, per phase)
-            }
+        if (attempt == 0 && e->fused.active() && turn.held) {
+            if ((rc = fused_look(e, shared_with_another_process(e, true)))) return rc;      // (a yield drops the graph: captured again, per phase)
         }
     }
     Range range("dr_sample: launch the chain graph");
@@ -612,12 +590,7 @@ int dr_finish(dr_engine* e, void* stream) {
     if (rc) return rc;
     drop_graph(e);
     e->unverified = false;
-    if (e->opt_stack) e->healed_from = e->opt_stack;      // (option "fused_rearm" may restore it after clean chains)
-    else if (e->yielded_from) e->healed_from = e->yielded_from;
-    e->clean_chains = 0;
-    e->opt_stack = 0;
-    e->yielded_from = 0;                                  // (a time-out outranks a pending yield: only fused_rearm re-arms now)
-    e->stack_fallbacks += 1;
+    e->fused.timeout();         // (option "fused_rearm" may fuse again after clean chains; looks no longer do)
     static std::atomic<bool> warned{false};           // (engines of several host threads may get here together)
     if (!warned.exchange(true)) {
         fprintf(stderr, "[diffroll_amd] a group barrier of the fused residual-stack kernel timed out (another stream, engine or "
@@ -636,8 +609,9 @@ int dr_sample_checked(dr_engine* e, int sampler, float* d_x, const float* d_nois
     DeviceGuard guard(e->cfg.device);
     hipStream_t st = (hipStream_t)stream;
     const size_t per = (size_t)B * T * 88;
-    const bool may_fuse = e->opt_stack != 0;
-    if (may_fuse) {       // only a fused launch can time out: keep x_T so that the chain can be re-run
+    // only a fused launch can time out: keep x_T so that the chain can be re-run (a yielded engine may re-arm in dr_sample)
+    const bool may_fuse = e->fused.may_fuse();
+    if (may_fuse) {
         if (per > e->xsave_cap) {
             HIPCHK(e, hipStreamSynchronize(st));
             int rc = dev_alloc(e, &e->xsave, per, false);
@@ -653,16 +627,10 @@ int dr_sample_checked(dr_engine* e, int sampler, float* d_x, const float* d_nois
     }
     if (rc) return rc;
     rc = dr_finish(e, st);
-    if (rc == DR_OK && e->healed_from && e->opt_rearm > 0 && !e->opt_stack && ++e->clean_chains >= e->opt_rearm) {
-        // option "fused_rearm": the tenant that caused the time-out has had opt_rearm chains to leave - fuse again
-        drop_graph(e);
-        e->opt_stack = e->healed_from;
-        e->healed_from = 0;
-        e->clean_chains = 0;
-        e->stack_rearms += 1;
-    }
+    // option "fused_rearm": the tenant that caused a time-out has had that many chains to leave - fuse again
+    if (rc == DR_OK && e->fused.clean_chain() && (rc = drop_chain(e))) return rc;
     if (rc != DR_ETIMEOUT) return rc;
-    if (!may_fuse) return rc;         // cannot happen: no fused launch was issued
+    if (!may_fuse) return rc;         // (guard: fusing was not possible on entry, so no fused launch was issued)
     HIPCHK(e, hipMemcpyAsync(d_x, e->xsave, per * sizeof(float), hipMemcpyDeviceToDevice, st));
     rc = dr_sample(e, sampler, d_x, d_noise, B, T, w, seed, first_sample, use_graph, st);     // per-phase kernels now
     if (rc) return rc;
@@ -692,10 +660,10 @@ int dr_pending_timeout(dr_engine* e, void* stream) {
 int dr_launch_state(dr_engine* e, dr_launch_info* out) {
     if (!e || !out) return DR_EINVAL;
     out->mode = e->last_mode;
-    out->fused_enabled = e->opt_stack;
-    out->fallbacks = e->stack_fallbacks;
-    out->yields = e->stack_yields;
-    out->rearms = e->stack_rearms;
+    out->fused_enabled = e->fused.active();
+    out->fallbacks = e->fused.fallbacks;
+    out->yields = e->fused.yields;
+    out->rearms = e->fused.rearms;
     out->stack_launches = e->stack_launches;
     out->tail_launches = e->tail_launches;
     return DR_OK;
@@ -764,9 +732,7 @@ int dr_set_precision(dr_engine* e, int mode) {
     if (mode != e->prec) {
         DeviceGuard guard(e->cfg.device);     // the graph may still be executing on the ENGINE's device
         (void)hipDeviceSynchronize();
-        if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
-        if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-        e->gkey = GraphKey{};
+        drop_graph(e);
         if (mode) {           // the mode changes only once its packings exist (520 MB of uploads: the build can fail)
             int rc = ensure_s3(e);
             if (rc) return rc;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/diffroll_amd_debug.h"      // (includes the boundary, diffroll_amd.h)
+#include "fused_mode.h"
 #include "kernels.h"
 
 namespace drh {
@@ -120,8 +121,9 @@ struct dr_engine {
     bool use_dyn = false;               // set while the chain is being captured: run_step points the update at d_dyn
 
     // fused residual stack (stack_kernel): one persistent launch for the residual layers when every block of the
-    // launch is resident at once; opt_stack 0 = always one launch per phase
-    int opt_stack = 1;
+    // launch is resident at once; fused.active() 0 = one launch per phase (options fused_stack / fused_rearm, yields,
+    // time-outs and re-arms: fused_mode.h)
+    drh::FusedMode fused;
     int opt_stack_xcd = 1;              // group-per-XCD block mapping (0: weight-panel-per-XCD)
     int opt_stack_fault = 0;            // test hook (option "stack_fault_test")
     int opt_stack_warm = 0;             // idle waves of the fused kernel warm the L2 for the next phase (measured: +-0)
@@ -137,11 +139,6 @@ struct dr_engine {
     int64_t tail_launches = 0;
     float* xalt = nullptr;              // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
-    int64_t stack_fallbacks = 0;        // time-outs detected by dr_finish: each one switched this engine to per-phase launches
-    int64_t stack_yields = 0;           // times this engine gave up fusing because another process was computing on the device (no time-out)
-    int64_t stack_rearms = 0;           // times fused launches were switched back on (after a time-out: fused_rearm; after a yield: clean looks)
-    int yielded_from = 0;               // the fused_stack value a yield switched off (0: none pending)
-    int yield_clean = 0;                // looks in a row, in front of later chains, that found the GPU exclusive again
     int last_mode = 0;                  // DR_MODE_* of the most recently planned evaluation (dr_launch_state)
     unsigned tuning_epoch = 0;          // tuning_epoch() when the cached chain was captured
     long kfd_gpu_id = -1;               // the driver's id of this GPU in /sys/class/kfd (tenants.h); -1: unknown, no scans
@@ -151,9 +148,6 @@ struct dr_engine {
     bool unverified = false;            // persistent launches have been issued since the last check of the time-out flag
     hipStream_t fused_stream = nullptr; // ... on this stream (the last one): what a check synchronises before it reads the flag
     int opt_blocked = 2;                // option "blocked_accumulation": 2 (default) = every fp32 flavour that has a blocked form, 1 = 128-frame blocks keep one chain per output (-0.5 % per chain, 2-3x the rounding error)
-    int opt_rearm = 0;                  // option "fused_rearm": clean chains after a time-out before fusing again (0: never)
-    int healed_from = 0;                // the fused_stack value a time-out switched off (0: none pending re-arm)
-    int clean_chains = 0;               // chains finished cleanly since that time-out
     float* xsave = nullptr;             // dr_sample_checked: copy of x_T, so that a timed-out chain can be re-run
     size_t xsave_cap = 0;
     long long* stack_dbg = nullptr;     // phase tick marks of block 0 (dr_debug_stack_ticks)

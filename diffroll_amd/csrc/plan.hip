@@ -154,8 +154,6 @@ int build_trainable_cond(dr_engine* e, int T) {
     return DR_OK;
 }
 
-void drop_graph(dr_engine* e);
-
 int ensure_workspace(dr_engine* e, int NB, int T) {
     if (NB <= e->ws_NB && T == e->ws_T) return DR_OK;
     drop_graph(e);       // a captured chain holds the addresses of the buffers that are about to be replaced
@@ -175,11 +173,7 @@ int ensure_workspace(dr_engine* e, int NB, int T) {
     if ((rc = dev_alloc(e, &e->cond_dummy, (size_t)2 * e->Cp * T))) return rc;
     e->ws_NB = nb;
     e->ws_T = T;
-    if ((rc = build_trainable_cond(e, T))) return rc;
-    if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
-    if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-    e->gkey = GraphKey{};
-    return DR_OK;
+    return build_trainable_cond(e, T);
 }
 
 // One network evaluation for NB samples (first n_cond conditional) at step t.
@@ -203,7 +197,8 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
     bool fused_step = false;
     // (the split-bf16 precision has its own flavour of the kernel: 128-channel S3 chunks in the 1x1 phases need Cp % 128 == 0)
     const int stack3 = tuning().stack3;
-    if (e->opt_stack && (prec == 0 || (stack3 && Cp % 128 == 0)) && L <= DR_STACK_MAX_LAYERS && e->n_cus > 0) {
+    const int fuse = e->fused.active();
+    if (fuse && (prec == 0 || (stack3 && Cp % 128 == 0)) && L <= DR_STACK_MAX_LAYERS && e->n_cus > 0) {
         int maxdil = 1;
         for (int l = 0; l < L; ++l) maxdil = std::max(maxdil, e->layers[l].dil);
         // Flavours 1 / 2 / 5 (128 packed rows x 64 / 128 / 160 frames per block) are chosen automatically; tune.stack_fl = n
@@ -245,11 +240,11 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
             // (a single launch that leaves more than a fifth of the CUs idle is better served by the per-phase kernels'
             // split-K, which this cost model does not see: they cut the same work into many short blocks that balance
             // over all CUs - 8 evaluations x 125 frames (half the chip): 1365 vs 2422 us per step, 10 / 12 evaluations
-            // (62 / 75 %): 1994 / 2022 vs 2425, 14 (87 %): 2526 vs 2424; opt_stack == 2 fuses regardless: tests)
-            const bool ok = e->opt_stack == 2 || (chunks == 1 ? 5 * NB * gsize > 4 * (long)e->n_cus : true);
+            // (62 / 75 %): 1994 / 2022 vs 2425, 14 (87 %): 2526 vs 2424; fuse == 2 fuses regardless: tests)
+            const bool ok = fuse == 2 || (chunks == 1 ? 5 * NB * gsize > 4 * (long)e->n_cus : true);
             if (ok && cost < best) { best = cost; stack_ni = fl; stack_chunks = (int)chunks; }
         }
-        if (stack_ni && e->opt_stack != 2 && best > per_phase_cost()) stack_ni = 0;
+        if (stack_ni && fuse != 2 && best > per_phase_cost()) stack_ni = 0;
         const bool dual0 = (bmod > 0 && NB == 2 * bmod && n_cond == bmod);
         if (stack_ni) stack_from = dual0 ? 1 : 0;
         // fused step (option "fused_tail"): everything behind the stack launch - skip / output projection, update, and

@@ -6,7 +6,7 @@
 //   holders  = processes with at least one queue on our GPU                      (we are one of them once HIP is up)
 //   busy_cus = the sum of their cu_occupancy, confirmed after OUR engine's stream has drained (so what is busy is somebody
 //              else's - another process, or another stream of this one: either way not the engine's own device)
-// holders >= 2 and busy_cus > 0  =>  the engine yields: one launch per phase from then on (abi.hip: yield_fused).
+// holders >= 2 and busy_cus > 0  =>  the engine yields: one launch per phase from then on (abi.hip: fused_look).
 // Idle co-holders (a sibling rank's context, a launcher, a notebook that imported torch) do not count, and a tenant that
 // arrives between the scan and the launch is what the barriers' ~1 s spin bound remains the backstop for.
 // Where the files are not readable (no sysfs in the container, another driver) the answer is "unknown": exclusive is assumed.
