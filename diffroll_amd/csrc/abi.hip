@@ -129,7 +129,7 @@ struct FusedTurn {
 
 // After a barrier time-out (device idle): re-arm the group counters, forget the published XCC tags, lower both flags.
 int clear_stack_timeout(dr_engine* e) {
-    HIPCHK(e, hipMemset(e->stack_bar, 0, (size_t)(12 * dr_engine::STACK_GROUPS) * sizeof(unsigned)));    // all three counter arrays
+    HIPCHK(e, hipMemset(e->stack_bar, 0, (size_t)(12 * STACK_GROUPS) * sizeof(unsigned)));    // all three counter arrays
     HIPCHK(e, hipMemset(e->stack_xid, 0xFF, 1024 * sizeof(unsigned)));
     HIPCHK(e, hipMemset(e->stack_derr, 0, 16 * sizeof(unsigned)));
     *e->stack_err_host = 0;
@@ -256,14 +256,13 @@ int dr_create(dr_engine** out, const dr_config* cfg) {
     e->NM = cfg->n_mels;
     e->n_bins = cfg->n_fft / 2 + 1;
     e->bins_p = round_up(e->n_bins, 64);
-    int maxdil = 1;
     for (int i = 0; i < e->L; ++i) {
         int d = 1;
         for (int q = 0; q < i % cfg->dilation_bound; ++q) d *= cfg->dilation_base;
-        maxdil = std::max(maxdil, d);
+        e->max_dil = std::max(e->max_dil, d);
     }
-    if (gemm_lds_bytes(1, 1, e->K, maxdil, 1, EPI_GATE) > 160 * 1024) {
-        const int rf = (e->K - 1) * maxdil;
+    if (gemm_lds_bytes(1, 1, e->K, e->max_dil, 1, EPI_GATE) > 160 * 1024) {
+        const int rf = (e->K - 1) * e->max_dil;
         delete e;
         return fail(nullptr, DR_EINVAL, "receptive halo (k-1)*dil = %d does not fit the 160 KiB LDS tile", rf);
     }

@@ -121,7 +121,7 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     }
     a.dbg = e->dbg_ticks;
     allow_splitk(e, a);
-    HIPCHK(e, launch_tiled(a, EPI_GATE, pick_tile(Cp / 64, NB, T, e->K, w.dil, e->prec, EPI_GATE, true, e->opt_blocked >= 2), (hipStream_t)stream, e->prec));
+    HIPCHK(e, launch_tiled(a, EPI_GATE, pick_tile(plan_knobs(), Cp / 64, NB, T, e->K, w.dil, e->prec, EPI_GATE, true, e->opt_blocked >= 2), (hipStream_t)stream, e->prec));
     return DR_OK;
 }
 
@@ -156,7 +156,7 @@ int dr_bench_pointwise(dr_engine* e, int layer, int NB, int T, void* stream) {
     }
     a.dbg = e->dbg_ticks;
     allow_splitk(e, a);
-    HIPCHK(e, launch_tiled(a, EPI_RES_SKIP, pick_pointwise_tile(Cp / 64, NB, T, e->prec), (hipStream_t)stream, e->prec));
+    HIPCHK(e, launch_tiled(a, EPI_RES_SKIP, pick_pointwise_tile(plan_knobs(), Cp / 64, NB, T, e->prec), (hipStream_t)stream, e->prec));
     return DR_OK;
 }
 

@@ -1,7 +1,7 @@
 // Host side of the DiffRoll sampling engine, shared declarations: the engine object behind the C-ABI handle and the
 // helpers the four host translation units use -
 //   pack.hip       weight packing, staged uploads, dr_set_param / dr_set_tables / dr_commit (+ the split-bf16 packings)
-//   plan.hip       tile / split-K / fused-stack planning and the launch sequences of one evaluation and one reverse step
+//   plan.hip       the launch sequences of one evaluation and one reverse step (their planning: launch_plan.h)
 //   abi.hip        the C-ABI of include/diffroll_amd.h: life cycle, front-end, forward / step / sample (hipGraph), time-outs
 //   debug_abi.hip  measurement and checker entry points (dr_bench_*, dr_debug_*, dr_profile_*)
 // Not part of the public ABI.
@@ -63,6 +63,7 @@ struct GraphKey {
 struct dr_engine {
     dr_config cfg{};
     int C = 0, Cp = 0, L = 0, K = 0, S = 0, NM = 0;
+    int max_dil = 1;                     // the largest dilation of the residual layers
     int n_bins = 0, bins_p = 0;          // n_fft/2+1 and its 64-multiple padding
     std::string err;
     std::map<std::string, std::vector<float>> params;
@@ -84,10 +85,9 @@ struct dr_engine {
 
     // activation workspace (sized for ws_NB samples x ws_T frames)
     int ws_NB = 0, ws_T = 0;
-    // split-K workspace (partials) and ticket counters, see gemm_kernel
+    // split-K workspace (partials) and ticket counters, see gemm_kernel (sizes SK_WS_FLOATS / SK_CNT_N: launch_plan.h)
     float* sk_ws = nullptr;
     unsigned* sk_cnt = nullptr;
-    static constexpr size_t SK_WS_FLOATS = (size_t)16 << 20, SK_CNT_N = 4096;     // 64 MiB: up to 1024 partial tiles of 128 x 128
     float *h = nullptr, *hd = nullptr, *g = nullptr, *skip = nullptr, *tmp = nullptr, *x0buf = nullptr;
     float* xwork = nullptr;                // the captured chain runs in place on this engine-owned roll buffer
     float *hd3 = nullptr, *g3 = nullptr;   // split-bf16 (S3) versions of hd and g: 1.5x the fp32 size
@@ -153,7 +153,6 @@ struct dr_engine {
     long long* stack_dbg = nullptr;     // phase tick marks of block 0 (dr_debug_stack_ticks)
     int stack_dbg_on = 0;
     int64_t stack_launches = 0;         // fused-kernel launches issued (captured launches count once, at capture)
-    static constexpr int STACK_GROUPS = 512;
 
     // profiling of the dominant kernel
     double prof_flops = 0.0;            // algorithmic FLOPs of the timed launches
@@ -239,11 +238,7 @@ int ensure_s3(dr_engine* e);            // the split-bf16 packings, built on fir
 int commit(dr_engine* e, hipStream_t st);
 
 // ---- plan.hip
-struct Tile { int flavor, n; };
-Tile pick_tile(int MT, int NB, int T, int taps, int dil, int prec, int epi, bool allow16, bool wide32 = false);
-int pick_ni(int MT, int NB, int T, int taps, int dil, int prec = 0);
 hipError_t launch_tiled(const GemmArgs& a, int epi, Tile t, hipStream_t s, int prec);
-Tile pick_pointwise_tile(int MT, int NB, int T, int prec, int kchunks = 0);
 void allow_splitk(const dr_engine* e, GemmArgs& a);
 constexpr int MAX_DEVICES = 64;
 extern const float* g_zero_vecs[MAX_DEVICES];

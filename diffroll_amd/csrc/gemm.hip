@@ -23,6 +23,13 @@ namespace dr {
 
 Tuning& tuning() { static Tuning t; return t; }
 std::atomic<unsigned>& tuning_epoch() { static std::atomic<unsigned> n{0}; return n; }
+PlanKnobs plan_knobs() {
+    const Tuning& t = tuning();
+    PlanKnobs k;
+    k.tile = t.tile; k.pw = t.pw; k.pw_nw = t.pw_nw; k.pwk = t.pwk; k.ksplit_max = t.ksplit_max;
+    k.ksplit_blocks = t.ksplit_blocks; k.stack3 = t.stack3; k.stack_fl = t.stack_fl;
+    return k;
+}
 
 DR_BOUNDS_TU(gemm)
 hipError_t read_bounds(unsigned long long* out4) {
@@ -339,32 +346,6 @@ static hipError_t init_gemm16() {
     return hipSuccess;
 }
 
-size_t gemm_lds_bytes(int NI, int KS, int taps, int dil, int prec, int epi) {
-    const int halo = ((taps - 1) / 2) * dil;
-    const int BN = gemm_block_frames(NI);
-    const int FW = BN + 2 * halo;
-    return (size_t)2 * (prec ? 12 : 8) * KS * FW * 16 + (epi == EPI_RES_SKIP ? (size_t)32 * BN * 16 : 0);
-}
-
-KSplitPlan plan_ksplit(long tiles, int nchunks, int kchunks, int taps, int NI, int prec, size_t ws_floats, size_t ws_cnt_n) {
-    const int ks_max = tuning().ksplit_max;
-    const long forced_blocks = tuning().ksplit_blocks.load();
-    const long max_blocks = forced_blocks ? forced_blocks : (prec ? 256 : 2048);
-    const int BN = gemm_block_frames(NI);
-    const double t_full = (double)kchunks * taps * 16.0 * (BN / 32) * 69.0 / 2400.0;
-    auto cost = [&](int ks) {
-        return (double)((tiles * ks + 255) / 256) * t_full / ks + (ks > 1 ? 4.0 + ks : 0.0);
-    };
-    KSplitPlan p{1, cost(1), cost(1)};
-    for (int ks = 2; ks <= ks_max && ks <= 16; ks *= 2) {
-        if (tiles * ks > max_blocks || nchunks % ks != 0) break;
-        if ((size_t)tiles * ks * 128 * BN > ws_floats || (size_t)tiles * 4 > ws_cnt_n) break;
-        const double c = cost(ks);
-        if (tiles * ks <= 256 || c < 0.97 * p.us) { p.us = std::min(p.us, c); p.ks = ks; }
-    }
-    return p;
-}
-
 template <int NI, int KS, int EPI, int PREC>
 static hipError_t launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     const int BN = gemm_block_frames(NI);
@@ -378,7 +359,7 @@ static hipError_t launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     // frames are 160 tiles = one round of full-K blocks on 62 % of the CUs; cut 4x in K they are 640 blocks = 3 rounds
     // of quarter-length blocks: 136 -> 107 us per conv launch.  The decision is plan_ksplit's (shared with the engine).
     b.ksplit = 1;
-    if (a.ws && a.ws_cnt) b.ksplit = plan_ksplit((long)a.MT * NT, a.kchunks / KS, a.kchunks, a.taps, NI, PREC, a.ws_floats, a.ws_cnt_n).ks;
+    if (a.ws && a.ws_cnt) b.ksplit = plan_ksplit(plan_knobs(), (long)a.MT * NT, a.kchunks / KS, a.kchunks, a.taps, NI, PREC, a.ws_floats, a.ws_cnt_n).ks;
     b.lds_bytes = (int)lds;
     const dim3 grid((unsigned)(a.MT * NT * b.ksplit));
     // weights: MT*128 rows x 32*kchunks*taps floats; activations: NT*BN frames x 32*kchunks floats

@@ -6,6 +6,8 @@
 
 #include <atomic>
 
+#include "launch_plan.h"      // Epilogue, tile / split-K / fused-stack planning
+
 namespace dr {
 
 // ---------------------------------------------------------------------------------------------
@@ -52,16 +54,7 @@ struct Tuning {
 };
 Tuning& tuning();            // gemm.hip
 std::atomic<unsigned>& tuning_epoch();
-
-enum Epilogue : int {
-    EPI_PLAIN = 0,     // y = alpha*acc + bias
-    EPI_RELU = 1,      // y = relu(alpha*acc + bias)
-    EPI_SILU = 2,      // y = silu(acc + bias)
-    EPI_GATE = 3,      // rows paired (gate, filter): y = sigmoid(a0 + c0) * tanh(a1 + c1)
-    EPI_RES_SKIP = 4,  // first half of M: h = (h + acc + b)/sqrt(2) in place; second half: skip (+)= acc + b
-    EPI_POWER = 5,     // rows paired (cos, sin): y = a0^2 + a1^2
-    EPI_LOG = 6        // y = log(acc + 1e-6)
-};
+PlanKnobs plan_knobs();      // what the planners read of tuning(), now
 
 struct GemmArgs {
     // A operand
@@ -137,19 +130,6 @@ hipError_t launch_gemm16(const GemmArgs& a, int epi, int NJ, hipStream_t s);
 // (NW in {2,3,4,5}), 256 threads
 hipError_t launch_pointwise(const GemmArgs& a, int NW, hipStream_t s);
 hipError_t launch_pointwise_ksplit(const GemmArgs& a, int NW, hipStream_t s);   // under-filled launches: 32-row tiles, K split over the block's waves
-// frames per block of gemm_kernel<NI, ...>: 64 / 128 (NI = 1 / 2), 96 / 160 (NI = 3 / 5: that many 32-frame MFMA tiles per
-// consumer wave, the gated conv only)
-inline int gemm_block_frames(int NI) { return (NI == 3 || NI == 5) ? 32 * NI : 64 * NI; }
-size_t gemm_lds_bytes(int NI, int KS, int taps, int dil, int prec, int epi);
-// THE split-K decision of gemm_kernel launches (the launcher takes it; the engine's tile choice prices a launch with it,
-// so the estimate and the launch cannot disagree): for `tiles` output tiles of 128 rows x 64 NI frames, `nchunks` hand-over
-// chunks of K (kchunks / KS), a workspace of ws_floats / ws_cnt_n: the number of K slices and the modelled time.
-// Model (fp32, fitted to 3..8 guided clips of 125 frames, tools/lab/small_batch_ab.py): equal blocks run in lockstep rounds
-// over the 256 CUs - rounds x t_full / ks + exchange, t_full = a full-K tile (MFMA count x 69 cycles at 2.4 GHz), the
-// exchange (store, ticket, the last arriver's ordered re-read) ~(4 + ks) us.  Inside one resident round more slices are
-// always taken; beyond it a split must win by 3 %.
-struct KSplitPlan { int ks; double us; double us_unsplit; };
-KSplitPlan plan_ksplit(long tiles, int nchunks, int kchunks, int taps, int NI, int prec, size_t ws_floats, size_t ws_cnt_n);
 
 // ---------------------------------------------------------------------------------------------
 // Fused residual stack: ONE persistent launch runs a range of the 2L phases of the residual layers
@@ -159,7 +139,6 @@ KSplitPlan plan_ksplit(long tiles, int nchunks, int kchunks, int taps, int NI, i
 // form a GROUP that synchronises on a device counter between phases - nothing is exchanged between groups, so
 // there is no grid-wide barrier.  See stack_kernel in stack.hip.
 // ---------------------------------------------------------------------------------------------
-constexpr int DR_STACK_MAX_LAYERS = 30;
 struct StackLayer {
     const float *conv_w, *conv_b, *conv_b2;   // packed dilated-conv weights; bias of samples < n_cond / >= n_cond
     const float *cond, *cond2;                // conditioner tensors of this layer (see GemmArgs)
@@ -195,10 +174,6 @@ struct StackArgs {
 // NB * stack_group_blocks(FL, Cp, T) <= #CUs and stack_lds_bytes(..) <= 160 KiB.
 // prec = 1: the split-bf16 flavour (s.hd / s.g = the S3 tensors; Cp % 128 == 0; LDS: stack3_lds_bytes)
 hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st, int prec = 0);
-size_t stack3_lds_bytes(int FL, int taps, int max_dil);
-int stack_tile_frames(int FL);
-int stack_group_blocks(int FL, int Cp, int T);      // blocks per clip evaluation
-size_t stack_lds_bytes(int FL, int taps, int max_dil);
 
 // Per-call scalars of the update that must not be baked into a captured graph: the chain graph reads them from
 // this device block, which a one-thread kernel rewrites (stream-ordered) before every graph launch - a new

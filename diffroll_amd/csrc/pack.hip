@@ -433,17 +433,17 @@ int commit(dr_engine* e, hipStream_t st) {
     if ((rc = dev_alloc(e, &e->d_coef, (size_t)DR_COEF_FAMILIES * S * 5))) return rc;
     HIPCHK(e, hipMemcpy(e->d_coef, e->h_coef.data(), (size_t)DR_COEF_FAMILIES * S * 5 * sizeof(float), hipMemcpyHostToDevice));
     if ((rc = dev_alloc(e, &e->d_dtab, (size_t)S * L * Cp))) return rc;
-    if ((rc = dev_alloc(e, &e->sk_ws, dr_engine::SK_WS_FLOATS, false))) return rc;
+    if ((rc = dev_alloc(e, &e->sk_ws, SK_WS_FLOATS, false))) return rc;
     if (!e->sk_cnt) {       // ticket counters: zero between launches (the kernels re-arm them)
         void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, dr_engine::SK_CNT_N * sizeof(unsigned)));
-        HIPCHK(e, hipMemset(q, 0, dr_engine::SK_CNT_N * sizeof(unsigned)));
+        HIPCHK(e, hipMalloc(&q, SK_CNT_N * sizeof(unsigned)));
+        HIPCHK(e, hipMemset(q, 0, SK_CNT_N * sizeof(unsigned)));
         e->sk_cnt = (unsigned*)q;
     }
     if (!e->d_dyn) { void* q = nullptr; HIPCHK(e, hipMalloc(&q, sizeof(DynParams))); e->d_dyn = (DynParams*)q; }
     if (!e->stack_bar) {     // group counters of the fused residual stack: zero between launches (re-armed in-kernel)
         void* q = nullptr;
-        const size_t G4 = (size_t)4 * dr_engine::STACK_GROUPS;
+        const size_t G4 = (size_t)4 * STACK_GROUPS;
         const size_t nb = (3 * G4 + 1024 + 16) * sizeof(unsigned);
         HIPCHK(e, hipMalloc(&q, nb));
         HIPCHK(e, hipMemset(q, 0, nb));

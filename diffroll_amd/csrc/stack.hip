@@ -325,22 +325,6 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
-int stack_tile_frames(int FL) { return FL == 5 ? 160 : 64 * FL; }
-// split-bf16 flavour: max over its two phase bodies (conv: S3 X tiles; 1x1: 128-channel S3 X tiles + the 64-frame h / skip tile)
-size_t stack3_lds_bytes(int FL, int taps, int max_dil) {
-    return std::max(gemm_lds_bytes(FL, 1, taps, max_dil, 1, EPI_GATE), gemm_lds_bytes(1, 4, 1, 1, 1, EPI_RES_SKIP)) + 16;
-}
-// blocks of one clip evaluation (= one barrier group): M tiles x frame tiles
-int stack_group_blocks(int FL, int Cp, int T) {
-    const int BN = stack_tile_frames(FL);
-    return (Cp >> 6) * ((T + BN - 1) / BN);
-}
-// the conv's double-buffered X tiles + the resident h / skip tile
-size_t stack_lds_bytes(int FL, int taps, int max_dil) {
-    const int BN = stack_tile_frames(FL), halo = ((taps - 1) / 2) * max_dil;
-    return (size_t)2 * 8 * (BN + 2 * halo) * 16 + (size_t)32 * BN * 16 + 16;     // + one flag word (16-byte slot)
-}
-
 hipError_t init_stack_kernels() {
     hipError_t e;
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
