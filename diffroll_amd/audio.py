@@ -12,7 +12,7 @@ mp3 decoding needs a codec this image lacks and is not attempted.
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -90,10 +90,14 @@ def load_wav(path: str) -> Tuple[torch.Tensor, int]:
     return torch.from_numpy(np.ascontiguousarray(x.T)), int(rate)
 
 
-def ingest(path: str, sample_rate: int, segment_samples: int) -> torch.Tensor:
-    """One clip as AudioDataset.__getitem__ builds it (utils/custom_dataset.py:55-91): (segment_samples,) float32."""
+def ingest(path: str, sample_rate: int, segment_samples: Optional[int]) -> torch.Tensor:
+    """One clip as AudioDataset.__getitem__ builds it (utils/custom_dataset.py:55-91): (segment_samples,) float32;
+    segment_samples None: the whole recording (L,) - what the reference's config documents for None
+    (utils/custom_dataset.py:21), for long-form transcription (diffroll_amd/longform.py)."""
     wav, rate = load_wav(path)
     mono = to_mono(wav)
     if rate != sample_rate:
         mono = resample(mono, rate, sample_rate)
+    if segment_samples is None:
+        return mono.contiguous()
     return crop_or_pad(mono, int(segment_samples))

@@ -4,6 +4,7 @@
     python sampling.py task=transcription dataset=Custom dataset.args.audio_path=my_audio dataset.args.audio_ext=wav \
         checkpoint_path=weights/Pretrain_MAESTRO-retrain_MAESTRO-k=9.ckpt
     python sampling.py task=inpainting task.inpainting_t=[500,650] dataset=Custom ...
+    python sampling.py task=transcription dataset=Custom dataset.args.max_segment_samples=null task.window_overlap=160 ...
     torchrun --nproc-per-node 8 sampling.py task=generation gpus=8 dataset.num_samples=128 dataloader.batch_size=128
 
 Hydra is not a dependency: the same ``group=name`` / ``dotted.key=value`` override syntax is parsed here over
@@ -12,6 +13,12 @@ config/model/ClassifierFreeDiffRoll.yaml and config/spec/mel.yaml.  Differences 
 no Lightning Trainer / TensorBoard; rolls are written as ``rolls_batch<i>.npy`` plus ``raw_midi_<batch>_<i>.mid`` / ``clean_midi_e<batch>_<i>.mid``;
 audio ingestion (utils/custom_dataset.py:55-91) reads .wav only (no mp3 codec in this image); resampling restates
 torchaudio 0.11's windowed-sinc kernel (diffroll_amd/audio.py).
+
+Long-form: ``dataset=Custom dataset.args.max_segment_samples=null`` transcribes every file whole (the reference
+documents None as "get the full audio", utils/custom_dataset.py:21, but crashes on it): each recording is one chain of
+jointly sampled 640-frame windows overlapping by ``task.window_overlap`` frames (default 160; diffroll_amd/longform.py),
+written as ``roll_<stem>.npy`` (1, 1, ceil(L / hop), 88), ``raw_midi_<stem>.mid`` and ``clean_midi_<stem>.mid``.  With
+``gpus=N`` every rank takes the files round-robin and writes its own outputs.
 """
 from __future__ import annotations
 
@@ -93,19 +100,74 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
         for part in parts[:-1]:
             node = node.setdefault(part, {})
         node[parts[-1]] = _parse_value(v)
+    if is_long_form(cfg):
+        sampler = cfg["task"]["sampling"]["type"]
+        if sampler == "inpainting_ddpm_x0":
+            raise SystemExit("max_segment_samples=null (long-form) cannot run inpainting_ddpm_x0: its masks are in the "
+                             "coordinates of one 640-frame clip, not of a recording")
+        overlap = cfg["task"].get("window_overlap", DEFAULT_WINDOW_OVERLAP)
+        if not isinstance(overlap, int) or not 1 <= overlap <= 320:
+            raise SystemExit(f"task.window_overlap must be an integer in [1, 320] (half the 640-frame window), got {overlap!r}")
     return cfg
+
+
+DEFAULT_WINDOW_OVERLAP = 160
+
+
+def is_long_form(cfg: Dict[str, Any]) -> bool:
+    """dataset=Custom with max_segment_samples=null: every file is transcribed whole (diffroll_amd/longform.py)."""
+    return cfg["dataset"]["name"] == "Custom" and cfg["dataset"]["args"].get("max_segment_samples", 0) is None
 
 
 def load_wav_folder(args: Dict[str, Any]) -> torch.Tensor:
     """utils/custom_dataset.py:55-91 over a folder: mono mix, torchaudio-0.11 windowed-sinc resampling, crop /
     zero-pad to max_segment_samples (diffroll_amd/audio.py)."""
     from .audio import ingest
+    files = wav_files(args)
+    return torch.stack([ingest(f, int(args["sample_rate"]), int(args["max_segment_samples"])) for f in files])
+
+
+def wav_files(args: Dict[str, Any]) -> List[str]:
     if str(args["audio_ext"]).lower() != "wav":
         raise SystemExit("only .wav can be decoded in this environment (no mp3/flac codec)")
     files = sorted(glob.glob(os.path.join(args["audio_path"], f"*.{args['audio_ext']}")))
     if not files:
         raise SystemExit(f"no *.{args['audio_ext']} files under {args['audio_path']}")
-    return torch.stack([ingest(f, int(args["sample_rate"]), int(args["max_segment_samples"])) for f in files])
+    return files
+
+
+def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> List[str]:
+    """Every file of the Custom folder whole (max_segment_samples=null): this rank's share, dealt round-robin, one
+    sample_long chain per recording (file i: seed = seed + i, recording = i); writes roll_<stem>.npy,
+    raw_midi_<stem>.mid and clean_midi_<stem>.mid.  Returns the roll paths written."""
+    from .audio import ingest
+    from .longform import deal
+    args = cfg["dataset"]["args"]
+    files = wav_files(args)
+    if cfg["dataset"].get("num_samples"):
+        files = files[:int(cfg["dataset"]["num_samples"])]
+    overlap = int(cfg["task"].get("window_overlap", DEFAULT_WINDOW_OVERLAP))
+    generation = cfg["task"]["sampling"]["type"] == "generation_ddpm_x0"
+    hop = int(cfg["hop_length"])
+    out = cfg["output_dir"]
+    written = []
+    for i, path in deal(list(enumerate(files)), rank, world):
+        stem = os.path.splitext(os.path.basename(path))[0]
+        wav = ingest(path, int(args["sample_rate"]), None)
+        seed = int(cfg["seed"]) + i
+        if generation:          # (the waveform is ignored, sampling.py:45: a roll of the recording's length)
+            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i)
+        else:
+            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i)
+        roll_path = os.path.join(out, f"roll_{stem}.npy")
+        np.save(roll_path, roll.cpu().numpy())
+        written.append(roll_path)
+        # export_midi names files <prefix><index in the batch>: one recording = index 0
+        tmp_raw, tmp_clean = os.path.join(out, f".raw_{stem}_"), os.path.join(out, f".clean_{stem}_")
+        model.export_midi(roll, tmp_raw, clean_prefix=tmp_clean)
+        os.replace(tmp_raw + "0.mid", os.path.join(out, f"raw_midi_{stem}.mid"))
+        os.replace(tmp_clean + "0.mid", os.path.join(out, f"clean_midi_{stem}.mid"))
+    return written
 
 
 def make_model(cfg: Dict[str, Any], device):
@@ -163,6 +225,19 @@ def main(argv: List[str] = None, default_task: str = "generation") -> None:
     dist = launch.init_process_group(device) if world > 1 else None
     from .distributed import sample_sharded
 
+    if is_long_form(cfg):
+        model = make_model(cfg, device)
+        os.makedirs(cfg["output_dir"], exist_ok=True)
+        t0 = time.perf_counter()
+        rolls = transcribe_long_form(cfg, model, rank, world)
+        frames = sum(int(np.load(p, mmap_mode="r").shape[2]) for p in rolls)
+        dt = time.perf_counter() - t0
+        print(f"rank {rank}: {len(rolls)} recording(s) whole, {frames} frames, {cfg['task']['timesteps']} steps, sampler "
+              f"{cfg['task']['sampling']['type']}: {dt:.2f} s -> {cfg['output_dir']}/")
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     S = int(cfg["dataset"]["num_samples"])
     hop = int(cfg["hop_length"])
     g = torch.Generator().manual_seed(int(cfg["seed"]))

@@ -132,6 +132,8 @@ int clear_stack_timeout(dr_engine* e) {
     HIPCHK(e, hipMemset(e->stack_bar, 0, (size_t)(12 * STACK_GROUPS) * sizeof(unsigned)));    // all three counter arrays
     HIPCHK(e, hipMemset(e->stack_xid, 0xFF, 1024 * sizeof(unsigned)));
     HIPCHK(e, hipMemset(e->stack_derr, 0, 16 * sizeof(unsigned)));
+    HIPCHK(e, hipMemset(e->win_ready, 0, STACK_GROUPS * sizeof(unsigned)));
+    e->win_epoch = 0;
     *e->stack_err_host = 0;
     return DR_OK;
 }
@@ -154,6 +156,13 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
     return DR_OK;
 }
 
+// option "window_overlap": at most two windows share a frame (O <= T / 2)
+int check_windows(dr_engine* e, int T) {
+    if (2 * e->opt_win_O > T)
+        return fail(e, DR_EINVAL, "window_overlap %d exceeds half the window (T = %d frames)", e->opt_win_O, T);
+    return DR_OK;
+}
+
 // dr_set_option (lab = false: the product's options) / dr_debug_set_option (lab = true: the A/B and test knobs too)
 int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (!e || !name) return fail(e, DR_EINVAL, "null argument");
@@ -172,6 +181,12 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         return DR_OK;
     }
     if (n == "fused_tail") { if (e->opt_tail != value) drop(); e->opt_tail = value; return DR_OK; }
+    if (n == "window_overlap") {      // (O <= T / 2 is checked by dr_step / dr_sample, which know T)
+        if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
+        if (e->opt_win_O != value) drop();
+        e->opt_win_O = value;
+        return DR_OK;
+    }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
     if (n == "fused_stack_xcd") { if (e->opt_stack_xcd != value) drop(); e->opt_stack_xcd = value; return DR_OK; }
     if (n == "fused_stack_warm") { if (e->opt_stack_warm != value) drop(); e->opt_stack_warm = value; return DR_OK; }
@@ -471,6 +486,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     int rc = check_ready(e, sampler, B, T);
     if (rc) return rc;
     if (t < 0 || t >= e->S) return fail(e, DR_EINVAL, "step %d out of range", t);
+    if ((rc = check_windows(e, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = ensure_workspace(e, NB, T))) return rc;
@@ -489,6 +505,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     DeviceGuard guard(e->cfg.device);
     int rc = check_ready(e, sampler, B, T);
     if (rc) return rc;
+    if ((rc = check_windows(e, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = ensure_workspace(e, NB, T))) return rc;
@@ -563,7 +580,9 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     Range range("dr_sample: launch the chain graph");
     // the graph owns no caller address: x_T is copied in, the finished roll copied out (0.7 MB each way)
     HIPCHK(e, hipMemcpyAsync(e->xwork, d_x, per * sizeof(float), hipMemcpyDeviceToDevice, st));
-    HIPCHK(e, launch_set_dyn(e->d_dyn, seed, first_sample, w, (float)(1.0 + (double)w), st));
+    // (the chain's tail launches publish epochs win_epoch + 1 .. win_epoch + S: TailArgs::ready)
+    HIPCHK(e, launch_set_dyn(e->d_dyn, seed, first_sample, w, (float)(1.0 + (double)w), e->win_epoch, st));
+    e->win_epoch += (unsigned)e->S;
     HIPCHK(e, hipGraphLaunch(e->gexec, st));
     e->graph_stream = st; e->graph_stream_set = true;
     if (e->stack_launches || e->tail_launches) { e->unverified = true; e->fused_stream = st; }      // (the captured chain may hold persistent launches)

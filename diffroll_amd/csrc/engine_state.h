@@ -137,6 +137,10 @@ struct dr_engine {
     unsigned* tail_pbar = nullptr;
     int opt_tail = 1;                   // fused step: layer 0's shared conv inside the stack launch + the tail kernel
     int64_t tail_launches = 0;
+    int opt_win_O = 0;                  // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
+                                        // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
+    unsigned* win_ready = nullptr;      // [STACK_GROUPS] the tail kernel's per-window ready words (TailArgs::ready)
+    unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
     float* xalt = nullptr;              // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
     int last_mode = 0;                  // DR_MODE_* of the most recently planned evaluation (dr_launch_state)

@@ -182,8 +182,10 @@ struct DynParams {
     unsigned long long seed;
     int first_sample;
     float w, onepw;
+    unsigned epoch;        // long-form windows: the tail launches of this chain publish epoch + TailArgs::epoch (see tail_kernel)
 };
-hipError_t launch_set_dyn(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, hipStream_t s);
+hipError_t launch_set_dyn(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, unsigned epoch,
+                          hipStream_t s);
 
 struct UpdateArgs {
     float* x;              // (B, T, 88) in/out
@@ -199,6 +201,12 @@ struct UpdateArgs {
     uint64_t seed;
     int first_sample;
     const DynParams* dyn;  // non-null: w / onepw / seed / first_sample are read from here instead
+    // Long-form windows (option "window_overlap" = O > 0; 0 = off): the B rolls are B consecutive windows of ONE
+    // recording on a canvas of (B - 1) * win_H + T frames, window b starting at canvas frame b * win_H, win_H = T - O,
+    // 2 O <= T.  A frame shared by windows b and b + 1 (frames [win_H, T) of b = frames [0, O) of b + 1) uses the mean
+    // 0.5 (y_b + y_b+1) of the two windows' guided predictions, and Philox is keyed by (seed, first_sample = the
+    // recording, t, canvas element / 4): both windows compute the same x_{t-1} there, bit for bit.
+    int win_H;
 };
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
 
@@ -231,6 +239,12 @@ struct TailArgs {
     long long* dbg;                           // optional: block 0 writes s_memtime at the start and after T1, its barrier, T2, its
                                               // barrier, T3, its barrier, T4 (8 marks)
     unsigned *bar, *pbar, *err, *derr;        // counters as in StackArgs (own arrays), time-out flags (shared with the stack)
+    // long-form windows (u.win_H > 0): T3 of window b reads the x0 that windows b - 1 / b + 1 wrote in their T2.  After
+    // its pair barrier, window b publishes ready[b] = epoch and waits for its neighbours' words to reach it.  The words
+    // only ever grow (epoch = (u.dyn ? u.dyn->epoch : 0) + this launch's epoch, a per-engine count of tail launches):
+    // a replayed graph and a neighbour that has already left the launch are both seen correctly.
+    unsigned* ready;                          // [STACK_GROUPS] one word per window, zero after a time-out's re-arm
+    unsigned epoch;
 };
 hipError_t launch_tail(const TailArgs& s, hipStream_t st);
 

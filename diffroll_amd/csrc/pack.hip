@@ -444,14 +444,15 @@ int commit(dr_engine* e, hipStream_t st) {
     if (!e->stack_bar) {     // group counters of the fused residual stack: zero between launches (re-armed in-kernel)
         void* q = nullptr;
         const size_t G4 = (size_t)4 * STACK_GROUPS;
-        const size_t nb = (3 * G4 + 1024 + 16) * sizeof(unsigned);
+        const size_t nb = (3 * G4 + 1024 + 16 + STACK_GROUPS) * sizeof(unsigned);
         HIPCHK(e, hipMalloc(&q, nb));
         HIPCHK(e, hipMemset(q, 0, nb));
-        e->stack_bar = (unsigned*)q;                                     // [bar][tail bar][tail pair bar][xid][derr]
+        e->stack_bar = (unsigned*)q;                                     // [bar][tail bar][tail pair bar][xid][derr][ready]
         e->tail_bar = e->stack_bar + G4;
         e->tail_pbar = e->stack_bar + 2 * G4;
         e->stack_xid = e->stack_bar + 3 * G4;                            // one word per block (<= 1024 CUs)
         e->stack_derr = e->stack_xid + 1024;
+        e->win_ready = e->stack_derr + 16;                               // [STACK_GROUPS] ready words of long-form windows
         HIPCHK(e, hipMemset(e->stack_xid, 0xFF, 1024 * sizeof(unsigned)));   // no tag of a launch ever equals 0xFFFFFFFF
         // the "a barrier wait gave up" flag lives in host-visible memory: every later API call sees it without a
         // synchronisation and fails loudly instead of returning rolls computed from a broken hand-off

@@ -82,6 +82,34 @@ DR_DEVINL void group_barrier(unsigned* ctr, const unsigned target, unsigned* err
     __syncthreads();
 }
 
+// Long-form windows (tail.hip, between the pair barrier after T2 and T3): thread 0 of a block of window i waits until
+// the ready words of windows i - 1 and i + 1 (those that exist, i < n) have reached `epoch`, then drops its CU's L1 lines
+// (agent-scope acquire), as group_barrier does after a match; the caller's __syncthreads() releases the block.  A
+// neighbour publishes its word once every block of its pair has passed the pair barrier, i.e. once its T2 stores (write-
+// through, drained) are out.  Its PAIR counters are never polled here: the last block to leave a launch re-arms them, so a
+// neighbour that has already finished T3 / T4 would look like one that never arrived.  The words only grow (a per-engine
+// epoch, compared as a signed difference): nothing re-arms them in-kernel.  Same spin bound and flags as group_barrier.
+// Deadlock-free because the tail kernel only runs when the whole evaluation is one resident launch (launch_plan.h:
+// stack_chunks == 1) and publishing does not wait for anything.
+DR_DEVINL void neighbour_wait(const unsigned* ready, const int i, const int n, const unsigned epoch, unsigned* err,
+                              unsigned* derr) {
+    unsigned spins = 0;
+    for (int j = i - 1; j <= i + 1; j += 2) {
+        if (j < 0 || j >= n) continue;
+        while ((int)(__hip_atomic_load(ready + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0) {
+            __builtin_amdgcn_s_sleep(4);
+            ++spins;
+            if (spins > (1u << 20) ||
+                ((spins == 64u || (spins & 4095u) == 0) && __hip_atomic_load(derr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(derr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
 // Group-per-XCD dealing of a persistent launch (block b is dispatched to XCD b % 8): groups g, g + 8, g + 16, ... share
 // XCD g, so it needs every XCD's share - ceil(NB / 8) groups - to fit that XCD's CUs.  When NB is not a multiple of 8
 // the grid is padded with idle groups (their blocks exit at once) if that still holds; else the launch falls back to

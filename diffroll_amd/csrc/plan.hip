@@ -305,6 +305,11 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
         }
     }
     ta.bar = e->tail_bar; ta.pbar = e->tail_pbar; ta.err = e->stack_err; ta.derr = e->stack_derr;
+    // long-form windows: every window of the chain is in this one resident launch (the plan only takes the tail when
+    // stack_chunks == 1), so the neighbour wait of T3 always has its neighbours running.  Epoch: position in the chain
+    // for a captured one (added to DynParams::epoch at run time), else the next value of the engine's count.
+    ta.ready = e->win_ready;
+    ta.epoch = v.e->use_dyn ? (unsigned)(e->S - v.t) : ++e->win_epoch;
     // ticks 112..119 of dr_stack_status: the last tail launch of a chain that has a next step (all its parts run)
     ta.dbg = (e->stack_dbg_on && tail->next_t >= 0) ? e->stack_dbg + 112 : nullptr;
     HIPCHK(e, launch_tail(ta, v.st));
@@ -399,6 +404,7 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     u.seed = seed; u.first_sample = first_sample;
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
+    u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
     TailPlan plan;
     plan.u = u; plan.x_out = e->xalt; plan.u_B = B;
     plan.next_t = chain ? chain->next_t : -1;

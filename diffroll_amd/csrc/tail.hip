@@ -19,7 +19,8 @@ DR_BOUNDS_TU(tail)
 //   --  group barrier (+ L1 invalidate: T2 reads tmp with plain loads)
 //   T2  output projection -> x0 in the (B, T, 88) roll layout.  Items = 32-frame chunks (pw_body<1>; 88 rows: three
 //       of the four waves).  Output write-through.
-//   --  pair barrier (group barrier without guidance) + L1 invalidate
+//   --  pair barrier (group barrier without guidance) + L1 invalidate; long-form windows (UpdateArgs::win_H) also wait for
+//       the neighbouring windows' T2 (neighbour_wait) - T3 reads their x0 on the shared frames
 //   T3  per item (128-row tile of the input projection, 32-frame chunk) of the pair's clip: the classifier-free
 //       combine + posterior update of those 32 frames x 88 keys (update_quad: the arithmetic of update_kernel) into
 //       LDS - the item with row tile 0 also writes x_{t-1} back - then, when a step follows, its input projection
@@ -97,6 +98,15 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
     mark();
     if (paired) group_barrier<true>(pctr, 2u * gsize + DR_FAULT_EXTRA(s), s.err, s.derr);
     else group_barrier<true>(ctr, 2u * (gsize + DR_FAULT_EXTRA(s)), s.err, s.derr);
+    if (s.u.win_H > 0) {
+        // long-form windows: T3 reads the neighbouring windows' x0 on the shared frames (neighbour_wait, persistent.h)
+        if (threadIdx.x == 0) {
+            const unsigned epoch = (s.u.dyn ? s.u.dyn->epoch : 0u) + s.epoch;
+            if (member == 0 && pair_half == 0) __hip_atomic_store(s.ready + pair_i, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            neighbour_wait(s.ready, pair_i, s.u_B, epoch, s.err, s.derr);
+        }
+        __syncthreads();
+    }
     mark();
     // ---- T3: combine + update (+ the next step's input projection) per (row tile, 32-frame chunk) of the pair's clip
     if (pair_i < s.u_B) {       // (groups without a roll of their own - none today - would skip)
@@ -216,6 +226,7 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
     if ((s.Cp & 63) || s.NB < 1 || s.T < 1) return hipErrorInvalidValue;
     if (s.dual > 0 && s.NB != 2 * s.dual) return hipErrorInvalidValue;
     if (!s.x_out || s.x_out == s.u.x) return hipErrorInvalidValue;
+    if (s.u.win_H > 0 && (!s.ready || s.u_B > STACK_GROUPS || 2 * s.u.win_H < s.T || s.u.win_H >= s.T)) return hipErrorInvalidValue;
     const int tps = (s.T + s.BN - 1) / s.BN, MT = s.Cp >> 6;
     TailArgs b = s;
     const int NBp = xcd_padded_groups(s.NB, MT * tps, &b.xcd_n);       // idle padding groups, as launch_stack

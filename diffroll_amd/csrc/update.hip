@@ -11,11 +11,12 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
     reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4);
 }
 
-__global__ void set_dyn_kernel(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw) {
-    d->seed = seed; d->first_sample = first_sample; d->w = w; d->onepw = onepw;
+__global__ void set_dyn_kernel(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, unsigned epoch) {
+    d->seed = seed; d->first_sample = first_sample; d->w = w; d->onepw = onepw; d->epoch = epoch;
 }
-hipError_t launch_set_dyn(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, hipStream_t s) {
-    hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, d, seed, first_sample, w, onepw);
+hipError_t launch_set_dyn(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, unsigned epoch,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(set_dyn_kernel, dim3(1), dim3(1), 0, s, d, seed, first_sample, w, onepw, epoch);
     return hipGetLastError();
 }
 

@@ -35,22 +35,52 @@ DR_DEVINL void box_muller(uint32_t u0, uint32_t u1, float& z0, float& z1) {
     z1 = rad * sn;
 }
 
-// Classifier-free combine + x0-prediction posterior update of ONE float4 (4 consecutive elements, index i4) of the
-// roll.  Same operation order as task/diffusion.py:953 and :957-967; contraction off so that no FMA is formed where
-// the reference rounds twice.  Shared by update_kernel and the tail kernel (identical arithmetic).
-DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
+// The guided prediction of one float4 (index i4) of the roll: (1 + w) x0c - w x0u, or x0c alone (task/diffusion.py:953).
+DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, const float g1pw, float (&y)[4]) {
 #pragma clang fp contract(off)
     const float4 xc = reinterpret_cast<const float4*>(a.x0c)[i4];
-    float x0[4] = {xc.x, xc.y, xc.z, xc.w};
-    // per-call scalars: by value (eager launches) or from the device block (captured chain)
-    const float gw = a.dyn ? a.dyn->w : a.w, g1pw = a.dyn ? a.dyn->onepw : a.onepw;
-    const uint64_t seed = a.dyn ? a.dyn->seed : a.seed;
-    const int first_sample = a.dyn ? a.dyn->first_sample : a.first_sample;
+    y[0] = xc.x; y[1] = xc.y; y[2] = xc.z; y[3] = xc.w;
     if (a.x0u) {
         const float4 xu = reinterpret_cast<const float4*>(a.x0u)[i4];
         const float u[4] = {xu.x, xu.y, xu.z, xu.w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x0[e] = g1pw * x0[e] - gw * u[e];
+        for (int e = 0; e < 4; ++e) y[e] = g1pw * y[e] - gw * u[e];
+    }
+}
+
+// Classifier-free combine + x0-prediction posterior update of ONE float4 (4 consecutive elements, index i4) of the
+// roll.  Same operation order as task/diffusion.py:953 and :957-967; contraction off so that no FMA is formed where
+// the reference rounds twice.  Shared by update_kernel and the tail kernel (identical arithmetic).
+// Long-form windows (a.win_H > 0, UpdateArgs): on a frame shared with a neighbouring window the prediction is the mean
+// 0.5f * (y_lower + y_upper) of both windows' guided predictions - the same bits in both (the operands are the same
+// two values, added in the same order) - and the noise is keyed by the canvas element.
+DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
+#pragma clang fp contract(off)
+    float x0[4];
+    // per-call scalars: by value (eager launches) or from the device block (captured chain)
+    const float gw = a.dyn ? a.dyn->w : a.w, g1pw = a.dyn ? a.dyn->onepw : a.onepw;
+    const uint64_t seed = a.dyn ? a.dyn->seed : a.seed;
+    const int first_sample = a.dyn ? a.dyn->first_sample : a.first_sample;
+    guided_quad(a, i4, gw, g1pw, x0);
+    long key_smp = -1, key_q = 0;             // Philox sample / quad key of a window (win_H > 0): canvas coordinates
+    if (a.win_H > 0) {
+        const long e0 = i4 * 4;
+        const long smp = e0 / a.per_sample;
+        const long within = e0 - smp * a.per_sample;
+        const int f = (int)(within / 88);
+        const long o4 = a.per_sample / 4 - (long)a.win_H * 22;      // O frames x 22 quads: window b's frame f <-> b + 1's f - H
+        long p4 = -1;
+        bool upper = false;                                        // the partner is the upper window (b + 1)
+        if (f >= a.win_H && (smp + 1) * a.per_sample < a.n) { p4 = i4 + o4; upper = true; }
+        else if (f < (int)(o4 / 22) && smp > 0) p4 = i4 - o4;
+        if (p4 >= 0) {
+            float yp[4];
+            guided_quad(a, p4, gw, g1pw, yp);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x0[e] = upper ? 0.5f * (x0[e] + yp[e]) : 0.5f * (yp[e] + x0[e]);
+        }
+        key_smp = first_sample;
+        key_q = (smp * a.win_H * 88 + within) >> 2;
     }
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];
@@ -66,12 +96,17 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
             const float4 zv = reinterpret_cast<const float4*>(a.noise)[i4];
             z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
         } else {
-            const long e0 = i4 * 4;
-            const long smp = e0 / a.per_sample;
-            const long within = (e0 - smp * a.per_sample) >> 2;
+            long within, sk;
+            if (key_smp >= 0) { within = key_q; sk = key_smp; }
+            else {
+                const long e0 = i4 * 4;
+                const long smp = e0 / a.per_sample;
+                within = (e0 - smp * a.per_sample) >> 2;
+                sk = first_sample + smp;
+            }
             uint32_t rnd[4];
             philox4x32_10((uint32_t)within, (uint32_t)(within >> 32), (uint32_t)a.t,
-                          (uint32_t)(first_sample + smp), (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+                          (uint32_t)sk, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
             box_muller(rnd[0], rnd[1], z[0], z[1]);
             box_muller(rnd[2], rnd[3], z[2], z[3]);
         }

@@ -332,6 +332,10 @@ class Engine:
         (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
         self._check(fn(self.h, name.encode(), int(value)))
+        if name == "window_overlap":
+            self.window_overlap = int(value)
+
+    window_overlap = 0      # the last value set for option 'window_overlap' (0 = off, the library's default)
 
     def stack_status(self, n_ticks: int = 0):
         """(timed_out, ticks): synchronises; timed_out != 0 means a fused-kernel barrier hit its spin bound.

@@ -474,6 +474,58 @@ class ClassifierFreeDiffRoll(nn.Module):
         eng.sample(sampler, xb, z, w, seed, first_sample, use_graph, check)
         return xb.unsqueeze(1), spec
 
+    @torch.no_grad()
+    def sample_long(self, waveform=None, frames: Optional[int] = None, overlap: int = 160, seed: int = 0,
+                    recording: int = 0, x_T=None, noise=None, use_graph: bool = True, check: bool = True) -> torch.Tensor:
+        """One recording of any length as jointly sampled 640-frame windows (diffroll_amd/longform.py; option
+        "window_overlap" of include/diffroll_amd.h): returns the stitched roll (1, 1, T_out, 88) on the device.
+        Conditional samplers take waveform (L,) (T_out = ceil(L / hop)); generation_ddpm_x0 takes frames = T_out.
+        x_T: (1, 1, T_c, 88) canvas, or None: drawn from torch.Generator().manual_seed(seed) on the host; noise: None
+        (Philox keyed by seed, first_sample = recording and the canvas element) or a canvas tensor
+        (timesteps, 1, 1, T_c, 88).  Every window is one row of ONE Engine.sample chain (check=True heals)."""
+        from . import longform
+        sampler = self.hparams.sampling.type
+        if sampler == "inpainting_ddpm_x0":
+            raise ValueError("sample_long does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) are in "
+                             "the coordinates of one 640-frame clip, not of a recording")
+        eng = self.engine
+        if sampler == "generation_ddpm_x0":
+            if frames is None or waveform is not None:
+                raise ValueError("generation_ddpm_x0: pass frames= (the roll length), not a waveform")
+            plan = longform.plan_windows(int(frames), None, longform.WINDOW_FRAMES, overlap)
+        else:
+            if waveform is None or frames is not None:
+                raise ValueError(f"{sampler}: pass waveform= (L,), not frames")
+            waveform = torch.as_tensor(waveform).to("cpu", torch.float32)
+            if waveform.dim() != 1:
+                raise ValueError(f"waveform must be one recording (L,), got {tuple(waveform.shape)}")
+            plan = longform.plan_windows(waveform.shape[0], eng.hop_length, longform.WINDOW_FRAMES, overlap)
+        if plan.n > longform.MAX_WINDOWS:
+            raise ValueError(f"{plan.n} windows of {plan.T} frames: one chain holds at most {longform.MAX_WINDOWS} "
+                             f"(longform.MAX_WINDOWS); split the recording")
+        S = int(self.hparams.timesteps)
+        if x_T is None:
+            x_T = torch.randn(1, 1, plan.T_c, 88, generator=torch.Generator().manual_seed(int(seed)))
+        if tuple(x_T.shape) != (1, 1, plan.T_c, 88):
+            raise ValueError(f"x_T must be the canvas (1, 1, {plan.T_c}, 88), got {tuple(x_T.shape)}")
+        xb = longform.gather_windows(x_T.reshape(plan.T_c, 88).to(eng.device, torch.float32), plan)
+        z = None
+        if noise is not None:
+            if noise.numel() != S * plan.T_c * 88:
+                raise ValueError(f"noise must be the canvas ({S}, 1, 1, {plan.T_c}, 88), got {tuple(noise.shape)}")
+            z = longform.gather_windows(noise.reshape(S, plan.T_c, 88).to(eng.device, torch.float32), plan)
+        if sampler != "generation_ddpm_x0":
+            eng.frontend(longform.window_audio(waveform, plan, eng.hop_length), plan.T)
+            self._fe_key = None          # the engine's conditioner is the windows' now: sample() recomputes its own
+        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
+        prev = eng.window_overlap
+        eng.set_option("window_overlap", plan.overlap)
+        try:
+            eng.sample(sampler, xb, z, w, seed, recording, use_graph, check)
+        finally:
+            eng.set_option("window_overlap", prev)
+        return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
+
     def sample_trajectory(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0):
         """The same chain, keeping every intermediate roll on the device: returns (trajectory (timesteps, B, 1,
         T', 88) with row i = x after step t = timesteps-1-i, spec).  This is what the reference's sampling()

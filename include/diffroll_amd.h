@@ -337,6 +337,16 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          2 launches per reverse step instead of 6 (the first step of a chain still runs its input
  *                          projection and first-layer conv as launches of their own).  0 = separate launches
  *                          (bit-identical without split-K).
+ *   "window_overlap"   [0] O > 0: long-form transcription.  The B rolls of dr_step / dr_sample / dr_sample_checked are B
+ *                          consecutive T-frame windows of ONE recording, window b starting at frame b * H (H = T - O) of
+ *                          a canvas of (B - 1) * H + T frames; at every reverse step a frame shared by windows b and
+ *                          b + 1 (frames [H, T) of b, [0, O) of b + 1) takes 0.5f * (y_b + y_b+1), the mean of the two
+ *                          windows' guided x0 predictions, before the posterior update (MultiDiffusion, Bar-Tal et al.
+ *                          2023), and Philox noise is keyed (seed, first_sample = the recording, t, canvas element / 4);
+ *                          injected noise rows are used as given.  If x_T agrees on shared frames, every x_t does, bit for
+ *                          bit: the stitched roll is a plain gather from the canvas.  O > T / 2 -> DR_EINVAL at the call
+ *                          (at most two windows share a frame).  dr_forward / dr_forward_steps are unaffected; 0 = off
+ *                          (every clip on its own, bit-identical to an engine that never set it).
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
