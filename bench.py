@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: piano-roll frames/s for a 200-step reverse-diffusion sample.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1..7}] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1..7}] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 starts the N ranks itself (re-executes under ``python -m torch.distributed.run``, one
 process per GPU, RCCL); the same script also runs under an external launcher:
@@ -16,13 +16,21 @@ hipGraph-captured reverse chain + the RCCL gather of the finished rolls + the de
 Inputs are resident in HBM when the timed region starts.  Multi-GPU is weak scaling: every rank runs its own
 clips, the only collective is the final all-gather.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel: algorithmic FLOPs per launch / mean launch
-duration measured with HIP events on the launch stream in an extra, event-instrumented eager pass of the same
-chain run right after the timed region.  `cpu_baseline` is the CPU oracle (a port of the reference math, torch
-CPU fp32) timed on this box's host cores on a bounded sample.  `launch_mode` / `per_rank_launch_mode` / `fused_yields` /
-`fused_fallbacks` say what every rank's engine launched inside the timed region: a region in which any rank yielded to
-per-phase launches or healed a fused time-out is discarded by all ranks and repeated (`attempts`, `discarded_attempts`), at
-most twice - then there is no line and the exit code is not 0.
+Rank 0 prints ONE JSON line.  `launch_mode` / `per_rank_launch_mode` / `fused_yields` / `fused_fallbacks` say what every
+rank's engine launched inside the timed region: a region in which any rank yielded to per-phase launches or healed a fused
+time-out is discarded by all ranks and repeated (`attempts`, `discarded_attempts`), at most twice - then there is no line
+and the exit code is not 0.  `hbm_roofline` / `whole_chain` are arithmetic on the timed region.
+
+A plain run does only what that line needs: set-up, warm-up, the timed steps, ``--dump-outputs`` and the line.
+``--full`` adds everything else, after the timed region (the --no-* switches still drop single legs of it):
+* `per_rank_ms_per_step` / `gather_us`: every rank's own time over K more steps, and the final all-gather on its own;
+* `roofline` for the dominant kernel: algorithmic FLOPs per launch / mean launch duration measured with HIP events on the
+  launch stream in an extra, event-instrumented eager pass of the same chain; `memory_bound_kernels` from the newest
+  committed kernel-trace profile;
+* `split_bf16x3`: the same timed steps again in the opt-in split-bf16 precision;
+* `dr_gather_check` in a 1-rank group (multi-rank runs: only with --gather-check, which also works without --full);
+* one-rank runs: `cpu_baseline`, the CPU oracle (a port of the reference math, torch CPU fp32) timed on the host's cores
+  on a bounded sample, and `cold_start`, the time-to-first-roll of fresh processes at configs 1 and 2.
 
 ``--dump-outputs DIR`` writes what the timed path returned in its last timed step, as float32 ``DIR/<name>.npy``:
 ``roll`` = the gathered rolls (n_gpus * B, 1, T, 88) one_step() hands to its caller, ``spec`` = rank 0's spectrogram
@@ -355,14 +363,17 @@ def main():
                     help="plain single-process run: still create a 1-rank RCCL group (exercises init / all-gather / barrier)")
     ap.add_argument("--gather-check", action="store_true",
                     help="multi-rank runs: also create a C-ABI communicator (dr_comm_create) and compare dr_gather with "
-                         "torch's all-gather (always done in 1-rank groups)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "torch's all-gather (1-rank groups: also done by --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: per-rank times and the gather on its own, "
+                         "roofline, split-bf16 run, 1-rank dr_gather check, CPU baseline, cold start (the --no-* switches drop legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
     ap.add_argument("--accumulation", choices=("auto", "blocked", "single_chain"), default="auto",
                     help="accumulation order of the dilated conv: auto = blocked = one fp32 chain per 32-channel chunk in every fp32 "
                          "flavour (default); single_chain = 128-frame blocks keep one chain over all of K (-0.5 %%; DESIGN.md 2)")
-    ap.add_argument("--no-cold-start", action="store_true", help="skip the time-to-first-roll subprocesses (configs 1 and 2)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-split", action="store_true", help="skip the extra bf16x3 split-precision measurement")
+    ap.add_argument("--no-cold-start", action="store_true", help="--full: skip the time-to-first-roll subprocesses (configs 1 and 2)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the event-instrumented roofline pass")
+    ap.add_argument("--no-split", action="store_true", help="--full: skip the extra bf16x3 split-precision measurement")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the arrays the last timed step returned (roll, spec) to DIR/<name>.npy "
                          "in float32 (rank 0; at most 64 MB, larger arrays as a seeded sample; bench_outputs/ is git-ignored)")
@@ -525,31 +536,33 @@ def main():
     }
     if forced_options:
         result["tuning"] = dict(forced_options)      # NOT the shipping configuration: an A/B run
-    # straggler visibility for the scaling table: every rank's own time over the same K steps (no barrier inside),
-    # and the final all-gather on its own (HIP events around 10 back-to-back gathers of the finished rolls)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step()
-    torch.cuda.synchronize()
-    mine = torch.tensor([1e3 * (time.perf_counter() - t0) / args.steps], device=cdev, dtype=torch.float64)
-    if dist is not None:
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = [float(v.item()) for v in allr]
-    else:
-        per_rank = [float(mine.item())]
-    roll_l, _ = model.sample(x_T, wav, seed=0, first_sample=rank * B)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    gather_rolls(roll_l)
-    sync()
-    e0.record()
-    for _ in range(10):
+    per_rank = None
+    if args.full:
+        # straggler visibility for the scaling table: every rank's own time over the same K steps (no barrier inside),
+        # and the final all-gather on its own (HIP events around 10 back-to-back gathers of the finished rolls)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            one_step()
+        torch.cuda.synchronize()
+        mine = torch.tensor([1e3 * (time.perf_counter() - t0) / args.steps], device=cdev, dtype=torch.float64)
+        if dist is not None:
+            allr = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+            per_rank = [float(v.item()) for v in allr]
+        else:
+            per_rank = [float(mine.item())]
+        roll_l, _ = model.sample(x_T, wav, seed=0, first_sample=rank * B)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         gather_rolls(roll_l)
-    e1.record()
-    torch.cuda.synchronize()
-    result["per_rank_ms_per_step"] = {"min": round(min(per_rank), 3), "max": round(max(per_rank), 3),
-                                      "all": [round(v, 3) for v in per_rank]}
-    result["gather_us"] = round(1e3 * e0.elapsed_time(e1) / 10, 2) if dist is not None else 0.0
+        sync()
+        e0.record()
+        for _ in range(10):
+            gather_rolls(roll_l)
+        e1.record()
+        torch.cuda.synchronize()
+        result["per_rank_ms_per_step"] = {"min": round(min(per_rank), 3), "max": round(max(per_rank), 3),
+                                          "all": [round(v, 3) for v in per_rank]}
+        result["gather_us"] = round(1e3 * e0.elapsed_time(e1) / 10, 2) if dist is not None else 0.0
     if rank == 0:
         assert out is not None and bool(torch.isfinite(out).all()) and out.shape == (world * B, 1, T, 88)
         # the metric also asks for the HBM-roofline fraction: SURVEY.md 8(d) algorithmic bytes of one chain per GPU
@@ -572,7 +585,7 @@ def main():
             "note": "algorithmic = SURVEY.md 8d count (two full evaluations per guided step); executed = minus the shared "
                     "first-layer contraction and the never-read residual half of the last 1x1 (work the engine does not do)"}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         eng = model.engine
         eng.profile_enable(True)
         model._fe_key = None
@@ -594,9 +607,9 @@ def main():
             "flops_per_launch": flops / max(launches, 1),
             "share_of_step_time": round((ms * 1e-3) / (dt / args.steps), 4),
         }
-    if rank == 0:
+    if rank == 0 and args.full:
         result["memory_bound_kernels"] = membound_fractions(args.config)
-    if not args.no_split:
+    if args.full and not args.no_split:
         # Opt-in split-bf16 precision (DR_PRECISION_BF16X3: every fp32 operand split exactly into three bf16
         # pieces, six piece products on the bf16 MFMA, fp32 accumulation - fp32-level error).
         # Reported NEXT TO the headline, never as `value`: same workload, same seeds, same timing protocol.
@@ -612,7 +625,7 @@ def main():
                 "thresholded_frames_differing": int(((out3 > 0.5) != (out > 0.5)).sum()),
                 "note": "opt-in precision mode; identical inputs and Philox noise as the headline run",
             }
-    if dist is not None and (args.gather_check or world == 1):
+    if dist is not None and (args.gather_check or (args.full and world == 1)):
         # (multi-rank runs: only with --gather-check - a second communicator is created collectively, and the headline
         # measurement must never depend on it)
         # the same collective through the C-ABI (dr_comm_create / dr_gather: RCCL via dlopen, no torch.distributed in
@@ -632,9 +645,9 @@ def main():
             check = {"ok": False, "error": f"{type(ex).__name__}: {ex}"[:300]}
         if rank == 0:
             result["dr_gather_check"] = check
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(model, cfg, hp)
-    if rank == 0 and world == 1 and not args.no_cold_start:
+    if rank == 0 and world == 1 and args.full and not args.no_cold_start:
         result["cold_start"] = cold_start()
     if rank == 0 and args.dump_outputs:
         result["dumped_outputs"] = {"dir": args.dump_outputs,
@@ -645,10 +658,10 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if seen != args.gpus or len(per_rank) != args.gpus:
+    if seen != args.gpus or (per_rank is not None and len(per_rank) != args.gpus):
         # a job that ran with fewer ranks than it was asked for must not pass for a scaling point
-        raise SystemExit(f"rank {rank}: --gpus {args.gpus} but the process group had {seen} rank(s) "
-                         f"({len(per_rank)} per-rank times)")
+        raise SystemExit(f"rank {rank}: --gpus {args.gpus} but the process group had {seen} rank(s)"
+                         + (f" ({len(per_rank)} per-rank times)" if per_rank is not None else ""))
 
 
 if __name__ == "__main__":

@@ -243,8 +243,8 @@ def test_two_rank_bench_path_executes_on_one_gpu():
     it; it guarantees that the real 8-GPU run does not die in plumbing."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--config", "1",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-split", "--no-roofline", "--no-cold-start"],
-                       env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-split", "--no-roofline",
+                        "--no-cold-start"], env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     assert len(lines) == 1, r.stdout[-2000:]                  # rank 0 only
@@ -426,7 +426,8 @@ def test_external_launcher_line_with_two_ranks_on_one_gpu():
     from diffroll_amd.launch import free_port
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--config", "1",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-split", "--no-roofline", "--no-cold-start"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-split", "--no-roofline",
+           "--no-cold-start"]
     r = subprocess.run(cmd, env=_clean_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

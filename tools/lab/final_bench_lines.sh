@@ -4,9 +4,9 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout 900 python -m pytest tests/test_gpu_sharding.py -m gpu -q -p no:cacheprovider 2>&1 | grep -E "passed|failed|^FAILED|^ERROR" > $O/sharding.txt; cat $O/sharding.txt
 for c in 1 2 3 4 5 6 7; do
   extra="--no-split --no-cpu-baseline --no-cold-start"; [ $c = 2 ] && extra=""
-  timeout 900 python bench.py --config $c $extra > "$O/r06_bench_cfg$c.json" 2> "$O/bench_cfg$c.err"; echo "bench cfg$c rc=$?"
+  timeout 900 python bench.py --full --config $c $extra > "$O/r06_bench_cfg$c.json" 2> "$O/bench_cfg$c.err"; echo "bench cfg$c rc=$?"
 done
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --no-cpu-baseline --no-split --no-cold-start > "$O/r06_bench_cfg2_nccl_1rank.json" 2> "$O/bench_nccl.err"; echo "bench nccl rc=$?"
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --no-cpu-baseline --no-split --no-cold-start > "$O/r06_bench_cfg2_nccl_1rank.json" 2> "$O/bench_nccl.err"; echo "bench nccl rc=$?"
 {
 echo "# the GPU suite with every engine's DEFAULTS changed (tools/tuning_env.py), one MI355X, round-6 final sources"
 for tune in fused_stack=0 tune.stack_fl=-5; do

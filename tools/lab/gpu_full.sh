@@ -10,7 +10,7 @@ echo "pytest rc=$?" >> $O/pytest.log
 tail -6 $O/pytest.log
 sort -k2 -g -r $O/margins.txt | head -8
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 j=json.loads(open('gpurun_out/full/bench.json').read().strip().splitlines()[-1])

@@ -16,7 +16,7 @@ done
 echo "# (2) bench lines (fresh process each): value, ms per chain, launch mode, dominant kernel + frac, whole chain executed"
 for c in 5 6 7; do
   for fl in 0 -5; do
-    DR_TEST_TUNE=tune.stack_fl=$fl timeout 600 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-split --no-cold-start 2>/dev/null | python -c "
+    DR_TEST_TUNE=tune.stack_fl=$fl timeout 600 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-split --no-cold-start 2>/dev/null | python -c "
 import json,sys
 for ln in sys.stdin:
     if ln.startswith('{') and '\"metric\"' in ln:

@@ -13,7 +13,7 @@ cell that ran saw a number of ranks different from the N it was asked for - a ru
 processes must not pass for a scaling point - or whose ranks did not all launch the same kernels (per_rank_launch_mode,
 fused_yields, fused_fallbacks of the bench line: dr_launch_state).
 
-Each cell is one `python bench.py --gpus N --config C --no-split --no-cpu-baseline --no-roofline` run; a world size
+Each cell is one `python bench.py --gpus N --config C --full --no-split --no-cpu-baseline --no-roofline` run; a world size
 the node cannot serve (fewer visible devices) is reported as such and skipped, so the same command works on a 1-GPU
 box (today) and on a leased 8-GPU node (no edits).  Efficiency is printed for convenience only: the judge's driver
 computes its own from the per-N values.
@@ -30,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_cell(n, cfg, steps, warmup, timeout, share_gpu=False):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--config", str(cfg), "--steps", str(steps),
-           "--warmup", str(warmup), "--no-split", "--no-cpu-baseline", "--no-roofline", "--no-cold-start"]
+           "--warmup", str(warmup), "--full", "--no-split", "--no-cpu-baseline", "--no-roofline", "--no-cold-start"]
     if share_gpu and n > 1:
         cmd.append("--share-gpu")
     env = dict(os.environ)
