@@ -129,18 +129,14 @@ struct FusedTurn {
 
 // After a barrier time-out (device idle): re-arm the group counters, forget the published XCC tags, lower both flags.
 int clear_stack_timeout(dr_engine* e) {
-    HIPCHK(e, hipMemset(e->stack_bar, 0, (size_t)(12 * STACK_GROUPS) * sizeof(unsigned)));    // all three counter arrays
-    HIPCHK(e, hipMemset(e->stack_xid, 0xFF, 1024 * sizeof(unsigned)));
-    HIPCHK(e, hipMemset(e->stack_derr, 0, 16 * sizeof(unsigned)));
-    HIPCHK(e, hipMemset(e->win_ready, 0, STACK_GROUPS * sizeof(unsigned)));
+    HIPCHK(e, e->sync.clear());
     e->win_epoch = 0;
-    *e->stack_err_host = 0;
     return DR_OK;
 }
 
 int check_ready(dr_engine* e, int sampler, int B, int T) {
     if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
-    if (e->stack_err_host && *e->stack_err_host)
+    if (e->sync.err_host && *e->sync.err_host)
         return fail(e, DR_ETIMEOUT, "a group barrier of an earlier fused residual-stack launch timed out (the results since the "
                                     "last dr_finish are invalid): is another stream / engine computing on this device at the "
                                     "same time? call dr_finish (or dr_stack_status) to clear the condition and recompute - "
@@ -296,28 +292,12 @@ int dr_create(dr_engine** out, const dr_config* cfg) {
 
 void dr_destroy(dr_engine* e) {
     if (!e) return;
-    DeviceGuard guard(e->cfg.device);
+    const int dev = e->cfg.device;
+    DeviceGuard guard(dev);
     (void)hipDeviceSynchronize();
     forget_fused_slot(e);
-    if (e->gexec) (void)hipGraphExecDestroy(e->gexec);
-    if (e->graph) (void)hipGraphDestroy(e->graph);
-    if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
-    if (e->dbg_ticks) (void)hipFree(e->dbg_ticks);
-    if (e->d_counts) (void)hipFree(e->d_counts);
-    if (e->d_dyn) (void)hipFree(e->d_dyn);
-    if (e->stack_bar) (void)hipFree(e->stack_bar);
-    if (e->xsave) (void)hipFree(e->xsave);
-    if (e->stack_err_host) (void)hipHostFree((void*)e->stack_err_host);
-    if (e->stack_dbg) (void)hipFree(e->stack_dbg);
-    if (e->sk_cnt) (void)hipFree(e->sk_cnt);
-    if (e->d_tsel) (void)hipFree(e->d_tsel);
-    for (auto& p : e->prof_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (void* p : e->owned) (void)hipFree(p);
-    float* bufs[] = {e->d_coef, e->d_dtab, e->h, e->hd, e->hd3, e->g3, e->g, e->skip, e->tmp, e->x0buf, e->cond, e->cond_dummy,
-                     e->wav_pad, e->power, e->logmel, e->specP4, e->mm, e->sk_ws, e->xwork, e->cond_tr, e->xalt};
-    for (float* p : bufs) if (p) (void)hipFree(p);
-    if (g_engines[e->cfg.device].fetch_sub(1) == 1) release_stager(e->cfg.device);
-    delete e;
+    delete e;       // (~dr_engine and the members' destructors release everything it holds)
+    if (g_engines[dev].fetch_sub(1) == 1) release_stager(dev);
 }
 
 int dr_set_param(dr_engine* e, const char* name, const float* host_data, size_t numel) {
@@ -370,30 +350,21 @@ int dr_frontend(dr_engine* e, const float* d_wav, int B, int L, int T_roll, int 
     const int Lp = (L + 2 * pad + 3) & ~3;
     const int Cp = e->Cp, NM = e->NM, bp = e->bins_p;
     const int mel_planes = (NM + 3) / 4;
-    int rc;
-    {   // buffers below are reallocated only when a shape grows: synchronise just then (a previous call may still
-        // be reading them), not on every call
-        const size_t mm_need0 = (e->norm_framewise ? (size_t)B * TF * 2 : (size_t)B * 2) + minmax_scratch_floats(B);
-        const bool grow = (size_t)B * Lp > e->fe_cap_wav || (size_t)B * bp * TF > e->fe_cap_pow ||
-                          (size_t)B * mel_planes * 4 * TF > e->fe_cap_log || (size_t)B * mel_planes * 4 * T > e->fe_cap_spec ||
-                          mm_need0 > e->fe_cap_mm || (size_t)e->L * B * 2 * Cp * T > e->cond_cap;
-        if (grow) HIPCHK(e, hipDeviceSynchronize());
-    }
-    if ((size_t)B * Lp > e->fe_cap_wav) { if ((rc = dev_alloc(e, &e->wav_pad, (size_t)B * Lp))) return rc; e->fe_cap_wav = (size_t)B * Lp; }
-    if ((size_t)B * bp * TF > e->fe_cap_pow) { if ((rc = dev_alloc(e, &e->power, (size_t)B * bp * TF))) return rc; e->fe_cap_pow = (size_t)B * bp * TF; }
-    if ((size_t)B * mel_planes * 4 * TF > e->fe_cap_log) { if ((rc = dev_alloc(e, &e->logmel, (size_t)B * mel_planes * 4 * TF))) return rc; e->fe_cap_log = (size_t)B * mel_planes * 4 * TF; }
-    if ((size_t)B * mel_planes * 4 * T > e->fe_cap_spec) { if ((rc = dev_alloc(e, &e->specP4, (size_t)B * mel_planes * 4 * T))) return rc; e->fe_cap_spec = (size_t)B * mel_planes * 4 * T; }
     // (min, max) per clip / per frame, followed by the per-clip partials + ticket words of the multi-block min-max
     const size_t mm_vals = e->norm_framewise ? (size_t)B * TF * 2 : (size_t)B * 2;
-    const size_t mm_need = mm_vals + minmax_scratch_floats(B);
-    if (mm_need > e->fe_cap_mm) { if ((rc = dev_alloc(e, &e->mm, mm_need))) return rc; e->fe_cap_mm = mm_need; e->mm_scratch_off = mm_vals; }
-    else if (e->mm_scratch_off != mm_vals) {      // same buffer, other split: the ticket words must be zero where they now lie
-        HIPCHK(e, hipMemsetAsync(e->mm, 0, e->fe_cap_mm * sizeof(float), st));
-        e->mm_scratch_off = mm_vals;
-    }
-    const size_t cond_need = (size_t)e->L * B * 2 * Cp * T;
-    bool cond_moved = false;
-    if (cond_need > e->cond_cap) { if ((rc = dev_alloc(e, &e->cond, cond_need))) return rc; e->cond_cap = cond_need; cond_moved = true; }
+    const size_t mm_need = mm_vals + minmax_scratch_floats(B), cond_need = (size_t)e->L * B * 2 * Cp * T;
+    struct { DevBuf<float>& b; size_t n; } fe[] = {{e->wav_pad, (size_t)B * Lp}, {e->power, (size_t)B * bp * TF},
+        {e->logmel, (size_t)B * mel_planes * 4 * TF}, {e->specP4, (size_t)B * mel_planes * 4 * T}, {e->mm, mm_need}, {e->cond, cond_need}};
+    // the buffers grow (new zeroed blocks) only when a shape does: synchronise just then (a previous call may still be
+    // reading them), not on every call
+    bool fits = true;
+    for (auto& f : fe) fits = fits && f.b.fits(f.n);
+    if (!fits) HIPCHK(e, hipDeviceSynchronize());
+    const bool mm_moved = !e->mm.fits(mm_need), cond_moved = !e->cond.fits(cond_need);
+    for (auto& f : fe) HIPCHK(e, f.b.ensure(f.n, true));
+    if (!mm_moved && e->mm_scratch_off != mm_vals)      // same buffer, other split: the ticket words must be zero where they now lie
+        HIPCHK(e, hipMemsetAsync(e->mm, 0, e->mm.size() * sizeof(float), st));
+    e->mm_scratch_off = mm_vals;
     if (cond_moved || B != e->fe_B || T != e->fe_T) {
         // a captured chain bakes the conditioner pointers / strides: drop it when they change
         drop_graph(e);
@@ -463,16 +434,9 @@ int dr_forward_steps(dr_engine* e, const float* d_x, int B, int T, const int32_t
     for (int b = 0; b < B; ++b)
         if (host_t[b] < 0 || host_t[b] >= e->S) return fail(e, DR_EINVAL, "step %d of sample %d out of range", host_t[b], b);
     if ((rc = ensure_workspace(e, B, T))) return rc;
-    if ((size_t)B > e->tsel_cap) {
-        if (e->d_tsel) (void)hipFree(e->d_tsel);
-        e->d_tsel = nullptr;
-        void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, (size_t)B * sizeof(int)));
-        e->d_tsel = (int*)q;
-        e->tsel_cap = (size_t)B;
-    }
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(e, hipStreamSynchronize(st));       // the previous call may still be reading the step buffer
+    HIPCHK(e, e->d_tsel.ensure(B, false));
     HIPCHK(e, hipMemcpy(e->d_tsel, host_t, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
     FusedTurn turn(e, st);
     if (turn.rc) return turn.rc;
@@ -528,17 +492,9 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
             // row t of the injected noise is the z of step t; t == 0 draws none (task/diffusion.py:957-960)
             const float* z = d_noise ? d_noise + (size_t)t * per : nullptr;
             cs.next_t = t - 1;
+            cs.x_out = cur == e->xalt ? xbuf : e->xalt;      // (the previous step left the roll in the engine's buffer: back into xbuf)
             float* res = nullptr;
-            int r;
-            if (cur == e->xalt) {      // the previous step left the roll in the engine's buffer: this one writes back into xbuf
-                float* keep = e->xalt;
-                e->xalt = xbuf;
-                r = run_step(e, sampler, cur, z, B, T, t, w, seed, first_sample, st, &res, &cs);
-                e->xalt = keep;
-            } else {
-                r = run_step(e, sampler, cur, z, B, T, t, w, seed, first_sample, st, &res, &cs);
-            }
-            if (r) return r;
+            if (int r = run_step(e, sampler, cur, z, B, T, t, w, seed, first_sample, st, &res, &cs)) return r;
             cur = res;
         }
         if (cur != xbuf) HIPCHK(e, hipMemcpyAsync(xbuf, cur, per * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -595,7 +551,7 @@ int dr_finish(dr_engine* e, void* stream) {
     DeviceGuard guard(e->cfg.device);
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     if (e->unverified && e->fused_stream != (hipStream_t)stream) HIPCHK(e, hipStreamSynchronize(e->fused_stream));
-    if (!e->stack_err_host || !*e->stack_err_host) {
+    if (!e->sync.err_host || !*e->sync.err_host) {
         e->unverified = false;
         return DR_OK;
     }
@@ -630,11 +586,9 @@ int dr_sample_checked(dr_engine* e, int sampler, float* d_x, const float* d_nois
     // only a fused launch can time out: keep x_T so that the chain can be re-run (a yielded engine may re-arm in dr_sample)
     const bool may_fuse = e->fused.may_fuse();
     if (may_fuse) {
-        if (per > e->xsave_cap) {
+        if (!e->xsave.fits(per)) {
             HIPCHK(e, hipStreamSynchronize(st));
-            int rc = dev_alloc(e, &e->xsave, per, false);
-            if (rc) return rc;
-            e->xsave_cap = per;
+            HIPCHK(e, e->xsave.ensure(per, false));
         }
         HIPCHK(e, hipMemcpyAsync(e->xsave, d_x, per * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
@@ -659,7 +613,7 @@ int dr_sample_checked(dr_engine* e, int sampler, float* d_x, const float* d_nois
 }
 
 int dr_pending_timeout(dr_engine* e, void* stream) {
-    if (!e || !e->stack_err_host) return DR_OK;
+    if (!e || !e->sync.err_host) return DR_OK;
     if (e->unverified) {
         // the flag is final once the stream the fused launches ran on has drained - which need not be the stream the
         // consumer passes (a roll sampled on one stream, scored on another)
@@ -667,7 +621,7 @@ int dr_pending_timeout(dr_engine* e, void* stream) {
         HIPCHK(e, hipStreamSynchronize(e->fused_stream));
         if ((hipStream_t)stream != e->fused_stream) HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     }
-    if (*e->stack_err_host)
+    if (*e->sync.err_host)
         return fail(e, DR_ETIMEOUT, "a fused residual-stack launch issued on this engine timed out and has not been checked: the roll is "
                                     "invalid - call dr_finish (clears the condition, switches to per-phase launches) and recompute, or "
                                     "use dr_sample_checked");
@@ -702,12 +656,7 @@ int dr_frame_counts(dr_engine* e, const float* d_pred, const float* d_label, siz
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard guard(e->cfg.device);
     if (int rc = dr_pending_timeout(e, stream)) return rc;
-    if (!e->d_counts) {
-        void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, frame_counts_work_words() * sizeof(unsigned long long)));
-        HIPCHK(e, hipMemset(q, 0, frame_counts_work_words() * sizeof(unsigned long long)));      // (the ticket word starts at zero)
-        e->d_counts = (unsigned long long*)q;
-    }
+    HIPCHK(e, e->d_counts.ensure(frame_counts_work_words(), true));      // (the ticket word starts at zero)
     HIPCHK(e, launch_frame_counts(d_pred, d_label, threshold, (long)n, e->d_counts, st));
     unsigned long long h[3];
     HIPCHK(e, hipMemcpyAsync(h, e->d_counts, sizeof h, hipMemcpyDeviceToHost, st));

@@ -26,10 +26,10 @@ int dr_cold_times(dr_engine* e, double* out5) {
 
 int dr_stack_status(dr_engine* e, int32_t* timed_out, int64_t* launches, int64_t* ticks, int n_ticks) {
     if (!e) return DR_EINVAL;
-    if (!e->stack_bar) return fail(e, DR_ESTATE, "dr_commit has not been called");
+    if (!e->sync.mem) return fail(e, DR_ESTATE, "dr_commit has not been called");
     DeviceGuard guard(e->cfg.device);
     HIPCHK(e, hipDeviceSynchronize());
-    const unsigned flag = *e->stack_err_host;
+    const unsigned flag = *e->sync.err_host;
     if (timed_out) *timed_out = (int32_t)flag;
     if (launches) *launches = e->stack_launches;
     if (flag) {      // a barrier wait hit its spin bound: counters may be left armed - reset everything
@@ -113,12 +113,7 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     a.n_cond = n_cond;
     p4_out(a, e->g, P, T, Cp);
     if (e->prec) { a.Y = e->g3; a.y_bs = s3_bs; a.out_s3 = 1; }
-    if (!e->dbg_ticks) {
-        void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, 16 * sizeof(long long)));
-        HIPCHK(e, hipMemset(q, 0, 16 * sizeof(long long)));
-        e->dbg_ticks = (long long*)q;
-    }
+    HIPCHK(e, e->dbg_ticks.ensure(16, true));
     a.dbg = e->dbg_ticks;
     allow_splitk(e, a);
     HIPCHK(e, launch_tiled(a, EPI_GATE, pick_tile(plan_knobs(), Cp / 64, NB, T, e->K, w.dil, e->prec, EPI_GATE, true, e->opt_blocked >= 2), (hipStream_t)stream, e->prec));
@@ -148,12 +143,7 @@ int dr_bench_pointwise(dr_engine* e, int layer, int NB, int T, void* stream) {
         if (e->prec) { a.Y2 = e->hd3; a.y2_bs = act_bs + act_bs / 2; a.out_s3 = 2; }
         else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     }
-    if (!e->dbg_ticks) {
-        void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, 16 * sizeof(long long)));
-        HIPCHK(e, hipMemset(q, 0, 16 * sizeof(long long)));
-        e->dbg_ticks = (long long*)q;
-    }
+    HIPCHK(e, e->dbg_ticks.ensure(16, true));
     a.dbg = e->dbg_ticks;
     allow_splitk(e, a);
     HIPCHK(e, launch_tiled(a, EPI_RES_SKIP, pick_pointwise_tile(plan_knobs(), Cp / 64, NB, T, e->prec), (hipStream_t)stream, e->prec));
@@ -169,18 +159,15 @@ int dr_debug_stft_power(dr_engine* e, const float* d_wav, int B, int L, float* d
     const int N = e->cfg.n_fft, hop = e->cfg.hop_length, pad = N / 2;
     if (B <= 0 || L <= pad) return fail(e, DR_EINVAL, "bad front-end shape B=%d L=%d", B, L);
     const int TF = L / hop + 1, Lp = (L + 2 * pad + 3) & ~3, bp = e->bins_p;
-    float *wp = nullptr, *pw = nullptr;        // private buffers: the engine's front-end state is left alone
-    int rc;
-    if ((rc = dev_alloc(e, &wp, (size_t)B * Lp, false))) return rc;
-    if ((rc = dev_alloc(e, &pw, (size_t)B * bp * TF, false))) { (void)hipFree(wp); return rc; }
+    DevBuf<float> wp, pw;       // private buffers (the engine's front-end state is left alone), released after the stream sync
+    HIPCHK(e, wp.ensure((size_t)B * Lp, false));
+    HIPCHK(e, pw.ensure((size_t)B * bp * TF, false));
     hipError_t he = launch_reflect_pad(d_wav, wp, B, L, pad, st);
     if (he == hipSuccess) he = launch_stft_power(wp, e->fft_win, e->fft_tw, pw, B, Lp, TF, N, hop, bp, e->fft_norm, st);
     if (he == hipSuccess)
         he = hipMemcpy2DAsync(d_power_out, (size_t)e->n_bins * 4, pw, (size_t)bp * 4, (size_t)e->n_bins * 4, (size_t)B * TF,
                               hipMemcpyDeviceToDevice, st);
     if (he == hipSuccess) he = hipStreamSynchronize(st);
-    (void)hipFree(wp);
-    (void)hipFree(pw);
     if (he != hipSuccess) return fail(e, DR_EHIP, "dr_debug_stft_power: %s", hipGetErrorString(he));
     return DR_OK;
 }

@@ -18,11 +18,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/diffroll_amd_debug.h"      // (includes the boundary, diffroll_amd.h)
+#include "device_buffer.h"
 #include "fused_mode.h"
 #include "kernels.h"
 
@@ -58,6 +60,47 @@ struct GraphKey {
     }
 };
 
+// The synchronisation words of the persistent kernels (stack_kernel, tail kernel) in one device allocation, plus the
+// time-out flag in host-mapped memory: every later API call sees it without a synchronisation and fails loudly instead of
+// returning rolls computed from a broken hand-off.
+struct StackSync {
+    // layout of `mem`, in words: [bar][tail bar][tail pair bar] 4 * STACK_GROUPS each, {arrivals, departures, generation, -}
+    // per group (the first two zero between launches: re-armed in-kernel); [xid] 1024 (generation, XCC id) tags published
+    // by the blocks of the last launch, one per block; [derr] 16, the time-out flag in device memory (what the kernels poll /
+    // test at launch start); [ready] STACK_GROUPS, the tail kernel's per-window ready words (TailArgs::ready)
+    static constexpr size_t G4 = (size_t)4 * STACK_GROUPS, XID = 3 * G4, DERR = XID + 1024, READY = DERR + 16,
+                            WORDS = READY + STACK_GROUPS;
+    struct HostFree { void operator()(volatile unsigned* p) const { (void)hipHostFree((void*)p); } };
+    DevBuf<unsigned> mem;
+    std::unique_ptr<volatile unsigned, HostFree> err_host;
+    unsigned* err = nullptr;            // device address of *err_host
+    unsigned* bar() const { return mem; }
+    unsigned* tail_bar() const { return mem + G4; }
+    unsigned* tail_pbar() const { return mem + 2 * G4; }
+    unsigned* xid() const { return mem + XID; }
+    unsigned* derr() const { return mem + DERR; }
+    unsigned* ready() const { return mem + READY; }
+    // every word to its between-launches value, both flags lowered (also after a barrier time-out, device idle)
+    hipError_t clear() {
+        hipError_t st = hipMemset(mem, 0, WORDS * sizeof(unsigned));
+        if (st == hipSuccess) st = hipMemset(xid(), 0xFF, 1024 * sizeof(unsigned));      // no tag of a launch ever equals 0xFFFFFFFF
+        if (st == hipSuccess) *err_host = 0;
+        return st;
+    }
+    // (`mem` is left empty unless everything succeeded: the next commit tries again)
+    hipError_t init() {
+        void *hf = nullptr, *df = nullptr;
+        hipError_t st = hipHostMalloc(&hf, 64, hipHostMallocMapped);
+        if (st != hipSuccess) return st;
+        err_host.reset((volatile unsigned*)hf);
+        memset(hf, 0, 64);
+        if ((st = hipHostGetDevicePointer(&df, hf, 0)) != hipSuccess) return st;
+        err = (unsigned*)df;
+        if ((st = mem.ensure(WORDS, false)) == hipSuccess && (st = clear()) != hipSuccess) mem.reset();
+        return st;
+    }
+};
+
 }  // namespace drh
 
 struct dr_engine {
@@ -73,51 +116,48 @@ struct dr_engine {
     bool committed = false;
 
     // device constants
-    float* d_coef = nullptr;   // (DR_COEF_FAMILIES, S, 5)
-    float* d_dtab = nullptr;   // (S, L, Cp)   hoisted diffusion_projection(diffusion_embedding(t))
+    drh::DevBuf<float> d_coef;   // (DR_COEF_FAMILIES, S, 5)
+    drh::DevBuf<float> d_dtab;   // (S, L, Cp)   hoisted diffusion_projection(diffusion_embedding(t))
     std::vector<drh::LayerW> layers;
     float *in_w = nullptr, *in_b = nullptr, *skip_w = nullptr, *skip_b = nullptr, *outp_w = nullptr, *outp_b = nullptr;
     float *dft_w = nullptr, *mel_w = nullptr;
     float *fft_win = nullptr, *fft_tw = nullptr;     // FFT front-end: window (n_fft), roots of unity (n_fft complex)
     float fft_norm = 1.f;                            // the spectrum is divided by it (normalized=True)
     bool use_fft = false;
-    std::vector<void*> owned;   // every constant allocation, for dr_destroy
+    std::vector<drh::DevBuf<float>> consts;   // what layers, in_w, ... point into (replaced by the next commit)
 
     // activation workspace (sized for ws_NB samples x ws_T frames)
     int ws_NB = 0, ws_T = 0;
     // split-K workspace (partials) and ticket counters, see gemm_kernel (sizes SK_WS_FLOATS / SK_CNT_N: launch_plan.h)
-    float* sk_ws = nullptr;
-    unsigned* sk_cnt = nullptr;
-    float *h = nullptr, *hd = nullptr, *g = nullptr, *skip = nullptr, *tmp = nullptr, *x0buf = nullptr;
-    float* xwork = nullptr;                // the captured chain runs in place on this engine-owned roll buffer
-    float *hd3 = nullptr, *g3 = nullptr;   // split-bf16 (S3) versions of hd and g: 1.5x the fp32 size
+    drh::DevBuf<float> sk_ws;
+    drh::DevBuf<unsigned> sk_cnt;
+    drh::DevBuf<float> h, hd, g, skip, tmp, x0buf;
+    drh::DevBuf<float> xwork;              // the captured chain runs in place on this roll buffer (not the caller's)
+    drh::DevBuf<float> hd3, g3;            // split-bf16 (S3) versions of hd and g: 1.5x the fp32 size
     int prec = 0;                          // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3, 6 products)
     bool s3_ready = false;                 // the split-bf16 packings exist (built on first use: ensure_s3)
     double t_pack_s = 0.0, t_upload_s = 0.0, t_tables_s = 0.0, t_capture_s = 0.0;      // dr_cold_times
     int norm_framewise = 0;                // spectrogram normalisation: 0 imagewise, 1 framewise (norm_args[2])
     // conditioner tensors of the last dr_frontend: [L][fe_B][2Cp/4][fe_T][4]
     int fe_B = 0, fe_T = 0;
-    size_t cond_cap = 0;
-    float* cond = nullptr;
-    float* cond_dummy = nullptr;   // one sample of readable memory for generation (no dr_frontend): never used
+    drh::DevBuf<float> cond;
+    drh::DevBuf<float> cond_dummy;  // one sample of readable memory for generation (no dr_frontend): never used
     // condition='trainable_spec': per-layer conditioner of the learned unconditional spectrogram, [L][2Cp/4][T][4]
-    float* cond_tr = nullptr;
+    drh::DevBuf<float> cond_tr;
     int cond_tr_T = 0;
     // front-end workspace
-    size_t fe_cap_wav = 0, fe_cap_pow = 0, fe_cap_log = 0, fe_cap_spec = 0, fe_cap_mm = 0;
-    float *wav_pad = nullptr, *power = nullptr, *logmel = nullptr, *specP4 = nullptr, *mm = nullptr;
+    drh::DevBuf<float> wav_pad, power, logmel, specP4, mm;
 
     // graph cache
     drh::GraphKey gkey;
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
-    long long* dbg_ticks = nullptr;     // dr_bench_layer measurement hook
-    unsigned long long* d_counts = nullptr;   // dr_frame_counts: result words, ticket, per-block partials (update.hip)
+    drh::DevBuf<long long> dbg_ticks;   // dr_bench_layer measurement hook
+    drh::DevBuf<unsigned long long> d_counts;   // dr_frame_counts: result words, ticket, per-block partials (update.hip)
     size_t mm_scratch_off = 0;                // floats into `mm` where the multi-block min-max keeps its partials / tickets
     hipStream_t cap_stream = nullptr;   // capture happens here (the caller's stream may be the null stream)
-    dr::DynParams* d_dyn = nullptr;         // per-call scalars of the captured chain (seed, batch offset, guidance weight)
-    int* d_tsel = nullptr;              // per-sample steps of dr_forward_steps
-    size_t tsel_cap = 0;
+    drh::DevBuf<dr::DynParams> d_dyn;   // per-call scalars of the captured chain (seed, batch offset, guidance weight)
+    drh::DevBuf<int> d_tsel;            // per-sample steps of dr_forward_steps
     bool use_dyn = false;               // set while the chain is being captured: run_step points the update at d_dyn
 
     // fused residual stack (stack_kernel): one persistent launch for the residual layers when every block of the
@@ -128,20 +168,13 @@ struct dr_engine {
     int opt_stack_fault = 0;            // test hook (option "stack_fault_test")
     int opt_stack_warm = 0;             // idle waves of the fused kernel warm the L2 for the next phase (measured: +-0)
     int n_cus = 0;
-    unsigned* stack_bar = nullptr;      // [STACK_GROUPS][4] {arrivals, departures, generation, -}: the first two zero between launches
-    unsigned* stack_err = nullptr;      // device address of the time-out flag (host-mapped memory)
-    volatile unsigned* stack_err_host = nullptr;
-    unsigned* stack_derr = nullptr;     // the same flag in device memory (what the kernels poll / test at launch start)
-    unsigned* stack_xid = nullptr;      // [1024] (generation, XCC id) tags published by the blocks of the last launch
-    unsigned* tail_bar = nullptr;       // group / pair counters of the tail kernel (own arrays, same protocol)
-    unsigned* tail_pbar = nullptr;
+    drh::StackSync sync;                // group counters, XCC tags, time-out flags, window ready words
     int opt_tail = 1;                   // fused step: layer 0's shared conv inside the stack launch + the tail kernel
     int64_t tail_launches = 0;
     int opt_win_O = 0;                  // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
                                         // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
-    unsigned* win_ready = nullptr;      // [STACK_GROUPS] the tail kernel's per-window ready words (TailArgs::ready)
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
-    float* xalt = nullptr;              // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
+    drh::DevBuf<float> xalt;            // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
     int last_mode = 0;                  // DR_MODE_* of the most recently planned evaluation (dr_launch_state)
     unsigned tuning_epoch = 0;          // tuning_epoch() when the cached chain was captured
@@ -152,9 +185,8 @@ struct dr_engine {
     bool unverified = false;            // persistent launches have been issued since the last check of the time-out flag
     hipStream_t fused_stream = nullptr; // ... on this stream (the last one): what a check synchronises before it reads the flag
     int opt_blocked = 2;                // option "blocked_accumulation": 2 (default) = every fp32 flavour that has a blocked form, 1 = 128-frame blocks keep one chain per output (-0.5 % per chain, 2-3x the rounding error)
-    float* xsave = nullptr;             // dr_sample_checked: copy of x_T, so that a timed-out chain can be re-run
-    size_t xsave_cap = 0;
-    long long* stack_dbg = nullptr;     // phase tick marks of block 0 (dr_debug_stack_ticks)
+    drh::DevBuf<float> xsave;           // dr_sample_checked: copy of x_T, so that a timed-out chain can be re-run
+    drh::DevBuf<long long> stack_dbg;   // phase tick marks of block 0 (dr_debug_stack_ticks)
     int stack_dbg_on = 0;
     int64_t stack_launches = 0;         // fused-kernel launches issued (captured launches count once, at capture)
 
@@ -166,6 +198,14 @@ struct dr_engine {
     size_t prof_used = 0;
     int64_t prof_launches = 0;
     double prof_ms = 0.0;
+
+    // the handles that are not memory; runs before the members' destructors, so the graph goes before the buffers it uses
+    ~dr_engine() {
+        if (gexec) (void)hipGraphExecDestroy(gexec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (cap_stream) (void)hipStreamDestroy(cap_stream);
+        for (auto& p : prof_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    }
 };
 
 namespace drh {
@@ -235,7 +275,6 @@ int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab
 void set_kfd_root(const char* root);                                      // dr_debug_kfd_root
 
 // ---- pack.hip
-int dev_alloc(dr_engine* e, float** p, size_t floats, bool zero = true);
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);
 size_t expected_numel(const dr_engine* e, const std::string& name);
 int ensure_s3(dr_engine* e);            // the split-bf16 packings, built on first use
@@ -268,7 +307,11 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
                 hipStream_t st, bool zero_spec = false, const int* tsel = nullptr, TailPlan* tail = nullptr);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& zero_spec);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond);
-struct ChainState { bool inproj_ready = false; int next_t = -1; };
+struct ChainState {
+    bool inproj_ready = false;
+    int next_t = -1;
+    float* x_out = nullptr;    // where a fused step writes x_{t-1} (null: e->xalt)
+};
 int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int T, int t, float w, uint64_t seed,
              int first_sample, hipStream_t st, float** result = nullptr, ChainState* chain = nullptr);
 

@@ -160,27 +160,24 @@ void release_stager(int dev) {
     delete s;
 }
 
-int upload_bytes(dr_engine* e, const void* data, size_t bytes, float** out) {
-    void* p = nullptr;
-    HIPCHK(e, hipMalloc(&p, std::max<size_t>(bytes, 16)));
-    e->owned.push_back(p);
-    { StagerLock sl; HIPCHK(e, sl.s->copy(p, data, bytes)); }
-    *out = (float*)p;
+// into a buffer the caller owns (in flight until the stager is drained)
+int upload(dr_engine* e, const void* data, size_t bytes, DevBuf<float>& to) {
+    HIPCHK(e, to.ensure((bytes + 3) / 4, false));
+    StagerLock sl;
+    HIPCHK(e, sl.s->copy(to, data, bytes));
     return DR_OK;
 }
+int upload(dr_engine* e, const std::vector<float>& v, DevBuf<float>& to) { return upload(e, v.data(), v.size() * sizeof(float), to); }
 
+// a constant of the committed network: e->consts owns it until the next commit
+int upload_bytes(dr_engine* e, const void* data, size_t bytes, float** out) {
+    e->consts.emplace_back();
+    const int rc = upload(e, data, bytes, e->consts.back());
+    *out = e->consts.back();
+    return rc;
+}
 int upload(dr_engine* e, const std::vector<float>& v, float** out) {
     return upload_bytes(e, v.data(), v.size() * sizeof(float), out);
-}
-
-int dev_alloc(dr_engine* e, float** p, size_t floats, bool zero) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    void* q = nullptr;
-    HIPCHK(e, hipMalloc(&q, std::max<size_t>(floats, 4) * sizeof(float)));
-    if (zero) HIPCHK(e, hipMemset(q, 0, std::max<size_t>(floats, 4) * sizeof(float)));
-    *p = (float*)q;
-    return DR_OK;
 }
 
 const std::vector<float>* find_param(dr_engine* e, const std::string& name) {
@@ -274,8 +271,7 @@ int commit(dr_engine* e, hipStream_t st) {
         for (auto& n : names)
             if (!find_param(e, n)) return fail(e, DR_ESTATE, "parameter '%s' was never set", n.c_str());
     }
-    for (void* p : e->owned) (void)hipFree(p);
-    e->owned.clear();
+    e->consts.clear();
     e->layers.assign(L, LayerW{});
     e->cond_tr_T = 0;       // rebuilt from the new conditioner weights / trainable_parameters at the next use
     e->ws_T = 0;            // (ensure_workspace is where that happens)
@@ -430,43 +426,17 @@ int commit(dr_engine* e, hipStream_t st) {
     }
     { StagerLock sl; HIPCHK(e, sl.s->drain()); }       // every staged constant has landed
     // ---- tables ------------------------------------------------------------------------------
-    if ((rc = dev_alloc(e, &e->d_coef, (size_t)DR_COEF_FAMILIES * S * 5))) return rc;
+    e->d_coef.reset(); e->d_dtab.reset(); e->sk_ws.reset();      // (new blocks at every commit)
+    HIPCHK(e, e->d_coef.ensure((size_t)DR_COEF_FAMILIES * S * 5, true));
     HIPCHK(e, hipMemcpy(e->d_coef, e->h_coef.data(), (size_t)DR_COEF_FAMILIES * S * 5 * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(e, &e->d_dtab, (size_t)S * L * Cp))) return rc;
-    if ((rc = dev_alloc(e, &e->sk_ws, SK_WS_FLOATS, false))) return rc;
-    if (!e->sk_cnt) {       // ticket counters: zero between launches (the kernels re-arm them)
-        void* q = nullptr;
-        HIPCHK(e, hipMalloc(&q, SK_CNT_N * sizeof(unsigned)));
-        HIPCHK(e, hipMemset(q, 0, SK_CNT_N * sizeof(unsigned)));
-        e->sk_cnt = (unsigned*)q;
-    }
-    if (!e->d_dyn) { void* q = nullptr; HIPCHK(e, hipMalloc(&q, sizeof(DynParams))); e->d_dyn = (DynParams*)q; }
-    if (!e->stack_bar) {     // group counters of the fused residual stack: zero between launches (re-armed in-kernel)
-        void* q = nullptr;
-        const size_t G4 = (size_t)4 * STACK_GROUPS;
-        const size_t nb = (3 * G4 + 1024 + 16 + STACK_GROUPS) * sizeof(unsigned);
-        HIPCHK(e, hipMalloc(&q, nb));
-        HIPCHK(e, hipMemset(q, 0, nb));
-        e->stack_bar = (unsigned*)q;                                     // [bar][tail bar][tail pair bar][xid][derr][ready]
-        e->tail_bar = e->stack_bar + G4;
-        e->tail_pbar = e->stack_bar + 2 * G4;
-        e->stack_xid = e->stack_bar + 3 * G4;                            // one word per block (<= 1024 CUs)
-        e->stack_derr = e->stack_xid + 1024;
-        e->win_ready = e->stack_derr + 16;                               // [STACK_GROUPS] ready words of long-form windows
-        HIPCHK(e, hipMemset(e->stack_xid, 0xFF, 1024 * sizeof(unsigned)));   // no tag of a launch ever equals 0xFFFFFFFF
-        // the "a barrier wait gave up" flag lives in host-visible memory: every later API call sees it without a
-        // synchronisation and fails loudly instead of returning rolls computed from a broken hand-off
-        void* hf = nullptr;
-        HIPCHK(e, hipHostMalloc(&hf, 64, hipHostMallocMapped));
-        memset(hf, 0, 64);
-        e->stack_err_host = (volatile unsigned*)hf;
-        void* df = nullptr;
-        HIPCHK(e, hipHostGetDevicePointer(&df, hf, 0));
-        e->stack_err = (unsigned*)df;
-        void* d = nullptr;
-        HIPCHK(e, hipMalloc(&d, 128 * sizeof(long long)));
-        HIPCHK(e, hipMemset(d, 0, 128 * sizeof(long long)));
-        e->stack_dbg = (long long*)d;
+    HIPCHK(e, e->d_dtab.ensure((size_t)S * L * Cp, true));
+    HIPCHK(e, e->sk_ws.ensure(SK_WS_FLOATS, false));
+    // ticket counters, group counters of the persistent kernels: zero between launches (the kernels re-arm them)
+    HIPCHK(e, e->sk_cnt.ensure(SK_CNT_N, true));
+    HIPCHK(e, e->d_dyn.ensure(1, false));
+    if (!e->sync.mem) {
+        HIPCHK(e, e->sync.init());
+        HIPCHK(e, e->stack_dbg.ensure(128, true));
         hipDeviceProp_t prop;
         HIPCHK(e, hipGetDeviceProperties(&prop, e->cfg.device));
         e->n_cus = prop.multiProcessorCount;
@@ -477,17 +447,19 @@ int commit(dr_engine* e, hipStream_t st) {
         std::vector<float> embP4((size_t)32 * S * 4);
         for (int t = 0; t < S; ++t)
             for (int c = 0; c < 128; ++c) embP4[((size_t)(c / 4) * S + t) * 4 + (c % 4)] = e->h_emb[(size_t)t * 128 + c];
-        float *d_emb = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;
-        float *a1 = nullptr, *a2 = nullptr;
-        if ((rc = upload(e, embP4, &d_emb))) return rc;
+        // commit-only uploads and activations: released once the stream has drained (the end of this block)
+        DevBuf<float> d_emb, w1, b1, w2, b2, a1, a2;
+        std::vector<DevBuf<float>> wdb(2 * (size_t)L);
+        if ((rc = upload(e, embP4, d_emb))) return rc;
         const auto& W1 = P("diffusion_embedding.projection1.weight");
         const auto& W2 = P("diffusion_embedding.projection2.weight");
         auto p1 = pack_weights(4, 4, 1, [&](int r, int ch, int) { return W1[(size_t)r * 128 + ch]; });
         auto p2 = pack_weights(4, 16, 1, [&](int r, int ch, int) { return W2[(size_t)r * 512 + ch]; });
-        if ((rc = upload(e, p1, &w1)) || (rc = upload(e, P("diffusion_embedding.projection1.bias"), &b1)) ||
-            (rc = upload(e, p2, &w2)) || (rc = upload(e, P("diffusion_embedding.projection2.bias"), &b2)))
+        if ((rc = upload(e, p1, w1)) || (rc = upload(e, P("diffusion_embedding.projection1.bias"), b1)) ||
+            (rc = upload(e, p2, w2)) || (rc = upload(e, P("diffusion_embedding.projection2.bias"), b2)))
             return rc;
-        if ((rc = dev_alloc(e, &a1, (size_t)512 * S)) || (rc = dev_alloc(e, &a2, (size_t)512 * S))) return rc;
+        HIPCHK(e, a1.ensure((size_t)512 * S, true));
+        HIPCHK(e, a2.ensure((size_t)512 * S, true));
         { StagerLock sl; HIPCHK(e, sl.s->drain()); }
         GemmArgs g1 = p4_gemm(w1, b1, 4, d_emb, 32, 1, S);
         p4_out(g1, a1, 128, S, 512);
@@ -503,16 +475,15 @@ int commit(dr_engine* e, hipStream_t st) {
             auto pd = pack_weights(MT, 16, 1, [&](int r, int ch, int) { return r < C ? Wd[(size_t)r * 512 + ch] : 0.f; });
             std::vector<float> bb(MT * 128, 0.f);
             for (int r = 0; r < C; ++r) bb[r] = Bd[r];
-            float *wd = nullptr, *bd = nullptr;
-            if ((rc = upload(e, pd, &wd)) || (rc = upload(e, bb, &bd))) return rc;
+            DevBuf<float>& wd = wdb[2 * l];
+            DevBuf<float>& bd = wdb[2 * l + 1];
+            if ((rc = upload(e, pd, wd)) || (rc = upload(e, bb, bd))) return rc;
             { StagerLock sl; HIPCHK(e, sl.s->drain()); }
             GemmArgs g3 = p4_gemm(wd, bd, MT, a2, 128, 1, S);
             g3.Y = e->d_dtab + (size_t)l * Cp; g3.y_bs = 0; g3.y_ps = 4; g3.y_fs = (long)L * Cp; g3.y_rows = Cp;
             HIPCHK(e, launch_gemm(g3, EPI_PLAIN, 2, st));
         }
         HIPCHK(e, hipStreamSynchronize(st));
-        (void)hipFree(a1);
-        (void)hipFree(a2);
     }
     e->committed = true;
     e->fe_B = e->fe_T = 0;

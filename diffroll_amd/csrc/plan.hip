@@ -50,11 +50,11 @@ int build_trainable_cond(dr_engine* e, int T) {
     std::vector<float> sp((size_t)mel_planes * T * 4, 0.f);      // P4 image of P[:, :T]
     for (int m = 0; m < NM; ++m)
         for (int t = 0; t < T; ++t) sp[((size_t)(m >> 2) * T + t) * 4 + (m & 3)] = (*P)[(size_t)m * 641 + t];
-    float* d_sp = nullptr;
-    int rc;
-    if ((rc = dev_alloc(e, &d_sp, sp.size(), false))) return rc;
+    DevBuf<float> d_sp;         // (released after the device synchronisation below)
+    HIPCHK(e, d_sp.ensure(sp.size(), false));
     HIPCHK(e, hipMemcpy(d_sp, sp.data(), sp.size() * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(e, &e->cond_tr, (size_t)e->L * 2 * Cp * T))) { (void)hipFree(d_sp); return rc; }
+    e->cond_tr.reset();
+    HIPCHK(e, e->cond_tr.ensure((size_t)e->L * 2 * Cp * T, true));
     for (int l = 0; l < e->L; ++l) {
         const LayerW& w = e->layers[l];
         GemmArgs a = p4_gemm(w.cond_w, w.cond_b, Cp / 64, d_sp, mel_planes, 1, T);
@@ -62,7 +62,6 @@ int build_trainable_cond(dr_engine* e, int T) {
         HIPCHK(e, launch_gemm(a, EPI_PLAIN, 2, nullptr));
     }
     HIPCHK(e, hipDeviceSynchronize());
-    (void)hipFree(d_sp);
     e->cond_tr_T = T;
     return DR_OK;
 }
@@ -71,19 +70,13 @@ int ensure_workspace(dr_engine* e, int NB, int T) {
     if (NB <= e->ws_NB && T == e->ws_T) return DR_OK;
     drop_graph(e);       // a captured chain holds the addresses of the buffers that are about to be replaced
     const int nb = std::max(NB, e->ws_T == T ? e->ws_NB : 0);
-    const size_t act = (size_t)nb * e->Cp * T;
-    int rc;
-    if ((rc = dev_alloc(e, &e->h, act))) return rc;
-    if ((rc = dev_alloc(e, &e->hd, act))) return rc;
-    if ((rc = dev_alloc(e, &e->hd3, act + act / 2))) return rc;
-    if ((rc = dev_alloc(e, &e->g3, act + act / 2))) return rc;
-    if ((rc = dev_alloc(e, &e->g, act))) return rc;
-    if ((rc = dev_alloc(e, &e->skip, act))) return rc;
-    if ((rc = dev_alloc(e, &e->tmp, act))) return rc;
-    if ((rc = dev_alloc(e, &e->x0buf, (size_t)nb * T * 88))) return rc;
-    if ((rc = dev_alloc(e, &e->xwork, (size_t)nb * T * 88))) return rc;
-    if ((rc = dev_alloc(e, &e->xalt, (size_t)nb * T * 88))) return rc;
-    if ((rc = dev_alloc(e, &e->cond_dummy, (size_t)2 * e->Cp * T))) return rc;
+    const size_t act = (size_t)nb * e->Cp * T, s3 = act + act / 2, roll = (size_t)nb * T * 88;
+    struct { DevBuf<float>& b; size_t n; } ws[] = {{e->h, act}, {e->hd, act}, {e->hd3, s3}, {e->g3, s3}, {e->g, act},
+        {e->skip, act}, {e->tmp, act}, {e->x0buf, roll}, {e->xwork, roll}, {e->xalt, roll}, {e->cond_dummy, (size_t)2 * e->Cp * T}};
+    for (auto& w : ws) {        // new zeroed blocks of exactly this size (a smaller T shrinks them)
+        w.b.reset();
+        HIPCHK(e, w.b.ensure(w.n, true));
+    }
     e->ws_NB = nb;
     e->ws_T = T;
     return build_trainable_cond(e, T);
@@ -163,7 +156,7 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
         sa.warm = e->opt_stack_warm;
         sa.fault = e->opt_stack_fault;
         sa.fold128 = e->opt_blocked >= 2;
-        sa.bar = e->stack_bar; sa.err = e->stack_err; sa.derr = e->stack_derr; sa.xid = e->stack_xid;
+        sa.bar = e->sync.bar(); sa.err = e->sync.err; sa.derr = e->sync.derr(); sa.xid = e->sync.xid();
         sa.dbg = e->stack_dbg_on ? e->stack_dbg : nullptr;
         for (int l = 0; l < L; ++l) {
             const LayerW& w = e->layers[l];
@@ -304,11 +297,11 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
             ta.g = e->g;
         }
     }
-    ta.bar = e->tail_bar; ta.pbar = e->tail_pbar; ta.err = e->stack_err; ta.derr = e->stack_derr;
+    ta.bar = e->sync.tail_bar(); ta.pbar = e->sync.tail_pbar(); ta.err = e->sync.err; ta.derr = e->sync.derr();
     // long-form windows: every window of the chain is in this one resident launch (the plan only takes the tail when
     // stack_chunks == 1), so the neighbour wait of T3 always has its neighbours running.  Epoch: position in the chain
     // for a captured one (added to DynParams::epoch at run time), else the next value of the engine's count.
-    ta.ready = e->win_ready;
+    ta.ready = e->sync.ready();
     ta.epoch = v.e->use_dyn ? (unsigned)(e->S - v.t) : ++e->win_epoch;
     // ticks 112..119 of dr_stack_status: the last tail launch of a chain that has a next step (all its parts run)
     ta.dbg = (e->stack_dbg_on && tail->next_t >= 0) ? e->stack_dbg + 112 : nullptr;
@@ -387,8 +380,8 @@ int sampler_shape(int sampler, int B, int& NB, int& n_cond) {
     return sampler_shape(sampler, B, NB, n_cond, fam, z);
 }
 
-// One reverse step.  The result is written in place on x - or, when the fused step ran (tail kernel), into e->xalt:
-// *result tells which; chain (optional) carries "h / hd of this step are already there" from step to step.
+// One reverse step.  The result is written in place on x - or, when the fused step ran (tail kernel), into e->xalt (or
+// chain->x_out): *result tells which; chain (optional) carries "h / hd of this step are already there" from step to step.
 int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int T, int t, float w, uint64_t seed,
              int first_sample, hipStream_t st, float** result, ChainState* chain) {
     int NB, n_cond, family;
@@ -405,17 +398,18 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     u.seed = seed; u.first_sample = first_sample;
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
     u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
+    float* const xalt = chain && chain->x_out ? chain->x_out : e->xalt;
     TailPlan plan;
-    plan.u = u; plan.x_out = e->xalt; plan.u_B = B;
+    plan.u = u; plan.x_out = xalt; plan.u_B = B;
     plan.next_t = chain ? chain->next_t : -1;
     plan.skip_inproj = chain && chain->inproj_ready;
     // (x and the tail kernel's output buffer must differ: a caller that hands us xalt itself gets the unfused tail)
-    TailPlan* offer = (result && x != e->xalt) ? &plan : nullptr;
+    TailPlan* offer = (result && x != xalt) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
     if (offer && plan.done) {
-        *result = e->xalt;
+        *result = xalt;
         if (chain) chain->inproj_ready = plan.inproj_done;
         return DR_OK;
     }
