@@ -5,6 +5,7 @@
         checkpoint_path=weights/Pretrain_MAESTRO-retrain_MAESTRO-k=9.ckpt
     python sampling.py task=inpainting task.inpainting_t=[500,650] dataset=Custom ...
     python sampling.py task=transcription dataset=Custom dataset.args.max_segment_samples=null task.window_overlap=160 ...
+    python sampling.py task=transcription task.sampling.steps=50 ...      # 50 respaced steps instead of 200
     torchrun --nproc-per-node 8 sampling.py task=generation gpus=8 dataset.num_samples=128 dataloader.batch_size=128
 
 Hydra is not a dependency: the same ``group=name`` / ``dotted.key=value`` override syntax is parsed here over
@@ -100,6 +101,12 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
         for part in parts[:-1]:
             node = node.setdefault(part, {})
         node[parts[-1]] = _parse_value(v)
+    # task.sampling.steps=N: the chain on N respaced steps (option "sampling_steps"); absent / null / 0 = every step
+    steps, S = cfg["task"]["sampling"].get("steps"), cfg["task"].get("timesteps")
+    if steps is not None and (isinstance(steps, bool) or not isinstance(steps, int) or not isinstance(S, int)
+                              or not (steps == 0 or 2 <= steps <= S)):
+        raise SystemExit(f"task.sampling.steps must be an integer in [2, task.timesteps = {S}] (or 0 / null: every "
+                         f"step), got {steps!r}")
     if is_long_form(cfg):
         sampler = cfg["task"]["sampling"]["type"]
         if sampler == "inpainting_ddpm_x0":
@@ -112,6 +119,11 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
 
 
 DEFAULT_WINDOW_OVERLAP = 160
+
+
+def steps_label(cfg: Dict[str, Any]) -> str:
+    S, n = int(cfg["task"]["timesteps"]), cfg["task"]["sampling"].get("steps")
+    return f"{n} of {S} steps" if n and n != S else f"{S} steps"
 
 
 def is_long_form(cfg: Dict[str, Any]) -> bool:
@@ -232,7 +244,7 @@ def main(argv: List[str] = None, default_task: str = "generation") -> None:
         rolls = transcribe_long_form(cfg, model, rank, world)
         frames = sum(int(np.load(p, mmap_mode="r").shape[2]) for p in rolls)
         dt = time.perf_counter() - t0
-        print(f"rank {rank}: {len(rolls)} recording(s) whole, {frames} frames, {cfg['task']['timesteps']} steps, sampler "
+        print(f"rank {rank}: {len(rolls)} recording(s) whole, {frames} frames, {steps_label(cfg)}, sampler "
               f"{cfg['task']['sampling']['type']}: {dt:.2f} s -> {cfg['output_dir']}/")
         if dist is not None:
             dist.barrier()
@@ -278,7 +290,7 @@ def main(argv: List[str] = None, default_task: str = "generation") -> None:
     torch.cuda.synchronize()
     if rank == 0:
         dt = time.perf_counter() - t0
-        print(f"{cfg['task']['name']}: {S} clips x {T} frames, {cfg['task']['timesteps']} steps, sampler "
+        print(f"{cfg['task']['name']}: {S} clips x {T} frames, {steps_label(cfg)}, sampler "
               f"{cfg['task']['sampling']['type']}, {world} GPU(s): {dt:.2f} s ({S * T / dt:.1f} frames/s incl. load "
               f"and capture) -> {cfg['output_dir']}/")
         # the split a one-shot run pays once (sampling.py:53-73 is one process per batch of clips): see bench.py cold_start

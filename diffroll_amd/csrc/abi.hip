@@ -3,6 +3,7 @@
 #include "engine_state.h"
 #include "tenants.h"
 
+#include <algorithm>
 #include <condition_variable>
 #include <mutex>
 
@@ -159,6 +160,50 @@ int check_windows(dr_engine* e, int T) {
     return DR_OK;
 }
 
+// option "sampling_steps" (include/diffroll_amd.h): n visited steps t_i = round-half-up(i (S - 1) / (n - 1)), i = n-1 .. 0,
+// in integer arithmetic.  A visited t whose successor t' is t - 1 (or t == 0) keeps the committed row; every other one
+// gets a row derived in double precision from the committed fp32 sqrt_acp / sqrt_1m_acp of t and t' (family 0, columns
+// 2 and 3) and rounded to fp32 once, in the column order update_quad.h reads.  Rebuilt by dr_commit and by the option.
+int build_respaced(dr_engine* e) {
+    const int S = e->S, n = e->opt_steps;
+    e->rs_steps.clear();
+    e->d_coef_rs.reset();
+    if (n == 0 || n == S) return DR_OK;       // the full chain: committed rows
+    std::vector<int> steps(n);
+    for (int i = n - 1; i >= 0; --i)
+        steps[n - 1 - i] = (int)((2LL * i * (S - 1) + (n - 1)) / (2LL * (n - 1)));
+    std::vector<float> tab(e->h_coef);
+    const float* h = e->h_coef.data();        // family 0 row t: [.., .., sqrt_acp[t], sqrt_1m_acp[t], ..]
+    for (int i = 0; i + 1 < n; ++i) {
+        const int t = steps[i], tp = steps[i + 1];
+        if (tp == t - 1) continue;
+        const double A = h[(size_t)t * 5 + 2], Sm = h[(size_t)t * 5 + 3], Ap = h[(size_t)tp * 5 + 2], Smp = h[(size_t)tp * 5 + 3];
+        const double r2 = (A / Ap) * (A / Ap);                       // alpha of the stride: acp[t] / acp[t']
+        const double sigma = (Smp / Sm) * std::sqrt(1.0 - r2);
+        const double dir = std::sqrt(std::max(0.0, 1.0 - Ap * Ap - sigma * sigma));   // (>= 0 exactly; clamps rounding)
+        const double beta = 1.0 - r2;
+        const double rows[DR_COEF_FAMILIES][5] = {
+            {Ap, dir, A, Sm, sigma},                                  // ddpm_x0 family
+            {Ap, std::sqrt(1.0 - Ap * Ap), A, Sm, 0.0},               // ddim_x0 family
+            {Ap / A, beta, Sm, std::sqrt(beta * Smp * Smp / (Sm * Sm)), 0.0},   // ddpm (epsilon)
+            {Ap, Smp, A, Sm, 0.0},                                    // ddim (epsilon)
+            {Ap, dir, A, Sm, sigma}};                                 // ddim2ddpm (epsilon)
+        for (int f = 0; f < DR_COEF_FAMILIES; ++f)
+            for (int c = 0; c < 5; ++c) tab[((size_t)f * S + t) * 5 + c] = (float)rows[f][c];
+    }
+    HIPCHK(e, e->d_coef_rs.ensure(tab.size(), false));
+    HIPCHK(e, hipMemcpy(e->d_coef_rs, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    e->rs_steps = std::move(steps);
+    return DR_OK;
+}
+
+// the chain's steps: position i (0 = the first step, S - 1 or t_{n-1}) -> diffusion step t; -1 past the end
+int chain_steps(const dr_engine* e) { return e->rs_steps.empty() ? e->S : (int)e->rs_steps.size(); }
+int chain_step(const dr_engine* e, int i) {
+    if (i >= chain_steps(e)) return -1;
+    return e->rs_steps.empty() ? e->S - 1 - i : e->rs_steps[i];
+}
+
 // dr_set_option (lab = false: the product's options) / dr_debug_set_option (lab = true: the A/B and test knobs too)
 int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (!e || !name) return fail(e, DR_EINVAL, "null argument");
@@ -181,6 +226,16 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
         if (e->opt_win_O != value) drop();
         e->opt_win_O = value;
+        return DR_OK;
+    }
+    if (n == "sampling_steps") {
+        if (value != 0 && (value < 2 || value > e->S))
+            return fail(e, DR_EINVAL, "sampling_steps is 0 (off) or in [2, timesteps = %d], got %d", e->S, value);
+        if (e->opt_steps == value) return DR_OK;
+        drop();
+        e->opt_steps = value;
+        if (!e->committed) return DR_OK;      // (dr_commit builds it)
+        if (int rc = build_respaced(e)) { e->opt_steps = 0; return rc; }
         return DR_OK;
     }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
@@ -450,6 +505,8 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     int rc = check_ready(e, sampler, B, T);
     if (rc) return rc;
     if (t < 0 || t >= e->S) return fail(e, DR_EINVAL, "step %d out of range", t);
+    if (!e->rs_steps.empty() && std::find(e->rs_steps.begin(), e->rs_steps.end(), t) == e->rs_steps.end())
+        return fail(e, DR_EINVAL, "step %d is not visited by the respaced chain (option sampling_steps = %d)", t, e->opt_steps);
     if ((rc = check_windows(e, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
@@ -488,10 +545,12 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         // place), and each tail also computes the next step's input projection
         ChainState cs;
         float* cur = xbuf;
-        for (int t = e->S - 1; t >= 0; --t) {
+        // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows)
+        for (int i = 0, n = chain_steps(e); i < n; ++i) {
+            const int t = chain_step(e, i);
             // row t of the injected noise is the z of step t; t == 0 draws none (task/diffusion.py:957-960)
             const float* z = d_noise ? d_noise + (size_t)t * per : nullptr;
-            cs.next_t = t - 1;
+            cs.next_t = chain_step(e, i + 1);
             cs.x_out = cur == e->xalt ? xbuf : e->xalt;      // (the previous step left the roll in the engine's buffer: back into xbuf)
             float* res = nullptr;
             if (int r = run_step(e, sampler, cur, z, B, T, t, w, seed, first_sample, st, &res, &cs)) return r;
@@ -536,7 +595,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     Range range("dr_sample: launch the chain graph");
     // the graph owns no caller address: x_T is copied in, the finished roll copied out (0.7 MB each way)
     HIPCHK(e, hipMemcpyAsync(e->xwork, d_x, per * sizeof(float), hipMemcpyDeviceToDevice, st));
-    // (the chain's tail launches publish epochs win_epoch + 1 .. win_epoch + S: TailArgs::ready)
+    // (the chain's tail launches publish epochs in win_epoch + 1 .. win_epoch + S, one per step: TailArgs::ready)
     HIPCHK(e, launch_set_dyn(e->d_dyn, seed, first_sample, w, (float)(1.0 + (double)w), e->win_epoch, st));
     e->win_epoch += (unsigned)e->S;
     HIPCHK(e, hipGraphLaunch(e->gexec, st));

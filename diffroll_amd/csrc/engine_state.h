@@ -173,6 +173,10 @@ struct dr_engine {
     int64_t tail_launches = 0;
     int opt_win_O = 0;                  // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
                                         // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
+    int opt_steps = 0;                  // option "sampling_steps": n of a respaced chain; 0 (and S) = every step
+    std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
+    drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor
+                                        // is not t - 1 replaced by the respaced row (build_respaced); empty when rs_steps is
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
     drh::DevBuf<float> xalt;            // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
@@ -273,6 +277,7 @@ struct Range {
 int clear_stack_timeout(dr_engine* e);
 int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab: the names of dr_debug_set_option too
 void set_kfd_root(const char* root);                                      // dr_debug_kfd_root
+int build_respaced(dr_engine* e);       // option "sampling_steps": rs_steps and d_coef_rs from opt_steps and h_coef
 
 // ---- pack.hip
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);

@@ -302,6 +302,8 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
     // stack_chunks == 1), so the neighbour wait of T3 always has its neighbours running.  Epoch: position in the chain
     // for a captured one (added to DynParams::epoch at run time), else the next value of the engine's count.
     ta.ready = e->sync.ready();
+    // S - t grows strictly along any chain, a respaced one (option "sampling_steps") included - its visited t decrease
+    // strictly - and stays in [1, S], so the words keep growing across chains (dr_sample moves the base on by S per chain).
     ta.epoch = v.e->use_dyn ? (unsigned)(e->S - v.t) : ++e->win_epoch;
     // ticks 112..119 of dr_stack_status: the last tail launch of a chain that has a next step (all its parts run)
     ta.dbg = (e->stack_dbg_on && tail->next_t >= 0) ? e->stack_dbg + 112 : nullptr;
@@ -392,7 +394,10 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     if (w == 0.f && NB == 2 * B) { NB = B; n_cond = B; }
     UpdateArgs u{};
     u.x = x; u.x0c = e->x0buf; u.x0u = (NB == 2 * B) ? e->x0buf + (size_t)B * T * 88 : nullptr;
-    u.noise = noise; u.coef = e->d_coef + ((size_t)family * e->S + t) * 5; u.t = t; u.mode = family;
+    // row t of the family's table: the committed one, or under option "sampling_steps" the row for t's successor in the
+    // respaced chain (build_respaced; unvisited rows are never read)
+    const float* coef = e->rs_steps.empty() ? e->d_coef : e->d_coef_rs;
+    u.noise = noise; u.coef = coef + ((size_t)family * e->S + t) * 5; u.t = t; u.mode = family;
     u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     u.seed = seed; u.first_sample = first_sample;

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _cabi
-from .schedule import build_embedding, make_schedule, sampler_coef_tables
+from .schedule import build_embedding, make_schedule, respaced_steps, sampler_coef_tables
 
 
 class EngineError(RuntimeError):
@@ -327,15 +327,23 @@ class Engine:
         return n.value, ms.value, fl.value, buf.value.decode()
 
     def set_option(self, name: str, value: int):
-        """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation' (dr_set_option,
-        include/diffroll_amd.h); any other name - 'tune.*', 'fused_stack_xcd', 'stack_ticks', ... - is a lab knob
-        (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown names and values out of range raise ValueError."""
+        """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
+        'window_overlap', 'sampling_steps' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
+        names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
         self._check(fn(self.h, name.encode(), int(value)))
         if name == "window_overlap":
             self.window_overlap = int(value)
+        if name == "sampling_steps":
+            self.sampling_steps = int(value)
 
     window_overlap = 0      # the last value set for option 'window_overlap' (0 = off, the library's default)
+    sampling_steps = 0      # the last value set for option 'sampling_steps' (0 = every step, the library's default)
+
+    def visited_steps(self):
+        """The diffusion steps sample() visits, in chain order (option 'sampling_steps'; all of them when it is off)."""
+        return respaced_steps(self.timesteps, self.sampling_steps)
 
     def stack_status(self, n_ticks: int = 0):
         """(timed_out, ticks): synchronises; timed_out != 0 means a fused-kernel barrier hit its spin bound.

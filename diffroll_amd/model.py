@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .engine import Engine
+from .schedule import check_sampling_steps, respaced_steps
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
@@ -124,6 +125,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         spec_args = _attr(dict(spec_args))
         if sampling.type not in _SAMPLERS:
             raise AttributeError(sampling.type)                               # getattr at task/diffusion.py:255
+        # an extension: sampling.steps = n runs the chain on n respaced steps (option "sampling_steps"); absent / None in
+        # the reference's configs = every step
+        check_sampling_steps(sampling.get("steps"), timesteps)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -230,7 +234,21 @@ class ClassifierFreeDiffRoll(nn.Module):
         if getattr(self._engine, "_blocked", None) != want:
             self._engine.set_option("blocked_accumulation", want)
             self._engine._blocked = want
+        steps = self.sampling_steps()
+        if self._engine.sampling_steps != steps:          # (a change drops the engine's captured chain)
+            self._engine.set_option("sampling_steps", steps)
         return self._engine
+
+    def sampling_steps(self) -> int:
+        """n of hparams.sampling.steps (0: every step), or 0 while one of the reference's single-step methods runs."""
+        if self.__dict__.get("_stride1"):
+            return 0
+        hp = self.__dict__["hparams"]
+        return check_sampling_steps(hp.sampling.get("steps"), hp.timesteps)
+
+    def visited_steps(self):
+        """The diffusion steps sample() visits, in chain order (timesteps-1 .. 0, or hparams.sampling.steps of them)."""
+        return respaced_steps(int(self.hparams.timesteps), self.sampling_steps())
 
     # schedule vectors, exposed like the reference's attributes (task/diffusion.py:239-256)
     def __getattr__(self, name):
@@ -352,7 +370,18 @@ class ClassifierFreeDiffRoll(nn.Module):
             return out
 
     # ------------------------------------------------------------------ samplers (one step)
-    def _one_step(self, sampler: str, x, waveform, t_index: int, noise=None):
+    def _one_step(self, sampler: str, x, waveform, t_index: int, noise=None, respaced=False):
+        """One dr_step.  The reference's single-step methods keep their stride-1 meaning (t -> t - 1) whatever
+        hparams.sampling.steps says (the option is off while they run: under a respaced config that costs the engine its
+        captured chain); respaced=True (sample_trajectory) takes the respaced chain's step."""
+        prev = self.__dict__.get("_stride1", False)
+        self.__dict__["_stride1"] = not respaced
+        try:
+            return self._one_step_as_set(sampler, x, waveform, t_index, noise)
+        finally:
+            self.__dict__["_stride1"] = prev
+
+    def _one_step_as_set(self, sampler: str, x, waveform, t_index: int, noise=None):
         eng = self.engine
         B, _, T, _ = x.shape
         spec = None
@@ -439,9 +468,10 @@ class ClassifierFreeDiffRoll(nn.Module):
     @torch.no_grad()
     def sample(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0,
                use_graph: bool = True, check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The reverse chain t = timesteps-1 .. 0 (task/diffusion.py:528-534) on the device with no
-        host round trip.  x_T (B,1,T,88); noise: None (on-device Philox keyed by seed and global
-        sample index) or (timesteps, B, 1, T, 88) injected z's (row t is used at step t >= 1).
+        """The reverse chain t = timesteps-1 .. 0 (task/diffusion.py:528-534) - or, with hparams.sampling.steps = n,
+        the n respaced steps of visited_steps() - on the device with no host round trip.  x_T (B,1,T,88); noise: None
+        (on-device Philox keyed by seed, global sample index and step) or (timesteps, B, 1, T, 88) injected z's (row t
+        is used at step t >= 1, also in a respaced chain).
         Returns (roll (B,1,T',88), spec (B,n_mels,T')).
         check=True (default): the call returns with the FINISHED, verified roll, as task/diffusion.py:528-538 does
         (synchronous; a fused-kernel time-out caused by another tenant of the device is healed by re-running the chain
@@ -527,24 +557,23 @@ class ClassifierFreeDiffRoll(nn.Module):
         return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
 
     def sample_trajectory(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0):
-        """The same chain, keeping every intermediate roll on the device: returns (trajectory (timesteps, B, 1,
-        T', 88) with row i = x after step t = timesteps-1-i, spec).  This is what the reference's sampling()
-        collects as `noise_list` - on the host, with one D2H copy per step (task/diffusion.py:779-788) - for its
-        animation; here it is an opt-in eager loop over dr_step (one launch sequence per step, no graph), and the
-        last row equals sample()'s result bit for bit."""
+        """The same chain, keeping every intermediate roll on the device: returns (trajectory (n, B, 1, T', 88) with
+        row i = x after the i-th visited step - n = timesteps (t = timesteps-1-i), or hparams.sampling.steps - and spec).
+        This is what the reference's sampling() collects as `noise_list` - on the host, with one D2H copy per step
+        (task/diffusion.py:779-788) - for its animation; here it is an opt-in eager loop over dr_step (one launch sequence
+        per step, no graph), and the last row equals sample()'s result bit for bit."""
         eng = self.engine
         sampler = self.hparams.sampling.type
-        S = int(self.hparams.timesteps)
         B = x_T.shape[0]
         x = x_T
         rows = []
         spec = None
-        for t in range(S - 1, -1, -1):
+        for t in self.visited_steps():
             z = None if noise is None else noise[t]
             if z is None and t > 0:       # Philox keyed by (seed, global sample, step): same draws as sample()
                 xx, spec = self._step_philox(sampler, x, waveform, t, seed, first_sample)
             else:
-                xx, spec = self._one_step(sampler, x, waveform, t, z if t > 0 else torch.zeros_like(x))
+                xx, spec = self._one_step(sampler, x, waveform, t, z if t > 0 else torch.zeros_like(x), respaced=True)
             rows.append(xx)
             x = xx
         return torch.stack(rows, 0), spec

@@ -8,7 +8,7 @@ engine through dr_set_tables().
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, List
 
 import torch
 import torch.nn.functional as F
@@ -92,6 +92,27 @@ def build_embedding(max_steps: int) -> torch.Tensor:
     dims = torch.arange(64).unsqueeze(0)
     table = steps * 10.0 ** (dims * 4.0 / 63.0)
     return torch.cat([torch.sin(table), torch.cos(table)], dim=1)
+
+
+def check_sampling_steps(n, timesteps: int) -> int:
+    """Option "sampling_steps" (include/diffroll_amd.h): None / 0 = every step, else 2 <= n <= timesteps.  Returns n
+    (0 for None); anything else raises ValueError."""
+    if n is None:
+        return 0
+    if isinstance(n, bool) or not isinstance(n, int) or (n != 0 and not 2 <= n <= int(timesteps)):
+        raise ValueError(f"sampling steps must be 0 / None (every step) or an integer in [2, timesteps = {timesteps}], "
+                         f"got {n!r}")
+    return n
+
+
+def respaced_steps(timesteps: int, n: int) -> List[int]:
+    """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
+    integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""
+    S = int(timesteps)
+    n = check_sampling_steps(n, S)
+    if n in (0, S):
+        return list(range(S - 1, -1, -1))
+    return [(2 * i * (S - 1) + (n - 1)) // (2 * (n - 1)) for i in range(n - 1, -1, -1)]
 
 
 def sampler_coef_tables(sch: Dict[str, torch.Tensor]) -> torch.Tensor:

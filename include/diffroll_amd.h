@@ -192,7 +192,8 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
             float w, uint64_t seed, int first_sample, void* stream);
 
 /*
- * The whole reverse chain t = timesteps-1 .. 0, in place on d_x, no host synchronisation.
+ * The whole reverse chain t = timesteps-1 .. 0 (or the visited steps of option "sampling_steps"), in place on d_x, no
+ * host synchronisation.
  * d_noise: (timesteps, B, T, 88) injected noise (row t used at step t >= 1) or NULL for Philox.
  * use_graph != 0: the chain is captured once into a hipGraph and replayed; the graph is cached per
  * (sampler, B, T, d_noise): the chain runs on an engine-owned copy of d_x, and w, seed and first_sample are
@@ -347,6 +348,24 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          bit: the stitched roll is a plain gather from the canvas.  O > T / 2 -> DR_EINVAL at the call
  *                          (at most two windows share a frame).  dr_forward / dr_forward_steps are unaffected; 0 = off
  *                          (every clip on its own, bit-identical to an engine that never set it).
+ *   "sampling_steps"   [0] n, 2 <= n < timesteps (S): a RESPACED reverse chain of n network steps instead of S.  Visited
+ *                          steps t_i = (2 i (S - 1) + (n - 1)) / (2 (n - 1)) in integer arithmetic (linspace rounded half
+ *                          up), i = n-1 .. 0: strictly decreasing from S - 1 to 0; t' = the next visited step.  The row of
+ *                          step t: the committed row t unchanged when t == 0 or t' == t - 1; otherwise one derived in double
+ *                          precision from the committed fp32 A = sqrt_acp[t], Ap = sqrt_acp[t'], Sm = sqrt_1m_acp[t], Smp =
+ *                          sqrt_1m_acp[t'] (columns 2 and 3 of DR_COEF_DDPM_X0) and rounded to fp32 once - with
+ *                          sigma = (Smp / Sm) sqrt(1 - (A / Ap)^2) and beta' = 1 - (A / Ap)^2:
+ *                            DR_COEF_DDPM_X0, DR_COEF_DDIM2DDPM_EPS  [Ap, sqrt(max(0, 1 - Ap^2 - sigma^2)), A, Sm, sigma]
+ *                            DR_COEF_DDIM_X0                         [Ap, sqrt(1 - Ap^2), A, Sm, 0]
+ *                            DR_COEF_DDPM_EPS                        [Ap / A, beta', Sm, sqrt(beta' Smp^2 / Sm^2), 0]
+ *                            DR_COEF_DDIM_EPS                        [Ap, Smp, A, Sm, 0]
+ *                          (the stride-1 rows of the same formulas, mathematically).  Noise stays keyed by the real t: Philox
+ *                          by (seed, sample, t), injected noise keeps its (S, B, T, 88) shape and row t is used at visited
+ *                          step t - a respaced chain draws exactly the z's the full chain draws at those steps.  Applies to
+ *                          dr_sample / dr_sample_checked (whose re-run uses the same steps) and dr_step (a t that is not
+ *                          visited -> DR_EINVAL); dr_forward, dr_forward_steps, dr_q_sample, dr_extract_x0 are unaffected.
+ *                          Combines with "window_overlap", both precisions and sharding.  0 or S = the full chain, bit for
+ *                          bit; any other value -> DR_EINVAL.
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
