@@ -11,6 +11,7 @@ namespace dr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define DR_DEVINL __device__ __forceinline__
 
@@ -102,9 +103,28 @@ hipError_t init_stack_kernels();
 hipError_t init_tail_kernels();
 hipError_t init_frontend_kernels();
 
-struct A8 { float4 v[8]; };                          // A fragments of one K step: [group g][row tile mi]
-struct A12 { uint4 v[12]; };                         // split-bf16 A fragments of one K step: [(g*3 + piece)*2 + mi]
+struct AF4 { float4 v[4]; };                         // fp32 A fragments of one K step (32 channels): one per 8-channel group
+struct AF6 { uint4 v[6]; };                          // split-bf16 A fragments of one K step: [g16 * 3 + piece]
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// allow the whole 160 KiB of dynamic LDS for every kernel given; stops at the first error
+template <class... K>
+static hipError_t allow_max_lds(K*... kernels) {
+    hipError_t e = hipSuccess;
+    (void)(((e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) == hipSuccess) && ...);
+    return e;
+}
+
+DR_DEVINL void f4arr(const float4 v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; }
+// 16-byte buffer load (resource in SGPRs, per-lane byte offset, scalar byte offset): an operand fragment as float4 / uint4
+DR_DEVINL float4 buffer_load_f4(const __amdgpu_buffer_rsrc_t rsrc, const int voff, const int soff) {
+    const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+    return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
+}
+DR_DEVINL uint4 buffer_load_u4(const __amdgpu_buffer_rsrc_t rsrc, const int voff, const int soff) {
+    const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+    return make_uint4(u.x, u.y, u.z, u.w);
+}
 
 // ---------------------------------------------------------------------------------------------
 // "S3" split precision: an fp32 value x is carried as three bf16 pieces x = p0 + p1 + p2 (each the

@@ -300,7 +300,7 @@ hipError_t launch_normalize(const float* logmel, const float* mm, float* specP4,
 
 hipError_t init_frontend_kernels() {
     // the FFT front-end holds two n_fft/2-point complex buffers: n_fft * 8 bytes (128 KiB at its largest size, 16384)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_power_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return allow_max_lds(&stft_power_kernel);
 }
 
 }  // namespace dr

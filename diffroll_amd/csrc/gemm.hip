@@ -51,46 +51,45 @@ hipError_t reset_bounds() {
     return reset_bounds_tail();
 }
 
+// Block -> (M tile, frame tile, K split) of a per-phase GEMM launch.
+// blockIdx.x % MT = M tile: with MT == 8 each XCD (block b runs on XCD b % 8) streams exactly
+// one 128-row weight panel, which then stays resident in that XCD's private L2.
+// xcd_n != 0 (X-heavy 1x1 GEMMs: small weights, big activations): the 8 M tiles of one frame tile
+// run on the SAME XCD instead, so the X tile is fetched from HBM once per XCD and hits L2 for the
+// other M tiles, while the (small) weight matrix is L2-resident in every XCD.
+// Split-K (ksplit > 1, gemm_kernel's under-filled launches only: few samples / narrow GEMMs): ksplit blocks share
+// one output tile, each contracts a contiguous range of the K chunks; see the reduction in gemm_body.
+struct BlockTile { int mt, nt, ks; };
+DR_DEVINL BlockTile block_tile(const GemmArgs& a, const int ksplit) {
+    BlockTile o;
+    if (a.xcd_n) {
+        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+        o.mt = idx % a.MT;
+        const int rest = idx / a.MT;
+        o.ks = rest % ksplit;
+        o.nt = (rest / ksplit) * 8 + xcd;
+    } else {
+        o.mt = blockIdx.x % a.MT;
+        const int rest = blockIdx.x / a.MT;
+        o.ks = rest % ksplit;
+        o.nt = rest / ksplit;
+    }
+    return o;
+}
+
 template <int NI, int KS, int EPI, int PREC, int FOLDP = (NI == 1)>
 __global__ __launch_bounds__(512) void gemm_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // blockIdx.x % MT = M tile: with MT == 8 each XCD (block b runs on XCD b % 8) streams exactly
-    // one 128-row weight panel, which then stays resident in that XCD's private L2.
-    // xcd_n != 0 (X-heavy 1x1 GEMMs: small weights, big activations): the 8 M tiles of one frame tile
-    // run on the SAME XCD instead, so the X tile is fetched from HBM once per XCD and hits L2 for the
-    // other M tiles, while the (small) weight matrix is L2-resident in every XCD.
-    // Split-K (ksplit > 1, under-filled launches only: few samples / narrow GEMMs): ksplit blocks share
-    // one output tile, each contracts a contiguous range of the K chunks; see the reduction in gemm_body.
-    int mt, nt, ks;
-    if (a.xcd_n) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        mt = idx % a.MT;
-        const int rest = idx / a.MT;
-        ks = rest % a.ksplit;
-        nt = (rest / a.ksplit) * 8 + xcd;
-    } else {
-        mt = blockIdx.x % a.MT;
-        const int rest = blockIdx.x / a.MT;
-        ks = rest % a.ksplit;
-        nt = rest / a.ksplit;
-    }
-    gemm_body<NI, KS, EPI, PREC, 0, FOLDP>(a, smem, mt, nt, ks);
+    const BlockTile bt = block_tile(a, a.ksplit);
+    gemm_body<NI, KS, EPI, PREC, 0, FOLDP>(a, smem, bt.mt, bt.nt, bt.ks);
 }
 
 template <int NW>
 __global__ __launch_bounds__(256) void pw_kernel(const GemmArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int mt, nt;
-    if (a.xcd_n) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        mt = idx % a.MT;
-        nt = (idx / a.MT) * 8 + xcd;
-    } else {
-        mt = blockIdx.x % a.MT;
-        nt = blockIdx.x / a.MT;
-    }
-    mt += a.mt0;    // launches over a sub-range of the M tiles (the last layer only needs its skip rows)
-    pw_body<NW, 0, 0>(a, mt, nt, wave);
+    const BlockTile bt = block_tile(a, 1);
+    // + mt0: launches over a sub-range of the M tiles (the last layer only needs its skip rows)
+    pw_body<NW, 0, 0>(a, bt.mt + a.mt0, bt.nt, wave);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -118,7 +117,6 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
     const int NS = a.kchunks, NSW = NS >> 2;                   // slabs (32 channels) in all / per wave
     const int s0 = wave * NSW;
 
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.Wp + (long)mt * NS * 4096), 0, (unsigned)NS * 16384u, 0x00020000);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
@@ -128,25 +126,15 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
     int xvo[NW];
 #pragma unroll
     for (int ni = 0; ni < NW; ++ni) xvo[ni] = hi * xps + min(t0 + ni * 32 + r, a.T - 1) * 16;
-    auto asf4 = [](const u32x4 u) { return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)); };
-    struct AF { float4 v[4]; };
     struct BF { float4 v[4][NW]; };
-    auto load_a = [&](int slab) -> AF {
-        AF o;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, 140, slab, NS);
-            o.v[g] = asf4(__builtin_amdgcn_raw_buffer_load_b128(wr, wvo, slab * 16384 + g * 4096, 0));
-        }
-        return o;
-    };
+    auto load_a = [&](int slab) { return load_a4(wr, wvo, slab, NS, 140); };
     auto load_b = [&](int slab) -> BF {
         BF o;
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int ni = 0; ni < NW; ++ni)
-                o.v[g][ni] = asf4(__builtin_amdgcn_raw_buffer_load_b128(xr, xvo[ni], (slab * 8 + g * 2) * xps, 0));
+                o.v[g][ni] = buffer_load_f4(xr, xvo[ni], (slab * 8 + g * 2) * xps);
         return o;
     };
     // the epilogue operands of THIS wave's quad (q = wave): requested first, their latency hides behind the K loop
@@ -168,9 +156,9 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
     for (int ni = 0; ni < NW; ++ni)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[ni][e] = 0.f;
-    AF aA = load_a(s0), aB;
+    AF4 aA = load_a(s0), aB;
     BF bA = load_b(s0), bB;
-    auto mma = [&](const AF& af, const BF& bf) {
+    auto mma = [&](const AF4& af, const BF& bf) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
 #pragma unroll
@@ -200,14 +188,11 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
         for (int q = 0; q < 4; ++q)
             part[wave][ni][q][lane] = make_float4(acc[ni][4 * q], acc[ni][4 * q + 1], acc[ni][4 * q + 2], acc[ni][4 * q + 3]);
     __syncthreads();
-    auto f4arr = [](const float4 v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; };
-    float bb[4], dd[4];
-    f4arr(ebias, bb); f4arr(ed2, dd);
 #pragma unroll
     for (int ni = 0; ni < NW; ++ni) {
         const int t = t0 + ni * 32 + r;
         if (t >= a.T) continue;
-        float v[4], pv[4], o[4], u[4];
+        float v[4], o[4], u[4];
         f4arr(part[0][ni][wave][lane], v);
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
@@ -215,20 +200,19 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += u[e];
         }
-        f4arr(eop[ni], pv);
-        if (res_rows) {          // h = (h + (acc + b)) / sqrt(2) in place, hd = h + d_{l+1}   (model/diffwave.py:151, :139)
+        if (res_rows) {          // h in place, hd = h + d_{l+1}
             float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = div_sqrt2(pv[e] + (v[e] + bb[e]));
+            residual_quad(v, ebias, eop[ni], o);
             *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-            if (a.Y2) {
+            if (a.Y2) {          // (fp32 only: launch_pointwise_ksplit)
+                float o2[4];
+                hd_quad(o, ed2, o2);
                 float* dst2 = a.Y2 + (long)b * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                *reinterpret_cast<float4*>(dst2) = make_float4(o[0] + dd[0], o[1] + dd[1], o[2] + dd[2], o[3] + dd[3]);
+                *reinterpret_cast<float4*>(dst2) = make_float4(o2[0], o2[1], o2[2], o2[3]);
             }
-        } else {                 // skip (+)= acc + b   (model/diffwave.py:680)
+        } else {
             float* dst = a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = a.skip_init ? v[e] + bb[e] : (v[e] + bb[e]) + pv[e];
+            skip_quad(v, ebias, eop[ni], a.skip_init, o);
             *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
         }
     }
@@ -254,7 +238,10 @@ hipError_t launch_pointwise_ksplit(const GemmArgs& a, int NW, hipStream_t s) {
 // every XCD streams its share of X once and ALL panels - once if the whole weight matrix fits its L2, else once per
 // round of concurrently resident frame tiles.  (Until round 3 the rule was "xbytes > wbytes", which picked mapping 1
 // for 5-round launches of big convs - 640-frame generation batches - and paid 13.9x the algorithmic traffic.)
-static int pick_xcd_mapping(int MT, int NT, double wbytes, double xbytes) {
+static int pick_xcd_mapping(const GemmArgs& a, int NT, int BN) {
+    // weights: MT*128 rows x 32*kchunks*taps floats; activations: NT frame tiles of BN frames x 32*kchunks floats
+    const int MT = a.MT;
+    const double wbytes = 4.0 * 128.0 * a.MT * 32.0 * a.kchunks * a.taps, xbytes = 4.0 * (double)NT * BN * 32.0 * a.kchunks;
     if (MT <= 1 || NT % 8 != 0) return 0;
     if (tuning().xcd_n >= 0) return tuning().xcd_n;      // A/B experiments
     if (!tuning().xcd_model) return xbytes > wbytes ? 1 : 0;
@@ -273,8 +260,7 @@ static hipError_t launch_pw_t(const GemmArgs& a, hipStream_t s) {
     const int BN = 32 * NW;
     const int NT = a.NB * ((a.T + BN - 1) / BN);
     GemmArgs b = a;
-    const double wbytes = 4.0 * 128.0 * a.MT * 32.0 * a.kchunks, xbytes = 4.0 * (double)NT * BN * 32.0 * a.kchunks;
-    b.xcd_n = pick_xcd_mapping(a.MT, NT, wbytes, xbytes);
+    b.xcd_n = pick_xcd_mapping(a, NT, BN);      // (a.taps == 1: launch_pointwise)
     DR_CHECK_EXTENTS(b, EPI_RES_SKIP, 0, "pw_kernel");
     hipLaunchKernelGGL((pw_kernel<NW>), dim3((unsigned)(a.MT * NT)), dim3(256), 0, s, b);
     return hipGetLastError();
@@ -294,16 +280,8 @@ hipError_t launch_pointwise(const GemmArgs& a, int NW, hipStream_t s) {
 template <int NJ, int KS, int EPI>
 __global__ __launch_bounds__(512) void gemm16_kernel(const GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int mt, nt;
-    if (a.xcd_n) {
-        const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        mt = idx % a.MT;
-        nt = (idx / a.MT) * 8 + xcd;
-    } else {
-        mt = blockIdx.x % a.MT;
-        nt = blockIdx.x / a.MT;
-    }
-    gemm16_body<NJ, KS, EPI, 0>(a, smem, mt, nt);
+    const BlockTile bt = block_tile(a, 1);
+    gemm16_body<NJ, KS, EPI>(a, smem, bt.mt, bt.nt);
 }
 
 template <int NJ, int KS, int EPI>
@@ -314,8 +292,7 @@ static hipError_t launch_gemm16_t(const GemmArgs& a, hipStream_t s) {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int NT = a.NB * ((a.T + BN - 1) / BN);
     GemmArgs b = a;
-    const double wbytes = 4.0 * 128.0 * a.MT * 32.0 * a.kchunks * a.taps, xbytes = 4.0 * (double)NT * BN * 32.0 * a.kchunks;
-    b.xcd_n = pick_xcd_mapping(a.MT, NT, wbytes, xbytes);
+    b.xcd_n = pick_xcd_mapping(a, NT, BN);
     b.lds_bytes = (int)lds;
     DR_CHECK_EXTENTS(b, EPI, 0, "gemm16_kernel");
     hipLaunchKernelGGL((gemm16_kernel<NJ, KS, EPI>), dim3((unsigned)(a.MT * NT)), dim3(512), lds, s, b);
@@ -335,15 +312,8 @@ hipError_t launch_gemm16(const GemmArgs& a, int epi, int NJ, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 static hipError_t init_gemm16() {
-    hipError_t e;
-#define DR_INIT16(NJ, KS, EPI)                                                                           \
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm16_kernel<NJ, KS, EPI>),            \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) \
-        return e;
-    DR_INIT16(3, 1, EPI_GATE) DR_INIT16(5, 1, EPI_GATE)
-    DR_INIT16(3, 2, EPI_RES_SKIP) DR_INIT16(5, 2, EPI_RES_SKIP)
-#undef DR_INIT16
-    return hipSuccess;
+    return allow_max_lds(&gemm16_kernel<3, 1, EPI_GATE>, &gemm16_kernel<5, 1, EPI_GATE>,
+                         &gemm16_kernel<3, 2, EPI_RES_SKIP>, &gemm16_kernel<5, 2, EPI_RES_SKIP>);
 }
 
 template <int NI, int KS, int EPI, int PREC>
@@ -362,9 +332,7 @@ static hipError_t launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     if (a.ws && a.ws_cnt) b.ksplit = plan_ksplit(plan_knobs(), (long)a.MT * NT, a.kchunks / KS, a.kchunks, a.taps, NI, PREC, a.ws_floats, a.ws_cnt_n).ks;
     b.lds_bytes = (int)lds;
     const dim3 grid((unsigned)(a.MT * NT * b.ksplit));
-    // weights: MT*128 rows x 32*kchunks*taps floats; activations: NT*BN frames x 32*kchunks floats
-    const double wbytes = 4.0 * 128.0 * a.MT * 32.0 * a.kchunks * a.taps, xbytes = 4.0 * (double)NT * BN * 32.0 * a.kchunks;
-    b.xcd_n = pick_xcd_mapping(a.MT, NT, wbytes, xbytes);
+    b.xcd_n = pick_xcd_mapping(a, NT, BN);
     DR_CHECK_EXTENTS(b, EPI, PREC, "gemm_kernel");
     // the 128-frame gated conv exists with and without blocked accumulation (GemmArgs::fold128)
     if constexpr (NI == 2 && KS == 1 && EPI == EPI_GATE) {
@@ -388,21 +356,11 @@ static hipError_t launch_gemm_t(const GemmArgs& a, hipStream_t s) {
     }
 }
 
-template <int NI, int KS, int EPI, int PREC>
-static hipError_t init_gemm_t() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<NI, KS, EPI, PREC>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
 template <int NI, int KS>
 static hipError_t init_gemm_ni() {
-    hipError_t e;
-    if ((e = init_gemm_t<NI, KS, EPI_PLAIN, 0>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<NI, KS, EPI_RELU, 0>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<NI, KS, EPI_SILU, 0>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<NI, KS, EPI_GATE, 0>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<NI, KS, EPI_RES_SKIP, 0>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<NI, KS, EPI_POWER, 0>()) != hipSuccess) return e;
-    return init_gemm_t<NI, KS, EPI_LOG, 0>();
+    return allow_max_lds(&gemm_kernel<NI, KS, EPI_PLAIN, 0>, &gemm_kernel<NI, KS, EPI_RELU, 0>, &gemm_kernel<NI, KS, EPI_SILU, 0>,
+                         &gemm_kernel<NI, KS, EPI_GATE, 0>, &gemm_kernel<NI, KS, EPI_RES_SKIP, 0>, &gemm_kernel<NI, KS, EPI_POWER, 0>,
+                         &gemm_kernel<NI, KS, EPI_LOG, 0>);
 }
 // allow > 64 KiB of dynamic LDS for every instantiation; call once per process before any launch
 // (and never inside a stream capture)
@@ -415,15 +373,11 @@ hipError_t init_kernels() {
     if ((e = init_gemm_ni<1, 4>()) != hipSuccess) return e;
     if ((e = init_gemm_ni<2, 4>()) != hipSuccess) return e;
     // split-bf16 instantiations: dilated conv (KS = 1) and 1x1 (NI = 1: KS = 4)
-    if ((e = init_gemm_t<1, 1, EPI_GATE, 1>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<2, 1, EPI_GATE, 1>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<1, 4, EPI_RES_SKIP, 1>()) != hipSuccess) return e;
-    if ((e = init_gemm_t<1, 1, EPI_RES_SKIP, 1>()) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<2, 1, EPI_GATE, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<1, 1, EPI_GATE, 0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<2, 1, EPI_GATE, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<5, 1, EPI_GATE, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<3, 1, EPI_GATE, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = allow_max_lds(&gemm_kernel<1, 1, EPI_GATE, 1>, &gemm_kernel<2, 1, EPI_GATE, 1>, &gemm_kernel<1, 4, EPI_RES_SKIP, 1>,
+                           &gemm_kernel<1, 1, EPI_RES_SKIP, 1>)) != hipSuccess) return e;
+    // the explicit FOLDP flavours of the gated conv, and the 96 / 160-frame blocks
+    if ((e = allow_max_lds(&gemm_kernel<2, 1, EPI_GATE, 0, 1>, &gemm_kernel<1, 1, EPI_GATE, 0, 0>, &gemm_kernel<2, 1, EPI_GATE, 1, 1>,
+                           &gemm_kernel<5, 1, EPI_GATE, 0, 1>, &gemm_kernel<3, 1, EPI_GATE, 0, 1>)) != hipSuccess) return e;
     if ((e = init_frontend_kernels()) != hipSuccess) return e;
     if ((e = init_update_kernels()) != hipSuccess) return e;
     if ((e = init_tail_kernels()) != hipSuccess) return e;

@@ -2,10 +2,170 @@
 // 32x32x2 fp32 / 32x32x16 split-bf16 MFMA), pw_body (1x1, both operands straight from L2) and gemm16_body (16x16x4 MFMA,
 // 96 / 160-frame blocks).  Included by gemm.hip (one launch per phase), stack.hip and tail.hip (persistent kernels): the
 // same device code everywhere, which is what makes the fused kernels bit-identical to the per-phase launches.
+// What the bodies have in common is written once, in front of them: the epilogue arithmetic on register quads
+// (residual_quad, skip_quad, gate_quad, hd_quad / store_y2 - pwk_kernel uses them too), the A-fragment loader (load_a4) and the
+// producer waves of the two LDS-staged bodies (producer, with dma_tile for the read-modify-write tile - also used by
+// stack_kernel for its resident tile).  Where a result goes stays with the body that computed it.
 #pragma once
 #include "device_common.h"
 
 namespace dr {
+
+// ---------------------------------------------------------------------------------------------
+// Epilogue arithmetic on one C/D register quad (4 consecutive packed rows of one frame = one float4 of the P4 layout).
+// ---------------------------------------------------------------------------------------------
+// h = (h + (acc + b)) / sqrt(2)   (model/diffwave.py:151)
+DR_DEVINL void residual_quad(const float (&v)[4], const float4 bias, const float4 prev, float (&o)[4]) {
+    float bb[4], pv[4];
+    f4arr(bias, bb); f4arr(prev, pv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = div_sqrt2(pv[e] + (v[e] + bb[e]));
+}
+// skip (+)= acc + b   (model/diffwave.py:680); the first layer starts the sum
+DR_DEVINL void skip_quad(const float (&v)[4], const float4 bias, const float4 prev, const bool skip_init, float (&o)[4]) {
+    float bb[4], pv[4];
+    f4arr(bias, bb); f4arr(prev, pv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = skip_init ? v[e] + bb[e] : (v[e] + bb[e]) + pv[e];
+}
+// y = conv + b_conv + (Wc spec + bc), gate = first half, filter = second   [model/diffwave.py:143-147]: v0 / v1 = the
+// gate / filter rows of the same 4 channels; samples without a conditioner (has_c = false) carry the constant
+// unconditional one inside their bias
+DR_DEVINL void gate_quad(const float (&v0)[4], const float (&v1)[4], const float4 bias0, const float4 bias1,
+                         const float4 cond0, const float4 cond1, const bool has_c, float (&o)[4]) {
+    float b0[4], b1[4], c0[4], c1[4];
+    f4arr(bias0, b0); f4arr(bias1, b1);
+    f4arr(cond0, c0); f4arr(cond1, c1);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float a0 = has_c ? b0[e] + c0[e] : b0[e];
+        const float a1 = has_c ? b1[e] + c1[e] : b1[e];
+        o[e] = gatef_(v0[e] + a0, v1[e] + a1);
+    }
+}
+// the second output hd = h + d: the next dilated conv's input (model/diffwave.py:139)
+DR_DEVINL void hd_quad(const float (&h)[4], const float4 d, float (&o)[4]) {
+    float dd[4];
+    f4arr(d, dd);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = h[e] + dd[e];
+}
+// ... and its store for rows p0..p0+3, frame t of sample b: split-bf16 (a.out_s3 & 2) or fp32 P4.  COH3 / COH4: that
+// flavour's store is write-through when a.wt_store says so (tensors handed to other workgroups of a fused launch), else plain.
+template <int COH3, int COH4>
+DR_DEVINL void store_y2(const GemmArgs& a, const int b, const float (&o)[4], const float4 d, const int p0, const int t) {
+    float o2[4];
+    hd_quad(o, d, o2);
+    if (a.out_s3 & 2) {
+        store_s3_quad<COH3>(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3, a.wt_store);
+    } else {
+        float* dst2 = a.Y2 + (long)b * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+        store_f4<COH4>(dst2, make_float4(o2[0], o2[1], o2[2], o2[3]), a.wt_store);
+    }
+}
+
+// The 4 fp32 A fragments of K step `slab` of a weight panel (fragment-shaped packing: 16 KiB per 32-channel slab, 4 KiB
+// per 8-channel group; wvo = this lane's byte offset inside a group)
+DR_DEVINL AF4 load_a4(const __amdgpu_buffer_rsrc_t wrsrc, const int wvo, const int slab, const int NS, const int code) {
+    AF4 o;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, code, slab, NS);
+        o.v[g] = buffer_load_f4(wrsrc, wvo, slab * 16384 + g * 4096);
+    }
+    return o;
+}
+
+typedef __attribute__((address_space(3))) void* lds_ptr;
+
+// LDS-DMA of a read-modify-write tile, global -> Rs = [32 planes (4 packed rows each)][BN frames] float4, frames t0.. of
+// the planes plane_of(pl) (global address of frame 0; T frames of 16 B: frames >= T read 0), dealt over the waves
+// first, first + stride, ...  AUX = 16: sc1 loads (the tile was written by this workgroup in an earlier phase of the same
+// launch - bypass the L1).
+template <int BN, int AUX, class PlaneOf>
+DR_DEVINL void dma_tile(float4* Rs, PlaneOf plane_of, const int T, const int t0, const int first, const int stride, const int lane, const int code) {
+    constexpr int RWL = (BN + 63) / 64;                 // 64-frame segments of a tile row
+    for (int i = first; i < 32 * RWL; i += stride) {
+        const int pl = i / RWL, seg = i - pl * RWL;
+        const int f = seg * 64 + lane;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)plane_of(pl), 0, (unsigned)T * 16u, 0x00020000);
+        if (BN % 64 == 0 || f < BN) {
+            DR_CHECK_LDS(Rs + pl * BN + f, lds_off(Rs), lds_off(Rs) + 32u * BN * 16u, code);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(Rs + pl * BN + seg * 64), 16, (t0 + f) * 16, 0, 0, AUX);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The producer waves (pw = 0..3) of the LDS-staged bodies: they stage the X tile of chunks [c0, c1) of frame tile
+// (b, t0) into Xs = [2 buffers][XP planes][FW frames] float4, one chunk ahead of the consumers, and first - RBN != 0,
+// EPI_RES_SKIP - the block's read-modify-write tile (h rows of M tile mt below y_rows, skip rows above) into Rs.
+//   Each X-tile plane row (FW float4 = frames t0-halo .. t0+BN+halo-1 of 4 channels) is copied
+//   global -> LDS by ceil(FW/64) `buffer_load_dwordx4 ... lds` instructions (64 lanes x 16 B, LDS
+//   destination = wave-uniform base + lane*16).  The buffer descriptor covers exactly frames
+//   [0, T) of that plane, so frames outside the clip - the conv's zero padding and the tail of the
+//   last tile - come back as 0 from the hardware bounds check: no VALU, no ds_write, no VGPR
+//   staging.  Producers therefore issue a handful of instructions per chunk and no longer steal
+//   issue slots from the consumers' MFMA stream (measured: 70.7 -> 66 ticks per MFMA when idle).
+//   PREC = 1: the X tile rows are the split-bf16 planes [(sub*2 + g)*6 + piece*2 + kq] (see gemm_body).
+//   AUX = 16: sc1 loads (COH bodies: X was written by other workgroups of the same launch).
+// ---------------------------------------------------------------------------------------------
+template <int KS, int PREC, int AUX, int RBN>
+DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw, const int lane, const int mt, const int b, const int t0,
+                        const int halo, const int FW, const int c0, const int c1, const int code_x, const int code_r) {
+    constexpr int XP = (PREC ? 12 : 8) * KS;            // 16-byte rows per X tile
+    const int bx = a.x_bmod ? (b % a.x_bmod) : b;
+    const float* Xg = a.X + (long)bx * a.x_bs;
+    const int last_plane = a.x_planes - 1;
+    const unsigned recs = ((unsigned)(a.T - 1) * (unsigned)a.x_fs + 4u) * 4u;   // bytes of one plane row
+    const int wl = (FW + 63) >> 6;                  // wave-loads per plane row
+    const int total = XP * wl;
+    auto issue = [&](int chunk) {
+        for (int i = pw; i < total; i += 4) {
+            const int pl = i / wl, seg = i - pl * wl;
+            const int f = seg * 64 + lane;
+            // planes beyond Cin (K padding) re-read the last valid plane: finite data x zero weights
+            const float* src;
+            if constexpr (PREC) {
+                const int sg = pl / 6, rem = pl - sg * 6, pce = rem >> 1, kq = rem & 1;
+                const int pc = min(chunk * (4 * KS) + sg * 2 + kq, last_plane);       // plane8
+                src = Xg + (long)pce * a.x_piece + (long)pc * a.x_ps;
+            } else {
+                src = Xg + (long)min(chunk * XP + pl, last_plane) * a.x_ps;
+            }
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, recs, 0x00020000);
+            const int voff = (t0 - halo + f) * (int)a.x_fs * 4;   // negative / past the end => reads 0
+            float4* dst = Xs + (((chunk - c0) & 1) * XP + pl) * FW + seg * 64;
+            if (f < FW) DR_CHECK_LDS(dst + lane, lds_off(Xs), lds_off(Xs) + 2u * XP * FW * 16u, code_x);
+            if (f < FW) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)dst, 16, voff, 0, 0, AUX);
+        }
+    };
+    if constexpr (RBN != 0) {
+        auto plane_of = [&](int pl) -> const float* {
+            const int row0 = mt * 128 + pl * 4;
+            return (row0 < a.y_rows) ? a.Y + (long)b * a.y_bs + (long)(row0 >> 2) * a.y_ps
+                                     : a.skip + (long)b * a.s_bs + (long)((row0 - a.y_rows) >> 2) * a.T * 4;
+        };
+        dma_tile<RBN, AUX>(Rs, plane_of, a.T, t0, pw, 4, lane, code_r);
+    }
+    issue(c0);
+    for (int chunk = c0; chunk < c1; ++chunk) {
+        // hand-over #chunk: this wave's DMA of tile #chunk must have LANDED before the barrier releases the
+        // consumers - barriers do not drain VMEM, and hipcc does not reliably insert the wait for a
+        // __syncthreads() behind LDS-DMA builtins (it did in the stand-alone kernels and did NOT in the fused
+        // ones: tools/isa_audit.py; the consumers then read the previous occupant of the buffer whenever the tile
+        // was slower than their own first weight fragments - observed with cross-XCD hand-offs).  Hence explicit.
+        // The consumers' matching barrier opens their chunk; only then may the OTHER buffer be refilled (the
+        // consumers finished reading it before they arrived here).
+#if DR_FAULT != 1
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#else                       // litmus build 1: the hand-over WITHOUT the wait - a bare s_barrier, so that hipcc's own fence
+        __builtin_amdgcn_s_barrier();       // handling cannot put it back (which kernels of rounds 1-2 had it was luck)
+#endif
+        if (chunk + 1 < c1) issue(chunk + 1);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Implicit-GEMM kernel.
@@ -71,11 +231,6 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // of a wave are [16 gate (cos) channels, 16 filter (sin) channels], i.e. C/D register quads q and q+2
     // of the same lane.
     constexpr bool PAIRED = (EPI == EPI_GATE || EPI == EPI_POWER);
-    constexpr int WNC = 1;                        // consumer waves along N
-    constexpr int MI = 1;                         // 32-row MFMA tiles per wave
-    constexpr int WROWS = MI * 32;                // rows per wave
-    constexpr int WFR = NW * 32;                  // frames per wave
-
     int tid = threadIdx.x;
     // COH (the persistent kernels call this body once per phase inside a loop): everything this call derives from the lane
     // index must be computed INSIDE the call.  Without the opaque barrier the compiler hoists the per-lane address
@@ -106,93 +261,21 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     const int cps = a.kchunks / KS / a.ksplit;      // chunks (hand-overs) of this block: [c0, c1)
     const int c0 = ks * cps, c1 = c0 + cps;
 
-    if (wave >= 4) {
-        // ------------------------------------------------------------------ producers (LDS-DMA)
-        // Each X-tile plane row (FW float4 = frames t0-halo .. t0+BN+halo-1 of 4 channels) is copied
-        // global -> LDS by ceil(FW/64) `buffer_load_dwordx4 ... lds` instructions (64 lanes x 16 B, LDS
-        // destination = wave-uniform base + lane*16).  The buffer descriptor covers exactly frames
-        // [0, T) of that plane, so frames outside the clip - the conv's zero padding and the tail of the
-        // last tile - come back as 0 from the hardware bounds check: no VALU, no ds_write, no VGPR
-        // staging.  Producers therefore issue a handful of instructions per chunk and no longer steal
-        // issue slots from the consumers' MFMA stream (measured: 70.7 -> 66 ticks per MFMA when idle).
-        const int pw = wave - 4;
-        const int bx = a.x_bmod ? (b % a.x_bmod) : b;
-        const float* Xg = a.X + (long)bx * a.x_bs;
-        const int last_plane = a.x_planes - 1;
-        const unsigned recs = ((unsigned)(a.T - 1) * (unsigned)a.x_fs + 4u) * 4u;   // bytes of one plane row
-        const int wl = (FW + 63) >> 6;                  // wave-loads per plane row
-        const int total = XP * wl;
-        typedef __attribute__((address_space(3))) void* lds_ptr;
-        auto issue = [&](int chunk) {
-            for (int i = pw; i < total; i += 4) {
-                const int pl = i / wl, seg = i - pl * wl;
-                const int f = seg * 64 + lane;
-                // planes beyond Cin (K padding) re-read the last valid plane: finite data x zero weights
-                const float* src;
-                if constexpr (PREC) {
-                    const int sg = pl / 6, rem = pl - sg * 6, pce = rem >> 1, kq = rem & 1;
-                    const int pc = min(chunk * (4 * KS) + sg * 2 + kq, last_plane);       // plane8
-                    src = Xg + (long)pce * a.x_piece + (long)pc * a.x_ps;
-                } else {
-                    src = Xg + (long)min(chunk * XP + pl, last_plane) * a.x_ps;
-                }
-                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, recs, 0x00020000);
-                const int voff = (t0 - halo + f) * (int)a.x_fs * 4;   // negative / past the end => reads 0
-                float4* dst = Xs + (((chunk - c0) & 1) * XP + pl) * FW + seg * 64;
-                if (f < FW) DR_CHECK_LDS(dst + lane, xs0, xs1, 101);
-                if (f < FW) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)dst, 16, voff, 0, 0, COH ? 16 : 0);
-            }
-        };
-        if constexpr (EPI == EPI_RES_SKIP) {
-            const unsigned rrecs = (unsigned)a.T * 16u;
-            constexpr int RWL = BN / 64;
-            for (int i = pw; i < 32 * RWL; i += 4) {
-                const int pl = i / RWL, seg = i - pl * RWL;
-                const int row0 = mt * 128 + pl * 4;
-                const float* src = (row0 < a.y_rows)
-                    ? a.Y + (long)b * a.y_bs + (long)(row0 >> 2) * a.y_ps
-                    : a.skip + (long)b * a.s_bs + (long)((row0 - a.y_rows) >> 2) * a.T * 4;
-                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, rrecs, 0x00020000);
-                const int voff = (t0 + seg * 64 + lane) * 16;
-                DR_CHECK_LDS(Rs + pl * BN + seg * 64 + lane, xs1, rs1, 102);
-                // (COH: the tile was written by THIS workgroup in an earlier phase of the same launch - bypass the L1)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(Rs + pl * BN + seg * 64), 16, voff, 0, 0, COH ? 16 : 0);
-            }
-        }
-        issue(c0);
-        for (int chunk = c0; chunk < c1; ++chunk) {
-            // hand-over #chunk: this wave's DMA of tile #chunk must have LANDED before the barrier releases the
-            // consumers - barriers do not drain VMEM, and hipcc does not reliably insert the wait for a
-            // __syncthreads() behind LDS-DMA builtins (it did in the stand-alone kernels and did NOT in the fused
-            // ones: tools/isa_audit.py; the consumers then read the previous occupant of the buffer whenever the tile
-            // was slower than their own first weight fragments - observed with cross-XCD hand-offs).  Hence explicit.
-            // The consumers' matching barrier opens their chunk; only then may the OTHER buffer be refilled (the
-            // consumers finished reading it before they arrived here).
-#if DR_FAULT != 1
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-#else                       // litmus build 1: the hand-over WITHOUT the wait - a bare s_barrier, so that hipcc's own fence
-            __builtin_amdgcn_s_barrier();       // handling cannot put it back (which kernels of rounds 1-2 had it was luck)
-#endif
-            if (chunk + 1 < c1) issue(chunk + 1);
-        }
+    if (wave >= 4) {      // producers (LDS-DMA)
+        producer<KS, PREC, COH ? 16 : 0, EPI == EPI_RES_SKIP ? BN : 0>(a, Xs, Rs, wave - 4, lane, mt, b, t0, halo, FW, c0, c1, 101, 102);
         return;
     }
 
-    // ---------------------------------------------------------------------- consumers
-    const int wr = wave / WNC, wc = wave % WNC;
+    // ---------------------------------------------------------------------- consumers (wave = its 32 rows of the M tile)
     const int r = lane & 31, hi = lane >> 5;
     // this lane's A fragments inside a slab: fp32 [g][hi][row][4] (16 KiB); S3 [g16][piece][kq][row][8 bf16] (24 KiB)
 
-    f32x16 acc[MI][NW];
+    f32x16 acc[NW];
 #pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
+    for (int ni = 0; ni < NW; ++ni)
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+        for (int e = 0; e < 16; ++e) acc[ni][e] = 0.f;
     // blocked accumulation (see the header): acc = the running chunk's chain, outer = the sum of the finished chunks
-    static_assert(MI == 1, "one 32-row MFMA tile per consumer wave");
     f32x16 outer[NW];
 #pragma unroll
     for (int ni = 0; ni < NW; ++ni)
@@ -203,7 +286,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     auto fold = [&]() {
         if constexpr (FOLD) {
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) outer[ni] = outer[ni] + acc[0][ni];
+            for (int ni = 0; ni < NW; ++ni) outer[ni] = outer[ni] + acc[ni];
             // The adds happen HERE.  Their results are only needed after the K loop, and left alone the compiler sinks
             // them to the bottom of the chunk - which keeps the previous chain alive through the whole chunk in a THIRD
             // register set (16*NW copies per chunk behind the last MFMAs; at NW = 4 also what pushed the kernel into
@@ -216,27 +299,24 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // Epilogue operands are NOT prefetched into VGPRs: bias / d2 / conditioner are L2-resident and are
     // loaded as unconditional batches at the start of the epilogue (a conditional load there compiles to
     // a branch + s_waitcnt vmcnt(0) per quad), the EPI_RES_SKIP read-modify-write tile waits in LDS (Rs).
-    float4 eop[MI][NW][4];
+    float4 eop[NW][4];
 
     if constexpr (PREC == 1) {
         // A fragments through buffer loads with scalar per-step offsets (see the fp32 path): slab = 24 KiB,
         // [g16 2][piece 3][kq 2][row 128][8 bf16]
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(a.Wp + (long)mt * NS * 6144), 0, (unsigned)NS * 24576u, 0x00020000);
-        const int wvo = (hi * 128 + wr * WROWS + r) * 16;
-        static_assert(MI == 1, "one 32-row MFMA tile per consumer wave");
-        auto load_a3 = [&](int slab) -> A12 {
-            A12 o;
+        const int wvo = (hi * 128 + wave * 32 + r) * 16;
+        auto load_a3 = [&](int slab) -> AF6 {
+            AF6 o;
 #pragma unroll
             for (int gp = 0; gp < 6; ++gp) {
                 DR_CHECK(slab >= 0 && wvo + slab * 24576 + gp * 4096 + 16 <= NS * 24576, 103, slab, NS);
-                const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvo, slab * 24576 + gp * 4096, 0);
-                o.v[gp * 2] = make_uint4(u.x, u.y, u.z, u.w);
+                o.v[gp] = buffer_load_u4(wrsrc, wvo, slab * 24576 + gp * 4096);
             }
             return o;
         };
-        A12 wA = load_a3(c0 * KS * a.taps), wB;
+        AF6 wA = load_a3(c0 * KS * a.taps), wB;
         const int cen = (a.taps - 1) >> 1;
         const int per_chunk = a.taps * KS;
         const uint4* Xs3 = reinterpret_cast<const uint4*>(Xs);
@@ -245,7 +325,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         BF3 b0, b1;
         auto xaddr = [&](int chunk, int q) -> const uint4* {
             const int j = q / KS, sub = q - j * KS;
-            return Xs3 + (((chunk - c0) & 1) * XP + sub * 12 + hi) * FW + halo + (j - cen) * a.dil + wc * WFR + r;
+            return Xs3 + (((chunk - c0) & 1) * XP + sub * 12 + hi) * FW + halo + (j - cen) * a.dil + r;
         };
         auto rd3 = [&](const uint4* Xb, int g) -> BF3 {
             BF3 o;
@@ -263,17 +343,17 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         auto mma6 = [&](auto FIRST, const uint4 a0, const uint4 a1, const uint4 a2, const BF3& bf) {
             constexpr bool kFirst = FOLD && decltype(FIRST)::value;      // the chunk's first products: C = 0 (a new chain)
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[0][ni] = mma_bf16(a2, bf.v[0][ni], kFirst ? zero16 : acc[0][ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(a2, bf.v[0][ni], kFirst ? zero16 : acc[ni]);
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[0][ni] = mma_bf16(a0, bf.v[2][ni], acc[0][ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(a0, bf.v[2][ni], acc[ni]);
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[0][ni] = mma_bf16(a1, bf.v[1][ni], acc[0][ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(a1, bf.v[1][ni], acc[ni]);
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[0][ni] = mma_bf16(a1, bf.v[0][ni], acc[0][ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(a1, bf.v[0][ni], acc[ni]);
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[0][ni] = mma_bf16(a0, bf.v[1][ni], acc[0][ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(a0, bf.v[1][ni], acc[ni]);
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[0][ni] = mma_bf16(a0, bf.v[0][ni], acc[0][ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(a0, bf.v[0][ni], acc[ni]);
         };
         // One K step (32 channels x 1 tap): 2 groups x 6 piece products x NW tiles = 12*NW MFMAs per wave.
         // A 32x32x16 bf16 MFMA is 32 cycles, so a step is only 384*NW cycles: every non-MFMA instruction
@@ -286,9 +366,9 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
             if constexpr (kB) wA = load_a3(min(slab + 1, NS - 1));
             else wB = load_a3(min(slab + 1, NS - 1));
             b1 = rd3(Xb, 1);
-            mma6(FIRST, kB ? wB.v[0] : wA.v[0], kB ? wB.v[2] : wA.v[2], kB ? wB.v[4] : wA.v[4], b0);
+            mma6(FIRST, kB ? wB.v[0] : wA.v[0], kB ? wB.v[1] : wA.v[1], kB ? wB.v[2] : wA.v[2], b0);
             b0 = rd3(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
-            mma6(std::false_type{}, kB ? wB.v[6] : wA.v[6], kB ? wB.v[8] : wA.v[8], kB ? wB.v[10] : wA.v[10], b1);
+            mma6(std::false_type{}, kB ? wB.v[3] : wA.v[3], kB ? wB.v[4] : wA.v[4], kB ? wB.v[5] : wA.v[5], b1);
             sgb_mix<3 * NW, 6>();           // + the 6 A-fragment loads of the next step, one per MFMA pair
             sgb_mix<3 * NW, 0>();
         };
@@ -315,23 +395,12 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // A fragments through buffer loads: the M tile's weight panel is the resource (SGPRs), the per-lane
     // byte offset is fixed for the whole kernel and the per-step offset is scalar - no vector address
     // arithmetic in the K loop (with flat 64-bit addresses it was ~12 exposed VALU instructions per step).
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.Wp + (long)mt * NS * 4096), 0, (unsigned)NS * 16384u, 0x00020000);
-    const int wvo = (hi * 128 + wr * WROWS + r) * 16;
-    auto load_a = [&](int slab) -> A8 {
-        A8 o;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, 105, slab, NS);
-            const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvo, slab * 16384 + g * 4096, 0);
-            o.v[g * 2] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
-        }
-        return o;
-    };
-    static_assert(MI == 1, "one 32-row MFMA tile per consumer wave");
+    const int wvo = (hi * 128 + wave * 32 + r) * 16;
+    auto load_a = [&](int slab) { return load_a4(wrsrc, wvo, slab, NS, 105); };
 
-    A8 wA = load_a(c0 * KS * a.taps), wB;
+    AF4 wA = load_a(c0 * KS * a.taps), wB;
     const int cen = (a.taps - 1) >> 1;
 
     // B fragments of one 8-channel group: NW float4 (one per 32-frame MFMA tile), conflict-free ds_read_b128
@@ -339,7 +408,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     BF b0, b1;                                   // groups 0/2 and 1/3 of the step in flight
     auto xaddr = [&](int chunk, int q) -> const float4* {     // X tile address of step q of a chunk
         const int j = q / KS, sub = q - j * KS;
-        return Xs + (((chunk - c0) & 1) * XP + sub * 8 + hi) * FW + halo + (j - cen) * a.dil + wc * WFR + r;
+        return Xs + (((chunk - c0) & 1) * XP + sub * 8 + hi) * FW + halo + (j - cen) * a.dil + r;
     };
     auto rd = [&](const float4* Xb, int g) -> BF {
         BF o;
@@ -355,13 +424,13 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     auto mma4 = [&](auto FIRST, const float4 af, const BF& bf) {
         constexpr bool kFirst = FOLD && decltype(FIRST)::value;  // the chunk's first MFMAs: C = 0 (a new chain)
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[0][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.v[ni].x, kFirst ? zero16 : acc[0][ni], 0, 0, 0);
+        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.v[ni].x, kFirst ? zero16 : acc[ni], 0, 0, 0);
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[0][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.v[ni].y, acc[0][ni], 0, 0, 0);
+        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.v[ni].y, acc[ni], 0, 0, 0);
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[0][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.v[ni].z, acc[0][ni], 0, 0, 0);
+        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.v[ni].z, acc[ni], 0, 0, 0);
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[0][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.v[ni].w, acc[0][ni], 0, 0, 0);
+        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.v[ni].w, acc[ni], 0, 0, 0);
     };
 
     // One K step (32 channels x 1 tap): 16*NW MFMAs per wave in 4 groups of 8 channels.  Software pipeline,
@@ -381,11 +450,11 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         b1 = rd(Xb, 1);
         mma4(FIRST, kB ? wB.v[0] : wA.v[0], b0);
         b0 = rd(Xb, 2);
-        mma4(std::false_type{}, kB ? wB.v[2] : wA.v[2], b1);
+        mma4(std::false_type{}, kB ? wB.v[1] : wA.v[1], b1);
         b1 = rd(Xb, 3);
-        mma4(std::false_type{}, kB ? wB.v[4] : wA.v[4], b0);
+        mma4(std::false_type{}, kB ? wB.v[2] : wA.v[2], b0);
         b0 = rd(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
-        mma4(std::false_type{}, kB ? wB.v[6] : wA.v[6], b1);
+        mma4(std::false_type{}, kB ? wB.v[3] : wA.v[3], b1);
         // pinned schedule: the 4 A-fragment loads ride inside group 0's MFMAs (one per NW MFMAs: issued in the
         // shadow of a running MFMA instead of as a burst with the matrix pipe idle; hipcc on its own sinks them
         // to their first use and exposes the whole L2 latency once per step)
@@ -403,8 +472,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     constexpr bool AINP = (NI == 2 || NI == 5) && FOLD;
     auto load_ag = [&](int slab, int g) -> float4 {
         DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, 112, slab, NS);
-        const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvo, slab * 16384 + g * 4096, 0);
-        return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
+        return buffer_load_f4(wrsrc, wvo, slab * 16384 + g * 4096);
     };
     auto stepi = [&](auto FIRST, int slab, int chunk, int q) {
         const float4* Xb = xaddr(chunk, q);
@@ -413,14 +481,14 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         mma4(FIRST, wA.v[0], b0);
         wA.v[0] = load_ag(nx, 0);
         b0 = rd(Xb, 2);
-        mma4(F_{}, wA.v[2], b1);
-        wA.v[2] = load_ag(nx, 1);
+        mma4(F_{}, wA.v[1], b1);
+        wA.v[1] = load_ag(nx, 1);
         b1 = rd(Xb, 3);
-        mma4(F_{}, wA.v[4], b0);
-        wA.v[4] = load_ag(nx, 2);
+        mma4(F_{}, wA.v[2], b0);
+        wA.v[2] = load_ag(nx, 2);
         b0 = rd(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
-        mma4(F_{}, wA.v[6], b1);
-        wA.v[6] = load_ag(nx, 3);
+        mma4(F_{}, wA.v[3], b1);
+        wA.v[3] = load_ag(nx, 3);
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
@@ -469,7 +537,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // the last chunk's chain; from here on acc holds the block's (partial) sums
     if constexpr (FOLD) {
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[0][ni] = outer[ni] + acc[0][ni];
+        for (int ni = 0; ni < NW; ++ni) acc[ni] = outer[ni] + acc[ni];
     }
 
     const long long tick1 = a.dbg ? clock64() : 0;
@@ -485,7 +553,6 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // costs an L2-wide write-back + invalidate per wave (measured: 25 us per launch).
     // ----------------------------------------------------------------------------------------
     if (a.ksplit > 1) {
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         constexpr int WQ = NW * 4;                                   // float4 per lane per wave region
         constexpr int WSCOH = 17;                                    // buffer cache policy: sc0 | sc1
         const int tile = nt * a.MT + mt;
@@ -497,8 +564,8 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         for (int ni = 0; ni < NW; ++ni)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const u32x4 v = {__float_as_uint(acc[0][ni][4 * q]), __float_as_uint(acc[0][ni][4 * q + 1]),
-                                 __float_as_uint(acc[0][ni][4 * q + 2]), __float_as_uint(acc[0][ni][4 * q + 3])};
+                const u32x4 v = {__float_as_uint(acc[ni][4 * q]), __float_as_uint(acc[ni][4 * q + 1]),
+                                 __float_as_uint(acc[ni][4 * q + 2]), __float_as_uint(acc[ni][4 * q + 3])};
                 DR_CHECK((size_t)(base + ks * sstride + (ni * 4 + q) * 1024) + 16 <= a.ws_floats * 4, 107, base + ks * sstride, a.ws_floats);
                 __builtin_amdgcn_raw_buffer_store_b128(v, wsr, base + ks * sstride + (ni * 4 + q) * 1024, 0, WSCOH);
             }
@@ -513,7 +580,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
 #pragma unroll
         for (int ni = 0; ni < NW; ++ni)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[0][ni][e] = 0.f;
+            for (int e = 0; e < 16; ++e) acc[ni][e] = 0.f;
         // U splits in flight per wait (the loads are pure latency: ~1.5 us each when taken one by one);
         // the adds stay in split order whatever U is
         auto reduce = [&](auto UU, int sp0) {
@@ -533,7 +600,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[0][ni][4 * q + e] += __uint_as_float(v[u][ni * 4 + q][e]);
+                        for (int e = 0; e < 4; ++e) acc[ni][4 * q + e] += __uint_as_float(v[u][ni * 4 + q][e]);
         };
         constexpr int UMAX = (NW == 2) ? 4 : 2;
         if (a.ksplit % UMAX == 0) {
@@ -546,7 +613,6 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // epilogue.  C/D fragment of 32x32: column = lane&31 (frame), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
     // => per register quad q a lane owns 4 consecutive rows 8q+4hi..+3 = one float4 of the P4 layout.
     // ----------------------------------------------------------------------------------------
-    auto f4arr = [](const float4 v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; };
     // Dual-output mode (EPI_GATE, a.dual = B > 0): classifier-free guidance feeds the SAME x_t to the conditional
     // and the unconditional evaluation, so in the first residual layer the dilated conv of sample b and of
     // sample b + B is the same contraction - it is done once, and the epilogue runs twice (conditioner of
@@ -555,38 +621,31 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
 #pragma unroll 1
     for (int pass = 0; pass < npass; ++pass) {
         const int be = b + pass * a.dual;
-        float4 ebias[MI][4];                        // [mi][q]
-        float4 ed2[MI][4];                          // second-output offset (step embedding of the next conv)
+        float4 ebias[4];                            // [q]
+        float4 ed2[4];                              // second-output offset (step embedding of the next conv)
         {
             const float* bsrc = a.bias;
             if constexpr (EPI == EPI_GATE) bsrc = (be < a.n_cond) ? a.bias : a.bias2;
     #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-    #pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    ebias[mi][q] = *reinterpret_cast<const float4*>(bsrc + mt * 128 + wr * WROWS + mi * 32 + 8 * q + 4 * hi);
+            for (int q = 0; q < 4; ++q) ebias[q] = *reinterpret_cast<const float4*>(bsrc + mt * 128 + wave * 32 + 8 * q + 4 * hi);
             if constexpr (EPI == EPI_RELU || EPI == EPI_RES_SKIP) {
     #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-    #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        // residual rows only exist below y_rows; the clamp keeps the (unused) skip-row loads in range
-                        const int p0 = min(mt * 128 + wr * WROWS + mi * 32 + 8 * q + 4 * hi, a.y_rows - 4);
-                        ed2[mi][q] = *reinterpret_cast<const float4*>(a.d2 + (a.tsel ? (long)a.tsel[be] * a.d2_ts : 0) + p0);
-                    }
+                for (int q = 0; q < 4; ++q) {
+                    // residual rows only exist below y_rows; the clamp keeps the (unused) skip-row loads in range
+                    const int p0 = min(mt * 128 + wave * 32 + 8 * q + 4 * hi, a.y_rows - 4);
+                    ed2[q] = *reinterpret_cast<const float4*>(a.d2 + (a.tsel ? (long)a.tsel[be] * a.d2_ts : 0) + p0);
+                }
             }
         }
     #pragma unroll
         for (int ni = 0; ni < NW; ++ni) {
-            const int t = t0 + wc * WFR + ni * 32 + r;
+            const int t = t0 + ni * 32 + r;
             if constexpr (EPI == EPI_RES_SKIP) {
     #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-    #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        DR_CHECK_LDS(Rs + (wr * (WROWS / 4) + mi * 8 + 2 * q + hi) * BN + wc * WFR + ni * 32 + r, xs1, rs1, 110);
-                        eop[mi][ni][q] = Rs[(wr * (WROWS / 4) + mi * 8 + 2 * q + hi) * BN + wc * WFR + ni * 32 + r];
-                    }
+                for (int q = 0; q < 4; ++q) {
+                    DR_CHECK_LDS(Rs + (wave * 8 + 2 * q + hi) * BN + ni * 32 + r, xs1, rs1, 110);
+                    eop[ni][q] = Rs[(wave * 8 + 2 * q + hi) * BN + ni * 32 + r];
+                }
             }
             if constexpr (EPI == EPI_GATE) {
                 // conditioner quads of this frame column: one unconditional batch (unconditional samples read
@@ -596,37 +655,24 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                 // there is one, else sample 0's tensor as a readable dummy
                 const float* cb = ((be < a.n_cond || !a.cond2) ? a.cond + (long)(be < a.n_cond ? be : 0) * a.c_bs : a.cond2) + (long)tc * 4;
     #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-    #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int p0 = mt * 128 + wr * WROWS + mi * 32 + 8 * q + 4 * hi;
-                        eop[mi][ni][q] = *reinterpret_cast<const float4*>(cb + (long)(p0 >> 2) * a.T * 4);
-                    }
+                for (int q = 0; q < 4; ++q) {
+                    const int p0 = mt * 128 + wave * 32 + 8 * q + 4 * hi;
+                    eop[ni][q] = *reinterpret_cast<const float4*>(cb + (long)(p0 >> 2) * a.T * 4);
+                }
             }
             if (t >= a.T) continue;
     #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int rq = 8 * q + 4 * hi;   // row offset inside a 32-row MFMA tile
+                const int rq = 8 * q + 4 * hi;   // row offset inside the wave's 32-row MFMA tile
                 if constexpr (PAIRED) {
                     if (q >= 2) continue;                     // quads 0,1 = gate / cos rows, quads 2,3 = their partners
-                    const int c0 = mt * 64 + wr * 16 + rq;    // output channel of the quad (rq = 8q + 4hi < 16)
+                    const int c0 = mt * 64 + wave * 16 + rq;  // output channel of the quad (rq = 8q + 4hi < 16)
                     if (c0 >= a.y_rows) continue;
                     float v0[4], v1[4], o[4];
     #pragma unroll
-                    for (int e = 0; e < 4; ++e) { v0[e] = acc[0][ni][4 * q + e]; v1[e] = acc[0][ni][4 * (q + 2) + e]; }
+                    for (int e = 0; e < 4; ++e) { v0[e] = acc[ni][4 * q + e]; v1[e] = acc[ni][4 * (q + 2) + e]; }
                     if constexpr (EPI == EPI_GATE) {
-                        // y = conv + b_conv + (Wc spec + bc)   [model/diffwave.py:143-144]; unconditional samples
-                        // carry the constant conditioner inside bias2
-                        float b0[4], b1[4], c0v[4], c1v[4];
-                        f4arr(ebias[0][q], b0); f4arr(ebias[0][q + 2], b1);
-                        f4arr(eop[0][ni][q], c0v); f4arr(eop[0][ni][q + 2], c1v);
-                        const bool has_c = be < a.n_cond || a.cond2 != nullptr;
-    #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float a0 = has_c ? b0[e] + c0v[e] : b0[e];
-                            const float a1 = has_c ? b1[e] + c1v[e] : b1[e];
-                            o[e] = gatef_(v0[e] + a0, v1[e] + a1);   // gate = first half, filter = second (:146-147)
-                        }
+                        gate_quad(v0, v1, ebias[q], ebias[q + 2], eop[ni][q], eop[ni][q + 2], be < a.n_cond || a.cond2 != nullptr, o);
                     } else {
     #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = v0[e] * v0[e] + v1[e] * v1[e];
@@ -638,64 +684,38 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                         store_f4<COH>(dst, make_float4(o[0], o[1], o[2], o[3]), a.wt_store);
                     }
                 } else {
+                    const int p0 = mt * 128 + wave * 32 + rq;
+                    float v[4], o[4];
     #pragma unroll
-                    for (int mi = 0; mi < MI; ++mi) {
-                        const int p0 = mt * 128 + wr * WROWS + mi * 32 + rq;
-                        float v[4], bb[4], o[4];
-    #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = acc[mi][ni][4 * q + e];
-                        f4arr(ebias[mi][q], bb);
-                        if constexpr (EPI == EPI_RES_SKIP) {
-                            float pv[4];
-                            f4arr(eop[mi][ni][q], pv);
-                            // packed rows [0, y_rows) are the residual half, [y_rows, 2*y_rows) the skip half
-                            // (y_rows is a multiple of 64, so the branch is wave-uniform)
-                            if (p0 < a.y_rows) {   // h = (h + (acc + be)) / sqrt(2), in place (:151)
-                                float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-    #pragma unroll
-                                for (int e = 0; e < 4; ++e) o[e] = div_sqrt2(pv[e] + (v[e] + bb[e]));
-                                *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                                if (a.Y2) {        // hd = h + d_{l+1}: the next dilated conv's input (:139)
-                                    float dd[4];
-                                    f4arr(ed2[mi][q], dd);
-                                    const float o2[4] = {o[0] + dd[0], o[1] + dd[1], o[2] + dd[2], o[3] + dd[3]};
-                                    if (a.out_s3 & 2) {
-                                        store_s3_quad<COH>(a.Y2 + (long)be * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3, a.wt_store);
-                                    } else {
-                                        float* dst2 = a.Y2 + (long)be * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                                        *reinterpret_cast<float4*>(dst2) = make_float4(o2[0], o2[1], o2[2], o2[3]);
-                                    }
-                                }
-                            } else {               // skip (+)= acc + be (:680)
-                                float* dst = a.skip + (long)be * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
-    #pragma unroll
-                                for (int e = 0; e < 4; ++e) o[e] = a.skip_init ? v[e] + bb[e] : (v[e] + bb[e]) + pv[e];
-                                *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                            }
-                        } else {
-                            if (p0 >= a.y_rows) continue;
-    #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                if constexpr (EPI == EPI_PLAIN) o[e] = a.alpha * v[e] + bb[e];
-                                else if constexpr (EPI == EPI_RELU) o[e] = fmaxf(a.alpha * v[e] + bb[e], 0.f);
-                                else if constexpr (EPI == EPI_SILU) { const float z = v[e] + bb[e]; o[e] = z * sigmoidf_(z); }
-                                else o[e] = logf(v[e] + 1e-6f);
-                            }
+                    for (int e = 0; e < 4; ++e) v[e] = acc[ni][4 * q + e];
+                    if constexpr (EPI == EPI_RES_SKIP) {
+                        // packed rows [0, y_rows) are the residual half, [y_rows, 2*y_rows) the skip half
+                        // (y_rows is a multiple of 64, so the branch is wave-uniform)
+                        if (p0 < a.y_rows) {   // h, in place
                             float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                            residual_quad(v, ebias[q], eop[ni][q], o);
                             *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                            if constexpr (EPI == EPI_RELU) {
-                                if (a.Y2) {    // hd = h + d_0 for the first dilated conv
-                                    float dd[4];
-                                    f4arr(ed2[mi][q], dd);
-                                    const float o2[4] = {o[0] + dd[0], o[1] + dd[1], o[2] + dd[2], o[3] + dd[3]};
-                                    if (a.out_s3 & 2) {
-                                        store_s3_quad<COH>(a.Y2 + (long)be * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3, a.wt_store);
-                                    } else {
-                                        float* dst2 = a.Y2 + (long)be * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                                        *reinterpret_cast<float4*>(dst2) = make_float4(o2[0], o2[1], o2[2], o2[3]);
-                                    }
-                                }
-                            }
+                            if (a.Y2) store_y2<COH, 0>(a, be, o, ed2[q], p0, t);
+                        } else {
+                            float* dst = a.skip + (long)be * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
+                            skip_quad(v, ebias[q], eop[ni][q], a.skip_init, o);
+                            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                        }
+                    } else {
+                        if (p0 >= a.y_rows) continue;
+                        float bb[4];
+                        f4arr(ebias[q], bb);
+    #pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            if constexpr (EPI == EPI_PLAIN) o[e] = a.alpha * v[e] + bb[e];
+                            else if constexpr (EPI == EPI_RELU) o[e] = fmaxf(a.alpha * v[e] + bb[e], 0.f);
+                            else if constexpr (EPI == EPI_SILU) { const float z = v[e] + bb[e]; o[e] = z * sigmoidf_(z); }
+                            else o[e] = logf(v[e] + 1e-6f);
+                        }
+                        float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                        *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                        if constexpr (EPI == EPI_RELU) {
+                            if (a.Y2) store_y2<COH, 0>(a, be, o, ed2[q], p0, t);    // hd = h + d_0 for the first dilated conv
                         }
                     }
                 }
@@ -739,10 +759,6 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
     static_assert(EPI == EPI_RES_SKIP || EPI == EPI_RELU || EPI == EPI_PLAIN, "pw_body epilogues");
     static_assert(EPI == EPI_RES_SKIP || !RLDS, "the LDS-resident tile belongs to the residual / skip epilogue");
     constexpr int BN = TBN;
-    // X loads are PLAIN also in the fused kernel: the four waves of a block read the same B fragments, and only
-    // the CU's L1 turns that into one L2 request instead of four (measured: with L1-bypassing sc1 loads the phase
-    // ran 2x slower) - the fused kernel therefore invalidates the L1 once, in the barrier before this phase.
-    constexpr int XAUX = 0;
     int lane = threadIdx.x & 63;
     if constexpr (COH) asm volatile("" : "+v"(lane));      // (as gemm_body: no per-lane value of this call may be hoisted out of a phase loop)
     const int r = lane & 31, hi = lane >> 5;
@@ -758,7 +774,9 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
     // K step costs no vector address arithmetic (flat 64-bit addressing cost ~70 VALU ops per step, i.e.
     // ~12 of 76 ticks per MFMA, all exposed: nothing else runs on the SIMD).  Out-of-range reads (K padding
     // planes) return 0 from the bounds check; frames past T read the next plane's data (finite, never used).
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    // X loads are PLAIN also in the fused kernel: the four waves of a block read the same B fragments, and only
+    // the CU's L1 turns that into one L2 request instead of four (measured: with L1-bypassing sc1 loads the phase
+    // ran 2x slower) - the fused kernel therefore invalidates the L1 once, in the barrier before this phase.
     const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.Wp + (long)mt * NS * 4096), 0, (unsigned)NS * 16384u, 0x00020000);
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
@@ -769,25 +787,15 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
 #pragma unroll
     for (int ni = 0; ni < NW; ++ni) xvo[ni] = hi * xps + min(t0 + ni * 32 + r, a.T - 1) * 16;
 
-    struct AF { float4 v[4]; };
     struct BF { float4 v[4][NW]; };
-    auto asf4 = [](const u32x4 u) { return make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w)); };
-    auto load_a = [&](int slab) -> AF {
-        AF o;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, 120, slab, NS);
-            o.v[g] = asf4(__builtin_amdgcn_raw_buffer_load_b128(wr, wvo, slab * 16384 + g * 4096, 0));
-        }
-        return o;
-    };
+    auto load_a = [&](int slab) { return load_a4(wr, wvo, slab, NS, 120); };
     auto load_b = [&](int slab) -> BF {
         BF o;
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int ni = 0; ni < NW; ++ni)
-                o.v[g][ni] = asf4(__builtin_amdgcn_raw_buffer_load_b128(xr, xvo[ni], (slab * 8 + g * 2) * xps, XAUX));
+                o.v[g][ni] = buffer_load_f4(xr, xvo[ni], (slab * 8 + g * 2) * xps);
         return o;
     };
 
@@ -797,7 +805,7 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[ni][e] = 0.f;
 
-    AF aA = load_a(0), aB;
+    AF4 aA = load_a(0), aB;
     BF bA = load_b(0), bB;
     auto step = [&](auto ROLE, int slab) {
         constexpr bool kB = decltype(ROLE)::value;
@@ -827,7 +835,6 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
     // epilogue operands (EPI_RES_SKIP): rows [0, y_rows) h = (h + acc + b) / sqrt(2) in place (+ hd = h + d_next),
     // rows [y_rows, 2 y_rows) skip (+)= acc + b.  The read-modify-write tile comes straight from global and is
     // requested BEFORE the last two K steps, so its latency hides behind their MFMAs.
-    auto f4arr = [](const float4 v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; };
     const int rowb = mt * 128 + wave * 32 + 4 * hi;           // + 8q
     const bool res_rows = rowb < a.y_rows;                     // wave-uniform (y_rows is a multiple of 64)
     float4 ebias[4], ed2[4], eop[RLDS ? 1 : NW][4];
@@ -877,11 +884,12 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int p0 = rowb + 8 * q;
-            float v[4], bb[4], pv[4], o[4];
+            float v[4], o[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[ni][4 * q + e];
             if constexpr (EPI != EPI_RES_SKIP) {
                 if (p0 >= a.y_rows) continue;
+                float bb[4];
                 f4arr(ebias[q], bb);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -897,30 +905,18 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
 #ifdef DR_BOUNDS
             if constexpr (RLDS) DR_CHECK_LDS(rs, lds_off(Rs), lds_off(Rs) + 32u * BN * 16u, 121);
 #endif
-            f4arr(ebias[q], bb);
-            if constexpr (RLDS) f4arr(*rs, pv);
-            else f4arr(eop[ni][q], pv);
+            float4 pv;
+            if constexpr (RLDS) pv = *rs;
+            else pv = eop[ni][q];
             if (res_rows) {
                 float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = div_sqrt2(pv[e] + (v[e] + bb[e]));
+                residual_quad(v, ebias[q], pv, o);
                 if constexpr (RLDS) *rs = make_float4(o[0], o[1], o[2], o[3]);
                 else *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                if (a.Y2) {
-                    float dd[4];
-                    f4arr(ed2[q], dd);
-                    const float o2[4] = {o[0] + dd[0], o[1] + dd[1], o[2] + dd[2], o[3] + dd[3]};
-                    if (a.out_s3 & 2) {
-                        store_s3_quad(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3);
-                    } else {
-                        float* dst2 = a.Y2 + (long)b * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                        store_f4<COH>(dst2, make_float4(o2[0], o2[1], o2[2], o2[3]), a.wt_store);
-                    }
-                }
+                if (a.Y2) store_y2<0, COH>(a, b, o, ed2[q], p0, t);
             } else {
                 float* dst = a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = a.skip_init ? v[e] + bb[e] : (v[e] + bb[e]) + pv[e];
+                skip_quad(v, ebias[q], pv, a.skip_init, o);
                 if constexpr (RLDS) *rs = make_float4(o[0], o[1], o[2], o[3]);
                 else *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
             }
@@ -941,17 +937,14 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
 //   consumers 4 (M) x 1 (N): wave tile = 2 row tiles (paired epilogue: gate 16 / filter 16 of the same
 //   channels) x 2*NJ column tiles = 20 accumulators x 4 registers at NJ = 5.
 // ---------------------------------------------------------------------------------------------
-//   COH = 1 (fused residual-stack kernel): as gemm_body - X (hd) through sc1 LDS-DMA loads, the gated output
-//   (g) stored write-through unless a.wt_store == 0.
-template <int NJ, int KS, int EPI, int COH>
+template <int NJ, int KS, int EPI>
 DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const int nt) {
     static_assert(EPI == EPI_GATE || EPI == EPI_RES_SKIP, "16x16 variant: hot kernels only");
     constexpr int BN = 32 * NJ;
     constexpr int XP = 8 * KS;
-    constexpr int WNC = 1;                          // 4 (M) x 1 (N) consumers, as in gemm_kernel
+    // 4 (M) x 1 (N) consumers, as in gemm_kernel: wave = its 32 rows of the M tile
     constexpr int RT = 2;                           // 16-row tiles per wave (paired: tile 0 gate, tile 1 filter)
     constexpr int CT = 2 * NJ;                      // 16-frame tiles per wave
-    constexpr int WROWS = RT * 16, WFR = CT * 16;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -962,7 +955,7 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
     float4* Rs = Xs + 2 * XP * FW;                  // EPI_RES_SKIP: [32 planes][BN]
 #ifdef DR_BOUNDS
     const unsigned xs0 = lds_off(Xs), xs1 = xs0 + 2u * XP * FW * 16u, rs1 = xs1 + (EPI == EPI_RES_SKIP ? 32u * BN * 16u : 0u);
-    if (tid == 0 && !COH) DR_CHECK(rs1 <= (unsigned)a.lds_bytes, 140, rs1, a.lds_bytes);
+    if (tid == 0) DR_CHECK(rs1 <= (unsigned)a.lds_bytes, 140, rs1, a.lds_bytes);
 #endif
 
     const int tps = (a.T + BN - 1) / BN;
@@ -971,56 +964,14 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
     const int NS = a.kchunks * a.taps;
     const int nchunks = a.kchunks / KS;
 
-    if (wave >= 4) {   // producers: identical to gemm_kernel's (LDS-DMA, hardware zero padding)
-        const int pw = wave - 4;
-        const int bx = a.x_bmod ? (b % a.x_bmod) : b;
-        const float* Xg = a.X + (long)bx * a.x_bs;
-        const int last_plane = a.x_planes - 1;
-        const unsigned recs = ((unsigned)(a.T - 1) * (unsigned)a.x_fs + 4u) * 4u;
-        const int wl = (FW + 63) >> 6;
-        const int total = XP * wl;
-        typedef __attribute__((address_space(3))) void* lds_ptr;
-        auto issue = [&](int chunk) {
-            for (int i = pw; i < total; i += 4) {
-                const int pl = i / wl, seg = i - pl * wl;
-                const int f = seg * 64 + lane;
-                const float* src = Xg + (long)min(chunk * XP + pl, last_plane) * a.x_ps;
-                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, recs, 0x00020000);
-                const int voff = (t0 - halo + f) * (int)a.x_fs * 4;
-                float4* dst = Xs + ((chunk & 1) * XP + pl) * FW + seg * 64;
-                if (f < FW) DR_CHECK_LDS(dst + lane, xs0, xs1, 141);
-                if (f < FW) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)dst, 16, voff, 0, 0, COH ? 16 : 0);
-            }
-        };
-        if constexpr (EPI == EPI_RES_SKIP) {
-            const unsigned rrecs = (unsigned)a.T * 16u;
-            constexpr int RWL = (BN + 63) / 64;
-            for (int i = pw; i < 32 * RWL; i += 4) {
-                const int pl = i / RWL, seg = i - pl * RWL;
-                const int row0 = mt * 128 + pl * 4;
-                const float* src = (row0 < a.y_rows)
-                    ? a.Y + (long)b * a.y_bs + (long)(row0 >> 2) * a.y_ps
-                    : a.skip + (long)b * a.s_bs + (long)((row0 - a.y_rows) >> 2) * a.T * 4;
-                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, rrecs, 0x00020000);
-                const int f = seg * 64 + lane;
-                if (f < BN) DR_CHECK_LDS(Rs + pl * BN + seg * 64 + lane, xs1, rs1, 142);
-                if (f < BN)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(Rs + pl * BN + seg * 64), 16, (t0 + f) * 16, 0, 0, 0);
-            }
-        }
-        issue(0);
-        for (int chunk = 0; chunk < nchunks; ++chunk) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile #chunk has landed (see gemm_body)
-            __syncthreads();
-            if (chunk + 1 < nchunks) issue(chunk + 1);
-        }
+    if (wave >= 4) {   // producers (LDS-DMA, hardware zero padding)
+        producer<KS, 0, 0, EPI == EPI_RES_SKIP ? BN : 0>(a, Xs, Rs, wave - 4, lane, mt, b, t0, halo, FW, 0, nchunks, 141, 142);
         return;
     }
 
     // consumers.  16x16x4: A lane (i = l&15, kq = l>>4) holds W[row i][4 channels kq*4..+3 of a 16-channel
     // group] (one per MFMA), B lane (j = l&15, kq) the matching X values; C/D: column = l&15,
     // rows (l>>4)*4 + reg -> one float4 of the P4 layout per tile.
-    const int wr = wave / WNC, wc = wave % WNC;
     const int li = lane & 15, kq = lane >> 4;
     float4 acc[RT][CT];
 #pragma unroll
@@ -1029,24 +980,21 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
         for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = f4zero();
 
     // A fragments through buffer loads with scalar per-step offsets (as in gemm_kernel)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(a.Wp + (long)mt * NS * 4096), 0, (unsigned)NS * 16384u, 0x00020000);
-    const int wvo = (kq * 128 + wr * WROWS + li) * 16;
-    struct AF { float4 v[2 * RT]; };   // [g16][rt]
-    auto load_a = [&](int slab) -> AF {
-        AF o;
+    const int wvo = (kq * 128 + wave * 32 + li) * 16;
+    auto load_a = [&](int slab) -> AF4 {     // [g16][rt]
+        AF4 o;
 #pragma unroll
         for (int g = 0; g < 2; ++g)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 8192 + rt * 256 + 16 <= NS * 16384, 143, slab, NS);
-                const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvo, slab * 16384 + g * 8192 + rt * 256, 0);
-                o.v[g * RT + rt] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
+                o.v[g * RT + rt] = buffer_load_f4(wrsrc, wvo, slab * 16384 + g * 8192 + rt * 256);
             }
         return o;
     };
-    AF wA = load_a(0), wB;
+    AF4 wA = load_a(0), wB;
     const int cen = (a.taps - 1) >> 1;
     const int per_chunk = a.taps * KS;
     typedef float v4f __attribute__((ext_vector_type(4)));
@@ -1056,7 +1004,7 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
     BF b0, b1;
     auto xaddr = [&](int chunk, int q) -> const float4* {
         const int j = q / KS, sub = q - j * KS;
-        return Xs + ((chunk & 1) * XP + sub * 8 + kq) * FW + halo + (j - cen) * a.dil + wc * WFR + li;
+        return Xs + ((chunk & 1) * XP + sub * 8 + kq) * FW + halo + (j - cen) * a.dil + li;
     };
     auto rd = [&](const float4* Xb, int g) -> BF {
         BF o;
@@ -1116,8 +1064,7 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
     }
 
     // epilogue: per (row tile, column tile) a lane owns rows rowbase + kq*4 .. +3 of frame column li
-    auto f4arr = [](const float4 v, float (&o)[4]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; };
-    const int rowb = mt * 128 + wr * WROWS + kq * 4;     // + rt*16
+    const int rowb = mt * 128 + wave * 32 + kq * 4;     // + rt*16
     float4 ebias[RT], ed2[RT];
     {
         const float* bsrc = a.bias;
@@ -1131,7 +1078,7 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
     }
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-        const int t = t0 + wc * WFR + ct * 16 + li;
+        const int t = t0 + ct * 16 + li;
         if constexpr (EPI == EPI_GATE) {
             float4 cnd[RT];
             const int tc = min(t, a.T - 1);
@@ -1141,58 +1088,39 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
             if (t >= a.T) continue;
             const bool has_c = b < a.n_cond || a.cond2 != nullptr;
             {                                    // tile 0 = gate rows, tile 1 = filter rows of the same 16 channels
-                const int c0 = mt * 64 + wr * 16 + kq * 4;
+                const int c0 = mt * 64 + wave * 16 + kq * 4;
                 if (c0 >= a.y_rows) continue;
-                float v0[4], v1[4], b0[4], b1[4], c0v[4], c1v[4], o[4];
+                float v0[4], v1[4], o[4];
                 f4arr(acc[0][ct], v0); f4arr(acc[1][ct], v1);
-                f4arr(ebias[0], b0); f4arr(ebias[1], b1);
-                f4arr(cnd[0], c0v); f4arr(cnd[1], c1v);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a0 = has_c ? b0[e] + c0v[e] : b0[e];
-                    const float a1 = has_c ? b1[e] + c1v[e] : b1[e];
-                    o[e] = gatef_(v0[e] + a0, v1[e] + a1);
-                }
+                gate_quad(v0, v1, ebias[0], ebias[1], cnd[0], cnd[1], has_c, o);
                 if (a.out_s3 & 1) {
                     store_s3_quad(a.Y + (long)b * a.y_bs, o, c0, t, a.T, a.y_rows >> 3);
                 } else {
                     float* dst = a.Y + (long)b * a.y_bs + (long)(c0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                    store_f4<COH>(dst, make_float4(o[0], o[1], o[2], o[3]), a.wt_store);
+                    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
                 }
             }
         } else {
             float4 pv4[RT];
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
-                DR_CHECK_LDS(Rs + ((wr * WROWS + rt * 16) / 4 + kq) * BN + wc * WFR + ct * 16 + li, xs1, rs1, 145);
-                pv4[rt] = Rs[((wr * WROWS + rt * 16) / 4 + kq) * BN + wc * WFR + ct * 16 + li];
+                DR_CHECK_LDS(Rs + ((wave * 32 + rt * 16) / 4 + kq) * BN + ct * 16 + li, xs1, rs1, 145);
+                pv4[rt] = Rs[((wave * 32 + rt * 16) / 4 + kq) * BN + ct * 16 + li];
             }
             if (t >= a.T) continue;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
                 const int p0 = rowb + rt * 16;
-                float v[4], bb[4], pv[4], o[4];
-                f4arr(acc[rt][ct], v); f4arr(ebias[rt], bb); f4arr(pv4[rt], pv);
+                float v[4], o[4];
+                f4arr(acc[rt][ct], v);
                 if (p0 < a.y_rows) {
                     float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = div_sqrt2(pv[e] + (v[e] + bb[e]));
+                    residual_quad(v, ebias[rt], pv4[rt], o);
                     *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                    if (a.Y2) {
-                        float dd[4];
-                        f4arr(ed2[rt], dd);
-                        const float o2[4] = {o[0] + dd[0], o[1] + dd[1], o[2] + dd[2], o[3] + dd[3]};
-                        if (a.out_s3 & 2) {
-                            store_s3_quad(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3);
-                        } else {
-                            float* dst2 = a.Y2 + (long)b * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                            *reinterpret_cast<float4*>(dst2) = make_float4(o2[0], o2[1], o2[2], o2[3]);
-                        }
-                    }
+                    if (a.Y2) store_y2<0, 0>(a, b, o, ed2[rt], p0, t);
                 } else {
                     float* dst = a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = a.skip_init ? v[e] + bb[e] : (v[e] + bb[e]) + pv[e];
+                    skip_quad(v, ebias[rt], pv4[rt], a.skip_init, o);
                     *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
                 }
             }

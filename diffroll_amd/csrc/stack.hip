@@ -85,20 +85,10 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
     if constexpr (PREC) {
         if (pending_timeout) return;
     } else {
-        typedef __attribute__((address_space(3))) void* lds_ptr;
-        const int lane = threadIdx.x & 63;
-        for (int i = wave; i < RP * RWL; i += 8) {
-            const int pl = i / RWL, seg = i - pl * RWL;
-            bool is_res;
-            const float* src = tile_plane(pl, is_res);
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, (unsigned)s.T * 16u, 0x00020000);
 #ifdef DR_BOUNDS
-            if (seg * 64 + lane < BN) DR_CHECK_LDS(Rs + pl * BN + seg * 64 + lane, s.rs_off, s.rs_off + RP * BN * 16, 131);
-            if (threadIdx.x == 0 && i == 0) DR_CHECK(s.rs_off + RP * BN * 16 + 16 <= s.lds_bytes && lds_off(smem) == 0u, 132, s.rs_off, s.lds_bytes);
+        if (threadIdx.x == 0) DR_CHECK(s.rs_off + RP * BN * 16 + 16 <= s.lds_bytes && lds_off(smem) == 0u, 132, s.rs_off, s.lds_bytes);
 #endif
-            if (seg * 64 + lane < BN)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(Rs + pl * BN + seg * 64), 16, (t0_ + seg * 64 + lane) * 16, 0, 0, 0);
-        }
+        dma_tile<BN, 0>(Rs, [&](int pl) { bool is_res; return tile_plane(pl, is_res); }, s.T, t0_, wave, 8, threadIdx.x & 63, 131);
         if (pending_timeout) return;
         // (the first group barrier - or the end of a one-phase launch - drains these loads: s_waitcnt vmcnt(0)
         // + __syncthreads(); a launch that STARTS with a 1x1 phase waits right here)
@@ -326,15 +316,8 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
     return hipGetLastError();
 }
 hipError_t init_stack_kernels() {
-    hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<1, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<2, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_kernel<2, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    return hipSuccess;
+    return allow_max_lds(&stack_kernel<1>, &stack_kernel<2, 0>, &stack_kernel<5>, &stack_kernel<2, 1>,
+                         &stack_kernel<1, 1, 1>, &stack_kernel<2, 0, 1>, &stack_kernel<2, 1, 1>);
 }
 
 }  // namespace dr

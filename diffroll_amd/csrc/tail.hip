@@ -126,6 +126,7 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
                     v = update_quad(s.u, i4);
                     if (mti == 0) reinterpret_cast<float4*>(s.x_out)[i4] = v;
                 }
+                DR_CHECK_LDS(XT + pl * 32 + fi, lds_off(XT), lds_off(XT) + 24u * 32u * 16u, 151);
                 XT[pl * 32 + fi] = v;
             }
             if (!s.in_w) continue;
@@ -133,7 +134,6 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
             if (wave >= 4) continue;
             // input projection of the next step: 128 rows (this row tile) x 32 frames, K = 88 -> 96 (3 K steps); A
             // fragments from the packed weights (as pw_body), B fragments from XT (conflict-free ds_read_b128)
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             const int r = lane & 31, hi = lane >> 5;
             const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)(s.in_w + (long)mti * 3 * 4096), 0, 3u * 16384u, 0x00020000);
             const int wvo = (hi * 128 + wave * 32 + r) * 16;
@@ -144,12 +144,13 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
             for (int kc = 0; kc < 3; ++kc)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(wr, wvo, kc * 16384 + g * 4096, 0);
+                    const float4 af = buffer_load_f4(wr, wvo, kc * 16384 + g * 4096);
+                    DR_CHECK_LDS(XT + (kc * 8 + g * 2 + hi) * 32 + r, lds_off(XT), lds_off(XT) + 24u * 32u * 16u, 152);
                     const float4 bf = XT[(kc * 8 + g * 2 + hi) * 32 + r];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(u.x), bf.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(u.y), bf.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(u.z), bf.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(u.w), bf.w, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.x, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.y, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.z, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.w, acc, 0, 0, 0);
                 }
             const int t = f0 + r;
             if (t >= s.T) continue;
@@ -248,7 +249,7 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
 }
 
 hipError_t init_tail_kernels() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return allow_max_lds(&tail_kernel);
 }
 
 }  // namespace dr

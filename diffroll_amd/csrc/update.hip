@@ -151,7 +151,7 @@ hipError_t launch_note_runs(const float* roll, int* note_end, int B, int T, floa
     return hipGetLastError();
 }
 hipError_t init_update_kernels() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&note_runs_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    return allow_max_lds(&note_runs_kernel);
 }
 
 // Frame-level confusion counts of task/diffusion.py:381-383 (sklearn precision_recall_fscore_support,
@@ -188,7 +188,6 @@ __global__ __launch_bounds__(256) void frame_counts_kernel(const float* __restri
     __shared__ unsigned sh[4][3];
     __shared__ unsigned last_s;
     __shared__ unsigned long long tot[4][3];
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     // the partials travel as ONE 16-byte write-through store per block (sc0 sc1) and are re-read with L2-bypassing loads:
     // agent-scope atomic stores to neighbouring words serialise at the memory channel like the atomics they replace
     const __amdgpu_buffer_rsrc_t pr = __builtin_amdgcn_make_buffer_rsrc((void*)(work + 4), 0, (unsigned)FRAME_COUNTS_MAX_BLOCKS * 16u, 0x00020000);
