@@ -45,7 +45,7 @@ DEBUG_EXPORTS = [
     "dr_bench_layer", "dr_bench_pointwise",
 ]
 # the options dr_set_option knows; every other name goes to dr_debug_set_option (Engine.set_option)
-PUBLIC_OPTIONS = ("blocked_accumulation", "fused_rearm", "fused_stack", "fused_tail", "window_overlap", "sampling_steps")
+PUBLIC_OPTIONS = ("blocked_accumulation", "fused_rearm", "fused_stack", "fused_tail", "window_overlap", "window_break", "sampling_steps")
 MODES = {0: "none", 1: "per_phase", 2: "fused_stack", 3: "fused_stack+tail"}
 
 

@@ -20,6 +20,12 @@ documents None as "get the full audio", utils/custom_dataset.py:21, but crashes 
 jointly sampled 640-frame windows overlapping by ``task.window_overlap`` frames (default 160; diffroll_amd/longform.py),
 written as ``roll_<stem>.npy`` (1, 1, ceil(L / hop), 88), ``raw_midi_<stem>.mid`` and ``clean_midi_<stem>.mid``.  With
 ``gpus=N`` every rank takes the files round-robin and writes its own outputs.
+
+``task.recordings_per_chain=N`` (long-form only, default 1) puts up to N consecutive files into ONE chain
+(ClassifierFreeDiffRoll.sample_long_batch; longform.pack_chains closes a chain early at longform.MAX_WINDOWS windows):
+short recordings then fill the device together.  The chains are dealt round-robin to the ranks; a chain whose first
+file is file j runs with seed = seed + j, and the roll of file i equals ``sample_long(wav, seed=<that chain's seed>,
+recording=i)``.  It does NOT equal the N = 1 run, which seeds every file with seed + i.  The output files are the same.
 """
 from __future__ import annotations
 
@@ -107,6 +113,12 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
                               or not (steps == 0 or 2 <= steps <= S)):
         raise SystemExit(f"task.sampling.steps must be an integer in [2, task.timesteps = {S}] (or 0 / null: every "
                          f"step), got {steps!r}")
+    per_chain = cfg["task"].get("recordings_per_chain", 1)
+    if isinstance(per_chain, bool) or not isinstance(per_chain, int) or per_chain < 1:
+        raise SystemExit(f"task.recordings_per_chain must be an integer >= 1, got {per_chain!r}")
+    if per_chain > 1 and not is_long_form(cfg):
+        raise SystemExit("task.recordings_per_chain groups whole recordings: it needs dataset=Custom "
+                         "dataset.args.max_segment_samples=null (long-form)")
     if is_long_form(cfg):
         sampler = cfg["task"]["sampling"]["type"]
         if sampler == "inpainting_ddpm_x0":
@@ -150,8 +162,9 @@ def wav_files(args: Dict[str, Any]) -> List[str]:
 
 def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> List[str]:
     """Every file of the Custom folder whole (max_segment_samples=null): this rank's share, dealt round-robin, one
-    sample_long chain per recording (file i: seed = seed + i, recording = i); writes roll_<stem>.npy,
-    raw_midi_<stem>.mid and clean_midi_<stem>.mid.  Returns the roll paths written."""
+    sample_long chain per recording (file i: seed = seed + i, recording = i) - or, with task.recordings_per_chain > 1,
+    one sample_long_batch chain per group of consecutive files; writes roll_<stem>.npy, raw_midi_<stem>.mid and
+    clean_midi_<stem>.mid.  Returns the roll paths written."""
     from .audio import ingest
     from .longform import deal
     args = cfg["dataset"]["args"]
@@ -163,14 +176,9 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
     hop = int(cfg["hop_length"])
     out = cfg["output_dir"]
     written = []
-    for i, path in deal(list(enumerate(files)), rank, world):
+
+    def write(path, roll):
         stem = os.path.splitext(os.path.basename(path))[0]
-        wav = ingest(path, int(args["sample_rate"]), None)
-        seed = int(cfg["seed"]) + i
-        if generation:          # (the waveform is ignored, sampling.py:45: a roll of the recording's length)
-            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i)
-        else:
-            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i)
         roll_path = os.path.join(out, f"roll_{stem}.npy")
         np.save(roll_path, roll.cpu().numpy())
         written.append(roll_path)
@@ -179,6 +187,33 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
         model.export_midi(roll, tmp_raw, clean_prefix=tmp_clean)
         os.replace(tmp_raw + "0.mid", os.path.join(out, f"raw_midi_{stem}.mid"))
         os.replace(tmp_clean + "0.mid", os.path.join(out, f"clean_midi_{stem}.mid"))
+
+    per_chain = int(cfg["task"].get("recordings_per_chain", 1))
+    if per_chain > 1:
+        # task.recordings_per_chain: consecutive files share a chain (module docstring); every file is read up front,
+        # since the window counts decide the grouping
+        from .longform import deal_chains, pack_chains, plan_windows
+        wavs = [ingest(path, int(args["sample_rate"]), None) for path in files]
+        counts = [plan_windows(wv.shape[0], hop, overlap=overlap).n for wv in wavs]
+        for chain in deal_chains(pack_chains(counts, per_chain), rank, world):
+            j = chain[0]
+            seed = int(cfg["seed"]) + j
+            if generation:
+                rolls = model.sample_long_batch(frames=[-(-wavs[i].shape[0] // hop) for i in chain], overlap=overlap,
+                                                seed=seed, first_recording=j)
+            else:
+                rolls = model.sample_long_batch([wavs[i] for i in chain], overlap=overlap, seed=seed, first_recording=j)
+            for i, roll in zip(chain, rolls):
+                write(files[i], roll)
+        return written
+    for i, path in deal(list(enumerate(files)), rank, world):
+        wav = ingest(path, int(args["sample_rate"]), None)
+        seed = int(cfg["seed"]) + i
+        if generation:          # (the waveform is ignored, sampling.py:45: a roll of the recording's length)
+            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i)
+        else:
+            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i)
+        write(path, roll)
     return written
 
 

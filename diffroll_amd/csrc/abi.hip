@@ -154,9 +154,31 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
 }
 
 // option "window_overlap": at most two windows share a frame (O <= T / 2)
-int check_windows(dr_engine* e, int T) {
+// option "window_break": every mark names a window of this batch (marks are ignored while "window_overlap" is 0)
+int check_windows(dr_engine* e, int B, int T) {
     if (2 * e->opt_win_O > T)
         return fail(e, DR_EINVAL, "window_overlap %d exceeds half the window (T = %d frames)", e->opt_win_O, T);
+    if (e->opt_win_O > 0 && !e->win_marks.empty()) {
+        if (e->win_marks.back() >= B)
+            return fail(e, DR_EINVAL, "window_break %d is not a window of this batch (B = %d windows)", e->win_marks.back(), B);
+        if (B > STACK_GROUPS)
+            return fail(e, DR_EINVAL, "window_break: a batch with recording boundaries holds at most %d windows, got B = %d", STACK_GROUPS, B);
+    }
+    return DR_OK;
+}
+
+// The per-window table of this batch (engine_state.h: d_wintab) from the marks, written on `st` in front of the launches
+// that read it: an eager sequence with marks, and every launch of a captured chain (force: its graph holds the table's
+// address whether or not marks were set when it was captured).  Without marks: window b of recording 0.
+int write_windows(dr_engine* e, int B, bool force, hipStream_t st) {
+    if (e->opt_win_O <= 0 || B > STACK_GROUPS || (!force && e->win_marks.empty())) return DR_OK;
+    WindowTable tab;
+    size_t m = 0;
+    for (int b = 0, first = 0; b < B; ++b) {
+        if (m < e->win_marks.size() && e->win_marks[m] == b) { ++m; first = b; }
+        tab.w[b] = window_entry((unsigned)m, (unsigned)(b - first));
+    }
+    HIPCHK(e, launch_set_windows(e->d_wintab, tab, B, st));
     return DR_OK;
 }
 
@@ -226,6 +248,14 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
         if (e->opt_win_O != value) drop();
         e->opt_win_O = value;
+        return DR_OK;
+    }
+    // (a mark >= B is refused by dr_step / dr_sample, which know B; no captured chain is dropped: the table is data)
+    if (n == "window_break") {
+        if (value < 0) return fail(e, DR_EINVAL, "window_break is >= 0 (0 = clear all marks), got %d", value);
+        if (value == 0) { e->win_marks.clear(); return DR_OK; }
+        auto at = std::lower_bound(e->win_marks.begin(), e->win_marks.end(), value);
+        if (at == e->win_marks.end() || *at != value) e->win_marks.insert(at, value);
         return DR_OK;
     }
     if (n == "sampling_steps") {
@@ -507,12 +537,13 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if (t < 0 || t >= e->S) return fail(e, DR_EINVAL, "step %d out of range", t);
     if (!e->rs_steps.empty() && std::find(e->rs_steps.begin(), e->rs_steps.end(), t) == e->rs_steps.end())
         return fail(e, DR_EINVAL, "step %d is not visited by the respaced chain (option sampling_steps = %d)", t, e->opt_steps);
-    if ((rc = check_windows(e, T))) return rc;
+    if ((rc = check_windows(e, B, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
+    if ((rc = write_windows(e, B, false, (hipStream_t)stream))) return rc;
     float* res = nullptr;
     if ((rc = run_step(e, sampler, d_x, d_noise, B, T, t, w, seed, first_sample, (hipStream_t)stream, &res))) return rc;
     if (res != d_x)      // the fused step wrote x_{t-1} into the engine's buffer: hand it back in place
@@ -526,7 +557,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     DeviceGuard guard(e->cfg.device);
     int rc = check_ready(e, sampler, B, T);
     if (rc) return rc;
-    if ((rc = check_windows(e, T))) return rc;
+    if ((rc = check_windows(e, B, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = ensure_workspace(e, NB, T))) return rc;
@@ -561,6 +592,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     };
     if (!use_graph || e->prof) {
         Range range("dr_sample: eager chain");
+        if ((rc = write_windows(e, B, false, st))) return rc;
         return chain(d_x);
     }
 
@@ -597,6 +629,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     HIPCHK(e, hipMemcpyAsync(e->xwork, d_x, per * sizeof(float), hipMemcpyDeviceToDevice, st));
     // (the chain's tail launches publish epochs in win_epoch + 1 .. win_epoch + S, one per step: TailArgs::ready)
     HIPCHK(e, launch_set_dyn(e->d_dyn, seed, first_sample, w, (float)(1.0 + (double)w), e->win_epoch, st));
+    if ((rc = write_windows(e, B, true, st))) return rc;      // (the captured chain reads the table of THIS call's marks)
     e->win_epoch += (unsigned)e->S;
     HIPCHK(e, hipGraphLaunch(e->gexec, st));
     e->graph_stream = st; e->graph_stream_set = true;

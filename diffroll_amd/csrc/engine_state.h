@@ -173,6 +173,14 @@ struct dr_engine {
     int64_t tail_launches = 0;
     int opt_win_O = 0;                  // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
                                         // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
+    std::vector<int> win_marks;         // option "window_break", ascending: the windows that start a new recording (window 0 always does)
+    // The per-window table behind UpdateArgs::win_tab (kernels.h: window_entry).  A one-block kernel rewrites it on the
+    // call's stream in front of every launch sequence / graph launch that reads it, as launch_set_dyn rewrites d_dyn; its
+    // address is what a captured chain bakes in, so new marks at the same (sampler, B, T) replay the same graph.
+    // Overwriting it is safe while an earlier chain is still running: that chain and the rewriting kernel are on the same
+    // stream, so the rewrite starts only when every launch of the earlier chain has finished - and an engine is used
+    // from one stream at a time (diffroll_amd.h), as d_dyn, xwork and the activation workspace already require.
+    drh::DevBuf<unsigned> d_wintab;
     int opt_steps = 0;                  // option "sampling_steps": n of a respaced chain; 0 (and S) = every step
     std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
     drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor

@@ -207,7 +207,21 @@ struct UpdateArgs {
     // 0.5 (y_b + y_b+1) of the two windows' guided predictions, and Philox is keyed by (seed, first_sample = the
     // recording, t, canvas element / 4): both windows compute the same x_{t-1} there, bit for bit.
     int win_H;
+    // Recording boundaries inside the window batch (option "window_break"): null = one recording (the definition above);
+    // else the engine's per-window table, win_tab[b] = window_entry(r, i): window b is window i of recording r of the batch.
+    // Windows b and b + 1 share frames only when b + 1 is not the first window of a recording (i(b + 1) > 0), the canvas
+    // above is recording r's own ((n_r - 1) * win_H + T frames, window b at frame i * win_H) and Philox is keyed
+    // (seed, first_sample + r, t, canvas element of recording r / 4).
+    const unsigned* win_tab;
 };
+// one word per window: recording ordinal and index within the recording, both < STACK_GROUPS
+constexpr unsigned window_entry(unsigned rec, unsigned idx) { return (rec << 16) | idx; }
+constexpr int window_rec(unsigned w) { return (int)(w >> 16); }
+constexpr int window_idx(unsigned w) { return (int)(w & 0xFFFFu); }
+// The table travels to the device BY VALUE in the kernel arguments of a one-block launch (2 KiB: no host buffer has to
+// outlive the call), stream-ordered like launch_set_dyn.
+struct WindowTable { unsigned w[STACK_GROUPS]; };
+hipError_t launch_set_windows(unsigned* d_tab, const WindowTable& tab, int n, hipStream_t s);
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
 
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->

@@ -435,6 +435,7 @@ int commit(dr_engine* e, hipStream_t st) {
     // ticket counters, group counters of the persistent kernels: zero between launches (the kernels re-arm them)
     HIPCHK(e, e->sk_cnt.ensure(SK_CNT_N, true));
     HIPCHK(e, e->d_dyn.ensure(1, false));
+    HIPCHK(e, e->d_wintab.ensure(STACK_GROUPS, true));      // window 0 of recording 0 everywhere until a call writes it
     if (!e->sync.mem) {
         HIPCHK(e, e->sync.init());
         HIPCHK(e, e->stack_dbg.ensure(128, true));

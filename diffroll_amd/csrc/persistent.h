@@ -83,19 +83,22 @@ DR_DEVINL void group_barrier(unsigned* ctr, const unsigned target, unsigned* err
 }
 
 // Long-form windows (tail.hip, between the pair barrier after T2 and T3): thread 0 of a block of window i waits until
-// the ready words of windows i - 1 and i + 1 (those that exist, i < n) have reached `epoch`, then drops its CU's L1 lines
+// the ready words of windows i - 1 and i + 1 - those the caller names with `lower` / `upper`: the neighbours that exist
+// AND belong to window i's recording (option "window_break": T3 reads nothing of another recording's window, so it
+// must not spin on its word either) - have reached `epoch`, then drops its CU's L1 lines
 // (agent-scope acquire), as group_barrier does after a match; the caller's __syncthreads() releases the block.  A
 // neighbour publishes its word once every block of its pair has passed the pair barrier, i.e. once its T2 stores (write-
 // through, drained) are out.  Its PAIR counters are never polled here: the last block to leave a launch re-arms them, so a
 // neighbour that has already finished T3 / T4 would look like one that never arrived.  The words only grow (a per-engine
 // epoch, compared as a signed difference): nothing re-arms them in-kernel.  Same spin bound and flags as group_barrier.
 // Deadlock-free because the tail kernel only runs when the whole evaluation is one resident launch (launch_plan.h:
-// stack_chunks == 1) and publishing does not wait for anything.
-DR_DEVINL void neighbour_wait(const unsigned* ready, const int i, const int n, const unsigned epoch, unsigned* err,
-                              unsigned* derr) {
+// stack_chunks == 1) and publishing does not wait for anything - every window publishes its word, whether or not a
+// neighbour of its recording will wait for it, so a recording boundary only removes waits.
+DR_DEVINL void neighbour_wait(const unsigned* ready, const int i, const bool lower, const bool upper, const unsigned epoch,
+                              unsigned* err, unsigned* derr) {
     unsigned spins = 0;
     for (int j = i - 1; j <= i + 1; j += 2) {
-        if (j < 0 || j >= n) continue;
+        if (j < i ? !lower : !upper) continue;
         while ((int)(__hip_atomic_load(ready + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - epoch) < 0) {
             __builtin_amdgcn_s_sleep(4);
             ++spins;

@@ -403,6 +403,10 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     u.seed = seed; u.first_sample = first_sample;
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
     u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
+    // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
+    // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
+    // (the table has STACK_GROUPS words: a larger batch is one recording - check_windows refuses marks there)
+    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty())) ? (const unsigned*)e->d_wintab : nullptr;
     float* const xalt = chain && chain->x_out ? chain->x_out : e->xalt;
     TailPlan plan;
     plan.u = u; plan.x_out = xalt; plan.u_B = B;

@@ -20,7 +20,8 @@ DR_BOUNDS_TU(tail)
 //   T2  output projection -> x0 in the (B, T, 88) roll layout.  Items = 32-frame chunks (pw_body<1>; 88 rows: three
 //       of the four waves).  Output write-through.
 //   --  pair barrier (group barrier without guidance) + L1 invalidate; long-form windows (UpdateArgs::win_H) also wait for
-//       the neighbouring windows' T2 (neighbour_wait) - T3 reads their x0 on the shared frames
+//       the neighbouring windows' T2 (neighbour_wait) - T3 reads their x0 on the shared frames; only neighbours of the
+//       same recording count (UpdateArgs::win_tab)
 //   T3  per item (128-row tile of the input projection, 32-frame chunk) of the pair's clip: the classifier-free
 //       combine + posterior update of those 32 frames x 88 keys (update_quad: the arithmetic of update_kernel) into
 //       LDS - the item with row tile 0 also writes x_{t-1} back - then, when a step follows, its input projection
@@ -103,7 +104,13 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
         if (threadIdx.x == 0) {
             const unsigned epoch = (s.u.dyn ? s.u.dyn->epoch : 0u) + s.epoch;
             if (member == 0 && pair_half == 0) __hip_atomic_store(s.ready + pair_i, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            neighbour_wait(s.ready, pair_i, s.u_B, epoch, s.err, s.derr);
+            // the neighbours T3 reads: those of this window's recording (u.win_tab, written by an EARLIER launch of the
+            // stream: plain loads; null = the batch is one recording) - the same rule as update_quad's partners
+            const unsigned* tab = s.u.win_tab;
+            const bool mine = pair_i < s.u_B;
+            const bool lower = mine && (tab ? window_idx(tab[pair_i]) > 0 : pair_i > 0);
+            const bool upper = mine && pair_i + 1 < s.u_B && (!tab || window_idx(tab[pair_i + 1]) > 0);
+            neighbour_wait(s.ready, pair_i, lower, upper, epoch, s.err, s.derr);
         }
         __syncthreads();
     }
@@ -228,6 +235,7 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
     if (s.dual > 0 && s.NB != 2 * s.dual) return hipErrorInvalidValue;
     if (!s.x_out || s.x_out == s.u.x) return hipErrorInvalidValue;
     if (s.u.win_H > 0 && (!s.ready || s.u_B > STACK_GROUPS || 2 * s.u.win_H < s.T || s.u.win_H >= s.T)) return hipErrorInvalidValue;
+    if (s.u.win_tab && s.u.win_H <= 0) return hipErrorInvalidValue;      // (a table of u_B <= STACK_GROUPS words: windows only)
     const int tps = (s.T + s.BN - 1) / s.BN, MT = s.Cp >> 6;
     TailArgs b = s;
     const int NBp = xcd_padded_groups(s.NB, MT * tps, &b.xcd_n);       // idle padding groups, as launch_stack

@@ -20,6 +20,15 @@ hipError_t launch_set_dyn(DynParams* d, unsigned long long seed, int first_sampl
     return hipGetLastError();
 }
 
+__global__ __launch_bounds__(STACK_GROUPS) void set_windows_kernel(unsigned* d, const WindowTable tab, int n) {
+    if ((int)threadIdx.x < n) d[threadIdx.x] = tab.w[threadIdx.x];
+}
+hipError_t launch_set_windows(unsigned* d_tab, const WindowTable& tab, int n, hipStream_t s) {
+    if (!d_tab || n < 1 || n > STACK_GROUPS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(set_windows_kernel, dim3(1), dim3(STACK_GROUPS), 0, s, d_tab, tab, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s) {
     const long n4 = a.n / 4;
     hipLaunchKernelGGL(update_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a);

@@ -51,7 +51,7 @@ DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, c
 // Classifier-free combine + x0-prediction posterior update of ONE float4 (4 consecutive elements, index i4) of the
 // roll.  Same operation order as task/diffusion.py:953 and :957-967; contraction off so that no FMA is formed where
 // the reference rounds twice.  Shared by update_kernel and the tail kernel (identical arithmetic).
-// Long-form windows (a.win_H > 0, UpdateArgs): on a frame shared with a neighbouring window the prediction is the mean
+// Long-form windows (a.win_H > 0, UpdateArgs): on a frame shared with a neighbouring window of the same recording the prediction is the mean
 // 0.5f * (y_lower + y_upper) of both windows' guided predictions - the same bits in both (the operands are the same
 // two values, added in the same order) - and the noise is keyed by the canvas element.
 DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
@@ -71,16 +71,26 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
         const long o4 = a.per_sample / 4 - (long)a.win_H * 22;      // O frames x 22 quads: window b's frame f <-> b + 1's f - H
         long p4 = -1;
         bool upper = false;                                        // the partner is the upper window (b + 1)
-        if (f >= a.win_H && (smp + 1) * a.per_sample < a.n) { p4 = i4 + o4; upper = true; }
-        else if (f < (int)(o4 / 22) && smp > 0) p4 = i4 - o4;
+        // which neighbours exist, and this window's place on its canvas: one recording (rec 0, window smp of it), or the
+        // table's word (option "window_break": b + 1 shares frames with b unless it is the first window of a recording)
+        bool has_up = (smp + 1) * a.per_sample < a.n, has_lo = smp > 0;
+        long rec = 0, idx = smp;
+        if (a.win_tab) {
+            const unsigned me = a.win_tab[smp];
+            rec = window_rec(me); idx = window_idx(me);
+            has_lo = idx > 0;
+            has_up = has_up && window_idx(a.win_tab[smp + 1]) > 0;
+        }
+        if (f >= a.win_H && has_up) { p4 = i4 + o4; upper = true; }
+        else if (f < (int)(o4 / 22) && has_lo) p4 = i4 - o4;
         if (p4 >= 0) {
             float yp[4];
             guided_quad(a, p4, gw, g1pw, yp);
 #pragma unroll
             for (int e = 0; e < 4; ++e) x0[e] = upper ? 0.5f * (x0[e] + yp[e]) : 0.5f * (yp[e] + x0[e]);
         }
-        key_smp = first_sample;
-        key_q = (smp * a.win_H * 88 + within) >> 2;
+        key_smp = first_sample + rec;
+        key_q = (idx * a.win_H * 88 + within) >> 2;
     }
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];

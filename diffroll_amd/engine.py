@@ -328,17 +328,28 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'sampling_steps' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'sampling_steps' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
         self._check(fn(self.h, name.encode(), int(value)))
         if name == "window_overlap":
             self.window_overlap = int(value)
+        if name == "window_break":        # b >= 1 adds a mark, 0 clears them all
+            self.window_breaks = tuple(sorted(set(self.window_breaks) | {int(value)})) if int(value) else ()
         if name == "sampling_steps":
             self.sampling_steps = int(value)
 
+    def set_window_breaks(self, marks):
+        """Replace the marks of option 'window_break' (the windows of the next batch that start a new recording)."""
+        self.set_option("window_break", 0)
+        for b in marks:
+            if int(b) < 1:
+                raise ValueError(f"window_break mark {b}: marks are >= 1 (window 0 always starts a recording)")
+            self.set_option("window_break", int(b))
+
     window_overlap = 0      # the last value set for option 'window_overlap' (0 = off, the library's default)
+    window_breaks = ()      # the marks set with option 'window_break' (windows that start a new recording), ascending
     sampling_steps = 0      # the last value set for option 'sampling_steps' (0 = every step, the library's default)
 
     def visited_steps(self):

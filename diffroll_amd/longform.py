@@ -11,6 +11,9 @@ Definitions (include/diffroll_amd.h, option "window_overlap"):
     0.5f * (y_b + y_b+1), the mean of their guided x0 predictions, before the posterior update; noise is drawn per
     canvas frame.  If x_T agrees on shared frames, every x_t does, bit for bit, so the stitched roll is a plain gather
     from the canvas (stitch), sliced to T_out.
+  * several recordings in one chain (option "window_break", plan_batch): the windows of the recordings one after another;
+    a window shares frames only with windows of its own recording, and recording r of the batch draws the noise of
+    first_sample + r on its own canvas - each recording's roll is what a chain of its own would give.
 """
 from __future__ import annotations
 
@@ -79,6 +82,65 @@ def stitch(windows: torch.Tensor, plan: WindowPlan) -> torch.Tensor:
     return torch.cat(parts, dim=-2)[..., :plan.T_out, :]
 
 
+@dataclass(frozen=True)
+class BatchPlan:
+    """Several recordings in ONE chain (option "window_break"): recording r owns windows [first[r], first[r] + plans[r].n)
+    of the batch; marks = the first window of every recording but the first."""
+    plans: List[WindowPlan]
+    first: List[int]
+    marks: List[int]
+    n: int                   # windows in the batch
+
+
+def plan_batch(lengths_or_frames: Sequence[int], hop: Optional[int], T: int = WINDOW_FRAMES,
+               overlap: int = DEFAULT_OVERLAP) -> BatchPlan:
+    """plan_windows of every recording (lengths in samples, or frame counts when hop is None) and where each sits in the
+    window batch of one chain."""
+    plans = [plan_windows(L, hop, T, overlap) for L in lengths_or_frames]
+    if not plans:
+        raise ValueError("no recordings")
+    first, n = [], 0
+    for p in plans:
+        first.append(n)
+        n += p.n
+    return BatchPlan(plans=plans, first=first, marks=first[1:], n=n)
+
+
+def gather_batch(canvases: Sequence[torch.Tensor], batch: BatchPlan) -> torch.Tensor:
+    """Per-recording canvases (..., T_c_r, 88) -> the chain's window batch (..., n, T, 88): gather_windows per recording,
+    recordings in order."""
+    if len(canvases) != len(batch.plans):
+        raise ValueError(f"{len(canvases)} canvases for {len(batch.plans)} recordings")
+    return torch.cat([gather_windows(c, p) for c, p in zip(canvases, batch.plans)], dim=-3)
+
+
+def stitch_batch(windows: torch.Tensor, batch: BatchPlan) -> List[torch.Tensor]:
+    """The chain's window batch (..., n, T, 88) -> one roll (..., T_out_r, 88) per recording (stitch per recording)."""
+    if windows.shape[-3] != batch.n:
+        raise ValueError(f"{windows.shape[-3]} windows, the batch plan has {batch.n}")
+    return [stitch(windows[..., f:f + p.n, :, :], p) for f, p in zip(batch.first, batch.plans)]
+
+
+def pack_chains(window_counts: Sequence[int], max_recordings: int, max_windows: int = MAX_WINDOWS) -> List[List[int]]:
+    """Recordings (by their window counts, in file order) -> chains, greedily: a chain is a run of at most max_recordings
+    consecutive recordings, closed early when the next one would take its windows past max_windows.  Returns the
+    recording indices of each chain.  A single recording above max_windows cannot be placed: ValueError."""
+    if max_recordings < 1:
+        raise ValueError(f"max_recordings {max_recordings}: at least 1")
+    chains: List[List[int]] = []
+    total = 0
+    for i, n in enumerate(window_counts):
+        if n > max_windows:
+            raise ValueError(f"recording {i}: {n} windows, one chain holds at most {max_windows} (longform.MAX_WINDOWS); "
+                             f"split the recording")
+        if not chains or len(chains[-1]) >= max_recordings or total + n > max_windows:
+            chains.append([])
+            total = 0
+        chains[-1].append(i)
+        total += n
+    return chains
+
+
 _T = TypeVar("_T")
 
 
@@ -87,3 +149,8 @@ def deal(items: Sequence[_T], rank: int, world: int) -> List[_T]:
     if world < 1 or not 0 <= rank < world:
         raise ValueError(f"rank {rank} of world {world}")
     return list(items[rank::world])
+
+
+def deal_chains(chains: Sequence[_T], rank: int, world: int) -> List[_T]:
+    """Round-robin dealing of CHAINS (pack_chains) to ranks: the recordings of a chain stay together on one rank."""
+    return deal(chains, rank, world)

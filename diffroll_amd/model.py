@@ -17,7 +17,7 @@ What is deliberately different from the reference:
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -555,6 +555,65 @@ class ClassifierFreeDiffRoll(nn.Module):
         finally:
             eng.set_option("window_overlap", prev)
         return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
+
+    @torch.no_grad()
+    def sample_long_batch(self, waveforms=None, frames=None, overlap: int = 160, seed: int = 0, first_recording: int = 0,
+                          x_T=None, noise=None, use_graph: bool = True, check: bool = True) -> List[torch.Tensor]:
+        """Several recordings of any lengths in ONE chain (option "window_break" of include/diffroll_amd.h;
+        longform.plan_batch): their windows fill one batch, a window shares frames only with windows of its own
+        recording, and recording i draws the noise of first_sample = first_recording + i on its own canvas.  Returns one
+        stitched roll (1, 1, T_out_i, 88) per recording; roll i is what sample_long(waveforms[i], seed=seed,
+        recording=first_recording + i) returns (bit for bit where both chains take the same kernel flavours).
+        waveforms: a sequence of (L_i,) tensors; generation_ddpm_x0 takes frames = a sequence of roll lengths instead.
+        x_T / noise: None, or one canvas per recording in sample_long's shapes ((1, 1, T_c_i, 88) /
+        (timesteps, 1, 1, T_c_i, 88)); the default x_T of every recording is sample_long's for this seed."""
+        from . import longform
+        sampler = self.hparams.sampling.type
+        if sampler == "inpainting_ddpm_x0":
+            raise ValueError("sample_long_batch does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) "
+                             "are in the coordinates of one 640-frame clip, not of a recording")
+        eng = self.engine
+        if sampler == "generation_ddpm_x0":
+            if frames is None or waveforms is not None:
+                raise ValueError("generation_ddpm_x0: pass frames= (the roll lengths), not waveforms")
+            batch = longform.plan_batch([int(f) for f in frames], None, longform.WINDOW_FRAMES, overlap)
+        else:
+            if waveforms is None or frames is not None:
+                raise ValueError(f"{sampler}: pass waveforms= (a sequence of (L,) recordings), not frames")
+            waveforms = [torch.as_tensor(wv).to("cpu", torch.float32) for wv in waveforms]
+            for wv in waveforms:
+                if wv.dim() != 1:
+                    raise ValueError(f"every waveform must be one recording (L,), got {tuple(wv.shape)}")
+            batch = longform.plan_batch([wv.shape[0] for wv in waveforms], eng.hop_length, longform.WINDOW_FRAMES, overlap)
+        if batch.n > longform.MAX_WINDOWS:
+            raise ValueError(f"{batch.n} windows in {len(batch.plans)} recordings: one chain holds at most "
+                             f"{longform.MAX_WINDOWS} (longform.MAX_WINDOWS); use fewer recordings per chain (longform.pack_chains)")
+        R, S = len(batch.plans), int(self.hparams.timesteps)
+        if x_T is None:
+            x_T = [torch.randn(1, 1, p.T_c, 88, generator=torch.Generator().manual_seed(int(seed))) for p in batch.plans]
+        if len(x_T) != R or any(tuple(x.shape) != (1, 1, p.T_c, 88) for x, p in zip(x_T, batch.plans)):
+            raise ValueError(f"x_T must be one canvas (1, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
+        xb = longform.gather_batch([x.reshape(p.T_c, 88).to(eng.device, torch.float32) for x, p in zip(x_T, batch.plans)], batch)
+        z = None
+        if noise is not None:
+            if len(noise) != R or any(zr.numel() != S * p.T_c * 88 for zr, p in zip(noise, batch.plans)):
+                raise ValueError(f"noise must be one canvas ({S}, 1, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
+            z = longform.gather_batch([zr.reshape(S, p.T_c, 88).to(eng.device, torch.float32)
+                                       for zr, p in zip(noise, batch.plans)], batch).contiguous()
+        if sampler != "generation_ddpm_x0":
+            eng.frontend(torch.cat([longform.window_audio(wv, p, eng.hop_length) for wv, p in zip(waveforms, batch.plans)]),
+                         longform.WINDOW_FRAMES)
+            self._fe_key = None          # the engine's conditioner is the windows' now: sample() recomputes its own
+        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
+        prev_overlap, prev_marks = eng.window_overlap, eng.window_breaks
+        eng.set_option("window_overlap", batch.plans[0].overlap)
+        try:
+            eng.set_window_breaks(batch.marks)
+            eng.sample(sampler, xb, z, w, seed, first_recording, use_graph, check)
+        finally:
+            eng.set_window_breaks(prev_marks)
+            eng.set_option("window_overlap", prev_overlap)
+        return [r.reshape(1, 1, p.T_out, 88) for r, p in zip(longform.stitch_batch(xb, batch), batch.plans)]
 
     def sample_trajectory(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0):
         """The same chain, keeping every intermediate roll on the device: returns (trajectory (n, B, 1, T', 88) with

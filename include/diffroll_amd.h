@@ -348,6 +348,19 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          bit: the stitched roll is a plain gather from the canvas.  O > T / 2 -> DR_EINVAL at the call
  *                          (at most two windows share a frame).  dr_forward / dr_forward_steps are unaffected; 0 = off
  *                          (every clip on its own, bit-identical to an engine that never set it).
+ *   "window_break"    [-]  recording boundaries inside a window batch: SEVERAL recordings in one chain.  Value b >= 1 marks
+ *                          window b of the next dr_step / dr_sample / dr_sample_checked batches as the FIRST window of a new
+ *                          recording (marks accumulate; window 0 always starts one); value 0 clears all marks; a negative
+ *                          value -> DR_EINVAL.  Marks are engine state like "window_overlap" and are ignored while that is
+ *                          0.  With marks m_1 < m_2 < ... window b belongs to recording r(b) = the number of marks <= b
+ *                          and is window i(b) = b - (first window of r(b)) of that recording's own canvas: windows b and
+ *                          b + 1 share frames only if r(b) == r(b + 1), and Philox is keyed (seed, first_sample + r(b), t,
+ *                          (i(b) * H * 88 + element within the window) / 4) - every recording gets exactly the roll of a
+ *                          chain of its own with first_sample + r.  No marks = one recording, the definition above.  A mark
+ *                          >= B -> DR_EINVAL at the call (and a batch with marks holds at most 512 windows).  The marks are
+ *                          data of a captured chain, not part of it: setting them does NOT drop it, and a new
+ *                          segmentation at the same (sampler, B, T) replays the same graph.  dr_sample_checked's re-run
+ *                          uses the same marks; dr_forward / dr_forward_steps are unaffected.
  *   "sampling_steps"   [0] n, 2 <= n < timesteps (S): a RESPACED reverse chain of n network steps instead of S.  Visited
  *                          steps t_i = (2 i (S - 1) + (n - 1)) / (2 (n - 1)) in integer arithmetic (linspace rounded half
  *                          up), i = n-1 .. 0: strictly decreasing from S - 1 to 0; t' = the next visited step.  The row of
