@@ -12,7 +12,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DR_LIB") or os.path.join(_HERE, "lib", "libdiffroll_amd.so")   # DR_LIB: measurement builds
 
-DR_ABI_VERSION = 10
+DR_ABI_VERSION = 11
 DR_OK, DR_EINVAL, DR_ESTATE, DR_EHIP, DR_ENOMEM, DR_ENAME, DR_ETIMEOUT = 0, -1, -2, -3, -4, -5, -6
 
 SAMPLERS = {
@@ -45,7 +45,7 @@ DEBUG_EXPORTS = [
     "dr_bench_layer", "dr_bench_pointwise",
 ]
 # the options dr_set_option knows; every other name goes to dr_debug_set_option (Engine.set_option)
-PUBLIC_OPTIONS = ("blocked_accumulation", "fused_rearm", "fused_stack", "fused_tail", "window_overlap", "window_break", "sampling_steps")
+PUBLIC_OPTIONS = ("blocked_accumulation", "fused_rearm", "fused_stack", "fused_tail", "window_overlap", "window_break", "sampling_steps", "draws", "draw_stride")
 MODES = {0: "none", 1: "per_phase", 2: "fused_stack", 3: "fused_stack+tail"}
 
 

@@ -113,6 +113,10 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
                               or not (steps == 0 or 2 <= steps <= S)):
         raise SystemExit(f"task.sampling.steps must be an integer in [2, task.timesteps = {S}] (or 0 / null: every "
                          f"step), got {steps!r}")
+    # task.sampling.draws=D: D rolls per clip in one chain (option "draws"); their mean is exported; absent / null / 1 = one
+    draws = cfg["task"]["sampling"].get("draws")
+    if draws is not None and (isinstance(draws, bool) or not isinstance(draws, int) or draws < 1):
+        raise SystemExit(f"task.sampling.draws must be an integer >= 1 (or null: one roll per clip), got {draws!r}")
     per_chain = cfg["task"].get("recordings_per_chain", 1)
     if isinstance(per_chain, bool) or not isinstance(per_chain, int) or per_chain < 1:
         raise SystemExit(f"task.recordings_per_chain must be an integer >= 1, got {per_chain!r}")
@@ -176,9 +180,15 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
     hop = int(cfg["hop_length"])
     out = cfg["output_dir"]
     written = []
+    D = int(cfg["task"]["sampling"].get("draws") or 1)
+    more = {"draws": D} if D > 1 else {}
 
     def write(path, roll):
         stem = os.path.splitext(os.path.basename(path))[0]
+        if D > 1:       # (D, 1, T_out, 88): the mean roll takes the single roll's place, the votes go next to it
+            from .ensemble import aggregate
+            roll, votes, _ = aggregate(roll, D, float(cfg["task"]["frame_threshold"]))
+            np.save(os.path.join(out, f"votes_{stem}.npy"), votes.cpu().numpy())
         roll_path = os.path.join(out, f"roll_{stem}.npy")
         np.save(roll_path, roll.cpu().numpy())
         written.append(roll_path)
@@ -200,9 +210,9 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
             seed = int(cfg["seed"]) + j
             if generation:
                 rolls = model.sample_long_batch(frames=[-(-wavs[i].shape[0] // hop) for i in chain], overlap=overlap,
-                                                seed=seed, first_recording=j)
+                                                seed=seed, first_recording=j, **more)
             else:
-                rolls = model.sample_long_batch([wavs[i] for i in chain], overlap=overlap, seed=seed, first_recording=j)
+                rolls = model.sample_long_batch([wavs[i] for i in chain], overlap=overlap, seed=seed, first_recording=j, **more)
             for i, roll in zip(chain, rolls):
                 write(files[i], roll)
         return written
@@ -210,9 +220,9 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
         wav = ingest(path, int(args["sample_rate"]), None)
         seed = int(cfg["seed"]) + i
         if generation:          # (the waveform is ignored, sampling.py:45: a roll of the recording's length)
-            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i)
+            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i, **more)
         else:
-            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i)
+            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i, **more)
         write(path, roll)
     return written
 
@@ -300,6 +310,10 @@ def main(argv: List[str] = None, default_task: str = "generation") -> None:
     else:                                                        # generation: waveform is ignored (sampling.py:45)
         waveform = torch.zeros(S, int(cfg["sequence_length"]))
     x = torch.randn(S, 1, T, 88, generator=g)                    # x_T drawn on the host like sampling.py:27
+    # task.sampling.draws=D: draw 0 starts from that x_T, draws 1 .. D-1 from the next draws of the SAME generator (never the
+    # x_T of a run with a neighbouring seed)
+    D = int(cfg["task"]["sampling"].get("draws") or 1)
+    x_more = [torch.randn(S, 1, T, 88, generator=g) for _ in range(1, D)]
     bs = int(cfg["dataloader"]["batch_size"])
     if S < bs:
         warnings.warn(f"Batch size is larger than total number of audio clips. Forcing batch size to {S}")
@@ -316,7 +330,15 @@ def main(argv: List[str] = None, default_task: str = "generation") -> None:
     for bi, lo in enumerate(range(0, S, bs)):
         hi = min(lo + bs, S)
         tb = time.perf_counter()
-        roll = sample_sharded(model, x[lo:hi], waveform[lo:hi], seed=int(cfg["seed"]) + bi)
+        if D > 1:
+            from .ensemble import aggregate
+            rolls = sample_sharded(model, torch.cat([x[lo:hi]] + [xm[lo:hi] for xm in x_more], 0), waveform[lo:hi],
+                                   seed=int(cfg["seed"]) + bi, draws=D)
+            roll, votes, _ = aggregate(rolls, D, float(cfg["task"]["frame_threshold"]))
+            if rank == 0:
+                np.save(os.path.join(cfg["output_dir"], f"votes_batch{bi}.npy"), votes.cpu().numpy())
+        else:
+            roll = sample_sharded(model, x[lo:hi], waveform[lo:hi], seed=int(cfg["seed"]) + bi)
         batch_s.append(time.perf_counter() - tb)
         if rank == 0:
             np.save(os.path.join(cfg["output_dir"], f"rolls_batch{bi}.npy"), roll.cpu().numpy())

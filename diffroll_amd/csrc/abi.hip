@@ -147,9 +147,16 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
         int rc = ensure_s3(e);
         if (rc) return rc;
     }
-    if (sampler != DR_SAMPLER_GENERATION_DDPM_X0 && (e->fe_B != B || e->fe_T != T))
+    // option "draws": the B rolls are D draws of B / D clips, and the front-end ran on the clips
+    const int D = e->opt_draws;
+    if (B % D) return fail(e, DR_EINVAL, "B=%d rolls are not a whole number of draws (option draws = %d)", B, D);
+    if (sampler != DR_SAMPLER_GENERATION_DDPM_X0 && (e->fe_B != B / D || e->fe_T != T)) {
+        if (D > 1)
+            return fail(e, DR_ESTATE, "dr_frontend(B=%d,T=%d) must precede a conditional evaluation of %d draws of B/draws=%d clips (B=%d,T=%d)",
+                        e->fe_B, e->fe_T, D, B / D, B, T);
         return fail(e, DR_ESTATE, "dr_frontend(B=%d,T=%d) must precede a conditional evaluation with B=%d,T=%d",
                     e->fe_B, e->fe_T, B, T);
+    }
     return DR_OK;
 }
 
@@ -158,11 +165,22 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
 int check_windows(dr_engine* e, int B, int T) {
     if (2 * e->opt_win_O > T)
         return fail(e, DR_EINVAL, "window_overlap %d exceeds half the window (T = %d frames)", e->opt_win_O, T);
+    const int D = e->opt_draws, n = B / D;      // (option "draws": the marks are those of one draw and repeat per draw)
     if (e->opt_win_O > 0 && !e->win_marks.empty()) {
-        if (e->win_marks.back() >= B)
+        if (e->win_marks.back() >= n) {
+            if (D > 1)
+                return fail(e, DR_EINVAL, "window_break %d is not a window of one draw (B = %d windows in %d draws of %d)", e->win_marks.back(), B, D, n);
             return fail(e, DR_EINVAL, "window_break %d is not a window of this batch (B = %d windows)", e->win_marks.back(), B);
+        }
         if (B > STACK_GROUPS)
             return fail(e, DR_EINVAL, "window_break: a batch with recording boundaries holds at most %d windows, got B = %d", STACK_GROUPS, B);
+    }
+    if (e->opt_win_O > 0 && D > 1) {
+        if (B > STACK_GROUPS)
+            return fail(e, DR_EINVAL, "draws: a window batch of several draws holds at most %d windows, got B = %d", STACK_GROUPS, B);
+        const long R = (long)e->win_marks.size() + 1, G = e->opt_draw_G > 0 ? e->opt_draw_G : R;
+        if ((D - 1) * G + R > 65536)
+            return fail(e, DR_EINVAL, "draws: %d draws at key stride %ld do not fit the window table (sample key offsets < 65536)", D, G);
     }
     return DR_OK;
 }
@@ -171,12 +189,18 @@ int check_windows(dr_engine* e, int B, int T) {
 // that read it: an eager sequence with marks, and every launch of a captured chain (force: its graph holds the table's
 // address whether or not marks were set when it was captured).  Without marks: window b of recording 0.
 int write_windows(dr_engine* e, int B, bool force, hipStream_t st) {
-    if (e->opt_win_O <= 0 || B > STACK_GROUPS || (!force && e->win_marks.empty())) return DR_OK;
+    if (e->opt_win_O <= 0 || B > STACK_GROUPS || (!force && e->win_marks.empty() && e->opt_draws <= 1)) return DR_OK;
     WindowTable tab;
+    // option "draws": every draw starts new recordings, and draw d of recording r is keyed first_sample + r + d * stride
+    // (the recordings of one draw, or option "draw_stride")
+    const int n = B / e->opt_draws;
+    const size_t stride = e->opt_draw_G > 0 ? (size_t)e->opt_draw_G : e->win_marks.size() + 1;
     size_t m = 0;
     for (int b = 0, first = 0; b < B; ++b) {
-        if (m < e->win_marks.size() && e->win_marks[m] == b) { ++m; first = b; }
-        tab.w[b] = window_entry((unsigned)m, (unsigned)(b - first));
+        const int j = b % n;
+        if (j == 0) { m = 0; first = b; }
+        if (m < e->win_marks.size() && e->win_marks[m] == j) { ++m; first = b; }
+        tab.w[b] = window_entry((unsigned)((size_t)(b / n) * stride + m), (unsigned)(b - first));
     }
     HIPCHK(e, launch_set_windows(e->d_wintab, tab, B, st));
     return DR_OK;
@@ -256,6 +280,18 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value == 0) { e->win_marks.clear(); return DR_OK; }
         auto at = std::lower_bound(e->win_marks.begin(), e->win_marks.end(), value);
         if (at == e->win_marks.end() || *at != value) e->win_marks.insert(at, value);
+        return DR_OK;
+    }
+    if (n == "draws") {      // (B % D and the front-end's batch are checked by the calls, which know B)
+        // (no captured chain is dropped: the value is part of the chain's key - GraphKey - so a chain captured under
+        // another value is simply not replayed, and one captured under this value still is)
+        if (value < 1) return fail(e, DR_EINVAL, "draws is >= 1 (1 = every roll its own clip), got %d", value);
+        e->opt_draws = value;
+        return DR_OK;
+    }
+    if (n == "draw_stride") {
+        if (value < 0) return fail(e, DR_EINVAL, "draw_stride is >= 0 (0 = the clips of the batch), got %d", value);
+        e->opt_draw_G = value;
         return DR_OK;
     }
     if (n == "sampling_steps") {
@@ -598,6 +634,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
 
     GraphKey key;
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
+    key.draws = e->opt_draws; key.draw_G = e->opt_draws > 1 ? e->opt_draw_G : 0; key.fe_B = e->fe_B;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

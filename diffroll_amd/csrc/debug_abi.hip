@@ -93,7 +93,8 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
     if (layer < 0 || layer >= e->L || t < 0 || t >= e->S || n_cond < 0 || n_cond > NB)
         return fail(e, DR_EINVAL, "bad argument");
-    if (n_cond > 0 && (e->fe_B < n_cond || e->fe_T != T)) return fail(e, DR_ESTATE, "dr_frontend needed for n_cond > 0");
+    // (option "draws": the conditional rows are draws x the clips of the last dr_frontend, read modulo fe_B)
+    if (n_cond > 0 && ((long)e->fe_B * e->opt_draws < n_cond || e->fe_T != T)) return fail(e, DR_ESTATE, "dr_frontend needed for n_cond > 0");
     DeviceGuard guard(e->cfg.device);
     int rc = ensure_workspace(e, NB, T);
     if (rc) return rc;
@@ -110,6 +111,7 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     (void)t;
     a.cond = e->cond ? e->cond + (size_t)layer * e->fe_B * 2 * Cp * T : e->cond_dummy;
     a.c_bs = (long)2 * Cp * T;
+    a.c_n = e->fe_B;
     a.n_cond = n_cond;
     p4_out(a, e->g, P, T, Cp);
     if (e->prec) { a.Y = e->g3; a.y_bs = s3_bs; a.out_s3 = 1; }

@@ -66,7 +66,9 @@ static void check_gemm_extents(const GemmArgs& a, int epi, int prec, const char*
     const long planes = (a.y_rows + 3) / 4;
     if (!(a.out_s3 & 1)) host_extent(a.Y, (size_t)((nby - 1) * a.y_bs + (planes - 1) * a.y_ps + (long)(a.T - 1) * a.y_fs + 4) * 4, "Y", kernel);
     if (a.Y2 && !(a.out_s3 & 2)) host_extent(a.Y2, (size_t)((nby - 1) * a.y2_bs + (planes - 1) * a.y_ps + (long)(a.T - 1) * a.y_fs + 4) * 4, "Y2", kernel);
-    if (epi == EPI_GATE && a.cond) host_extent(a.cond, (size_t)((long)(a.n_cond > 1 ? a.n_cond - 1 : 0) * a.c_bs + (long)mts * 128 * a.T) * 4, "conditioner", kernel);
+    // (the conditional samples read tensors c_b0 .. c_b0 + n_cond - 1, wrapped into the c_n clips when c_n > 0)
+    const long c_hi = a.c_b0 + (a.n_cond > 1 ? a.n_cond - 1 : 0), c_last = (a.c_n > 0 && c_hi >= a.c_n) ? a.c_n - 1 : c_hi;
+    if (epi == EPI_GATE && a.cond) host_extent(a.cond, (size_t)(c_last * a.c_bs + (long)mts * 128 * a.T) * 4, "conditioner", kernel);
     if (epi == EPI_GATE && a.cond2) host_extent(a.cond2, (size_t)mts * 128 * a.T * 4, "conditioner (shared)", kernel);
     if (epi == EPI_RES_SKIP && a.skip && mts * 128 > a.y_rows)
         host_extent(a.skip, (size_t)((long)(a.NB - 1) * a.s_bs + (long)(mts * 128 - a.y_rows) * a.T) * 4, "skip", kernel);

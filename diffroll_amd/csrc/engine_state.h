@@ -55,8 +55,14 @@ struct GraphKey {
     float* x = nullptr;
     const float* noise = nullptr;
     bool w_zero = false;        // guidance weight 0 captures a different (conditional-only) chain
+    // A captured chain also bakes the clip count of the conditioner tensors (GemmArgs::c_n and the per-layer offsets
+    // l * fe_B * 2 Cp T) and the draw layout of the update's Philox keys (UpdateArgs::draw_n / draw_G): options "draws" /
+    // "draw_stride" do not drop the chain, they are part of its key (a façade that sets them around every call replays
+    // one graph), and so is fe_B - dr_frontend drops the chain when it changes, the key keeps that from being load-bearing.
+    int draws = 1, draw_G = 0, fe_B = 0;
     bool operator==(const GraphKey& o) const {
-        return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero;
+        return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
+               draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B;
     }
 };
 
@@ -181,6 +187,8 @@ struct dr_engine {
     // stream, so the rewrite starts only when every launch of the earlier chain has finished - and an engine is used
     // from one stream at a time (diffroll_amd.h), as d_dyn, xwork and the activation workspace already require.
     drh::DevBuf<unsigned> d_wintab;
+    int opt_draws = 1;                  // option "draws": D > 1 = the B rolls are D draws of the B / D clips of the last dr_frontend, draw-major
+    int opt_draw_G = 0;                 // option "draw_stride": Philox key distance between two draws of a clip; 0 = the clips of the batch
     int opt_steps = 0;                  // option "sampling_steps": n of a respaced chain; 0 (and S) = every step
     std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
     drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor

@@ -28,6 +28,13 @@ DR_DEVINL void skip_quad(const float (&v)[4], const float4 bias, const float4 pr
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = skip_init ? v[e] + bb[e] : (v[e] + bb[e]) + pv[e];
 }
+// The conditioner tensor conditional sample b of a launch reads (GemmArgs::c_b0 / c_n): once per (tile, sample), and the
+// division only where a row lies past the clips (option "draws" > 1)
+DR_DEVINL long cond_row(const GemmArgs& a, const int b) {
+    int r = a.c_b0 + b;
+    if (a.c_n > 0 && r >= a.c_n) r %= a.c_n;
+    return r;
+}
 // y = conv + b_conv + (Wc spec + bc), gate = first half, filter = second   [model/diffwave.py:143-147]: v0 / v1 = the
 // gate / filter rows of the same 4 channels; samples without a conditioner (has_c = false) carry the constant
 // unconditional one inside their bias
@@ -621,6 +628,12 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
 #pragma unroll 1
     for (int pass = 0; pass < npass; ++pass) {
         const int be = b + pass * a.dual;
+        // conditioner tensor of this (tile, sample), frame 0: the sample's clip (cond_row), or for samples >= n_cond the
+        // shared learned unconditional conditioner (condition='trainable_spec') when there is one, else clip 0's tensor
+        // as a readable dummy
+        const float* cbase = nullptr;
+        if constexpr (EPI == EPI_GATE)
+            cbase = (be < a.n_cond || !a.cond2) ? a.cond + (be < a.n_cond ? cond_row(a, be) : 0L) * a.c_bs : a.cond2;
         float4 ebias[4];                            // [q]
         float4 ed2[4];                              // second-output offset (step embedding of the next conv)
         {
@@ -651,9 +664,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                 // conditioner quads of this frame column: one unconditional batch (unconditional samples read
                 // sample 0's tensor - valid memory - and ignore it)
                 const int tc = min(t, a.T - 1);
-                // samples >= n_cond: the shared learned unconditional conditioner (condition='trainable_spec') when
-                // there is one, else sample 0's tensor as a readable dummy
-                const float* cb = ((be < a.n_cond || !a.cond2) ? a.cond + (long)(be < a.n_cond ? be : 0) * a.c_bs : a.cond2) + (long)tc * 4;
+                const float* cb = cbase + (long)tc * 4;
     #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int p0 = mt * 128 + wave * 32 + 8 * q + 4 * hi;
@@ -1066,6 +1077,9 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
     // epilogue: per (row tile, column tile) a lane owns rows rowbase + kq*4 .. +3 of frame column li
     const int rowb = mt * 128 + wave * 32 + kq * 4;     // + rt*16
     float4 ebias[RT], ed2[RT];
+    const float* cbase = nullptr;           // EPI_GATE: the sample's conditioner tensor, frame 0 (as in gemm_body)
+    if constexpr (EPI == EPI_GATE)
+        cbase = (b < a.n_cond || !a.cond2) ? a.cond + (b < a.n_cond ? cond_row(a, b) : 0L) * a.c_bs : a.cond2;
     {
         const float* bsrc = a.bias;
         if constexpr (EPI == EPI_GATE) bsrc = (b < a.n_cond) ? a.bias : a.bias2;
@@ -1082,7 +1096,7 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
         if constexpr (EPI == EPI_GATE) {
             float4 cnd[RT];
             const int tc = min(t, a.T - 1);
-            const float* cb = ((b < a.n_cond || !a.cond2) ? a.cond + (long)(b < a.n_cond ? b : 0) * a.c_bs : a.cond2) + (long)tc * 4;
+            const float* cb = cbase + (long)tc * 4;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) cnd[rt] = *reinterpret_cast<const float4*>(cb + (long)((rowb + rt * 16) >> 2) * a.T * 4);
             if (t >= a.T) continue;

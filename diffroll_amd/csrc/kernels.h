@@ -87,6 +87,9 @@ struct GemmArgs {
     const float* cond;       // EPI_GATE: [n_cond][MT*32 planes][T][4] in packed-row order; must point at valid memory
                              // of at least one sample even when n_cond == 0 (prefetched unconditionally, then ignored)
     long c_bs;
+    int c_b0, c_n;           // EPI_GATE: conditional sample b reads conditioner tensor c_b0 + b, taken modulo c_n when c_n > 0:
+                             // the launch's first row in the roll batch and the clips of the last dr_frontend (option "draws":
+                             // row b of the batch is draw b / n of clip b % n; a sample chunk may start inside a draw and wrap)
     const float* cond2;      // EPI_GATE, optional: one conditioner tensor [MT*32 planes][T][4] shared by all samples >= n_cond
                              // (the learned unconditional spectrogram of condition='trainable_spec'); null: they use bias2 only
     int n_cond;
@@ -153,6 +156,7 @@ struct StackArgs {
     const float* zero;                        // device zero vector (never-null operands)
     int NB, T, Cp, taps, n_cond, L;
     long c_bs;
+    int c_b0, c_n;                            // first row of this chunk in the roll batch / clips of the conditioner (GemmArgs)
     int p0, p1;                               // phases [p0, p1)
     int xcd_n;                                // block -> (M tile, frame tile) mapping, as in gemm_kernel
     int rs_off;                               // set by the launcher: LDS byte offset of the resident h / skip tile
@@ -213,8 +217,13 @@ struct UpdateArgs {
     // above is recording r's own ((n_r - 1) * win_H + T frames, window b at frame i * win_H) and Philox is keyed
     // (seed, first_sample + r, t, canvas element of recording r / 4).
     const unsigned* win_tab;
+    // Option "draws" (D > 1; draw_n = 0: off): roll b is draw b / draw_n of clip b % draw_n and its Philox sample key is
+    // first_sample + b % draw_n + (b / draw_n) * draw_G (draw_G = draw_n unless option "draw_stride" says otherwise).  Windows
+    // (win_H > 0) carry the draw in their table word instead: win_tab is then always set.
+    int draw_n, draw_G;
 };
-// one word per window: recording ordinal and index within the recording, both < STACK_GROUPS
+// one word per window: Philox key offset of its recording (the ordinal in the batch; + draw x stride under option "draws":
+// < 65536) and index within the recording (< STACK_GROUPS)
 constexpr unsigned window_entry(unsigned rec, unsigned idx) { return (rec << 16) | idx; }
 constexpr int window_rec(unsigned w) { return (int)(w >> 16); }
 constexpr int window_idx(unsigned w) { return (int)(w & 0xFFFFu); }
@@ -245,6 +254,7 @@ struct TailArgs {
     // the next step's shared first-layer conv (dual > 0 and in_w set; conv_w null: none): layer 0 as in StackLayer
     const float *conv_w, *conv_b, *conv_b2, *cond, *cond2;
     long c_bs;
+    int c_n;                                  // clips of the conditioner (GemmArgs::c_n)
     int taps, dil;
     int fold;                                 // blocked accumulation in that conv (gemm_body.h), as the stack launch that follows
     int t4_ni;                                // in: 0 = the launcher chooses T4's item width, 1 / 3 = force 64 / 96 frames; the launcher sets 1 or 3

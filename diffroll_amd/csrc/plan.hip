@@ -151,6 +151,9 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
         sa.NB = nb; sa.T = T; sa.Cp = Cp; sa.taps = e->K; sa.L = L;
         sa.n_cond = std::max(0, std::min(nb, v.n_cond - b0));
         sa.c_bs = c_bs;
+        // conditional sample b of this chunk is row b0 + b of the roll batch and reads clip (b0 + b) % fe_B (option "draws":
+        // a chunk may start inside a draw and wrap); the layers' pointers below are the tensors' un-offset bases
+        sa.c_b0 = b0 < v.n_cond ? b0 : 0; sa.c_n = e->fe_B;
         sa.p0 = p0; sa.p1 = p1;
         sa.xcd_n = e->opt_stack_xcd;
         sa.warm = e->opt_stack_warm;
@@ -165,10 +168,8 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
             y.conv_b2 = v.zero_spec ? w.conv_b_z : w.conv_b_u;
             y.cond2 = nullptr;
             if (e->cond_tr && !v.zero_spec) { y.cond2 = e->cond_tr + (size_t)l * 2 * Cp * T; y.conv_b2 = w.conv_b; }
-            // conditional samples of this chunk start at sample b0 of the layer's conditioner tensor (a chunk
-            // without any keeps a readable pointer: the kernel prefetches, then ignores it)
-            y.cond = e->cond ? e->cond + (size_t)l * e->fe_B * 2 * Cp * T + (b0 < v.n_cond ? (size_t)b0 * c_bs : 0)
-                             : e->cond_dummy;
+            // (a chunk without conditional samples keeps a readable pointer: the kernel prefetches, then ignores it)
+            y.cond = e->cond ? e->cond + (size_t)l * e->fe_B * 2 * Cp * T : e->cond_dummy;
             y.out_w = prec ? w.out_w3 : w.out_w; y.out_b = w.out_b; y.dil = w.dil;
         }
         int rc = profiled(e, v.st, true, [&]() -> int {
@@ -210,6 +211,7 @@ static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int 
     a.fold128 = e->opt_blocked >= 2;
     a.cond = e->cond ? e->cond + (size_t)l * e->fe_B * 2 * Cp * T : e->cond_dummy;
     a.c_bs = (long)2 * Cp * T;
+    a.c_n = e->fe_B;        // (option "draws": conditional row b reads clip b % fe_B)
     a.n_cond = v.n_cond;
     p4_out(a, e->g, Cp / 4, T, Cp);
     if (prec) { const long act_bs = (long)Cp * T; a.Y = e->g3; a.y_bs = act_bs + act_bs / 2; a.out_s3 = 1; }
@@ -290,7 +292,7 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
             ta.conv_b2 = v.zero_spec ? w0.conv_b_z : w0.conv_b_u;
             if (e->cond_tr && !v.zero_spec) { ta.cond2 = e->cond_tr; ta.conv_b2 = w0.conv_b; }
             ta.cond = e->cond ? e->cond : e->cond_dummy;
-            ta.c_bs = (long)2 * Cp * T;
+            ta.c_bs = (long)2 * Cp * T; ta.c_n = e->fe_B;
             ta.taps = e->K; ta.dil = w0.dil;
             ta.fold = p.fold;
             ta.t4_ni = tuning().tail_t4;
@@ -403,10 +405,12 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     u.seed = seed; u.first_sample = first_sample;
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
     u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
+    // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)
+    if (e->opt_draws > 1) { u.draw_n = B / e->opt_draws; u.draw_G = e->opt_draw_G > 0 ? e->opt_draw_G : u.draw_n; }
     // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
     // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
     // (the table has STACK_GROUPS words: a larger batch is one recording - check_windows refuses marks there)
-    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty())) ? (const unsigned*)e->d_wintab : nullptr;
+    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt_draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
     float* const xalt = chain && chain->x_out ? chain->x_out : e->xalt;
     TailPlan plan;
     plan.u = u; plan.x_out = xalt; plan.u_B = B;

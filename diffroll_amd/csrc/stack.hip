@@ -133,7 +133,7 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
                 a.Wp = ly.conv_w; a.bias = ly.conv_b; a.bias2 = ly.conv_b2;
                 a.X = s.hd; a.x_bs = s3_bs; a.x_piece = (long)(s.Cp >> 3) * s.T * 4; a.x_planes = s.Cp >> 3;
                 a.taps = s.taps; a.dil = ly.dil;
-                a.cond = ly.cond; a.cond2 = ly.cond2; a.c_bs = s.c_bs; a.n_cond = s.n_cond;
+                a.cond = ly.cond; a.cond2 = ly.cond2; a.c_bs = s.c_bs; a.c_b0 = s.c_b0; a.c_n = s.c_n; a.n_cond = s.n_cond;
                 a.Y = s.g; a.y_bs = s3_bs; a.out_s3 = 1;
                 gemm_body<FL, 1, EPI_GATE, 1, 1, FOLDP>(a, smem, mt, nt, 0);
             } else {
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
         if ((p & 1) == 0) {
             a.Wp = ly.conv_w; a.bias = ly.conv_b; a.bias2 = ly.conv_b2;
             a.X = s.hd; a.taps = s.taps; a.dil = ly.dil;
-            a.cond = ly.cond; a.cond2 = ly.cond2; a.c_bs = s.c_bs; a.n_cond = s.n_cond;
+            a.cond = ly.cond; a.cond2 = ly.cond2; a.c_bs = s.c_bs; a.c_b0 = s.c_b0; a.c_n = s.c_n; a.n_cond = s.n_cond;
             a.Y = s.g;
             if (s.dbg && p + 2 >= s.p1) a.dbg = s.dbg + 64;       // last conv phase: body tick marks of block 0
             gemm_body<FL, 1, EPI_GATE, 0, 1, FOLDP>(a, smem, mt, nt, 0);
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
                 // T x 16 B, contiguous) and the weight panel of the 1x1 phase that follows (128 rows x Cp x 4 B)
                 const int be = nt / tps;
                 if (be < s.n_cond)
-                    l2_touch(ly.cond + (long)be * s.c_bs + (long)mt * 32 * s.T * 4, (unsigned)(32 * s.T * 16), wave - 4, 4);
+                    l2_touch(ly.cond + cond_row(a, be) * s.c_bs + (long)mt * 32 * s.T * 4, (unsigned)(32 * s.T * 16), wave - 4, 4);
                 l2_touch(ly.out_w + (long)mt * (s.Cp >> 5) * 4096, (unsigned)((s.Cp >> 5) * 16384), wave - 4, 4);
             }
         } else {
@@ -292,7 +292,7 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
         g.MT = MT; g.NB = s.NB; g.T = s.T; g.taps = s.taps; g.kchunks = s.Cp >> 5; g.y_rows = s.Cp;
         g.x_bs = g.y_bs = g.y2_bs = g.s_bs = (long)s.Cp * s.T; g.x_ps = g.y_ps = (long)s.T * 4; g.x_fs = g.y_fs = 4; g.x_planes = s.Cp >> 2;
         g.Wp = s.layer[l].conv_w; g.bias = s.layer[l].conv_b; g.bias2 = s.layer[l].conv_b2; g.X = s.hd; g.Y = s.g;
-        g.cond = s.layer[l].cond; g.cond2 = s.layer[l].cond2; g.c_bs = s.c_bs; g.n_cond = s.n_cond;
+        g.cond = s.layer[l].cond; g.cond2 = s.layer[l].cond2; g.c_bs = s.c_bs; g.c_b0 = s.c_b0; g.c_n = s.c_n; g.n_cond = s.n_cond;
         check_gemm_extents(g, EPI_GATE, 0, "stack_kernel (conv phase)");
         g.taps = 1; g.Wp = s.layer[l].out_w; g.bias = s.layer[l].out_b; g.X = s.g; g.Y = s.h; g.Y2 = s.hd; g.skip = s.skip;
         check_gemm_extents(g, EPI_RES_SKIP, 0, "stack_kernel (1x1 phase)");

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
         a.y_bs = act_bs; a.y_ps = (long)s.T * 4; a.y_fs = 4; a.y_rows = s.Cp;
         a.Wp = s.conv_w; a.bias = s.conv_b; a.bias2 = s.conv_b2;
         a.X = s.hd; a.taps = s.taps; a.dil = s.dil;
-        a.cond = s.cond; a.cond2 = s.cond2; a.c_bs = s.c_bs; a.n_cond = s.dual;
+        a.cond = s.cond; a.cond2 = s.cond2; a.c_bs = s.c_bs; a.c_n = s.c_n; a.n_cond = s.dual;
         a.dual = s.dual;
         a.Y = s.g;
         // item width (launch_tail): 64 frames, or 96 where that needs fewer x narrower rounds over the pair's blocks (640-frame

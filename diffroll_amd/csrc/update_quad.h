@@ -112,7 +112,8 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
                 const long e0 = i4 * 4;
                 const long smp = e0 / a.per_sample;
                 within = (e0 - smp * a.per_sample) >> 2;
-                sk = first_sample + smp;
+                // (option "draws": draw smp / n of clip smp % n)
+                sk = a.draw_n > 0 ? first_sample + smp % a.draw_n + (smp / a.draw_n) * a.draw_G : first_sample + smp;
             }
             uint32_t rnd[4];
             philox4x32_10((uint32_t)within, (uint32_t)(within >> 32), (uint32_t)a.t,

@@ -151,14 +151,38 @@ def gather_rolls_uneven(local: torch.Tensor, n_total: int, group=None) -> torch.
     return unpad_gathered(gather_rolls(pad_shard(local, n_total, ws), group), n_total, ws)
 
 
+def clip_major(rolls: torch.Tensor, draws: int) -> torch.Tensor:
+    """Draw-major rolls (D * b, 1, T, 88) -> one row per CLIP, (b, 1, D * T, 88) with its D draws one after another: what
+    a rank contributes to the gather, whose padding and un-padding count clips."""
+    Db, _, T, K = rolls.shape
+    b = Db // draws
+    return rolls.reshape(draws, b, T, K).transpose(0, 1).reshape(b, 1, draws * T, K)
+
+
+def draw_major(rows: torch.Tensor, draws: int) -> torch.Tensor:
+    """The inverse of clip_major on the gathered global batch: (B, 1, D * T, 88) -> (D * B, 1, T, 88), draw-major."""
+    B, _, DT, K = rows.shape
+    T = DT // draws
+    return rows.reshape(B, draws, T, K).transpose(0, 1).reshape(draws * B, 1, T, K)
+
+
 def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noise: Optional[torch.Tensor],
-                 seed: int, rank: int, world_size: int) -> torch.Tensor:
+                 seed: int, rank: int, world_size: int, draws: int = 1) -> torch.Tensor:
     """The part of sample_sharded one rank computes: the chain of its contiguous shard of the GLOBAL batch,
     returned as (b_local, 1, T', 88) on the engine's device (b_local may be 0).  Philox noise is keyed by the
-    global sample index (first_sample = lo), so the rolls do not depend on the world size."""
-    B = x_T.shape[0]
+    global sample index (first_sample = lo), so the rolls do not depend on the world size.
+    draws = D > 1: x_T / noise hold D draws of the B global clips, draw-major; the rank runs its clip shard x all draws in
+    one chain with "draw_stride" = B - draw d of global clip c is keyed c + d * B on any world size - and returns
+    (D * b_local, 1, T', 88), draw-major over its shard."""
+    B = x_T.shape[0] // draws
     lo, hi = shard_bounds(B, rank, world_size)
     wav = None if waveform is None else waveform[lo:hi]
+    if draws > 1:
+        x_loc = x_T.reshape((draws, B) + tuple(x_T.shape[1:]))[:, lo:hi].reshape((-1,) + tuple(x_T.shape[1:]))
+        z = None if noise is None else noise.reshape((noise.shape[0], draws, B) + tuple(noise.shape[2:]))[:, :, lo:hi].reshape(
+            (noise.shape[0], -1) + tuple(noise.shape[2:]))
+        if hi > lo:
+            return model.sample(x_loc, wav, noise=z, seed=seed, first_sample=lo, draws=draws, draw_stride=B)[0]
     z = None if noise is None else noise[:, lo:hi]
     if hi > lo:
         roll, _ = model.sample(x_T[lo:hi], wav, noise=z, seed=seed, first_sample=lo)
@@ -170,22 +194,31 @@ def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noi
 
 
 def sample_sharded(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None,
-                   seed: int = 0, group=None) -> torch.Tensor:
+                   seed: int = 0, group=None, draws: int = 1) -> torch.Tensor:
     """Every rank passes the SAME global batch (x_T (B,1,T,88), waveform (B,L), optional injected noise
     (S,B,1,T,88)); each runs its contiguous shard and all ranks return the full (B,1,T',88) result.
-    Philox noise is keyed by the global sample index, so the result does not depend on the world size."""
+    Philox noise is keyed by the global sample index, so the result does not depend on the world size.
+    draws = D > 1: x_T (D*B,1,T,88) and noise (S,D*B,1,T,88) are draw-major over the global batch, and so is the
+    (D*B,1,T',88) result: the shards travel through the gather one row per clip and are regrouped behind it."""
     rank, ws = world()
-    roll = sample_shard(model, x_T, waveform, noise, seed, rank, ws)
+    roll = sample_shard(model, x_T, waveform, noise, seed, rank, ws, draws)
+    if draws > 1:
+        return draw_major(gather_rolls_uneven(clip_major(roll, draws), x_T.shape[0] // draws, group), draws)
     return gather_rolls_uneven(roll, x_T.shape[0], group)
 
 
 def sample_sharded_sequential(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor],
-                              noise: Optional[torch.Tensor] = None, seed: int = 0, world_size: int = 2) -> torch.Tensor:
+                              noise: Optional[torch.Tensor] = None, seed: int = 0, world_size: int = 2,
+                              draws: int = 1) -> torch.Tensor:
     """The world_size-rank job emulated on ONE device: every rank's sample_shard() is run in turn through the same
     slicing / padding / un-padding code the collective path uses (the all-gather itself is the concatenation of
     the padded shards in rank order).  Used by the GPU tests to hold the N-rank result to the unsharded one when
     only one GPU is leased."""
-    B = x_T.shape[0]
+    B = x_T.shape[0] // draws
+    if draws > 1:
+        shards = [pad_shard(clip_major(sample_shard(model, x_T, waveform, noise, seed, r, world_size, draws), draws), B, world_size)
+                  for r in range(world_size)]
+        return draw_major(unpad_gathered(torch.cat(shards, 0), B, world_size), draws)
     shards = [pad_shard(sample_shard(model, x_T, waveform, noise, seed, r, world_size), B, world_size)
               for r in range(world_size)]
     return unpad_gathered(torch.cat(shards, 0), B, world_size)

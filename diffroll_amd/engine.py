@@ -262,6 +262,8 @@ class Engine:
         roll is consumed."""
         assert x.device == self.device and x.dtype == torch.float32 and x.is_contiguous()
         B, T, _ = x.shape
+        if B % self.draws:
+            raise ValueError(f"a batch of {B} rolls is not a whole number of draws (option 'draws' = {self.draws})")
         if noise is not None:
             assert noise.device == self.device and noise.dtype == torch.float32 and noise.is_contiguous()
             assert noise.shape[0] == self.timesteps and noise.numel() == self.timesteps * x.numel()
@@ -328,7 +330,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'sampling_steps' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -339,6 +341,10 @@ class Engine:
             self.window_breaks = tuple(sorted(set(self.window_breaks) | {int(value)})) if int(value) else ()
         if name == "sampling_steps":
             self.sampling_steps = int(value)
+        if name == "draws":
+            self.draws = int(value)
+        if name == "draw_stride":
+            self.draw_stride = int(value)
 
     def set_window_breaks(self, marks):
         """Replace the marks of option 'window_break' (the windows of the next batch that start a new recording)."""
@@ -351,6 +357,8 @@ class Engine:
     window_overlap = 0      # the last value set for option 'window_overlap' (0 = off, the library's default)
     window_breaks = ()      # the marks set with option 'window_break' (windows that start a new recording), ascending
     sampling_steps = 0      # the last value set for option 'sampling_steps' (0 = every step, the library's default)
+    draws = 1               # the last value set for option 'draws' (rolls per clip of one chain, draw-major; 1 = the default)
+    draw_stride = 0         # the last value set for option 'draw_stride' (Philox key distance of two draws; 0 = the clips of the batch)
 
     def visited_steps(self):
         """The diffusion steps sample() visits, in chain order (option 'sampling_steps'; all of them when it is off)."""

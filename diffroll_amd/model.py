@@ -22,12 +22,32 @@ from typing import Any, Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
+import contextlib
+
 from .engine import Engine
+from .ensemble import aggregate, check_draws
 from .schedule import check_sampling_steps, respaced_steps
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
 _GUIDED = ("cfdg_ddpm_x0", "inpainting_ddpm_x0", "cfdg_ddim_x0")
+
+
+@contextlib.contextmanager
+def _draws_set(eng, draws: int, stride: int):
+    """Options "draws" / "draw_stride" around one chain, restored afterwards.  Neither drops the engine's captured chain -
+    they are part of its key (engine_state.h: GraphKey) - so a loop of sample(draws=D) calls replays one graph, and
+    restoring them behind an asynchronous call (check=False) touches nothing that is in flight."""
+    prev = (eng.draws, eng.draw_stride)
+    if prev != (draws, stride):
+        eng.set_option("draws", draws)
+        eng.set_option("draw_stride", stride)
+    try:
+        yield
+    finally:
+        if prev != (draws, stride):
+            eng.set_option("draws", prev[0])
+            eng.set_option("draw_stride", prev[1])
 
 
 class AttrDict(dict):
@@ -128,6 +148,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.steps = n runs the chain on n respaced steps (option "sampling_steps"); absent / None in
         # the reference's configs = every step
         check_sampling_steps(sampling.get("steps"), timesteps)
+        # an extension: sampling.draws = D samples D rolls per clip in one chain (option "draws") and scores / exports their
+        # mean (diffroll_amd/ensemble.py); absent / None / 1 = one roll per clip
+        check_draws(sampling.get("draws"))
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -245,6 +268,10 @@ class ClassifierFreeDiffRoll(nn.Module):
             return 0
         hp = self.__dict__["hparams"]
         return check_sampling_steps(hp.sampling.get("steps"), hp.timesteps)
+
+    def draws(self) -> int:
+        """D of hparams.sampling.draws: the rolls predict_step / sampling / test_step sample per clip (1: one)."""
+        return check_draws(self.__dict__["hparams"].sampling.get("draws"))
 
     def visited_steps(self):
         """The diffusion steps sample() visits, in chain order (timesteps-1 .. 0, or hparams.sampling.steps of them)."""
@@ -467,18 +494,27 @@ class ClassifierFreeDiffRoll(nn.Module):
 
     @torch.no_grad()
     def sample(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0,
-               use_graph: bool = True, check: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+               use_graph: bool = True, check: bool = True, draws: int = 1, draw_stride: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """The reverse chain t = timesteps-1 .. 0 (task/diffusion.py:528-534) - or, with hparams.sampling.steps = n,
         the n respaced steps of visited_steps() - on the device with no host round trip.  x_T (B,1,T,88); noise: None
         (on-device Philox keyed by seed, global sample index and step) or (timesteps, B, 1, T, 88) injected z's (row t
         is used at step t >= 1, also in a respaced chain).
         Returns (roll (B,1,T',88), spec (B,n_mels,T')).
+        draws = D > 1 (option "draws" of include/diffroll_amd.h): x_T (D*n,1,T,88) holds D draws of the n clips of waveform
+        (n, L), draw-major (row b = draw b // n of clip b % n); the front-end and the conditioner tensors exist once per
+        clip.  Returns (rolls (D*n,1,T',88), spec (n,n_mels,T')) - bit for bit the rolls of the waveform tiled D times.
+        Philox keys row b by first_sample + b % n + (b // n) * draw_stride (0 = n: the tiled batch's first_sample + b).
         check=True (default): the call returns with the FINISHED, verified roll, as task/diffusion.py:528-538 does
         (synchronous; a fused-kernel time-out caused by another tenant of the device is healed by re-running the chain
         on the per-phase kernels - Engine.sample).  check=False: asynchronous; call engine.finish() before use."""
         eng = self.engine
         sampler = self.hparams.sampling.type
         B, _, T, _ = x_T.shape
+        draws = check_draws(draws)
+        if B % draws:
+            raise ValueError(f"x_T holds {B} rolls: not a whole number of draws = {draws}")
+        if draws > 1 and waveform is not None and waveform.shape[0] != B // draws:
+            raise ValueError(f"{draws} draws of {B} rolls take the waveform of {B // draws} clips, got {waveform.shape[0]}")
         if sampler != "generation_ddpm_x0":
             if waveform is None:
                 raise ValueError("waveform is required for conditional samplers")
@@ -490,7 +526,7 @@ class ClassifierFreeDiffRoll(nn.Module):
             Tm = T if waveform is None else min(T, waveform.shape[-1] // eng.hop_length + 1)
             if self.hparams.condition == "trainable_spec":
                 Tm = min(T, 641)
-            spec = self._uncond_spec(B, Tm)
+            spec = self._uncond_spec(B // draws, Tm)
         # a fresh roll buffer per call: the engine's captured chain runs on its own work buffer, so caller
         # addresses never force a re-capture
         xb = x_T.to(eng.device, torch.float32).squeeze(1)[:, :Tm, :].clone(memory_format=torch.contiguous_format)
@@ -501,19 +537,27 @@ class ClassifierFreeDiffRoll(nn.Module):
             if Tm != T or not z.is_contiguous():
                 z = z[:, :, :Tm, :].contiguous()
         w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
-        eng.sample(sampler, xb, z, w, seed, first_sample, use_graph, check)
+        with _draws_set(eng, draws, draw_stride):
+            eng.sample(sampler, xb, z, w, seed, first_sample, use_graph, check)
         return xb.unsqueeze(1), spec
 
     @torch.no_grad()
     def sample_long(self, waveform=None, frames: Optional[int] = None, overlap: int = 160, seed: int = 0,
-                    recording: int = 0, x_T=None, noise=None, use_graph: bool = True, check: bool = True) -> torch.Tensor:
+                    recording: int = 0, x_T=None, noise=None, use_graph: bool = True, check: bool = True,
+                    draws: int = 1) -> torch.Tensor:
         """One recording of any length as jointly sampled 640-frame windows (diffroll_amd/longform.py; option
         "window_overlap" of include/diffroll_amd.h): returns the stitched roll (1, 1, T_out, 88) on the device.
         Conditional samplers take waveform (L,) (T_out = ceil(L / hop)); generation_ddpm_x0 takes frames = T_out.
         x_T: (1, 1, T_c, 88) canvas, or None: drawn from torch.Generator().manual_seed(seed) on the host; noise: None
         (Philox keyed by seed, first_sample = recording and the canvas element) or a canvas tensor
-        (timesteps, 1, 1, T_c, 88).  Every window is one row of ONE Engine.sample chain (check=True heals)."""
+        (timesteps, 1, 1, T_c, 88).  Every window is one row of ONE Engine.sample chain (check=True heals).
+        draws = D > 1: D draws of the recording in that one chain, as sample_long_batch([waveform], draws=D) - returns
+        (D, 1, T_out, 88); x_T (D, 1, T_c, 88), noise (timesteps, D, 1, T_c, 88)."""
         from . import longform
+        if check_draws(draws) > 1:
+            return self.sample_long_batch(None if waveform is None else [waveform], None if frames is None else [frames],
+                                          overlap, seed, recording, None if x_T is None else [x_T],
+                                          None if noise is None else [noise], use_graph, check, draws)[0]
         sampler = self.hparams.sampling.type
         if sampler == "inpainting_ddpm_x0":
             raise ValueError("sample_long does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) are in "
@@ -558,7 +602,7 @@ class ClassifierFreeDiffRoll(nn.Module):
 
     @torch.no_grad()
     def sample_long_batch(self, waveforms=None, frames=None, overlap: int = 160, seed: int = 0, first_recording: int = 0,
-                          x_T=None, noise=None, use_graph: bool = True, check: bool = True) -> List[torch.Tensor]:
+                          x_T=None, noise=None, use_graph: bool = True, check: bool = True, draws: int = 1) -> List[torch.Tensor]:
         """Several recordings of any lengths in ONE chain (option "window_break" of include/diffroll_amd.h;
         longform.plan_batch): their windows fill one batch, a window shares frames only with windows of its own
         recording, and recording i draws the noise of first_sample = first_recording + i on its own canvas.  Returns one
@@ -566,8 +610,14 @@ class ClassifierFreeDiffRoll(nn.Module):
         recording=first_recording + i) returns (bit for bit where both chains take the same kernel flavours).
         waveforms: a sequence of (L_i,) tensors; generation_ddpm_x0 takes frames = a sequence of roll lengths instead.
         x_T / noise: None, or one canvas per recording in sample_long's shapes ((1, 1, T_c_i, 88) /
-        (timesteps, 1, 1, T_c_i, 88)); the default x_T of every recording is sample_long's for this seed."""
+        (timesteps, 1, 1, T_c_i, 88)); the default x_T of every recording is sample_long's for this seed.
+        draws = D > 1 (option "draws"): D draws of every recording in the one chain - the window batch repeats per draw
+        over ONE set of conditioner tensors, and draw d is the chain of first_recording + d * (number of recordings) on
+        its own canvases.  Returns per recording (D, 1, T_out_i, 88); x_T / noise carry the draws in the canvases' batch
+        dimension ((D, 1, T_c_i, 88) / (timesteps, D, 1, T_c_i, 88)); the default x_T are the first D canvases of
+        torch.Generator().manual_seed(seed) (draw 0 = the single-draw default)."""
         from . import longform
+        D = check_draws(draws)
         sampler = self.hparams.sampling.type
         if sampler == "inpainting_ddpm_x0":
             raise ValueError("sample_long_batch does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) "
@@ -585,21 +635,23 @@ class ClassifierFreeDiffRoll(nn.Module):
                 if wv.dim() != 1:
                     raise ValueError(f"every waveform must be one recording (L,), got {tuple(wv.shape)}")
             batch = longform.plan_batch([wv.shape[0] for wv in waveforms], eng.hop_length, longform.WINDOW_FRAMES, overlap)
-        if batch.n > longform.MAX_WINDOWS:
-            raise ValueError(f"{batch.n} windows in {len(batch.plans)} recordings: one chain holds at most "
+        if D * batch.n > longform.MAX_WINDOWS:
+            raise ValueError(f"{D * batch.n} windows in {len(batch.plans)} recordings ({D} draw(s)): one chain holds at most "
                              f"{longform.MAX_WINDOWS} (longform.MAX_WINDOWS); use fewer recordings per chain (longform.pack_chains)")
         R, S = len(batch.plans), int(self.hparams.timesteps)
         if x_T is None:
-            x_T = [torch.randn(1, 1, p.T_c, 88, generator=torch.Generator().manual_seed(int(seed))) for p in batch.plans]
-        if len(x_T) != R or any(tuple(x.shape) != (1, 1, p.T_c, 88) for x, p in zip(x_T, batch.plans)):
-            raise ValueError(f"x_T must be one canvas (1, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
-        xb = longform.gather_batch([x.reshape(p.T_c, 88).to(eng.device, torch.float32) for x, p in zip(x_T, batch.plans)], batch)
+            x_T = [torch.randn(D, 1, p.T_c, 88, generator=torch.Generator().manual_seed(int(seed))) for p in batch.plans]
+        if len(x_T) != R or any(tuple(x.shape) != (D, 1, p.T_c, 88) for x, p in zip(x_T, batch.plans)):
+            raise ValueError(f"x_T must be one canvas ({D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
+        # the window batch of draw 0, then that of draw 1, ... (draw-major)
+        xb = torch.cat([longform.gather_batch([x[d].reshape(p.T_c, 88).to(eng.device, torch.float32)
+                                               for x, p in zip(x_T, batch.plans)], batch) for d in range(D)], 0)
         z = None
         if noise is not None:
-            if len(noise) != R or any(zr.numel() != S * p.T_c * 88 for zr, p in zip(noise, batch.plans)):
-                raise ValueError(f"noise must be one canvas ({S}, 1, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
-            z = longform.gather_batch([zr.reshape(S, p.T_c, 88).to(eng.device, torch.float32)
-                                       for zr, p in zip(noise, batch.plans)], batch).contiguous()
+            if len(noise) != R or any(zr.numel() != S * D * p.T_c * 88 for zr, p in zip(noise, batch.plans)):
+                raise ValueError(f"noise must be one canvas ({S}, {D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
+            z = torch.cat([longform.gather_batch([zr.reshape(S, D, p.T_c, 88)[:, d].to(eng.device, torch.float32)
+                                                  for zr, p in zip(noise, batch.plans)], batch) for d in range(D)], 1).contiguous()
         if sampler != "generation_ddpm_x0":
             eng.frontend(torch.cat([longform.window_audio(wv, p, eng.hop_length) for wv, p in zip(waveforms, batch.plans)]),
                          longform.WINDOW_FRAMES)
@@ -609,11 +661,13 @@ class ClassifierFreeDiffRoll(nn.Module):
         eng.set_option("window_overlap", batch.plans[0].overlap)
         try:
             eng.set_window_breaks(batch.marks)
-            eng.sample(sampler, xb, z, w, seed, first_recording, use_graph, check)
+            with _draws_set(eng, D, 0):
+                eng.sample(sampler, xb, z, w, seed, first_recording, use_graph, check)
         finally:
             eng.set_window_breaks(prev_marks)
             eng.set_option("window_overlap", prev_overlap)
-        return [r.reshape(1, 1, p.T_out, 88) for r, p in zip(longform.stitch_batch(xb, batch), batch.plans)]
+        rolls = longform.stitch_batch(xb.reshape(D, batch.n, longform.WINDOW_FRAMES, 88), batch)
+        return [r.reshape(D, 1, p.T_out, 88) for r, p in zip(rolls, batch.plans)]
 
     def sample_trajectory(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0):
         """The same chain, keeping every intermediate roll on the device: returns (trajectory (n, B, 1, T', 88) with
@@ -661,8 +715,19 @@ class ClassifierFreeDiffRoll(nn.Module):
         """batch = (x_T, waveform[, ...]) as built by sampling.py:27-46.  Returns the final roll
         (B,1,T,88) (the reference returns nothing and writes figures/MIDI instead)."""
         noise, waveform = batch[0], batch[1]
+        D = self.draws()
+        if D > 1:      # draw 0 starts from the batch's x_T, the others from host-seeded ones; the mean roll is returned
+            more = torch.randn((D - 1) * noise.shape[0], *noise.shape[1:], generator=torch.Generator().manual_seed(int(batch_idx)))
+            rolls, _ = self.sample(torch.cat([noise.to("cpu", torch.float32), more], 0), waveform, seed=batch_idx, draws=D)
+            return self._ensemble(rolls, D)
         roll, _ = self.sample(noise, waveform, seed=batch_idx)
         return roll
+
+    def _ensemble(self, rolls, D):
+        """Mean roll of D draws per clip; the per-cell votes and spread stay in self.last_ensemble = (votes, std)."""
+        mean, votes, std = aggregate(rolls, D, float(self.hparams.frame_threshold))
+        self.__dict__["last_ensemble"] = (votes, std)
+        return mean.contiguous()
 
     @staticmethod
     def frame_metrics(tp: int, fp: int, fn: int) -> Tuple[float, float, float]:
@@ -722,6 +787,16 @@ class ClassifierFreeDiffRoll(nn.Module):
                                       "(task/diffusion.py:780-781): a development switch of the reference, not a mode")
         frame = batch["frame"]
         x_T = batch.get("x_T")
+        D = self.draws()
+        if D > 1:
+            # hparams.sampling.draws: D rolls per clip in one chain ('x_T' (D*B, 1, T, 88) / 'noise' (timesteps, D*B, 1, T, 88),
+            # draw-major; x_T drawn on the host from a generator seeded with batch_idx when absent); the roll returned -
+            # scored by test_step, exported by the CLI - is their mean
+            if x_T is None:
+                x_T = torch.randn(D * frame.shape[0], 1, frame.shape[1], frame.shape[2],
+                                  generator=torch.Generator().manual_seed(int(batch_idx)))
+            rolls, spec = self.sample(x_T, batch["audio"], noise=batch.get("noise"), seed=batch_idx, draws=D)
+            return self._ensemble(rolls, D), spec
         if x_T is None:
             x_T = torch.randn(frame.shape[0], 1, frame.shape[1], frame.shape[2], device=self.engine.device)
         return self.sample(x_T, batch["audio"], noise=batch.get("noise"), seed=batch_idx)

@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define DR_ABI_VERSION 10
+#define DR_ABI_VERSION 11
 
 enum {
     DR_OK = 0,
@@ -379,6 +379,27 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          visited -> DR_EINVAL); dr_forward, dr_forward_steps, dr_q_sample, dr_extract_x0 are unaffected.
  *                          Combines with "window_overlap", both precisions and sharding.  0 or S = the full chain, bit for
  *                          bit; any other value -> DR_EINVAL.
+ *   "draws"            [1] D >= 1: SEVERAL draws per clip in one chain, sharing the conditioning.  The B rolls of dr_step /
+ *                          dr_sample / dr_sample_checked (and dr_forward / dr_forward_steps) are D draws of n = B / D clips,
+ *                          draw-major: row b is draw b / n of clip b % n.  The preceding dr_frontend was called with the n
+ *                          clips (its outputs stay at n clips); conditional row b reads conditioner tensor b % n, and the
+ *                          conditional / unconditional halves of a guided batch keep their meaning.  B % D != 0 ->
+ *                          DR_EINVAL, a front-end batch other than B / D for a conditional sampler -> DR_ESTATE, at the
+ *                          call.  The result is, bit for bit, that of the same rolls after a front-end run on the waveform
+ *                          tiled D times - without D copies of the conditioner tensors.  Injected noise keeps its
+ *                          (S, B, T, 88) shape, one row per roll.  With "window_overlap" the rows of ONE draw are the window
+ *                          batch: a new draw always starts new recordings (no averaging across a draw boundary),
+ *                          "window_break" marks are those of one draw (a mark >= n -> DR_EINVAL) and repeat per draw, draw
+ *                          d of recording r is keyed first_sample + r + d * R (R = the recordings of one draw, or
+ *                          "draw_stride") - exactly the chain of first_sample + d * R - and B, the whole batch, holds at
+ *                          most 512 windows.  1 = every roll its own clip, bit-identical to an engine that never set it;
+ *                          < 1 -> DR_EINVAL.  The value is part of a captured chain's key: a chain captured under another
+ *                          value is never replayed (the next dr_sample captures anew), and setting the option back
+ *                          before the next call costs nothing - nothing in flight is touched.
+ *   "draw_stride"      [0] G >= 0: the Philox sample key of row b under "draws" is first_sample + (b % n) + (b / n) * G, with
+ *                          0 = n (then the key is first_sample + b, that of the tiled batch).  A sharded run sets G to the
+ *                          global clip count: draw d of global clip c gets the same noise on any world size.  Ignored
+ *                          while "draws" is 1; < 0 -> DR_EINVAL.  Part of a captured chain's key, like "draws".
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
