@@ -6,6 +6,7 @@
     python sampling.py task=inpainting task.inpainting_t=[500,650] dataset=Custom ...
     python sampling.py task=transcription dataset=Custom dataset.args.max_segment_samples=null task.window_overlap=160 ...
     python sampling.py task=transcription task.sampling.steps=50 ...      # 50 respaced steps instead of 200
+    python sampling.py task=transcription task.sampling.guidance_interval=[60,140] ...      # guide steps 60..140 only
     torchrun --nproc-per-node 8 sampling.py task=generation gpus=8 dataset.num_samples=128 dataloader.batch_size=128
 
 Hydra is not a dependency: the same ``group=name`` / ``dotted.key=value`` override syntax is parsed here over
@@ -117,6 +118,17 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
     draws = cfg["task"]["sampling"].get("draws")
     if draws is not None and (isinstance(draws, bool) or not isinstance(draws, int) or draws < 1):
         raise SystemExit(f"task.sampling.draws must be an integer >= 1 (or null: one roll per clip), got {draws!r}")
+    # task.sampling.guidance_interval=[lo,hi]: guide the steps lo <= t <= hi only (options "guidance_t_min" / "guidance_t_max");
+    # absent / null = the whole chain
+    interval = cfg["task"]["sampling"].get("guidance_interval")
+    if interval is not None:
+        from .schedule import check_guidance_interval
+        try:
+            if not isinstance(S, int):
+                raise ValueError(f"task.timesteps = {S!r}")
+            check_guidance_interval(interval, S, cfg["task"]["sampling"]["type"])
+        except ValueError as err:
+            raise SystemExit(f"task.sampling.guidance_interval: {err}")
     per_chain = cfg["task"].get("recordings_per_chain", 1)
     if isinstance(per_chain, bool) or not isinstance(per_chain, int) or per_chain < 1:
         raise SystemExit(f"task.recordings_per_chain must be an integer >= 1, got {per_chain!r}")

@@ -160,6 +160,14 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
     return DR_OK;
 }
 
+// options "guidance_t_min" / "guidance_t_max": the samplers that guide need lo <= hi (the others ignore both)
+int check_guidance(dr_engine* e, int B, int NB) {
+    if (NB == 2 * B && e->opt_guid.empty(e->S))
+        return fail(e, DR_EINVAL, "guidance interval is empty: guidance_t_min = %d exceeds guidance_t_max = %d", e->opt_guid.lo,
+                    e->opt_guid.hi_eff(e->S));
+    return DR_OK;
+}
+
 // option "window_overlap": at most two windows share a frame (O <= T / 2)
 // option "window_break": every mark names a window of this batch (marks are ignored while "window_overlap" is 0)
 int check_windows(dr_engine* e, int B, int T) {
@@ -302,6 +310,16 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         e->opt_steps = value;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         if (int rc = build_respaced(e)) { e->opt_steps = 0; return rc; }
+        return DR_OK;
+    }
+    if (n == "guidance_t_min" || n == "guidance_t_max") {
+        // (no captured chain is dropped: the effective pair is part of the chain's key - GraphKey - as "draws" is; lo > hi is
+        // refused by dr_step / dr_sample, once both values are in)
+        const bool is_max = n == "guidance_t_max";
+        if (!guidance_value_ok(is_max, value, e->S))
+            return fail(e, DR_EINVAL, is_max ? "guidance_t_max is -1 (= timesteps - 1) or in [0, timesteps = %d), got %d"
+                                             : "guidance_t_min is in [0, timesteps = %d), got %d", e->S, value);
+        (is_max ? e->opt_guid.hi : e->opt_guid.lo) = value;
         return DR_OK;
     }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
@@ -576,6 +594,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if ((rc = check_windows(e, B, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
+    if ((rc = check_guidance(e, B, NB))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
@@ -596,6 +615,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if ((rc = check_windows(e, B, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
+    if ((rc = check_guidance(e, B, NB))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (e->tuning_epoch != tuning_epoch().load()) {      // a tune.* knob changed (any engine, any thread): the cached chain is stale
@@ -635,6 +655,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     GraphKey key;
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
     key.draws = e->opt_draws; key.draw_G = e->opt_draws > 1 ? e->opt_draw_G : 0; key.fe_B = e->fe_B;
+    if (NB == 2 * B) { key.g_lo = e->opt_guid.lo; key.g_hi = e->opt_guid.hi_eff(e->S); }
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

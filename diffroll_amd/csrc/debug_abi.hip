@@ -212,4 +212,11 @@ int dr_debug_ticks(dr_engine* e, int64_t* loop_ticks, int64_t* block_ticks) {
     return DR_OK;
 }
 
+int dr_debug_launch_counts(dr_engine* e, int64_t* out2) {
+    if (!e || !out2) return fail(e, DR_EINVAL, "null argument");
+    out2[0] = e->inproj_launches;
+    out2[1] = e->conv0_launches;
+    return DR_OK;
+}
+
 }  // extern "C"

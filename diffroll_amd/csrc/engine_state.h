@@ -60,9 +60,12 @@ struct GraphKey {
     // "draw_stride" do not drop the chain, they are part of its key (a façade that sets them around every call replays
     // one graph), and so is fe_B - dr_frontend drops the chain when it changes, the key keeps that from being load-bearing.
     int draws = 1, draw_G = 0, fe_B = 0;
+    // ... and which steps run the unconditional evaluation: options "guidance_t_min" / "guidance_t_max" (the effective pair)
+    // are part of the key too - a chain captured under another interval is never replayed
+    int g_lo = 0, g_hi = 0;
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
-               draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B;
+               draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi;
     }
 };
 
@@ -193,6 +196,9 @@ struct dr_engine {
     std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
     drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor
                                         // is not t - 1 replaced by the respaced row (build_respaced); empty when rs_steps is
+    dr::GuidanceInterval opt_guid;      // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
+    int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
+    int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
     drh::DevBuf<float> xalt;            // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
@@ -320,7 +326,9 @@ struct TailPlan {
     float* x_out = nullptr;    // where the tail kernel writes x_{t-1}
     int u_B = 0;               // rolls
     int next_t = -1;           // >= 0: the chain continues with step next_t (its input projection joins the tail)
-    bool skip_inproj = false;  // h / hd of THIS step (and, guided, layer 0's g) were written by the previous step's tail
+    StepEval next{};           // ... whose evaluation has this shape (launch_plan.h: a guidance interval may begin or end here)
+    bool skip_inproj = false;  // h / hd (and, guided, layer 0's g) were written by the previous step's tail ...
+    StepEval primed{};         // ... for an evaluation of this shape: honoured only when it is THIS step's shape
     bool done = false;         // out: the tail kernel ran (update included, result in x_out)
     bool inproj_done = false;  // out: ... and it wrote the next step's h / hd (and layer 0's g for a guided pair)
 };
@@ -330,6 +338,7 @@ int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& z
 int sampler_shape(int sampler, int B, int& NB, int& n_cond);
 struct ChainState {
     bool inproj_ready = false;
+    StepEval ready{};          // the shape inproj_ready holds for (TailPlan::primed of the next step)
     int next_t = -1;
     float* x_out = nullptr;    // where a fused step writes x_{t-1} (null: e->xalt)
 };

@@ -239,7 +239,11 @@ hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
 // ceil(T / BN) frame tiles x Cp / 64 blocks, all resident at once.
 struct TailArgs {
     int NB, T, Cp, BN;                        // BN = frames per block of the preceding stack launch (64 / 128 / 160): grouping only
-    int dual;                                 // B > 0: classifier-free pairs (sample b, sample b + B); 0: every sample on its own
+    int dual;                                 // B > 0: classifier-free pairs (sample b, sample b + B) NOW - how x0 is combined and who
+                                              // meets at the pair barriers; 0: every sample on its own
+    int dual_next;                            // B > 0: the NEXT step is guided - h / hd are written for rows b and b + B and conv_w
+                                              // may be set; 0: rows b only, no conv.  Differs from `dual` at the two ends of a
+                                              // guidance interval (options "guidance_t_min" / "guidance_t_max")
     int u_B;                                  // rolls to update (B)
     int xcd_n, fault;
     float alpha;                              // 1 / sqrt(residual_layers)
@@ -251,7 +255,7 @@ struct TailArgs {
     float* x_out;                             // x_{t-1} is written here (never u.x: other blocks still read x_t)
     const float *in_w, *in_b, *d2_next;       // input projection of the NEXT step (in_w null: the chain ends here / single step)
     float *h, *hd;                            // its outputs, P4 [NB][Cp/4][T][4]
-    // the next step's shared first-layer conv (dual > 0 and in_w set; conv_w null: none): layer 0 as in StackLayer
+    // the next step's shared first-layer conv (dual_next > 0 and in_w set; conv_w null: none): layer 0 as in StackLayer
     const float *conv_w, *conv_b, *conv_b2, *cond, *cond2;
     long c_bs;
     int c_n;                                  // clips of the conditioner (GemmArgs::c_n)

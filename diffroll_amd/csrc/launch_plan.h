@@ -272,4 +272,34 @@ inline NetPlan plan_network(const NetShape& s, const PlanKnobs& k) {
     return NetPlan{stack_ni, stack_chunks, stack_from, dual0, fold, fused_step, use_tail, mode};
 }
 
+// Guidance interval (options "guidance_t_min" / "guidance_t_max", include/diffroll_amd.h): a reverse step of a guiding
+// sampler at diffusion step t runs both evaluations and combines them with the caller's w iff lo <= t <= hi; every other
+// step is the w = 0 step - the conditional evaluation alone, consumed unchanged.  w == 0 is the empty interval.
+struct GuidanceInterval {
+    int lo = 0, hi = -1;        // as set; hi = -1: timesteps - 1
+    int hi_eff(int S) const { return hi < 0 ? S - 1 : hi; }
+    bool empty(int S) const { return lo > hi_eff(S); }
+};
+// what dr_set_option accepts for the two names (S = timesteps)
+inline bool guidance_value_ok(bool is_max, int v, int S) { return v < S && v >= (is_max ? -1 : 0); }
+inline bool step_guided(const GuidanceInterval& g, int S, bool w_zero, int t) {
+    return !w_zero && t >= 0 && g.lo <= t && t <= g.hi_eff(S);
+}
+// The evaluation batch of one reverse step: NB network evaluations of B rolls, the first n_cond conditional; dual = the
+// step is guided (rows b and b + B evaluate the same x_t: NB = 2 B).
+struct StepEval { int NB = 0, n_cond = 0; bool dual = false; };
+// (NB, n_cond: the sampler's own shape - sampler_shape, plan.hip; a sampler that does not guide keeps it at every step)
+inline StepEval step_eval(int NB, int n_cond, int B, bool guided) {
+    if (NB != 2 * B) return StepEval{NB, n_cond, false};
+    return guided ? StepEval{NB, n_cond, true} : StepEval{B, B, false};
+}
+// this step's shape and its successor's in the chain (next_t < 0: the chain ends here, `next` is all zero)
+struct StepShapes { StepEval now, next; };
+inline StepShapes plan_step(int NB, int n_cond, int B, const GuidanceInterval& g, int S, bool w_zero, int t, int next_t) {
+    StepShapes p;
+    p.now = step_eval(NB, n_cond, B, step_guided(g, S, w_zero, t));
+    if (next_t >= 0) p.next = step_eval(NB, n_cond, B, step_guided(g, S, w_zero, next_t));
+    return p;
+}
+
 }  // namespace dr

@@ -131,6 +131,7 @@ static int launch_inproj(const Eval& v, const PlanKnobs& k) {
     else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     allow_splitk(e, a);
     HIPCHK(e, launch_gemm(a, EPI_RELU, pick_ni(k, a.MT, v.NB, T, 1, 1), v.st));
+    e->inproj_launches += 1;
     return DR_OK;
 }
 
@@ -271,9 +272,20 @@ static int launch_res_skip(const Eval& v, const PlanKnobs& k, int l) {
 }
 
 // the rest of the step in one launch (tail kernel): skip projection, output projection, combine + update, next input projection
-static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
+static int launch_tail_step(const Eval& v, const NetPlan& p, const PlanKnobs& k, TailPlan* tail) {
     dr_engine* e = v.e;
     const int Cp = e->Cp, L = e->L, T = v.T;
+    // The successor's own plan decides what this tail leaves behind for it.  Under a guidance interval its shape may differ
+    // from this step's (2B evaluations -> B or back): h / hd go to the rows it will read, and the shared first-layer conv
+    // runs iff it is guided.  A successor that does not take the fused step (B evaluations may leave too much of the chip
+    // idle for the fused stack: plan_network) is not primed at all - it starts with launch_inproj like a chain's first step.
+    NetPlan np{};
+    bool prime = false;
+    if (tail->next_t >= 0) {
+        np = plan_network(NetShape{tail->next.NB, tail->next.n_cond, v.bmod, T, Cp, L, e->K, e->max_dil, e->prec, e->n_cus,
+                                   e->fused.active(), e->opt_blocked, e->opt_tail, false, true}, k);
+        prime = np.use_tail;
+    }
     TailArgs ta{};
     ta.NB = v.NB; ta.T = T; ta.Cp = Cp; ta.BN = stack_tile_frames(p.stack_fl);
     ta.dual = (v.bmod > 0 && v.NB == 2 * v.bmod) ? v.bmod : 0;
@@ -283,10 +295,11 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
     ta.skip = e->skip; ta.tmp = e->tmp; ta.x0 = v.x0_out;
     ta.skip_w = e->skip_w; ta.skip_b = e->skip_b; ta.outp_w = e->outp_w; ta.outp_b = e->outp_b; ta.zero = zero_vec();
     ta.u = tail->u; ta.x_out = tail->x_out;
-    if (tail->next_t >= 0) {
+    if (prime) {
+        ta.dual_next = np.dual0 ? v.bmod : 0;
         ta.in_w = e->in_w; ta.in_b = e->in_b; ta.d2_next = e->d_dtab + (size_t)tail->next_t * L * Cp;
         ta.h = e->h; ta.hd = e->hd;
-        if (p.dual0) {        // the next step's shared first-layer conv (as the dual launch of launch_conv)
+        if (np.dual0) {       // the next step's shared first-layer conv (as the dual launch of launch_conv)
             const LayerW& w0 = e->layers[0];
             ta.conv_w = w0.conv_w; ta.conv_b = w0.conv_b;
             ta.conv_b2 = v.zero_spec ? w0.conv_b_z : w0.conv_b_u;
@@ -294,7 +307,7 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
             ta.cond = e->cond ? e->cond : e->cond_dummy;
             ta.c_bs = (long)2 * Cp * T; ta.c_n = e->fe_B;
             ta.taps = e->K; ta.dil = w0.dil;
-            ta.fold = p.fold;
+            ta.fold = np.fold;
             ta.t4_ni = tuning().tail_t4;
             ta.g = e->g;
         }
@@ -308,12 +321,12 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, TailPlan* tail) {
     // strictly - and stays in [1, S], so the words keep growing across chains (dr_sample moves the base on by S per chain).
     ta.epoch = v.e->use_dyn ? (unsigned)(e->S - v.t) : ++e->win_epoch;
     // ticks 112..119 of dr_stack_status: the last tail launch of a chain that has a next step (all its parts run)
-    ta.dbg = (e->stack_dbg_on && tail->next_t >= 0) ? e->stack_dbg + 112 : nullptr;
+    ta.dbg = (e->stack_dbg_on && prime) ? e->stack_dbg + 112 : nullptr;
     HIPCHK(e, launch_tail(ta, v.st));
     e->tail_launches += 1;
     e->unverified = true; e->fused_stream = v.st;
     tail->done = true;
-    tail->inproj_done = tail->next_t >= 0;
+    tail->inproj_done = prime;
     return DR_OK;
 }
 
@@ -349,19 +362,24 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
     const NetPlan p = plan_network(NetShape{NB, n_cond, bmod, T, e->Cp, e->L, e->K, e->max_dil, e->prec, e->n_cus, e->fused.active(),
                                             e->opt_blocked, e->opt_tail, tsel != nullptr, tail != nullptr}, k);
     e->last_mode = p.mode;      // dr_launch_state
-    // h / hd of this step (and, guided, layer 0's g) were already written by the previous step's tail kernel
-    const bool primed = p.use_tail && tail->skip_inproj;
+    // h / hd of this step (and, guided, layer 0's g) were already written by the previous step's tail kernel - for an
+    // evaluation of exactly this shape (the rows written and whether layer 0's g exists depend on it)
+    const bool primed = p.use_tail && tail->skip_inproj && tail->primed.NB == NB && tail->primed.n_cond == n_cond &&
+                        tail->primed.dual == p.dual0;
     int rc;
     if (!primed && (rc = launch_inproj(v, k))) return rc;
     if (p.stack_from >= 0) {
         // (a guided pair's first conv is a launch of its own; everything from its 1x1 on is one launch)
-        if (p.stack_from == 1 && !primed && (rc = launch_conv(v, p, k, 0))) return rc;
+        if (p.stack_from == 1 && !primed) {
+            if ((rc = launch_conv(v, p, k, 0))) return rc;
+            e->conv0_launches += 1;
+        }
         if ((rc = launch_stack_range(v, p, p.stack_from, 2 * e->L))) return rc;
     } else {
         for (int l = 0; l < e->L; ++l)
             if ((rc = launch_conv(v, p, k, l)) || (rc = launch_res_skip(v, k, l))) return rc;
     }
-    return p.use_tail ? launch_tail_step(v, p, tail) : launch_head(v);
+    return p.use_tail ? launch_tail_step(v, p, k, tail) : launch_head(v);
 }
 
 int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& zero_spec) {
@@ -392,8 +410,13 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     bool zero_spec;
     if (sampler_shape(sampler, B, NB, n_cond, family, zero_spec)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     // Guidance weight 0: x0 = (1 + 0) c - 0 u = c (task/diffusion.py:953) - the unconditional evaluation is
-    // multiplied by zero, so it is not run (half the work; the w = 0 points of the paper's guidance sweeps).
-    if (w == 0.f && NB == 2 * B) { NB = B; n_cond = B; }
+    // multiplied by zero, so it is not run (half the work; the w = 0 points of the paper's guidance sweeps).  A step
+    // outside the guidance interval (options "guidance_t_min" / "guidance_t_max") is that step, whatever the caller's w;
+    // w == 0 is the empty interval (launch_plan.h: plan_step).
+    const bool guiding = NB == 2 * B;
+    const StepShapes shapes = plan_step(NB, n_cond, B, e->opt_guid, e->S, w == 0.f, t, chain ? chain->next_t : -1);
+    NB = shapes.now.NB; n_cond = shapes.now.n_cond;
+    if (guiding && !shapes.now.dual) w = 0.f;
     UpdateArgs u{};
     u.x = x; u.x0c = e->x0buf; u.x0u = (NB == 2 * B) ? e->x0buf + (size_t)B * T * 88 : nullptr;
     // row t of the family's table: the committed one, or under option "sampling_steps" the row for t's successor in the
@@ -415,7 +438,9 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     TailPlan plan;
     plan.u = u; plan.x_out = xalt; plan.u_B = B;
     plan.next_t = chain ? chain->next_t : -1;
+    plan.next = shapes.next;
     plan.skip_inproj = chain && chain->inproj_ready;
+    if (chain) plan.primed = chain->ready;
     // (x and the tail kernel's output buffer must differ: a caller that hands us xalt itself gets the unfused tail)
     TailPlan* offer = (result && x != xalt) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
@@ -423,7 +448,7 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     if (rc) return rc;
     if (offer && plan.done) {
         *result = xalt;
-        if (chain) chain->inproj_ready = plan.inproj_done;
+        if (chain) { chain->inproj_ready = plan.inproj_done; chain->ready = plan.next; }
         return DR_OK;
     }
     if (result) *result = x;

@@ -29,10 +29,15 @@ DR_BOUNDS_TU(tail)
 //       (the conditional and the unconditional evaluation start from the same x).  No barrier inside T3: the 4 row
 //       tiles of a chunk recompute the same (tiny) update instead of exchanging it.
 //   --  pair barrier (hd is stored write-through and read by T4 with L1-bypassing LDS-DMA)
-//   T4  (guided chains only) the next step's FIRST-LAYER dilated conv + conditioner + gate: both evaluations of a pair
+//   T4  (a guided step follows) the next step's FIRST-LAYER dilated conv + conditioner + gate: both evaluations of a pair
 //       convolve the same h + d_0, so the contraction is done once per pair - items = (M tile, 64-frame chunk) of the
 //       pair's clip dealt over the pair's blocks, gemm_body's dual epilogue writes both samples' g - exactly what the
 //       separate layer-0 launch did; the following stack launch starts at phase 1.
+// "Guided now" (TailArgs::dual: 2 B groups resident, T3 combines the pair's two predictions) and "guided next"
+// (TailArgs::dual_next: h / hd for rows b and b + B, T4) differ where a guidance interval begins or ends.  Leaving it, the
+// pair writes rows b alone and skips T4 (the next launch is an ordinary stack from layer 0); entering it, the B single
+// groups write both rows and run T4 on their own blocks behind a third GROUP barrier - "the pair's blocks" are then the
+// group's, and the dual epilogue writes g for rows b and b + B, of which only b has a group in this launch.
 // Same MFMA order (k ascending, one accumulator per output) and the same epilogue expressions as the per-phase
 // kernels without split-K: bit-identical to them.  512 threads (T1-T3: waves 0-3 contract, T4: 4 consumer + 4
 // producer waves); dynamic LDS = max(the 24-plane x 32-frame x tile of T3 (12 KiB), T4's X tiles).
@@ -174,35 +179,36 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
                 // (hd of the conditional sample is read by T4 of this launch, by other blocks: write-through)
                 *reinterpret_cast<float4*>(s.h + (long)pair_i * act_bs + off) = h4;
                 store_f4<1>(s.hd + (long)pair_i * act_bs + off, hd4, s.conv_w != nullptr);
-                if (paired) {
-                    *reinterpret_cast<float4*>(s.h + (long)(pair_i + s.dual) * act_bs + off) = h4;
-                    *reinterpret_cast<float4*>(s.hd + (long)(pair_i + s.dual) * act_bs + off) = hd4;
+                if (s.dual_next > 0) {
+                    *reinterpret_cast<float4*>(s.h + (long)(pair_i + s.dual_next) * act_bs + off) = h4;
+                    *reinterpret_cast<float4*>(s.hd + (long)(pair_i + s.dual_next) * act_bs + off) = hd4;
                 }
             }
         }
     }
     mark();
-    // ---- T4: the next step's shared first-layer conv (pairs only)
-    if (paired && s.conv_w) {
-        group_barrier<false>(pctr, 2u * (2u * gsize + DR_FAULT_EXTRA(s)), s.err, s.derr);
+    // ---- T4: the next step's shared first-layer conv (a guided step follows)
+    if (s.dual_next > 0 && s.conv_w) {
+        if (paired) group_barrier<false>(pctr, 2u * (2u * gsize + DR_FAULT_EXTRA(s)), s.err, s.derr);
+        else group_barrier<false>(ctr, 3u * (gsize + DR_FAULT_EXTRA(s)), s.err, s.derr);
         mark();
         GemmArgs a{};
         a.d2 = s.zero; a.wt_store = 0;                    // g is consumed by the NEXT launch: plain stores
         a.lds_bytes = s.lds_bytes;
-        a.MT = MT; a.NB = s.dual; a.T = s.T; a.alpha = 1.f; a.ksplit = 1;
+        a.MT = MT; a.NB = s.dual_next; a.T = s.T; a.alpha = 1.f; a.ksplit = 1;
         a.x_bs = act_bs; a.x_ps = (long)s.T * 4; a.x_fs = 4; a.x_planes = P; a.kchunks = s.Cp >> 5;
         a.y_bs = act_bs; a.y_ps = (long)s.T * 4; a.y_fs = 4; a.y_rows = s.Cp;
         a.Wp = s.conv_w; a.bias = s.conv_b; a.bias2 = s.conv_b2;
         a.X = s.hd; a.taps = s.taps; a.dil = s.dil;
-        a.cond = s.cond; a.cond2 = s.cond2; a.c_bs = s.c_bs; a.c_n = s.c_n; a.n_cond = s.dual;
-        a.dual = s.dual;
+        a.cond = s.cond; a.cond2 = s.cond2; a.c_bs = s.c_bs; a.c_n = s.c_n; a.n_cond = s.dual_next;
+        a.dual = s.dual_next;
         a.Y = s.g;
         // item width (launch_tail): 64 frames, or 96 where that needs fewer x narrower rounds over the pair's blocks (640-frame
         // clips in 32-block groups: 56 items of 96 frames = one round instead of 80 items of 64 frames = two)
         const int bn4 = s.t4_ni == 3 ? 96 : 64;
         const int tps4 = (s.T + bn4 - 1) / bn4;
         const int n4 = MT * tps4;
-        for (int it = pair_half * (int)gsize + member; it < n4; it += 2 * (int)gsize) {
+        for (int it = pair_half * (int)gsize + member; it < n4; it += (paired ? 2 : 1) * (int)gsize) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();                              // (the LDS tiles of the previous item / of T3 are free)
             // (same accumulation order as the stack launch that consumes g: blocked unless that is the unblocked 128-frame flavour)
@@ -233,6 +239,8 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
     if (s.BN != 64 && s.BN != 128 && s.BN != 160) return hipErrorInvalidValue;
     if ((s.Cp & 63) || s.NB < 1 || s.T < 1) return hipErrorInvalidValue;
     if (s.dual > 0 && s.NB != 2 * s.dual) return hipErrorInvalidValue;
+    // (a guided successor pairs row b with row b + u_B: the rolls of this launch, one per pair / single group)
+    if (s.dual_next < 0 || (s.dual_next > 0 && (s.dual_next != s.u_B || s.u_B != (s.dual > 0 ? s.dual : s.NB)))) return hipErrorInvalidValue;
     if (!s.x_out || s.x_out == s.u.x) return hipErrorInvalidValue;
     if (s.u.win_H > 0 && (!s.ready || s.u_B > STACK_GROUPS || 2 * s.u.win_H < s.T || s.u.win_H >= s.T)) return hipErrorInvalidValue;
     if (s.u.win_tab && s.u.win_H <= 0) return hipErrorInvalidValue;      // (a table of u_B <= STACK_GROUPS words: windows only)
@@ -241,10 +249,10 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
     const int NBp = xcd_padded_groups(s.NB, MT * tps, &b.xcd_n);       // idle padding groups, as launch_stack
     size_t lds = 24 * 32 * 16;
     if (s.conv_w) {
-        if (s.dual <= 0 || (s.taps & 1) == 0) return hipErrorInvalidValue;
-        // T4's item width: rounds over the pair's 2 * gsize blocks x frames per item, 64 unless 96 is strictly cheaper (the
-        // 96-frame body exists with blocked accumulation only)
-        const long pair_blocks = 2L * MT * tps;
+        if (s.dual_next <= 0 || !s.in_w || (s.taps & 1) == 0) return hipErrorInvalidValue;
+        // T4's item width: rounds over the pair's 2 * gsize blocks (gsize where this step is not guided) x frames per item,
+        // 64 unless 96 is strictly cheaper (the 96-frame body exists with blocked accumulation only)
+        const long pair_blocks = (s.dual > 0 ? 2L : 1L) * MT * tps;
         const long n64 = (long)MT * ((s.T + 63) / 64), n96 = (long)MT * ((s.T + 95) / 96);
         const long c64 = (n64 + pair_blocks - 1) / pair_blocks * 64, c96 = (n96 + pair_blocks - 1) / pair_blocks * 96;
         b.t4_ni = (s.fold && s.t4_ni != 1 && (c96 < c64 || s.t4_ni == 3)) ? 3 : 1;

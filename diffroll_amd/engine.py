@@ -330,7 +330,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -345,6 +345,29 @@ class Engine:
             self.draws = int(value)
         if name == "draw_stride":
             self.draw_stride = int(value)
+        if name == "guidance_t_min":
+            self.guidance_interval = (int(value), self.guidance_interval[1])
+        if name == "guidance_t_max":
+            self.guidance_interval = (self.guidance_interval[0], int(value))
+
+    def set_guidance_interval(self, lo: int = 0, hi: int = -1):
+        """Options 'guidance_t_min' / 'guidance_t_max' together: a guiding sampler guides the steps lo <= t <= hi (hi = -1:
+        timesteps - 1) and runs the conditional evaluation alone at the others.  Validated before either is set."""
+        S = self.timesteps
+        for v in (lo, hi):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"guidance interval bounds are integers, got {v!r}")
+        if not 0 <= lo < S or not -1 <= hi < S or lo > (S - 1 if hi < 0 else hi):
+            raise ValueError(f"guidance interval needs 0 <= lo <= hi < timesteps = {S} (hi = -1: timesteps - 1), got [{lo}, {hi}]")
+        self.set_option("guidance_t_min", lo)
+        self.set_option("guidance_t_max", hi)
+
+    def launch_counts(self):
+        """(standalone input-projection launches, standalone shared first-layer conv launches) issued so far: what no tail
+        kernel primed (dr_debug_launch_counts, include/diffroll_amd_debug.h)."""
+        out = (C.c_int64 * 2)()
+        self._check(self.lib.dr_debug_launch_counts(self.h, out))
+        return int(out[0]), int(out[1])
 
     def set_window_breaks(self, marks):
         """Replace the marks of option 'window_break' (the windows of the next batch that start a new recording)."""
@@ -358,6 +381,7 @@ class Engine:
     window_breaks = ()      # the marks set with option 'window_break' (windows that start a new recording), ascending
     sampling_steps = 0      # the last value set for option 'sampling_steps' (0 = every step, the library's default)
     draws = 1               # the last value set for option 'draws' (rolls per clip of one chain, draw-major; 1 = the default)
+    guidance_interval = (0, -1)   # the last values set for options 'guidance_t_min' / 'guidance_t_max' ((0, -1) = the whole chain)
     draw_stride = 0         # the last value set for option 'draw_stride' (Philox key distance of two draws; 0 = the clips of the batch)
 
     def visited_steps(self):

@@ -26,7 +26,7 @@ import contextlib
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import check_sampling_steps, respaced_steps
+from .schedule import check_guidance_interval, check_sampling_steps, respaced_steps
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
@@ -151,6 +151,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.draws = D samples D rolls per clip in one chain (option "draws") and scores / exports their
         # mean (diffroll_amd/ensemble.py); absent / None / 1 = one roll per clip
         check_draws(sampling.get("draws"))
+        # an extension: sampling.guidance_interval = [lo, hi] guides the steps lo <= t <= hi only (options "guidance_t_min" /
+        # "guidance_t_max"); absent / None = the whole chain, the reference's behaviour
+        check_guidance_interval(sampling.get("guidance_interval"), timesteps, sampling.type)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -242,6 +245,7 @@ class ClassifierFreeDiffRoll(nn.Module):
 
     @property
     def engine(self) -> Engine:
+        interval = self.guidance_interval()               # (a malformed one raises here: before any GPU work)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
                                   fe_window=self.__dict__.get("_ckpt_window"), fe_fb=self.__dict__.get("_ckpt_fb"),
@@ -260,7 +264,16 @@ class ClassifierFreeDiffRoll(nn.Module):
         steps = self.sampling_steps()
         if self._engine.sampling_steps != steps:          # (a change drops the engine's captured chain)
             self._engine.set_option("sampling_steps", steps)
+        if self._engine.guidance_interval != interval:    # (part of the captured chain's key: nothing is dropped)
+            self._engine.set_guidance_interval(*interval)
         return self._engine
+
+    def guidance_interval(self):
+        """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain.  Read
+        at every use, like the other hparams.sampling keys; raises ValueError for a malformed interval or a sampler that
+        does not guide - before any GPU work (every sampling method reaches the engine through here)."""
+        hp = self.__dict__["hparams"]
+        return check_guidance_interval(hp.sampling.get("guidance_interval"), hp.timesteps, hp.sampling.type)
 
     def sampling_steps(self) -> int:
         """n of hparams.sampling.steps (0: every step), or 0 while one of the reference's single-step methods runs."""

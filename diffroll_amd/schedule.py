@@ -105,6 +105,27 @@ def check_sampling_steps(n, timesteps: int) -> int:
     return n
 
 
+GUIDING_SAMPLERS = ("cfdg_ddpm_x0", "inpainting_ddpm_x0", "cfdg_ddim_x0")
+
+
+def check_guidance_interval(interval, timesteps: int, sampler: str = None):
+    """Options "guidance_t_min" / "guidance_t_max" (include/diffroll_amd.h) as hparams.sampling.guidance_interval = [lo, hi]:
+    the steps lo <= t <= hi of a guiding sampler run both evaluations, the others the conditional one alone.  None = the
+    whole chain.  Returns the options' values (lo, hi), (0, -1) for None; a malformed interval - not two integers,
+    outside [0, timesteps), lo > hi - or a sampler that does not guide raises ValueError."""
+    if interval is None:
+        return 0, -1
+    S = int(timesteps)
+    ok = isinstance(interval, (list, tuple)) and len(interval) == 2 and all(
+        isinstance(v, int) and not isinstance(v, bool) for v in interval)
+    if not ok or not 0 <= interval[0] <= interval[1] < S:
+        raise ValueError(f"guidance_interval must be [lo, hi] with integers 0 <= lo <= hi < timesteps = {S} (or None: the "
+                         f"whole chain), got {interval!r}")
+    if sampler is not None and sampler not in GUIDING_SAMPLERS:
+        raise ValueError(f"guidance_interval needs a sampler that guides ({', '.join(GUIDING_SAMPLERS)}), not '{sampler}'")
+    return int(interval[0]), int(interval[1])
+
+
 def respaced_steps(timesteps: int, n: int) -> List[int]:
     """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
     integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""

@@ -400,6 +400,27 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          0 = n (then the key is first_sample + b, that of the tiled batch).  A sharded run sets G to the
  *                          global clip count: draw d of global clip c gets the same noise on any world size.  Ignored
  *                          while "draws" is 1; < 0 -> DR_EINVAL.  Part of a captured chain's key, like "draws".
+ *   "guidance_t_min"   [0] lo, 0 <= lo < timesteps, and
+ *   "guidance_t_max"  [-1] hi, -1 (= timesteps - 1) or 0 <= hi < timesteps: the GUIDANCE INTERVAL (limited-interval
+ *                          guidance).  A reverse step at the real diffusion step t of a sampler that guides
+ *                          (DR_SAMPLER_CFDG_DDPM_X0, _INPAINTING_DDPM_X0, _CFDG_DDIM_X0) is guided iff lo <= t <= hi: it is
+ *                          then exactly the step with the caller's w.  Every other step is exactly the step with w = 0:
+ *                          only the conditional evaluation of the B rolls runs (B network evaluations instead of 2 B) and the
+ *                          update consumes it unchanged - (1 + 0) c - 0 u == c, so no value changes by not computing u.  It
+ *                          is the reference's own sampler run with a per-step weight, w inside [lo, hi] and 0 outside.  The
+ *                          defaults guide the whole chain, bit-identical to an engine that never set the options; the other
+ *                          six samplers ignore both; w == 0 stays what it is whatever the interval.  A value out of range
+ *                          -> DR_EINVAL at the set; an effective lo > hi -> DR_EINVAL at the next dr_step / dr_sample /
+ *                          dr_sample_checked with a guiding sampler, naming both values.  Under "sampling_steps" the test
+ *                          uses the real t of each visited step (the derived rows are untouched); under "window_overlap" /
+ *                          "window_break" a step is guided or not for all windows alike, and the shared-frame mean is taken
+ *                          of whichever prediction the step uses; combines with "draws" / "draw_stride", both precisions and
+ *                          sharding (every rank sets the same interval).  dr_step: step t alone follows the rule;
+ *                          dr_sample_checked's re-run uses the same interval; dr_forward, dr_forward_steps, dr_q_sample,
+ *                          dr_extract_x0 are unaffected.  Philox keys and injected-noise rows are unchanged.  The effective
+ *                          pair is part of a captured chain's key, like "draws": setting the options drops nothing, and a
+ *                          chain captured under another interval is never replayed.  Nothing is known about the quality
+ *                          of a limited interval with this model.
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */

@@ -90,6 +90,12 @@ int dr_bench_pointwise(dr_engine* e, int layer, int NB, int T, void* stream);
  * wall time this gives the effective clock the kernel ran at. */
 int dr_debug_ticks(dr_engine* e, int64_t* loop_ticks, int64_t* block_ticks);
 
+/* Launches that a chain's tail kernel would have absorbed, counted since the engine was created (captured launches count
+ * once, at capture): out2 = {standalone input-projection launches, standalone launches of a guided step's shared
+ * first-layer conv in front of a fused stack}.  A fused chain issues one of the first (its first step) and at most one of
+ * the second, also across the ends of a guidance interval. */
+int dr_debug_launch_counts(dr_engine* e, int64_t* out2);
+
 #ifdef __cplusplus
 }
 #endif
