@@ -129,6 +129,14 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
             check_guidance_interval(interval, S, cfg["task"]["sampling"]["type"])
         except ValueError as err:
             raise SystemExit(f"task.sampling.guidance_interval: {err}")
+    # task.sampling.solver_order=N: integrate the x0 prediction with a multistep solver (option "solver_order"); absent /
+    # null / 0 = the sampler's own update
+    if cfg["task"]["sampling"].get("solver_order") is not None:
+        from .schedule import check_solver_order
+        try:
+            check_solver_order(cfg["task"]["sampling"]["solver_order"], cfg["task"]["sampling"]["type"])
+        except ValueError as err:
+            raise SystemExit(f"task.sampling.solver_order: {err}")
     per_chain = cfg["task"].get("recordings_per_chain", 1)
     if isinstance(per_chain, bool) or not isinstance(per_chain, int) or per_chain < 1:
         raise SystemExit(f"task.recordings_per_chain must be an integer >= 1, got {per_chain!r}")

@@ -258,6 +258,57 @@ int chain_step(const dr_engine* e, int i) {
     return e->rs_steps.empty() ? e->S - 1 - i : e->rs_steps[i];
 }
 
+// option "solver_order" (include/diffroll_amd.h): the (S, 5) rows solver_quad reads (update_quad.h), for the steps the chain
+// visits - all of them, or those of option "sampling_steps".  With lambda_t = log(sqrt_acp[t] / sqrt_1m_acp[t]), t' the
+// successor of t and t'' its predecessor in the chain, h = lambda_t' - lambda_t and h_prev = lambda_t - lambda_t'':
+//   t > 0:  [sqrt_1m_acp[t'] / sqrt_1m_acp[t], -sqrt_acp[t'] expm1(-h), sqrt_acp[t], c, 0]
+//           c = h / (2 h_prev) for order 2 when t is not the chain's first step and t' != 0, else 0: the step into 0 is
+//           first order (lambda jumps between steps 1 and 0 of the linear schedule; extrapolating across it hurts short chains)
+//   t == 0: [0, 0, sqrt_acp[0], 0, 0]
+// derived in double from the committed fp32 scalars (family 0, columns 2 and 3), rounded to fp32 once.  Rebuilt by
+// dr_commit and whenever "sampling_steps" or "solver_order" changes; the caller has made sure no chain is reading it.
+int build_solver(dr_engine* e) {
+    const int S = e->S, n = chain_steps(e);
+    e->h_solver.assign((size_t)S * 5, 0.f);
+    if (e->opt_solver == 0) return DR_OK;
+    const float* h = e->h_coef.data();
+    auto lambda = [&](int t) { return std::log((double)h[(size_t)t * 5 + 2] / (double)h[(size_t)t * 5 + 3]); };
+    for (int i = 0; i < n; ++i) {
+        const int t = chain_step(e, i);
+        float* row = e->h_solver.data() + (size_t)t * 5;
+        row[2] = h[(size_t)t * 5 + 2];
+        if (t == 0) continue;
+        const int tp = chain_step(e, i + 1);
+        const double Sm = h[(size_t)t * 5 + 3], Ap = h[(size_t)tp * 5 + 2], Smp = h[(size_t)tp * 5 + 3];
+        const double hh = lambda(tp) - lambda(t);
+        row[0] = (float)(Smp / Sm);
+        row[1] = (float)(-Ap * std::expm1(-hh));
+        if (e->opt_solver == 2 && i > 0 && tp != 0) row[3] = (float)(hh / (2.0 * (lambda(t) - lambda(chain_step(e, i - 1)))));
+    }
+    HIPCHK(e, e->d_solver.ensure(e->h_solver.size(), false));
+    HIPCHK(e, hipMemcpy(e->d_solver, e->h_solver.data(), e->h_solver.size() * sizeof(float), hipMemcpyHostToDevice));
+    return DR_OK;
+}
+
+// option "solver_order" applies to the x0-prediction samplers (DR_SAMPLER_* 0-5); the epsilon samplers refuse it
+int check_solver(dr_engine* e, int sampler) {
+    if (e->opt_solver != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
+        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: solver_order = %d integrates an x0 prediction (samplers 0-5); set "
+                                  "solver_order 0 for the sampler's own update", sampler, e->opt_solver);
+    return DR_OK;
+}
+// order 2: the two history buffers, before anything is launched or captured (a chain that may still read them is waited for)
+int ensure_history(dr_engine* e, int B, int T, hipStream_t st) {
+    if (e->opt_solver != 2) return DR_OK;
+    const size_t per = (size_t)B * T * 88;
+    if (e->hist[0].fits(per) && e->hist[1].fits(per)) return DR_OK;
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
+    e->hist_key.valid = false;
+    for (auto& b : e->hist) HIPCHK(e, b.ensure(per, true));
+    return DR_OK;
+}
+
 // dr_set_option (lab = false: the product's options) / dr_debug_set_option (lab = true: the A/B and test knobs too)
 int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (!e || !name) return fail(e, DR_EINVAL, "null argument");
@@ -294,6 +345,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // (no captured chain is dropped: the value is part of the chain's key - GraphKey - so a chain captured under
         // another value is simply not replayed, and one captured under this value still is)
         if (value < 1) return fail(e, DR_EINVAL, "draws is >= 1 (1 = every roll its own clip), got %d", value);
+        if (e->opt_draws != value) e->hist_key.valid = false;
         e->opt_draws = value;
         return DR_OK;
     }
@@ -310,7 +362,19 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         e->opt_steps = value;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         if (int rc = build_respaced(e)) { e->opt_steps = 0; return rc; }
-        return DR_OK;
+        return build_solver(e);               // (its rows belong to the steps this chain visits)
+    }
+    if (n == "solver_order") {
+        // (no captured chain is dropped: the value is part of the chain's key - GraphKey - as "draws" is.  A chain captured
+        // under this value reads the table at replay, and the table is this value's whenever that chain is replayed.)
+        if (value < 0 || value > 2)
+            return fail(e, DR_EINVAL, "solver_order is 0 (the sampler's own update), 1 or 2 (DPM-Solver++ 2M), got %d", value);
+        if (e->opt_solver == value) return DR_OK;
+        (void)hipDeviceSynchronize();         // a chain of the previous order may still be reading the table
+        e->opt_solver = value;
+        e->hist_key.valid = false;
+        if (!e->committed) return DR_OK;      // (dr_commit builds it)
+        return build_solver(e);
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
         // (no captured chain is dropped: the effective pair is part of the chain's key - GraphKey - as "draws" is; lo > hi is
@@ -594,8 +658,27 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if ((rc = check_windows(e, B, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
+    if ((rc = check_solver(e, sampler))) return rc;
     if ((rc = check_guidance(e, B, NB))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
+    if ((rc = ensure_history(e, B, T, (hipStream_t)stream))) return rc;
+    if (e->opt_solver == 2) {
+        // the history is engine state: the chain's first step starts one, every other step continues the one the previous
+        // dr_step left - the preceding visited step of the same (sampler, B, T)
+        const int first = chain_step(e, 0);
+        auto& k = e->hist_key;
+        if (t != first) {
+            const bool same = k.valid && k.sampler == sampler && k.B == B && k.T == T;
+            int expect = first;
+            if (same)
+                for (int i = 0, n = chain_steps(e); i + 1 < n; ++i)
+                    if (chain_step(e, i) == k.t) expect = chain_step(e, i + 1);
+            if (!same || expect != t)
+                return fail(e, DR_ESTATE, "solver_order = 2: dr_step at step %d continues no history - the step expected next is %d "
+                                          "(the chain's first step starts a new history; every other step follows its predecessor)", t, expect);
+        } else e->hist_par = 0;
+        k.valid = false;      // (until the step has been issued)
+    }
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
     if ((rc = write_windows(e, B, false, (hipStream_t)stream))) return rc;
@@ -603,6 +686,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if ((rc = run_step(e, sampler, d_x, d_noise, B, T, t, w, seed, first_sample, (hipStream_t)stream, &res))) return rc;
     if (res != d_x)      // the fused step wrote x_{t-1} into the engine's buffer: hand it back in place
         HIPCHK(e, hipMemcpyAsync(d_x, res, (size_t)B * T * 88 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (e->opt_solver == 2 && t > 0) { auto& k = e->hist_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
     return DR_OK;
 }
 
@@ -615,9 +699,12 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if ((rc = check_windows(e, B, T))) return rc;
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
+    if ((rc = check_solver(e, sampler))) return rc;
     if ((rc = check_guidance(e, B, NB))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_history(e, B, T, st))) return rc;
+    e->hist_key.valid = false;      // (a whole chain uses the history buffers: a dr_step sequence does not continue across it)
     if (e->tuning_epoch != tuning_epoch().load()) {      // a tune.* knob changed (any engine, any thread): the cached chain is stale
         if ((rc = drop_chain(e))) return rc;
         e->tuning_epoch = tuning_epoch().load();
@@ -632,6 +719,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         // place), and each tail also computes the next step's input projection
         ChainState cs;
         float* cur = xbuf;
+        e->hist_par = 0;      // (option "solver_order": the first step reads no history - its row has c = 0)
         // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows)
         for (int i = 0, n = chain_steps(e); i < n; ++i) {
             const int t = chain_step(e, i);
@@ -656,6 +744,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
     key.draws = e->opt_draws; key.draw_G = e->opt_draws > 1 ? e->opt_draw_G : 0; key.fe_B = e->fe_B;
     if (NB == 2 * B) { key.g_lo = e->opt_guid.lo; key.g_hi = e->opt_guid.hi_eff(e->S); }
+    key.order = e->opt_solver; key.hist = e->opt_solver == 2 ? (const float*)e->hist[0] : nullptr;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

@@ -63,9 +63,14 @@ struct GraphKey {
     // ... and which steps run the unconditional evaluation: options "guidance_t_min" / "guidance_t_max" (the effective pair)
     // are part of the key too - a chain captured under another interval is never replayed
     int g_lo = 0, g_hi = 0;
+    // ... and how the prediction is integrated: option "solver_order" (the update's mode, its table and the history
+    // buffers' parity per node), like "draws" part of the key - setting it drops nothing
+    int order = 0;
+    const float* hist = nullptr;      // the first history buffer (null: order < 2)
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
-               draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi;
+               draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi &&
+               order == o.order && hist == o.hist;
     }
 };
 
@@ -196,6 +201,18 @@ struct dr_engine {
     std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
     drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor
                                         // is not t - 1 replaced by the respaced row (build_respaced); empty when rs_steps is
+    // option "solver_order": 0 = the sampler's own update; 1 / 2 = the x0-prediction samplers integrate their prediction
+    // with the first-order exponential integrator in lambda / DPM-Solver++ (2M) (update_quad.h: solver_quad)
+    int opt_solver = 0;
+    std::vector<float> h_solver;        // (S, 5) rows of the chain's visited steps (build_solver); unvisited rows are zero
+    drh::DevBuf<float> d_solver;        // ... on the device
+    // order 2: the previous step's prediction.  Two (B, T, 88) buffers, allocated on first use and used ping-pong (the
+    // tail kernel's row tiles recompute a quad in different blocks: the one that stores must not overwrite what the
+    // others still read); hist_par = the one the next step reads.  A captured chain bakes the parity per node.
+    drh::DevBuf<float> hist[2];
+    int hist_par = 0;
+    // dr_step under order 2: what the history holds - the prediction of step hist_t of a (sampler, B, T) chain
+    struct { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; } hist_key;
     dr::GuidanceInterval opt_guid;      // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
@@ -300,6 +317,7 @@ int clear_stack_timeout(dr_engine* e);
 int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab: the names of dr_debug_set_option too
 void set_kfd_root(const char* root);                                      // dr_debug_kfd_root
 int build_respaced(dr_engine* e);       // option "sampling_steps": rs_steps and d_coef_rs from opt_steps and h_coef
+int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_solver from the chain's steps and h_coef
 
 // ---- pack.hip
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);

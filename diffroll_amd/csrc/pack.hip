@@ -430,6 +430,7 @@ int commit(dr_engine* e, hipStream_t st) {
     HIPCHK(e, e->d_coef.ensure((size_t)DR_COEF_FAMILIES * S * 5, true));
     HIPCHK(e, hipMemcpy(e->d_coef, e->h_coef.data(), (size_t)DR_COEF_FAMILIES * S * 5 * sizeof(float), hipMemcpyHostToDevice));
     if ((rc = build_respaced(e))) return rc;      // option "sampling_steps": rows derived from these tables
+    if ((rc = build_solver(e))) return rc;        // option "solver_order": likewise, for the steps that chain visits
     HIPCHK(e, e->d_dtab.ensure((size_t)S * L * Cp, true));
     HIPCHK(e, e->sk_ws.ensure(SK_WS_FLOATS, false));
     // ticket counters, group counters of the persistent kernels: zero between launches (the kernels re-arm them)

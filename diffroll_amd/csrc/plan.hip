@@ -426,6 +426,16 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     u.seed = seed; u.first_sample = first_sample;
+    // option "solver_order" (the callers have refused the epsilon samplers): the solver's own row and update, no noise and
+    // no Philox - their fields hold the history pointers (kernels.h).  Order 2 reads the previous step's prediction where
+    // the row says so and leaves this step's for the next (ping-pong); order 1 neither reads nor stores.
+    if (e->opt_solver != 0 && family <= DR_COEF_DDIM_X0) {
+        const bool hist = e->opt_solver == 2;
+        u.coef = e->d_solver + (size_t)t * 5; u.mode = 5;
+        u.hist_prev = hist ? (const float*)e->hist[e->hist_par] : nullptr;
+        u.hist_next = hist && t > 0 ? (float*)e->hist[e->hist_par ^ 1] : nullptr;
+        if (hist) e->hist_par ^= 1;
+    }
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
     u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
     // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)
@@ -460,6 +470,7 @@ void drop_graph(dr_engine* e) {
     if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
     if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
     e->gkey = GraphKey{};
+    e->hist_key.valid = false;      // (option "solver_order": whatever dropped the chain also ends a dr_step history)
 }
 
 }  // namespace drh

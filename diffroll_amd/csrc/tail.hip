@@ -135,8 +135,14 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
                 float4 v = f4zero();
                 if (pl < 22 && f0 + fi < s.T) {
                     const long i4 = (roll0 + (long)(f0 + fi) * 88 + pl * 4) >> 2;
-                    v = update_quad(s.u, i4);
-                    if (mti == 0) reinterpret_cast<float4*>(s.x_out)[i4] = v;
+                    float4 y;
+                    v = update_quad(s.u, i4, &y);
+                    if (mti == 0) {
+                        reinterpret_cast<float4*>(s.x_out)[i4] = v;
+                        // (option "solver_order": this step's prediction for the next one, under the same guard - into the
+                        // history buffer this launch does not read)
+                        if (s.u.mode == 5 && s.u.hist_next) reinterpret_cast<float4*>(s.u.hist_next)[i4] = y;
+                    }
                 }
                 DR_CHECK_LDS(XT + pl * 32 + fi, lds_off(XT), lds_off(XT) + 24u * 32u * 16u, 151);
                 XT[pl * 32 + fi] = v;

@@ -8,7 +8,9 @@ namespace dr {
 __global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
     const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
     if (i4 * 4 >= a.n) return;
-    reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4);
+    float4 y;
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4, &y);
+    if (a.mode == 5 && a.hist_next) reinterpret_cast<float4*>(a.hist_next)[i4] = y;      // (option "solver_order")
 }
 
 __global__ void set_dyn_kernel(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, unsigned epoch) {

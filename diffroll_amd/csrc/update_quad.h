@@ -1,5 +1,5 @@
-// Philox4x32-10 + Box-Muller and the posterior update of one roll quad: shared by update_kernel (update.hip) and part T3
-// of the tail kernel (tail.hip) - identical arithmetic.
+// Philox4x32-10 + Box-Muller, the posterior update and the multistep solver update of one roll quad: shared by
+// update_kernel (update.hip) and part T3 of the tail kernel (tail.hip) - identical arithmetic.
 #pragma once
 #include "device_common.h"
 
@@ -54,7 +54,38 @@ DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, c
 // Long-form windows (a.win_H > 0, UpdateArgs): on a frame shared with a neighbouring window of the same recording the prediction is the mean
 // 0.5f * (y_lower + y_upper) of both windows' guided predictions - the same bits in both (the operands are the same
 // two values, added in the same order) - and the noise is keyed by the canvas element.
-DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
+// mode 5 (option "solver_order", x0-prediction samplers): the exponential integrator in lambda = log(sqrt_acp / sqrt_1m_acp)
+// of Lu et al. 2022 (DPM-Solver++), row [sqrt_1m_acp' / sqrt_1m_acp, -sqrt_acp' expm1(-h), sqrt_acp, c, 0] (abi.hip:
+// build_solver).  y is the guided prediction after the shared-frame mean, p the y of the previous step (a.hist_prev):
+//   d = c != 0 ? y + c (y - p) : y      (2M; c = h / (2 h_prev), 0 = first order: p is not loaded)
+//   o = c0 x + c1 d;   t == 0: o = y / c2, the x0 samplers' own last step
+// One fp32 rounding per operation, no noise (deterministic).  The caller stores y to a.hist_next for the next step
+// (update_quad hands it out): in the tail kernel several blocks recompute a quad and one of them stores.
+DR_DEVINL float4 solver_quad(const UpdateArgs& a, const long i4, const float (&y)[4]) {
+#pragma clang fp contract(off)
+    const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c = a.coef[3];
+    float o[4];
+    if (a.t == 0) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = y[e] / c2;
+        return make_float4(o[0], o[1], o[2], o[3]);
+    }
+    const float4 xv = reinterpret_cast<const float4*>(a.x)[i4];
+    const float x[4] = {xv.x, xv.y, xv.z, xv.w};
+    float d[4] = {y[0], y[1], y[2], y[3]};
+    if (c != 0.f) {
+        const float4 pv = reinterpret_cast<const float4*>(a.hist_prev)[i4];
+        const float p[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = y[e] + c * (y[e] - p[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = c0 * x[e] + c1 * d[e];
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean (mode 5's history).
+DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr) {
 #pragma clang fp contract(off)
     float x0[4];
     // per-call scalars: by value (eager launches) or from the device block (captured chain)
@@ -92,6 +123,8 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4) {
         key_smp = first_sample + rec;
         key_q = (idx * a.win_H * 88 + within) >> 2;
     }
+    if (pred) *pred = make_float4(x0[0], x0[1], x0[2], x0[3]);
+    if (a.mode == 5) return solver_quad(a, i4, x0);
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];
     // which updates draw noise at t > 0: x0 DDPM (0), eps ddpm (2), eps ddim2ddpm (4)

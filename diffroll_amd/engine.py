@@ -330,7 +330,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -345,6 +345,8 @@ class Engine:
             self.draws = int(value)
         if name == "draw_stride":
             self.draw_stride = int(value)
+        if name == "solver_order":
+            self.solver_order = int(value)
         if name == "guidance_t_min":
             self.guidance_interval = (int(value), self.guidance_interval[1])
         if name == "guidance_t_max":
@@ -382,6 +384,7 @@ class Engine:
     sampling_steps = 0      # the last value set for option 'sampling_steps' (0 = every step, the library's default)
     draws = 1               # the last value set for option 'draws' (rolls per clip of one chain, draw-major; 1 = the default)
     guidance_interval = (0, -1)   # the last values set for options 'guidance_t_min' / 'guidance_t_max' ((0, -1) = the whole chain)
+    solver_order = 0        # the last value set for option 'solver_order' (0 = the sampler's own update, the library's default)
     draw_stride = 0         # the last value set for option 'draw_stride' (Philox key distance of two draws; 0 = the clips of the batch)
 
     def visited_steps(self):

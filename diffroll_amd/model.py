@@ -26,7 +26,7 @@ import contextlib
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import check_guidance_interval, check_sampling_steps, respaced_steps
+from .schedule import check_guidance_interval, check_sampling_steps, check_solver_order, respaced_steps
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
@@ -154,6 +154,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.guidance_interval = [lo, hi] guides the steps lo <= t <= hi only (options "guidance_t_min" /
         # "guidance_t_max"); absent / None = the whole chain, the reference's behaviour
         check_guidance_interval(sampling.get("guidance_interval"), timesteps, sampling.type)
+        # an extension: sampling.solver_order = 1 / 2 integrates the x0 prediction with a multistep ODE solver (option
+        # "solver_order": DPM-Solver++), the companion of sampling.steps; absent / None / 0 = the sampler's own update
+        check_solver_order(sampling.get("solver_order"), sampling.type)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -246,6 +249,7 @@ class ClassifierFreeDiffRoll(nn.Module):
     @property
     def engine(self) -> Engine:
         interval = self.guidance_interval()               # (a malformed one raises here: before any GPU work)
+        order = self.solver_order()                       # (likewise)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
                                   fe_window=self.__dict__.get("_ckpt_window"), fe_fb=self.__dict__.get("_ckpt_fb"),
@@ -266,7 +270,17 @@ class ClassifierFreeDiffRoll(nn.Module):
             self._engine.set_option("sampling_steps", steps)
         if self._engine.guidance_interval != interval:    # (part of the captured chain's key: nothing is dropped)
             self._engine.set_guidance_interval(*interval)
+        if self._engine.solver_order != order:            # (likewise part of the key)
+            self._engine.set_option("solver_order", order)
         return self._engine
+
+    def solver_order(self) -> int:
+        """hparams.sampling.solver_order as the engine's option takes it (0: the sampler's own update), or 0 while one of
+        the reference's single-step methods runs.  Read at every use; a bad value or an epsilon sampler raises ValueError
+        before any GPU work."""
+        hp = self.__dict__["hparams"]
+        order = check_solver_order(hp.sampling.get("solver_order"), hp.sampling.type)
+        return 0 if self.__dict__.get("_stride1") else order
 
     def guidance_interval(self):
         """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain.  Read
@@ -511,7 +525,8 @@ class ClassifierFreeDiffRoll(nn.Module):
         """The reverse chain t = timesteps-1 .. 0 (task/diffusion.py:528-534) - or, with hparams.sampling.steps = n,
         the n respaced steps of visited_steps() - on the device with no host round trip.  x_T (B,1,T,88); noise: None
         (on-device Philox keyed by seed, global sample index and step) or (timesteps, B, 1, T, 88) injected z's (row t
-        is used at step t >= 1, also in a respaced chain).
+        is used at step t >= 1, also in a respaced chain).  With hparams.sampling.solver_order = 1 / 2 (option
+        "solver_order": DPM-Solver++ on the x0 prediction) the chain is deterministic: noise and seed are not used.
         Returns (roll (B,1,T',88), spec (B,n_mels,T')).
         draws = D > 1 (option "draws" of include/diffroll_amd.h): x_T (D*n,1,T,88) holds D draws of the n clips of waveform
         (n, L), draw-major (row b = draw b // n of clip b % n); the front-end and the conditioner tensors exist once per

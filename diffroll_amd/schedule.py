@@ -105,6 +105,23 @@ def check_sampling_steps(n, timesteps: int) -> int:
     return n
 
 
+X0_SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0", "ddim_x0", "cfdg_ddim_x0")
+
+
+def check_solver_order(order, sampler: str = None) -> int:
+    """Option "solver_order" (include/diffroll_amd.h) as hparams.sampling.solver_order: None / 0 = the sampler's own update,
+    1 = the first-order exponential integrator in lambda, 2 = DPM-Solver++ (2M).  Returns the option's value; any other
+    value, or a non-zero order with a sampler that predicts epsilon, raises ValueError."""
+    if order is None:
+        return 0
+    if isinstance(order, bool) or not isinstance(order, int) or order not in (0, 1, 2):
+        raise ValueError(f"solver_order must be 0 / None (the sampler's own update), 1 or 2 (DPM-Solver++ 2M), got {order!r}")
+    if order and sampler is not None and sampler not in X0_SAMPLERS:
+        raise ValueError(f"solver_order = {order} integrates an x0 prediction ({', '.join(X0_SAMPLERS)}); '{sampler}' "
+                         f"predicts epsilon")
+    return order
+
+
 GUIDING_SAMPLERS = ("cfdg_ddpm_x0", "inpainting_ddpm_x0", "cfdg_ddim_x0")
 
 

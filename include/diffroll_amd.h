@@ -421,6 +421,38 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          pair is part of a captured chain's key, like "draws": setting the options drops nothing, and a
  *                          chain captured under another interval is never replayed.  Nothing is known about the quality
  *                          of a limited interval with this model.
+ *   "solver_order"     [0] 0, 1 or 2: how the x0-prediction samplers (DR_SAMPLER_* 0-5) INTEGRATE their prediction - a
+ *                          multistep ODE solver for few-step chains (Lu et al. 2022, DPM-Solver++), orthogonal to the
+ *                          sampler: the sampler keeps deciding which evaluations run (conditional, guided, unconditional,
+ *                          inpainting mask, zero-spectrogram branch).  0 = the sampler's own update, bit-identical to an
+ *                          engine that never set the option.  1 = the first-order exponential integrator in
+ *                          lambda_t = log(A_t / Sm_t), A = sqrt_acp, Sm = sqrt_1m_acp; 2 = DPM-Solver++ (2M).  For a
+ *                          visited step t > 0 with successor t' and predecessor t'' in the chain (the full chain, or the
+ *                          visited steps of "sampling_steps" - the intended use), h = lambda_t' - lambda_t, h_prev =
+ *                          lambda_t - lambda_t'', the row is [Smp / Sm, -Ap expm1(-h), A, c, 0] with c = h / (2 h_prev)
+ *                          when the order is 2, t is not the chain's first step and t' != 0, else c = 0 (the step into 0
+ *                          is always first order); the row of step 0 is [0, 0, A_0, 0, 0].  Rows are derived in double
+ *                          from the committed fp32 A and Sm (columns 2 and 3 of DR_COEF_DDPM_X0), rounded to fp32 once, and
+ *                          kept in a table of their own: dr_set_tables' shape is unchanged.  With y the step's (guided)
+ *                          prediction and p that of the previous step: d = c != 0 ? y + c (y - p) : y, x' = c0 x + c1 d,
+ *                          one fp32 rounding per operation; at t == 0 x' = y / c2, the x0 samplers' own last step.  The
+ *                          chain is DETERMINISTIC: no noise is drawn, d_noise is ignored, and "draws" differ through x_T
+ *                          only.  An epsilon sampler (DR_SAMPLER_* 6-8) with a non-zero order -> DR_EINVAL at dr_step /
+ *                          dr_sample / dr_sample_checked, naming both; any other value -> DR_EINVAL at the set.  Order 2
+ *                          keeps p in two engine-owned (B, T, 88) buffers (allocated on first use).  dr_step: at the
+ *                          chain's first visited step it starts a new history; at any other visited step the previous
+ *                          dr_step must have been the preceding visited step of the same (sampler, B, T), else
+ *                          DR_ESTATE naming the step expected; order 1 needs no history and runs any visited step.
+ *                          dr_sample, a healed time-out, and a change of "sampling_steps", "window_overlap" or "draws" end
+ *                          a dr_step history; dr_sample_checked's re-run starts its own.  Combines with
+ *                          "sampling_steps"; with "window_overlap" / "window_break" (y and p are the shared-frame means,
+ *                          so shared frames stay bit-identical in both windows); with "draws" / "draw_stride"; with
+ *                          "guidance_t_min" / "guidance_t_max" (p is whichever prediction the previous step used); with
+ *                          both precisions and with sharding (every rank sets the same order).  dr_forward,
+ *                          dr_forward_steps, dr_q_sample, dr_extract_x0 are unaffected.  The value is part of a captured
+ *                          chain's key, like "draws": setting it drops nothing, and a chain captured under another value
+ *                          is never replayed.  Nothing is known about the quality of either order with this model
+ *                          (INTEGRATION.md 3c).
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
