@@ -5,6 +5,7 @@ gfx950 kernel behind libdiffroll_amd.so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -36,6 +37,17 @@ def _clamp_range(r: Optional[Sequence[int]], n: int) -> Tuple[int, int]:
     if hi < lo:
         hi = lo
     return lo, hi
+
+
+# Options whose last value set is readable as the attribute of the same name, with the library's defaults
+_MIRRORED = {
+    "window_overlap": 0,         # frames two neighbouring windows share (0 = off)
+    "sampling_steps": 0,         # steps of the respaced chain (0 = every step)
+    "draws": 1,                  # rolls per clip of one chain, draw-major
+    "draw_stride": 0,            # Philox key distance of two draws (0 = the clips of the batch)
+    "solver_order": 0,           # 0 = the sampler's own update
+    "blocked_accumulation": 2,   # 2 = every fp32 flavour that has a blocked form, 1 = single chain on 128-frame blocks
+}
 
 
 class Engine:
@@ -97,6 +109,9 @@ class Engine:
             C.cast(self._fe_tables[2].data_ptr(), C.POINTER(C.c_float))))
         self.committed = False
         self.precision = "f32"
+        vars(self).update(_MIRRORED)
+        self.window_breaks = ()             # the marks set with option 'window_break' (windows that start a new recording), ascending
+        self.guidance_interval = (0, -1)    # the values set for options 'guidance_t_min' / 'guidance_t_max' ((0, -1) = the whole chain)
         self._keep = []   # tensors referenced by a captured graph must stay alive
 
     # ------------------------------------------------------------------
@@ -335,22 +350,35 @@ class Engine:
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
         self._check(fn(self.h, name.encode(), int(value)))
-        if name == "window_overlap":
-            self.window_overlap = int(value)
-        if name == "window_break":        # b >= 1 adds a mark, 0 clears them all
+        if name in _MIRRORED:
+            setattr(self, name, int(value))
+        elif name == "window_break":      # b >= 1 adds a mark, 0 clears them all
             self.window_breaks = tuple(sorted(set(self.window_breaks) | {int(value)})) if int(value) else ()
-        if name == "sampling_steps":
-            self.sampling_steps = int(value)
-        if name == "draws":
-            self.draws = int(value)
-        if name == "draw_stride":
-            self.draw_stride = int(value)
-        if name == "solver_order":
-            self.solver_order = int(value)
-        if name == "guidance_t_min":
-            self.guidance_interval = (int(value), self.guidance_interval[1])
-        if name == "guidance_t_max":
-            self.guidance_interval = (self.guidance_interval[0], int(value))
+        elif name in ("guidance_t_min", "guidance_t_max"):
+            lo, hi = self.guidance_interval
+            self.guidance_interval = (int(value), hi) if name == "guidance_t_min" else (lo, int(value))
+
+    @contextlib.contextmanager
+    def holding(self, **options):
+        """Options held for one call and put back afterwards, also when the call raises: mirrored option names, and
+        window_breaks = the marks.  An option that already has the value is not set at all - 'sampling_steps' would drop the
+        captured chain; 'draws', 'draw_stride' and the marks never do (they are part of its key or plain data), so a loop of
+        such calls replays one graph, and putting them back behind an asynchronous call touches nothing in flight."""
+        def put(name, value):
+            if name == "window_breaks":
+                self.set_window_breaks(value)
+            else:
+                self.set_option(name, value)
+
+        prev = {name: getattr(self, name) for name in options}
+        changed = [name for name, value in options.items() if prev[name] != (tuple(value) if name == "window_breaks" else value)]
+        try:
+            for name in changed:
+                put(name, options[name])
+            yield
+        finally:
+            for name in changed:
+                put(name, prev[name])
 
     def set_guidance_interval(self, lo: int = 0, hi: int = -1):
         """Options 'guidance_t_min' / 'guidance_t_max' together: a guiding sampler guides the steps lo <= t <= hi (hi = -1:
@@ -378,14 +406,6 @@ class Engine:
             if int(b) < 1:
                 raise ValueError(f"window_break mark {b}: marks are >= 1 (window 0 always starts a recording)")
             self.set_option("window_break", int(b))
-
-    window_overlap = 0      # the last value set for option 'window_overlap' (0 = off, the library's default)
-    window_breaks = ()      # the marks set with option 'window_break' (windows that start a new recording), ascending
-    sampling_steps = 0      # the last value set for option 'sampling_steps' (0 = every step, the library's default)
-    draws = 1               # the last value set for option 'draws' (rolls per clip of one chain, draw-major; 1 = the default)
-    guidance_interval = (0, -1)   # the last values set for options 'guidance_t_min' / 'guidance_t_max' ((0, -1) = the whole chain)
-    solver_order = 0        # the last value set for option 'solver_order' (0 = the sampler's own update, the library's default)
-    draw_stride = 0         # the last value set for option 'draw_stride' (Philox key distance of two draws; 0 = the clips of the batch)
 
     def visited_steps(self):
         """The diffusion steps sample() visits, in chain order (option 'sampling_steps'; all of them when it is off)."""

@@ -22,8 +22,6 @@ from typing import Any, Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-import contextlib
-
 from .engine import Engine
 from .ensemble import aggregate, check_draws
 from .schedule import check_guidance_interval, check_sampling_steps, check_solver_order, respaced_steps
@@ -33,21 +31,13 @@ _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x
 _GUIDED = ("cfdg_ddpm_x0", "inpainting_ddpm_x0", "cfdg_ddim_x0")
 
 
-@contextlib.contextmanager
-def _draws_set(eng, draws: int, stride: int):
-    """Options "draws" / "draw_stride" around one chain, restored afterwards.  Neither drops the engine's captured chain -
-    they are part of its key (engine_state.h: GraphKey) - so a loop of sample(draws=D) calls replays one graph, and
-    restoring them behind an asynchronous call (check=False) touches nothing that is in flight."""
-    prev = (eng.draws, eng.draw_stride)
-    if prev != (draws, stride):
-        eng.set_option("draws", draws)
-        eng.set_option("draw_stride", stride)
-    try:
-        yield
-    finally:
-        if prev != (draws, stride):
-            eng.set_option("draws", prev[0])
-            eng.set_option("draw_stride", prev[1])
+def _trimmed_frames(sampler: str, condition: str, T: int, spec_frames: Optional[int]) -> int:
+    """Frames left of a T-frame roll by trim_spec_roll (model/diffwave.py:30-39, :662): the spectrogram's length when that is
+    shorter - the clip's spec_frames = L // hop + 1 (None: no waveform), or the 641 frames of the learned unconditional
+    spectrogram that generation runs on under condition='trainable_spec' (model/diffwave.py:656-660)."""
+    if sampler == "generation_ddpm_x0" and condition == "trainable_spec":
+        return min(T, 641)
+    return T if spec_frames is None else min(T, spec_frames)
 
 
 class AttrDict(dict):
@@ -262,9 +252,8 @@ class ClassifierFreeDiffRoll(nn.Module):
         if self._engine.precision != self.precision:
             self._engine.set_precision(self.precision)
         want = 1 if self.accumulation == "single_chain" else 2
-        if getattr(self._engine, "_blocked", None) != want:
+        if self._engine.blocked_accumulation != want:
             self._engine.set_option("blocked_accumulation", want)
-            self._engine._blocked = want
         steps = self.sampling_steps()
         if self._engine.sampling_steps != steps:          # (a change drops the engine's captured chain)
             self._engine.set_option("sampling_steps", steps)
@@ -385,15 +374,8 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise ValueError(f"diffusion_step has {len(steps)} entries for a batch of {B}")
         t = steps[0]
         uniform = all(v == t for v in steps)      # the samplers' case (task/diffusion.py:947)
-        if sampling is True and self.hparams.condition == "trainable_spec":
-            # the learned unconditional spectrogram replaces the clip's (model/diffwave.py:656-658); it is 2-D and
-            # 641 frames long, and trim_spec_roll (:662) trims the roll to it
-            Tm = min(T, 641)
-            spec = self.trainable_parameters.detach()[:, :Tm].to(eng.device, torch.float32)
-        elif sampling is True:
-            TF = waveform.shape[-1] // eng.hop_length + 1
-            Tm = min(T, TF)
-            spec = torch.full((B, eng.n_mels, Tm), -1.0, device=eng.device)
+        if sampling is True:                       # the unconditional evaluation: what generation_ddpm_x0 runs on
+            spec, Tm = self._conditioning("generation_ddpm_x0", T, waveform, B)
         else:
             spec = self._frontend(waveform, T, inpainting_t, inpainting_f)
             Tm = spec.shape[-1]
@@ -424,49 +406,52 @@ class ClassifierFreeDiffRoll(nn.Module):
             return out
 
     # ------------------------------------------------------------------ samplers (one step)
-    def _one_step(self, sampler: str, x, waveform, t_index: int, noise=None, respaced=False):
+    def _conditioning(self, sampler: str, T: int, waveform, n: int):
+        """(spec, Tm): the spectrogram a call on n clips is conditioned on, and the frames its T-frame rolls are trimmed to.
+        The conditional samplers run the front-end (cached per waveform; the inpainting masks for inpainting_ddpm_x0 only);
+        generation_ddpm_x0 runs on the spectrogram of its sampling=True forward (task/diffusion.py:979-997): -1 everywhere,
+        or the learned one - 2-D, 641 frames - under condition='trainable_spec' (model/diffwave.py:656-660)."""
+        if sampler != "generation_ddpm_x0":
+            masked = sampler == "inpainting_ddpm_x0"
+            spec = self._frontend(waveform, T, self.hparams.inpainting_t if masked else None,
+                                  self.hparams.inpainting_f if masked else None)
+            return spec, spec.shape[-1]
+        eng = self.engine
+        Tm = _trimmed_frames(sampler, self.hparams.condition, T,
+                             None if waveform is None else waveform.shape[-1] // eng.hop_length + 1)
+        if self.hparams.condition == "trainable_spec":
+            return self.trainable_parameters.detach()[:, :Tm].to(eng.device, torch.float32), Tm
+        return torch.full((n, eng.n_mels, Tm), -1.0, device=eng.device), Tm
+
+    def _guidance_weight(self, sampler: str) -> float:
+        """hparams.sampling.w for the samplers that guide, 0 for the others."""
+        return float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
+
+    def _one_step(self, sampler: str, x, waveform, t_index: int, noise=None, respaced=False, philox=None):
         """One dr_step.  The reference's single-step methods keep their stride-1 meaning (t -> t - 1) whatever
         hparams.sampling.steps says (the option is off while they run: under a respaced config that costs the engine its
-        captured chain); respaced=True (sample_trajectory) takes the respaced chain's step."""
+        captured chain); respaced=True (sample_trajectory) takes the respaced chain's step.
+        The step's z is `noise` where that is a tensor; else the engine's Philox draws for philox = (seed, first_sample), keyed
+        as sample() keys them; else drawn here from torch's global generator when t > 0, as the reference's randn_like."""
         prev = self.__dict__.get("_stride1", False)
         self.__dict__["_stride1"] = not respaced
         try:
-            return self._one_step_as_set(sampler, x, waveform, t_index, noise)
+            eng = self.engine
+            B, _, T, _ = x.shape
+            spec, Tm = self._conditioning(sampler, T, waveform, B)
+            x_in = x.to(eng.device, torch.float32).squeeze(1)[:, :Tm, :].contiguous()
+            z, key = None, (0, 0)
+            if noise is not None:
+                z = noise.to(eng.device, torch.float32).reshape(B, Tm, 88).contiguous()
+            elif philox is not None:
+                key = philox
+            elif t_index > 0:
+                z = torch.randn(B, Tm, 88, device=eng.device)
+            w = self._guidance_weight(sampler)
+            xx = self._verified(lambda: eng.step(sampler, x_in.clone(), z, t_index, w, *key))
+            return xx.unsqueeze(1), spec
         finally:
             self.__dict__["_stride1"] = prev
-
-    def _one_step_as_set(self, sampler: str, x, waveform, t_index: int, noise=None):
-        eng = self.engine
-        B, _, T, _ = x.shape
-        spec = None
-        if sampler != "generation_ddpm_x0":
-            it = self.hparams.inpainting_t if sampler == "inpainting_ddpm_x0" else None
-            i_f = self.hparams.inpainting_f if sampler == "inpainting_ddpm_x0" else None
-            spec = self._frontend(waveform, T, it, i_f)
-            Tm = spec.shape[-1]
-        else:
-            Tm = min(T, waveform.shape[-1] // eng.hop_length + 1) if waveform is not None else T
-            if self.hparams.condition == "trainable_spec":
-                Tm = min(T, 641)
-        x_in = x.to(eng.device, torch.float32).squeeze(1)[:, :Tm, :].contiguous()
-        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
-        z = None
-        if noise is not None:
-            z = noise.to(eng.device, torch.float32).reshape(B, Tm, 88).contiguous()
-        elif t_index > 0:
-            z = torch.randn(B, Tm, 88, device=eng.device)   # reference: torch.randn_like(x), global generator
-        xx = self._verified(lambda: eng.step(sampler, x_in.clone(), z, t_index, w))
-        if spec is None:
-            spec = self._uncond_spec(B, Tm)
-        return xx.unsqueeze(1), spec
-
-    def _uncond_spec(self, B, Tm):
-        """The spectrogram generation_ddpm_x0 returns (task/diffusion.py:979-997: that of its sampling=True forward):
-        -1 everywhere, or the learned one under condition='trainable_spec' (model/diffwave.py:656-660)."""
-        eng = self.engine
-        if self.hparams.condition == "trainable_spec":
-            return self.trainable_parameters.detach()[:, :Tm].to(eng.device, torch.float32)
-        return torch.full((B, eng.n_mels, Tm), -1.0, device=eng.device)
 
     def ddpm_x0(self, x, waveform, t_index, noise=None):
         """task/diffusion.py:831-853."""
@@ -510,14 +495,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         """Frames of the roll sample() returns for a T-frame x_T (trim_spec_roll, model/diffwave.py:30-39, :662): the
         spectrogram's length when that is shorter - the clip's L // hop + 1, or the 641 frames of the learned
         unconditional spectrogram under condition='trainable_spec' for generation."""
-        sampler = self.hparams.sampling.type
         hop = self._engine_kwargs["hop_length"]
-        if sampler != "generation_ddpm_x0":
-            return min(T, waveform_samples // hop + 1)
-        Tm = T if waveform_samples is None else min(T, waveform_samples // hop + 1)
-        if self.hparams.condition == "trainable_spec":
-            Tm = min(T, 641)
-        return Tm
+        return _trimmed_frames(self.hparams.sampling.type, self.hparams.condition, T,
+                               None if waveform_samples is None else waveform_samples // hop + 1)
 
     @torch.no_grad()
     def sample(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0,
@@ -543,18 +523,9 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise ValueError(f"x_T holds {B} rolls: not a whole number of draws = {draws}")
         if draws > 1 and waveform is not None and waveform.shape[0] != B // draws:
             raise ValueError(f"{draws} draws of {B} rolls take the waveform of {B // draws} clips, got {waveform.shape[0]}")
-        if sampler != "generation_ddpm_x0":
-            if waveform is None:
-                raise ValueError("waveform is required for conditional samplers")
-            it = self.hparams.inpainting_t if sampler == "inpainting_ddpm_x0" else None
-            i_f = self.hparams.inpainting_f if sampler == "inpainting_ddpm_x0" else None
-            spec = self._frontend(waveform, T, it, i_f)
-            Tm = spec.shape[-1]
-        else:
-            Tm = T if waveform is None else min(T, waveform.shape[-1] // eng.hop_length + 1)
-            if self.hparams.condition == "trainable_spec":
-                Tm = min(T, 641)
-            spec = self._uncond_spec(B // draws, Tm)
+        if sampler != "generation_ddpm_x0" and waveform is None:
+            raise ValueError("waveform is required for conditional samplers")
+        spec, Tm = self._conditioning(sampler, T, waveform, B // draws)
         # a fresh roll buffer per call: the engine's captured chain runs on its own work buffer, so caller
         # addresses never force a re-capture
         xb = x_T.to(eng.device, torch.float32).squeeze(1)[:, :Tm, :].clone(memory_format=torch.contiguous_format)
@@ -564,9 +535,8 @@ class ClassifierFreeDiffRoll(nn.Module):
             z = noise.to(eng.device, torch.float32).reshape(S, B, T, 88)
             if Tm != T or not z.is_contiguous():
                 z = z[:, :, :Tm, :].contiguous()
-        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
-        with _draws_set(eng, draws, draw_stride):
-            eng.sample(sampler, xb, z, w, seed, first_sample, use_graph, check)
+        with eng.holding(draws=draws, draw_stride=draw_stride):
+            eng.sample(sampler, xb, z, self._guidance_weight(sampler), seed, first_sample, use_graph, check)
         return xb.unsqueeze(1), spec
 
     @torch.no_grad()
@@ -594,14 +564,15 @@ class ClassifierFreeDiffRoll(nn.Module):
         if sampler == "generation_ddpm_x0":
             if frames is None or waveform is not None:
                 raise ValueError("generation_ddpm_x0: pass frames= (the roll length), not a waveform")
-            plan = longform.plan_windows(int(frames), None, longform.WINDOW_FRAMES, overlap)
+            batch = longform.plan_batch([int(frames)], None, longform.WINDOW_FRAMES, overlap)
         else:
             if waveform is None or frames is not None:
                 raise ValueError(f"{sampler}: pass waveform= (L,), not frames")
             waveform = torch.as_tensor(waveform).to("cpu", torch.float32)
             if waveform.dim() != 1:
                 raise ValueError(f"waveform must be one recording (L,), got {tuple(waveform.shape)}")
-            plan = longform.plan_windows(waveform.shape[0], eng.hop_length, longform.WINDOW_FRAMES, overlap)
+            batch = longform.plan_batch([waveform.shape[0]], eng.hop_length, longform.WINDOW_FRAMES, overlap)
+        plan = batch.plans[0]
         if plan.n > longform.MAX_WINDOWS:
             raise ValueError(f"{plan.n} windows of {plan.T} frames: one chain holds at most {longform.MAX_WINDOWS} "
                              f"(longform.MAX_WINDOWS); split the recording")
@@ -610,23 +581,36 @@ class ClassifierFreeDiffRoll(nn.Module):
             x_T = torch.randn(1, 1, plan.T_c, 88, generator=torch.Generator().manual_seed(int(seed)))
         if tuple(x_T.shape) != (1, 1, plan.T_c, 88):
             raise ValueError(f"x_T must be the canvas (1, 1, {plan.T_c}, 88), got {tuple(x_T.shape)}")
-        xb = longform.gather_windows(x_T.reshape(plan.T_c, 88).to(eng.device, torch.float32), plan)
+        if noise is not None and noise.numel() != S * plan.T_c * 88:
+            raise ValueError(f"noise must be the canvas ({S}, 1, 1, {plan.T_c}, 88), got {tuple(noise.shape)}")
+        xb = self._sample_windows(batch, None if waveform is None else [waveform], [x_T], None if noise is None else [noise],
+                                  1, seed, recording, use_graph, check)
+        return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
+
+    def _sample_windows(self, batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check, marks=None):
+        """The one long-form chain: the recordings of `batch` (longform.plan_batch) as D draws of its windows.  waveforms: one
+        (L,) host tensor per recording, or None (generation); x_T / noise: one canvas per recording, (D, 1, T_c, 88) /
+        (timesteps, D, 1, T_c, 88), or noise None (Philox); marks: the window_break marks, the plan's unless given.  Options
+        "window_overlap", "window_break", "draws" hold for the chain only.  Returns the window batch (D * n, T, 88) after the
+        chain: that of draw 0, then that of draw 1, ... (draw-major)."""
+        from . import longform
+        eng = self.engine
+        sampler = self.hparams.sampling.type
+        S = int(self.hparams.timesteps)
+        xb = torch.cat([longform.gather_batch([x[d].reshape(p.T_c, 88).to(eng.device, torch.float32)
+                                               for x, p in zip(x_T, batch.plans)], batch) for d in range(D)], 0)
         z = None
         if noise is not None:
-            if noise.numel() != S * plan.T_c * 88:
-                raise ValueError(f"noise must be the canvas ({S}, 1, 1, {plan.T_c}, 88), got {tuple(noise.shape)}")
-            z = longform.gather_windows(noise.reshape(S, plan.T_c, 88).to(eng.device, torch.float32), plan)
-        if sampler != "generation_ddpm_x0":
-            eng.frontend(longform.window_audio(waveform, plan, eng.hop_length), plan.T)
+            z = torch.cat([longform.gather_batch([zr.reshape(S, D, p.T_c, 88)[:, d].to(eng.device, torch.float32)
+                                                  for zr, p in zip(noise, batch.plans)], batch) for d in range(D)], 1).contiguous()
+        if waveforms is not None:
+            eng.frontend(torch.cat([longform.window_audio(wv, p, eng.hop_length) for wv, p in zip(waveforms, batch.plans)]),
+                         batch.plans[0].T)
             self._fe_key = None          # the engine's conditioner is the windows' now: sample() recomputes its own
-        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
-        prev = eng.window_overlap
-        eng.set_option("window_overlap", plan.overlap)
-        try:
-            eng.sample(sampler, xb, z, w, seed, recording, use_graph, check)
-        finally:
-            eng.set_option("window_overlap", prev)
-        return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
+        with eng.holding(window_overlap=batch.plans[0].overlap, window_breaks=batch.marks if marks is None else marks,
+                         draws=D, draw_stride=0):
+            eng.sample(sampler, xb, z, self._guidance_weight(sampler), seed, first_recording, use_graph, check)
+        return xb
 
     @torch.no_grad()
     def sample_long_batch(self, waveforms=None, frames=None, overlap: int = 160, seed: int = 0, first_recording: int = 0,
@@ -671,29 +655,9 @@ class ClassifierFreeDiffRoll(nn.Module):
             x_T = [torch.randn(D, 1, p.T_c, 88, generator=torch.Generator().manual_seed(int(seed))) for p in batch.plans]
         if len(x_T) != R or any(tuple(x.shape) != (D, 1, p.T_c, 88) for x, p in zip(x_T, batch.plans)):
             raise ValueError(f"x_T must be one canvas ({D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
-        # the window batch of draw 0, then that of draw 1, ... (draw-major)
-        xb = torch.cat([longform.gather_batch([x[d].reshape(p.T_c, 88).to(eng.device, torch.float32)
-                                               for x, p in zip(x_T, batch.plans)], batch) for d in range(D)], 0)
-        z = None
-        if noise is not None:
-            if len(noise) != R or any(zr.numel() != S * D * p.T_c * 88 for zr, p in zip(noise, batch.plans)):
-                raise ValueError(f"noise must be one canvas ({S}, {D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
-            z = torch.cat([longform.gather_batch([zr.reshape(S, D, p.T_c, 88)[:, d].to(eng.device, torch.float32)
-                                                  for zr, p in zip(noise, batch.plans)], batch) for d in range(D)], 1).contiguous()
-        if sampler != "generation_ddpm_x0":
-            eng.frontend(torch.cat([longform.window_audio(wv, p, eng.hop_length) for wv, p in zip(waveforms, batch.plans)]),
-                         longform.WINDOW_FRAMES)
-            self._fe_key = None          # the engine's conditioner is the windows' now: sample() recomputes its own
-        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
-        prev_overlap, prev_marks = eng.window_overlap, eng.window_breaks
-        eng.set_option("window_overlap", batch.plans[0].overlap)
-        try:
-            eng.set_window_breaks(batch.marks)
-            with _draws_set(eng, D, 0):
-                eng.sample(sampler, xb, z, w, seed, first_recording, use_graph, check)
-        finally:
-            eng.set_window_breaks(prev_marks)
-            eng.set_option("window_overlap", prev_overlap)
+        if noise is not None and (len(noise) != R or any(zr.numel() != S * D * p.T_c * 88 for zr, p in zip(noise, batch.plans))):
+            raise ValueError(f"noise must be one canvas ({S}, {D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
+        xb = self._sample_windows(batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check)
         rolls = longform.stitch_batch(xb.reshape(D, batch.n, longform.WINDOW_FRAMES, 88), batch)
         return [r.reshape(D, 1, p.T_out, 88) for r, p in zip(rolls, batch.plans)]
 
@@ -703,41 +667,14 @@ class ClassifierFreeDiffRoll(nn.Module):
         This is what the reference's sampling() collects as `noise_list` - on the host, with one D2H copy per step
         (task/diffusion.py:779-788) - for its animation; here it is an opt-in eager loop over dr_step (one launch sequence
         per step, no graph), and the last row equals sample()'s result bit for bit."""
-        eng = self.engine
         sampler = self.hparams.sampling.type
-        B = x_T.shape[0]
-        x = x_T
-        rows = []
-        spec = None
+        x, rows, spec = x_T, [], None
         for t in self.visited_steps():
-            z = None if noise is None else noise[t]
-            if z is None and t > 0:       # Philox keyed by (seed, global sample, step): same draws as sample()
-                xx, spec = self._step_philox(sampler, x, waveform, t, seed, first_sample)
-            else:
-                xx, spec = self._one_step(sampler, x, waveform, t, z if t > 0 else torch.zeros_like(x), respaced=True)
-            rows.append(xx)
-            x = xx
+            # no noise given: Philox keyed by (seed, global sample, step), the draws of sample(); step 0 takes none
+            z = torch.zeros_like(x) if t == 0 else None if noise is None else noise[t]
+            x, spec = self._one_step(sampler, x, waveform, t, z, respaced=True, philox=(seed, first_sample))
+            rows.append(x)
         return torch.stack(rows, 0), spec
-
-    def _step_philox(self, sampler, x, waveform, t_index, seed, first_sample):
-        eng = self.engine
-        B, _, T, _ = x.shape
-        spec = None
-        if sampler != "generation_ddpm_x0":
-            it = self.hparams.inpainting_t if sampler == "inpainting_ddpm_x0" else None
-            i_f = self.hparams.inpainting_f if sampler == "inpainting_ddpm_x0" else None
-            spec = self._frontend(waveform, T, it, i_f)
-            Tm = spec.shape[-1]
-        else:
-            Tm = min(T, waveform.shape[-1] // eng.hop_length + 1) if waveform is not None else T
-            if self.hparams.condition == "trainable_spec":
-                Tm = min(T, 641)
-        x_in = x.to(eng.device, torch.float32).squeeze(1)[:, :Tm, :].contiguous()
-        w = float(self.hparams.sampling.get("w", 0.0)) if sampler in _GUIDED else 0.0
-        xx = self._verified(lambda: eng.step(sampler, x_in.clone(), None, t_index, w, seed, first_sample))
-        if spec is None:
-            spec = self._uncond_spec(B, Tm)
-        return xx.unsqueeze(1), spec
 
     def predict_step(self, batch, batch_idx=0):
         """batch = (x_T, waveform[, ...]) as built by sampling.py:27-46.  Returns the final roll

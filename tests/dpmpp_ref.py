@@ -2,15 +2,13 @@
 
 The first-order exponential integrator in lambda = log(sqrt_acp / sqrt_1m_acp) and DPM-Solver++ (2M) (Lu et al. 2022) on
 the x0 prediction, over the visited steps of tests/respaced_ref.py: the rows in float64 from the committed fp32 scalars
-(one rounding to fp32), the fp32 expression order of solver_quad in diffroll_amd/csrc/update_quad.h, the network and the
-shared-frame mean of respaced_ref - and a float64 variant of the pure integrator that takes any denoiser.
+(one rounding to fp32) and the fp32 expression order of solver_quad in diffroll_amd/csrc/update_quad.h, which the chain loop of
+respaced_ref runs under order = 1 / 2 - and a float64 variant of the pure integrator that takes any denoiser.
 """
 from typing import Callable, List, Optional
 
 import numpy as np
 import torch
-
-from oracle import diffroll_ref as R
 
 import respaced_ref as RR
 
@@ -54,25 +52,8 @@ def update(t: int, row: np.ndarray, x: torch.Tensor, y: torch.Tensor, p: Optiona
 
 def sample_chain(params, hp, sampler: str, x_T: torch.Tensor, spec: Optional[torch.Tensor], n: int, order: int,
                  w: float = 0.0, plan=None, guidance=None, trajectory: bool = False):
-    """The chain of n visited steps (0: all) under solver order 1 / 2: x_T (B, 1, T, 88), spec (B, n_mels, T) for the
-    conditional samplers.  plan: long-form windows, the shared-frame mean before each update (and in the history);
-    guidance = (lo, hi): the weight is w at lo <= t <= hi and 0 elsewhere.  Returns the final roll, or every intermediate
-    roll with trajectory=True."""
-    S = int(hp["timesteps"])
-    steps = RR.visited(S, n)
-    rw = rows(hp, n, order)
-    table = R.build_embedding(S)
-    x, p, traj = x_T, None, []
-    with torch.no_grad():
-        for t in steps:
-            wt = w if guidance is None or guidance[0] <= t <= guidance[1] else 0.0
-            y = RR.prediction(params, hp, sampler, x, spec, t, wt, table)
-            if plan is not None:
-                y = RR.shared_mean(y, plan)
-            x = update(t, rw[t], x, y, p)
-            p = y
-            traj.append(x)
-    return torch.stack(traj, 0) if trajectory else x
+    """respaced_ref.sample_chain under solver order 1 / 2 (no noise); guidance = (lo, hi): its interval."""
+    return RR.sample_chain(params, hp, sampler, x_T, spec, None, n, w, plan, trajectory, interval=guidance, order=order)
 
 
 def integrate64(denoise: Callable, AS: np.ndarray, steps: List[int], order: int, x_T: np.ndarray, final: bool = True):

@@ -106,25 +106,38 @@ def shared_mean(y: torch.Tensor, plan) -> torch.Tensor:
     return ym
 
 
-def sample_chain(params, hp, sampler: str, x_T: torch.Tensor, spec_c: Optional[torch.Tensor], noise: torch.Tensor,
-                 n: int, w: float = 0.0, plan=None, trajectory: bool = False):
-    """The respaced chain: x_T (B, 1, T, 88), spec_c (B, n_mels, T) (conditional samplers), noise (S, B, 1, T, 88) -
-    row t is the z of visited step t.  plan: long-form windows (B = plan.n), the shared-frame mean before each update.
+def sample_chain(params, hp, sampler: str, x_T: torch.Tensor, spec_c: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                 n: int, w: float = 0.0, plan=None, trajectory: bool = False, interval=None, order: int = 0):
+    """THE chain loop of the tests' restatements: predict -> shared-frame mean -> update, over the n visited steps (0: all).
+    x_T (B, 1, T, 88), spec_c (B, n_mels, T) (conditional samplers), noise (S, B, 1, T, 88) - row t is the z of visited step
+    t.  plan: long-form windows (B = plan.n), the shared-frame mean before each update (and in the solver's history).
+    interval = (lo, hi): a guidance interval - the weight is w at lo <= t <= hi and 0 elsewhere, as the reference's sampler
+    with hparams.sampling.w set per step; BOTH network branches are evaluated at every step and combined as
+    (1 + w_t) c - w_t u, so this is the reference's arithmetic, not the engine's shortcut.
+    order = 1 / 2: option "solver_order" - the rows and the update of tests/dpmpp_ref.py on the x0 prediction, no noise, the
+    previous step's prediction carried along; 0: the sampler's own update.
     Returns the final roll, or every intermediate roll (n, B, 1, T, 88) with trajectory=True."""
     S = int(hp["timesteps"])
     steps = visited(S, n)
-    rows = rows_for(committed(hp), steps)
     family = SAMPLERS[sampler][0]
+    if order:
+        import dpmpp_ref                       # (builds on this module)
+        rows = dpmpp_ref.rows(hp, n, order)
+    else:
+        rows = {t: r[family] for t, r in rows_for(committed(hp), steps).items()}
+    lo, hi = (0, S - 1) if interval is None else interval
     table = R.build_embedding(S)
-    x = x_T
-    traj = []
+    x, prev, traj = x_T, None, []
     with torch.no_grad():
         for t in steps:
-            y = prediction(params, hp, sampler, x, spec_c, t, w, table)
+            y = prediction(params, hp, sampler, x, spec_c, t, w if lo <= t <= hi else 0.0, table)
             if plan is not None:
                 y = shared_mean(y, plan)
-            noisy = family in (0, 2, 4) and t > 0
-            x = update(family, t, rows[t][family], x, y, noise[t] if noisy else None)
+            if order:
+                x = dpmpp_ref.update(t, rows[t], x, y, prev)
+            else:
+                x = update(family, t, rows[t], x, y, noise[t] if family in (0, 2, 4) and t > 0 else None)
+            prev = y
             traj.append(x)
     return torch.stack(traj, 0) if trajectory else x
 

@@ -16,6 +16,7 @@ import torch
 
 from oracle import diffroll_ref as R
 from test_gpu_parity import make_model
+from tuning_pins import pinned
 
 from diffroll_amd import longform
 from diffroll_amd.engine import EngineError
@@ -38,22 +39,6 @@ def clips(n, T, seed):
     wav = torch.stack([(0.05 + 0.1 * i) * torch.randn(T * HOP, generator=g) for i in range(n)])
     assert not torch.equal(wav[0], wav[-1]) or n == 1
     return wav, g
-
-
-class pins:
-    """Process-wide tuning knobs set for a block and restored (name -> (value, default))."""
-
-    def __init__(self, eng, knobs):
-        self.eng, self.knobs = eng, knobs
-
-    def __enter__(self):
-        for k, (v, _) in self.knobs.items():
-            self.eng.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, (_, v) in self.knobs.items():
-            self.eng.set_option(k, v)
-        self.eng.set_option("fused_stack", 1)
 
 
 # ---------------------------------------------------------------------------------------------- 1. the defining equivalence
@@ -109,7 +94,7 @@ def test_a_fused_chunk_that_starts_inside_a_draw_wraps_round_the_clips():
     eng = m.engine
     wav, g = clips(n, T, 23)
     x = torch.randn(D * n, 1, T, 88, generator=g)
-    with pins(eng, {"tune.stack_fl": (1, 0)}):
+    with pinned(eng, {"tune.stack_fl": (1, 0)}):
         eng.set_option("fused_stack", 2)
         eng.stack_status()
         n0 = eng.stack_launches
@@ -135,7 +120,7 @@ def test_640_frames_on_the_160_frame_stack():
     wav, g = clips(1, 640, 641)
     x = torch.randn(2, 1, 640, 88, generator=g)
     nz = torch.randn(4, 2, 1, 640, 88, generator=g)
-    with pins(eng, {"tune.stack_fl": (5, 0)}):
+    with pinned(eng, {"tune.stack_fl": (5, 0)}):
         eng.set_option("fused_stack", 2)
         eng.profile_enable(True)                    # (a profiled chain runs eager)
         got_e, _ = m.sample(x, wav, noise=nz, draws=2)
@@ -164,7 +149,7 @@ def test_two_clips_of_640_frames_wrap_on_the_160_frame_stack_and_the_tail():
     wav, g = clips(n, T, 643)
     x = torch.randn(D * n, 1, T, 88, generator=g)
     nz = torch.randn(4, D * n, 1, T, 88, generator=g)
-    with pins(eng, {"tune.stack_fl": (5, 0)}):
+    with pinned(eng, {"tune.stack_fl": (5, 0)}):
         eng.set_option("fused_stack", 2)
         eng.profile_enable(True)
         got_e, _ = m.sample(x, wav, noise=nz, draws=D)
@@ -199,7 +184,7 @@ def test_draw_stride_keys_draw_d_like_a_chain_of_first_sample_plus_d_G():
     eng = m.engine
     wav, g = clips(n, T, 31)
     x = torch.randn(D * n, 1, T, 88, generator=g)
-    with pins(eng, SAME_KERNELS):
+    with pinned(eng, SAME_KERNELS):
         eng.set_option("fused_stack", 0)
         for use_graph in (False, True):
             got, _ = m.sample(x, wav, seed=4, first_sample=first, use_graph=use_graph, draws=D, draw_stride=G)
@@ -216,22 +201,8 @@ LONG_PINS = {"tune.ksplit_max": (1, 16), "tune.tile": (3205, 0), "tune.pw_nw": (
 
 
 def windows_of_draws(m, batch, wavs, x_T, D, seed, first, use_graph):
-    """What sample_long_batch(draws=D) does, keeping the windows: (D, n, T, 88)."""
-    eng = m.engine
-    xb = torch.cat([longform.gather_batch([x[d].reshape(p.T_c, 88).to(eng.device) for x, p in zip(x_T, batch.plans)], batch)
-                    for d in range(D)], 0)
-    eng.frontend(torch.cat([longform.window_audio(wv, p, HOP) for wv, p in zip(wavs, batch.plans)]), 640)
-    m._fe_key = None
-    eng.set_option("window_overlap", batch.plans[0].overlap)
-    eng.set_option("draws", D)
-    try:
-        eng.set_window_breaks(batch.marks)
-        eng.sample("cfdg_ddpm_x0", xb, None, 0.5, seed, first, use_graph, True)
-    finally:
-        eng.set_window_breaks(())
-        eng.set_option("draws", 1)
-        eng.set_option("window_overlap", 0)
-    return xb.reshape(D, batch.n, 640, 88)
+    """sample_long_batch(draws=D)'s chain, keeping the windows: (D, n, T, 88)."""
+    return m._sample_windows(batch, wavs, x_T, None, D, seed, first, use_graph, True).reshape(D, batch.n, 640, 88)
 
 
 @pytest.mark.parametrize("fused", [False, True], ids=["per_phase", "fused"])
@@ -248,7 +219,7 @@ def test_long_form_draw_d_is_the_chain_of_first_recording_plus_d_R(fused):
     assert [q.n for q in batch.plans] == [2, 1] and batch.marks == [2]
     wavs = [0.1 * torch.randn(L, generator=g) for L in lengths]
     x_T = [torch.randn(D, 1, q.T_c, 88, generator=g) for q in batch.plans]
-    with pins(eng, LONG_PINS):
+    with pinned(eng, LONG_PINS):
         eng.set_option("fused_stack", 2 if fused else 0)
         rolls = m.sample_long_batch(wavs, overlap=160, seed=seed, first_recording=first, x_T=x_T, draws=D)
         assert eng.launch_state()["mode"] == ("fused_stack+tail" if fused else "per_phase"), eng.launch_state()

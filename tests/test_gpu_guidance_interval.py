@@ -17,6 +17,7 @@ import torch
 
 from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
+from tuning_pins import pinned
 
 import guidance_ref as GR
 import respaced_ref as RR
@@ -61,23 +62,6 @@ def model_of(sampler, hp=None, seed=70, **kw):
     p = R.synthetic_params(hp, seed=seed)
     it = MASK if sampler == "inpainting_ddpm_x0" else None
     return hp, p, make_model(hp, p, sampler=sampler, w=W, inpainting_t=it, **kw), it
-
-
-class pinned:
-    """Process-wide tuning knobs set for a block and restored; fused_stack back to its default."""
-
-    def __init__(self, eng):
-        self.eng = eng
-
-    def __enter__(self):
-        for k, (v, _) in PINS.items():
-            self.eng.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, (_, v) in PINS.items():
-            self.eng.set_option(k, v)
-        self.eng.set_option("fused_stack", 1)
-        self.eng.set_option("fused_tail", 1)
 
 
 def skip_if_forced():
@@ -181,7 +165,7 @@ def test_bit_identities_on_the_fused_path(sampler):
     eng = m.engine
     wav, x, noise = inputs(B, T, 73)
     xb, z = engine_inputs(eng, wav, x, noise)
-    with pinned(eng):
+    with pinned(eng, PINS, restore=("fused_stack", "fused_tail")):
         eng.set_option("fused_stack", 2)
         never_e, never_g = chain(eng, sampler, xb, z, False), chain(eng, sampler, xb, z, True)       # (a) options never set
         assert torch.equal(never_e, never_g)
@@ -220,7 +204,7 @@ def test_first_step_guided_primes_the_unguided_successor():
     eng = m.engine
     wav, x, noise = inputs(B, T, 74)
     xb, z = engine_inputs(eng, wav, x, noise)
-    with pinned(eng):
+    with pinned(eng, PINS, restore=("fused_stack", "fused_tail")):
         for (lo, hi), convs in (((6, 11), 1), ((0, 5), 0)):
             eng.set_guidance_interval(lo, hi)
             eng.set_option("fused_stack", 2)

@@ -12,6 +12,8 @@ from oracle import diffroll_ref as R
 from oracle import philox
 from test_gpu_parity import make_model, maxdiff
 
+import respaced_ref as RR
+
 from diffroll_amd import longform
 
 pytestmark = pytest.mark.gpu
@@ -29,52 +31,23 @@ def hp_of(layers=15, k=9, steps=4, channels=None):
 
 
 def oracle_long(p, hp, sampler, plan, wav, x_T, noise, w):
-    """The joint chain on the CPU: windows of the canvas x_T / noise, one front-end per window crop, at every step the
-    guided prediction of each window, the mean on shared frames, the posterior update.  Returns windows (n, 1, T, 88)."""
+    """The joint chain on the CPU: windows of the canvas x_T / noise, one front-end per window crop, and the chain loop of
+    tests/respaced_ref.py over every step - the guided prediction of each window, the mean on shared frames, the posterior
+    update.  Returns windows (n, 1, T, 88)."""
     S = int(hp["timesteps"])
-    sch = R.schedule(float(hp["beta_start"]), float(hp["beta_end"]), S)
-    table = R.build_embedding(S)
-    T, H, O, n = plan.T, plan.stride, plan.overlap, plan.n
     x = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     zs = longform.gather_windows(noise.reshape(S, plan.T_c, 88), plan).unsqueeze(2)
     spec = None
     if sampler != "generation_ddpm_x0":
-        spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, T)
-    with torch.no_grad():
-        for t in reversed(range(S)):
-            tt = torch.tensor(t).repeat(n)
-            if sampler == "generation_ddpm_x0":
-                y = R.denoise(p, hp, x, R.uncond_spec(p, hp, torch.empty(n, int(hp["n_mels"]), T)), tt, table)
-            else:
-                y_c = R.denoise(p, hp, x, spec, tt, table)
-                y_u = R.denoise(p, hp, x, R.uncond_spec(p, hp, spec), tt, table)
-                y = (1 + w) * y_c - w * y_u
-            ym = y.clone()
-            for b in range(n - 1):
-                m = 0.5 * (y[b, :, H:T] + y[b + 1, :, 0:O])
-                ym[b, :, H:T] = m
-                ym[b + 1, :, 0:O] = m
-            x = R.posterior_update(sch, x, ym, t, zs[t] if t > 0 else None)
-    return x
+        spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
+    return RR.sample_chain(p, hp, sampler, x, spec, zs, 0, w, plan=plan)
 
 
 def run_windows(m, plan, wav, x_T, noise, seed=0, recording=0, use_graph=True):
-    """What sample_long does, keeping the windows: (n, T, 88) on the host."""
-    eng = m.engine
-    sampler = m.hparams.sampling.type
-    S = int(m.hparams.timesteps)
-    xb = longform.gather_windows(x_T.reshape(plan.T_c, 88).to(eng.device), plan)
-    z = None if noise is None else longform.gather_windows(noise.reshape(S, plan.T_c, 88).to(eng.device), plan)
-    if sampler != "generation_ddpm_x0":
-        eng.frontend(longform.window_audio(wav, plan, HOP), plan.T)
-        m._fe_key = None
-    w = float(m.hparams.sampling.get("w", 0.0)) if sampler != "generation_ddpm_x0" else 0.0
-    eng.set_option("window_overlap", plan.overlap)
-    try:
-        eng.sample(sampler, xb, z, w, seed, recording, use_graph, True)
-    finally:
-        eng.set_option("window_overlap", 0)
-    return xb.cpu()
+    """sample_long's chain, keeping the windows: (n, T, 88) on the host."""
+    batch = longform.BatchPlan(plans=[plan], first=[0], marks=[], n=plan.n)
+    return m._sample_windows(batch, None if wav is None else [wav], [x_T], None if noise is None else [noise], 1, seed,
+                             recording, use_graph, True).cpu()
 
 
 def assert_shared_frames_agree(win, plan):

@@ -10,6 +10,7 @@ import torch
 from oracle import diffroll_ref as R
 from test_gpu_longform import assert_shared_frames_agree, hp_of, oracle_long
 from test_gpu_parity import make_model, maxdiff
+from tuning_pins import pinned
 
 from diffroll_amd import longform
 
@@ -23,48 +24,13 @@ W = 640 * HOP
 PINS = {"tune.ksplit_max": (1, 16), "tune.tile": (3205, 0), "tune.pw_nw": (5, 0), "tune.stack_fl": (5, 0)}
 
 
-class pinned:
-    def __init__(self, eng):
-        self.eng = eng
-
-    def __enter__(self):
-        for k, (v, _) in PINS.items():
-            self.eng.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, (_, v) in PINS.items():
-            self.eng.set_option(k, v)
-        self.eng.set_option("fused_stack", 1)
-
-
-def run_batch(m, batch, wavs, x_T, noise, marks="plan", seed=0, first=0, use_graph=True, overlap=True):
-    """What sample_long_batch does, keeping the windows: (n, T, 88) on the host.  marks: "plan" = the batch plan's, or a list
-    (an empty one = set and then cleared with "window_break" = 0)."""
-    eng = m.engine
-    sampler = m.hparams.sampling.type
-    S = int(m.hparams.timesteps)
-    xb = longform.gather_batch([x.reshape(p.T_c, 88).to(eng.device) for x, p in zip(x_T, batch.plans)], batch)
-    z = None
-    if noise is not None:
-        z = longform.gather_batch([zr.reshape(S, p.T_c, 88).to(eng.device) for zr, p in zip(noise, batch.plans)], batch).contiguous()
-    if sampler != "generation_ddpm_x0":
-        eng.frontend(torch.cat([longform.window_audio(wv, p, HOP) for wv, p in zip(wavs, batch.plans)]), 640)
-        m._fe_key = None
-    w = float(m.hparams.sampling.get("w", 0.0)) if sampler != "generation_ddpm_x0" else 0.0
-    marks = batch.marks if marks == "plan" else marks
-    if overlap:
-        eng.set_option("window_overlap", batch.plans[0].overlap)
-    try:
-        for b in marks or [1]:
-            eng.set_option("window_break", b)
-        if not marks:
-            eng.set_option("window_break", 0)
-        eng.sample(sampler, xb, z, w, seed, first, use_graph, True)
-    finally:
-        eng.set_option("window_break", 0)
-        if overlap:
-            eng.set_option("window_overlap", 0)
-    return xb.cpu()
+def run_batch(m, batch, wavs, x_T, noise, marks=None, seed=0, first=0, use_graph=True):
+    """sample_long_batch's chain, keeping the windows: (n, T, 88) on the host.  marks: None = the batch plan's, or a list (an
+    empty one = set and then cleared with "window_break" = 0).  An overlap the caller has set is the plan's: left alone."""
+    if marks is not None and not marks:
+        m.engine.set_option("window_break", 1)
+        m.engine.set_option("window_break", 0)
+    return m._sample_windows(batch, wavs, x_T, noise, 1, seed, first, use_graph, True, marks=marks).cpu()
 
 
 _FULL = {}
@@ -141,7 +107,7 @@ def test_three_recordings_against_the_oracle_per_phase_fused_graph():
         assert rolls[r].shape == (1, 1, q.T_out, 88) == (1, 1, math.ceil(c["lengths"][r] / HOP), 88)
         assert torch.equal(rolls[r].cpu()[0, 0], longform.stitch(dg[f:f + q.n], q))
     assert eng.window_overlap == 0 and eng.window_breaks == ()
-    with pinned(eng):
+    with pinned(eng, PINS):
         eng.set_option("fused_stack", 0)
         pp = run_batch(m, batch, wavs, x_T, noise)
         check_against_oracle(pp, c, "per-phase")
@@ -215,7 +181,7 @@ def test_batch_equals_solo_chains_with_philox_noise():
         solo = [m.sample_long(wv, seed=seed, recording=7 + i).cpu() for i, wv in enumerate(wavs)]
         return got, solo
 
-    with pinned(eng):
+    with pinned(eng, PINS):
         for mode in (0, 2):                                   # per-phase, forced fused
             eng.set_option("fused_stack", mode)
             got, solo = both()
@@ -253,8 +219,8 @@ def test_new_marks_replay_the_captured_chain():
     try:
         captures = []
         for marks in ([2, 3], [1, 2], []):
-            eager = run_batch(m, batch, wavs, x_T, None, marks=marks, seed=9, first=3, use_graph=False, overlap=False)
-            graph = run_batch(m, batch, wavs, x_T, None, marks=marks, seed=9, first=3, use_graph=True, overlap=False)
+            eager = run_batch(m, batch, wavs, x_T, None, marks=marks, seed=9, first=3, use_graph=False)
+            graph = run_batch(m, batch, wavs, x_T, None, marks=marks, seed=9, first=3, use_graph=True)
             assert torch.equal(graph, eager), (marks, maxdiff(graph, eager))
             st = eng.launch_state()
             captures.append((eng.cold_times()[3], st["stack_launches"], st["tail_launches"]))
@@ -264,8 +230,8 @@ def test_new_marks_replay_the_captured_chain():
         assert captures[1][1] - captures[0][1] == captures[2][1] - captures[1][1], captures
         assert captures[1][2] - captures[0][2] == captures[2][2] - captures[1][2], captures
         # the segmentations differ where they should: window 1 | 2 is a boundary under [2, 3] and [1, 2] only
-        a = run_batch(m, batch, wavs, x_T, None, marks=[2, 3], seed=9, first=3, overlap=False)
-        b = run_batch(m, batch, wavs, x_T, None, marks=[1, 2], seed=9, first=3, overlap=False)
+        a = run_batch(m, batch, wavs, x_T, None, marks=[2, 3], seed=9, first=3)
+        b = run_batch(m, batch, wavs, x_T, None, marks=[1, 2], seed=9, first=3)
         assert torch.equal(a[0, 480:], a[1, :160]) and not torch.equal(b[0, 480:], b[1, :160])
         assert torch.equal(b[2, 480:], b[3, :160]) and not torch.equal(a[2, 480:], a[3, :160])
     finally:
