@@ -7,6 +7,8 @@
     python sampling.py task=transcription dataset=Custom dataset.args.max_segment_samples=null task.window_overlap=160 ...
     python sampling.py task=transcription task.sampling.steps=50 ...      # 50 respaced steps instead of 200
     python sampling.py task=transcription task.sampling.guidance_interval=[60,140] ...      # guide steps 60..140 only
+    python sampling.py task=transcription dataset=Custom dataset.args.max_segment_samples=null task.sampling.strength=0.5 \
+        task.sampling.init_dir=outputs ...      # refine the rolls of an earlier run: the last half of the chain, from them
     torchrun --nproc-per-node 8 sampling.py task=generation gpus=8 dataset.num_samples=128 dataloader.batch_size=128
 
 Hydra is not a dependency: the same ``group=name`` / ``dotted.key=value`` override syntax is parsed here over
@@ -27,6 +29,10 @@ written as ``roll_<stem>.npy`` (1, 1, ceil(L / hop), 88), ``raw_midi_<stem>.mid`
 short recordings then fill the device together.  The chains are dealt round-robin to the ranks; a chain whose first
 file is file j runs with seed = seed + j, and the roll of file i equals ``sample_long(wav, seed=<that chain's seed>,
 recording=i)``.  It does NOT equal the N = 1 run, which seeds every file with seed + i.  The output files are the same.
+
+``task.sampling.strength=S`` (0 < S <= 1) or ``task.sampling.start_step=T`` with ``task.sampling.init_dir=DIR`` (long-form
+only) starts every chain from a given roll (options "start_step" / "start_noise"): for each input file,
+``DIR/roll_<stem>.npy`` - the file this path itself writes - is diffused to the start step and only the remaining steps run.
 """
 from __future__ import annotations
 
@@ -137,6 +143,26 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
             check_solver_order(cfg["task"]["sampling"]["solver_order"], cfg["task"]["sampling"]["type"])
         except ValueError as err:
             raise SystemExit(f"task.sampling.solver_order: {err}")
+    # task.sampling.strength=S / task.sampling.start_step=T with task.sampling.init_dir=DIR: start every chain from the roll
+    # DIR/roll_<stem>.npy (options "start_step" / "start_noise"); long-form only - the path that writes that file
+    samp = cfg["task"]["sampling"]
+    start_key = next((k for k in ("strength", "start_step") if samp.get(k) is not None), None)
+    if start_key is not None:
+        from .schedule import check_start, respaced_steps
+        try:
+            if not isinstance(S, int):
+                raise ValueError(f"task.timesteps = {S!r}")
+            check_start(samp.get("start_step"), samp.get("strength"), respaced_steps(S, steps or 0))
+        except ValueError as err:
+            raise SystemExit(f"task.sampling.{start_key}: {err}")
+        if not isinstance(samp.get("init_dir"), str):
+            raise SystemExit(f"task.sampling.{start_key} starts every chain from a given roll: task.sampling.init_dir=DIR (the "
+                             f"folder holding roll_<stem>.npy for every input file) is required")
+        if not is_long_form(cfg):
+            raise SystemExit(f"task.sampling.{start_key} is supported where roll_<stem>.npy is written: dataset=Custom "
+                             f"dataset.args.max_segment_samples=null (long-form)")
+    elif samp.get("init_dir") is not None:
+        raise SystemExit("task.sampling.init_dir needs task.sampling.strength=S or task.sampling.start_step=T")
     per_chain = cfg["task"].get("recordings_per_chain", 1)
     if isinstance(per_chain, bool) or not isinstance(per_chain, int) or per_chain < 1:
         raise SystemExit(f"task.recordings_per_chain must be an integer >= 1, got {per_chain!r}")
@@ -202,6 +228,19 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
     written = []
     D = int(cfg["task"]["sampling"].get("draws") or 1)
     more = {"draws": D} if D > 1 else {}
+    init_dir = cfg["task"]["sampling"].get("init_dir")
+
+    def init_roll(path, wav):
+        """task.sampling.init_dir: the roll this recording's chain starts from, (1, 1, ceil(L / hop), 88) (shared by the draws)"""
+        stem = os.path.splitext(os.path.basename(path))[0]
+        roll_path = os.path.join(init_dir, f"roll_{stem}.npy")
+        if not os.path.exists(roll_path):
+            raise SystemExit(f"task.sampling.init_dir: {roll_path} does not exist (the roll to start {os.path.basename(path)} from)")
+        roll = np.load(roll_path)
+        want = (1, 1, -(-wav.shape[0] // hop), 88)
+        if tuple(roll.shape) != want:
+            raise SystemExit(f"task.sampling.init_dir: {roll_path} has shape {tuple(roll.shape)}, the recording needs {want}")
+        return torch.from_numpy(roll).to(torch.float32)
 
     def write(path, roll):
         stem = os.path.splitext(os.path.basename(path))[0]
@@ -228,21 +267,23 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
         for chain in deal_chains(pack_chains(counts, per_chain), rank, world):
             j = chain[0]
             seed = int(cfg["seed"]) + j
+            kw = dict(more, init=[init_roll(files[i], wavs[i]) for i in chain]) if init_dir else more
             if generation:
                 rolls = model.sample_long_batch(frames=[-(-wavs[i].shape[0] // hop) for i in chain], overlap=overlap,
-                                                seed=seed, first_recording=j, **more)
+                                                seed=seed, first_recording=j, **kw)
             else:
-                rolls = model.sample_long_batch([wavs[i] for i in chain], overlap=overlap, seed=seed, first_recording=j, **more)
+                rolls = model.sample_long_batch([wavs[i] for i in chain], overlap=overlap, seed=seed, first_recording=j, **kw)
             for i, roll in zip(chain, rolls):
                 write(files[i], roll)
         return written
     for i, path in deal(list(enumerate(files)), rank, world):
         wav = ingest(path, int(args["sample_rate"]), None)
         seed = int(cfg["seed"]) + i
+        kw = dict(more, init=init_roll(path, wav)) if init_dir else more
         if generation:          # (the waveform is ignored, sampling.py:45: a roll of the recording's length)
-            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i, **more)
+            roll = model.sample_long(frames=-(-wav.shape[0] // hop), overlap=overlap, seed=seed, recording=i, **kw)
         else:
-            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i, **more)
+            roll = model.sample_long(wav, overlap=overlap, seed=seed, recording=i, **kw)
         write(path, roll)
     return written
 

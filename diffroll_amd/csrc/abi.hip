@@ -267,9 +267,12 @@ int chain_step(const dr_engine* e, int i) {
 //   t == 0: [0, 0, sqrt_acp[0], 0, 0]
 // derived in double from the committed fp32 scalars (family 0, columns 2 and 3), rounded to fp32 once.  Rebuilt by
 // dr_commit and whenever "sampling_steps" or "solver_order" changes; the caller has made sure no chain is reading it.
+// Rows [S, 2 S) repeat rows [0, S) with c = 0: step t as a chain's FIRST step (option "start_step": a started chain has no
+// previous prediction).  run_step picks row S + t for the step the option names - no row is rewritten when the option
+// changes, so a chain captured under another start reads at replay what it read when it was captured.
 int build_solver(dr_engine* e) {
     const int S = e->S, n = chain_steps(e);
-    e->h_solver.assign((size_t)S * 5, 0.f);
+    e->h_solver.assign((size_t)2 * S * 5, 0.f);
     if (e->opt_solver == 0) return DR_OK;
     const float* h = e->h_coef.data();
     auto lambda = [&](int t) { return std::log((double)h[(size_t)t * 5 + 2] / (double)h[(size_t)t * 5 + 3]); };
@@ -285,6 +288,12 @@ int build_solver(dr_engine* e) {
         row[1] = (float)(-Ap * std::expm1(-hh));
         if (e->opt_solver == 2 && i > 0 && tp != 0) row[3] = (float)(hh / (2.0 * (lambda(t) - lambda(chain_step(e, i - 1)))));
     }
+    for (int t = 0; t < S; ++t) {
+        const float* row = e->h_solver.data() + (size_t)t * 5;
+        float* first = e->h_solver.data() + ((size_t)S + t) * 5;
+        std::copy(row, row + 5, first);
+        first[3] = 0.f;
+    }
     HIPCHK(e, e->d_solver.ensure(e->h_solver.size(), false));
     HIPCHK(e, hipMemcpy(e->d_solver, e->h_solver.data(), e->h_solver.size() * sizeof(float), hipMemcpyHostToDevice));
     return DR_OK;
@@ -297,6 +306,40 @@ int check_solver(dr_engine* e, int sampler) {
                                   "solver_order 0 for the sampler's own update", sampler, e->opt_solver);
     return DR_OK;
 }
+// option "start_step": the chain position of the step a chain begins at - 0 when the option is off; a step the chain does
+// not visit is refused, naming the visited steps on either side of it
+int start_position(dr_engine* e, int& i0) {
+    i0 = 0;
+    const int ts = e->opt_start;
+    if (ts < 0) return DR_OK;
+    const int n = chain_steps(e);
+    for (int i = 0; i < n; ++i) {
+        const int t = chain_step(e, i);
+        if (t == ts) { i0 = i; return DR_OK; }
+        if (t < ts)       // (the steps decrease strictly and end at 0; the first one is S - 1 >= ts: i > 0 here)
+            return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits (option sampling_steps = %d): the visited steps "
+                                      "on either side of it are %d and %d", ts, e->opt_steps, chain_step(e, i - 1), t);
+    }
+    return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits", ts);      // (unreachable: step 0 is always visited)
+}
+// option "start_noise": the chain's first node - the clean roll in x becomes x at step ts (update.hip: diffuse_kernel).
+// z is row 0 of the injected noise (no reverse step reads it: step 0 draws none), else Philox with counter word S + ts,
+// keyed as run_step keys the updates of this chain (plan.hip).
+int run_diffuse(dr_engine* e, float* x, const float* d_noise, int B, int T, int ts, uint64_t seed, int first_sample, hipStream_t st) {
+    UpdateArgs u{};
+    u.x = x; u.noise = d_noise;
+    u.coef = e->d_coef + (size_t)ts * 5;      // family 0: [.., .., sqrt_acp[ts], sqrt_1m_acp[ts], ..], the committed row
+    u.t = e->S + ts;
+    u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
+    u.seed = seed; u.first_sample = first_sample;
+    u.dyn = e->use_dyn ? e->d_dyn : nullptr;
+    u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
+    if (e->opt_draws > 1) { u.draw_n = B / e->opt_draws; u.draw_G = e->opt_draw_G > 0 ? e->opt_draw_G : u.draw_n; }
+    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt_draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    HIPCHK(e, launch_diffuse(u, st));
+    return DR_OK;
+}
+
 // order 2: the two history buffers, before anything is launched or captured (a chain that may still read them is waited for)
 int ensure_history(dr_engine* e, int B, int T, hipStream_t st) {
     if (e->opt_solver != 2) return DR_OK;
@@ -375,6 +418,20 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         e->hist_key.valid = false;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         return build_solver(e);
+    }
+    if (n == "start_step") {
+        // (no captured chain is dropped: the effective start is part of the chain's key - GraphKey - as "draws" is; whether
+        // the chain visits the step is checked by dr_sample, which knows the chain)
+        if (value < -1 || value >= e->S)
+            return fail(e, DR_EINVAL, "start_step is -1 (the chain's first step) or in [0, timesteps = %d), got %d", e->S, value);
+        e->opt_start = value;
+        return DR_OK;
+    }
+    if (n == "start_noise") {      // (part of the chain's key too)
+        if (value != 0 && value != 1)
+            return fail(e, DR_EINVAL, "start_noise is 0 (x on entry is x at the start step) or 1 (a clean roll, diffused to it), got %d", value);
+        e->opt_start_noise = value;
+        return DR_OK;
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
         // (no captured chain is dropped: the effective pair is part of the chain's key - GraphKey - as "draws" is; lo > hi is
@@ -665,9 +722,10 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if (e->opt_solver == 2) {
         // the history is engine state: the chain's first step starts one, every other step continues the one the previous
         // dr_step left - the preceding visited step of the same (sampler, B, T)
+        // (option "start_step": the step it names starts a history too - its row has c = 0, run_step)
         const int first = chain_step(e, 0);
         auto& k = e->hist_key;
-        if (t != first) {
+        if (t != first && t != e->opt_start) {
             const bool same = k.valid && k.sampler == sampler && k.B == B && k.T == T;
             int expect = first;
             if (same)
@@ -701,6 +759,8 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = check_solver(e, sampler))) return rc;
     if ((rc = check_guidance(e, B, NB))) return rc;
+    int i0 = 0;      // option "start_step": the chain position of the first step this call runs
+    if ((rc = start_position(e, i0))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_history(e, B, T, st))) return rc;
@@ -720,8 +780,12 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         ChainState cs;
         float* cur = xbuf;
         e->hist_par = 0;      // (option "solver_order": the first step reads no history - its row has c = 0)
-        // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows)
-        for (int i = 0, n = chain_steps(e); i < n; ++i) {
+        // option "start_noise": xbuf holds a clean roll - diffuse it to the first step, in place, in front of everything
+        if (e->opt_start_noise)
+            if (int r = run_diffuse(e, xbuf, d_noise, B, T, chain_step(e, i0), seed, first_sample, st)) return r;
+        // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows) - from
+        // position i0 on (option "start_step"; 0: the whole chain)
+        for (int i = i0, n = chain_steps(e); i < n; ++i) {
             const int t = chain_step(e, i);
             // row t of the injected noise is the z of step t; t == 0 draws none (task/diffusion.py:957-960)
             const float* z = d_noise ? d_noise + (size_t)t * per : nullptr;
@@ -745,6 +809,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     key.draws = e->opt_draws; key.draw_G = e->opt_draws > 1 ? e->opt_draw_G : 0; key.fe_B = e->fe_B;
     if (NB == 2 * B) { key.g_lo = e->opt_guid.lo; key.g_hi = e->opt_guid.hi_eff(e->S); }
     key.order = e->opt_solver; key.hist = e->opt_solver == 2 ? (const float*)e->hist[0] : nullptr;
+    key.start = chain_step(e, i0); key.start_noise = e->opt_start_noise;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

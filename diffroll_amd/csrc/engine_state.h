@@ -67,10 +67,13 @@ struct GraphKey {
     // buffers' parity per node), like "draws" part of the key - setting it drops nothing
     int order = 0;
     const float* hist = nullptr;      // the first history buffer (null: order < 2)
+    // ... and where the chain begins: options "start_step" (the effective step: the chain's first visited step when the
+    // option is off) and "start_noise" (whether a diffusion node stands in front of the first step) - setting them drops nothing
+    int start = -1, start_noise = 0;
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi &&
-               order == o.order && hist == o.hist;
+               order == o.order && hist == o.hist && start == o.start && start_noise == o.start_noise;
     }
 };
 
@@ -204,7 +207,9 @@ struct dr_engine {
     // option "solver_order": 0 = the sampler's own update; 1 / 2 = the x0-prediction samplers integrate their prediction
     // with the first-order exponential integrator in lambda / DPM-Solver++ (2M) (update_quad.h: solver_quad)
     int opt_solver = 0;
-    std::vector<float> h_solver;        // (S, 5) rows of the chain's visited steps (build_solver); unvisited rows are zero
+    std::vector<float> h_solver;        // (2 S, 5): rows [0, S) of the chain's visited steps (build_solver; unvisited rows are
+                                        // zero), rows [S, 2 S) the same rows with c = 0 - step t as the FIRST step of a chain
+                                        // (option "start_step"); a table of their own, so no row a captured chain reads moves
     drh::DevBuf<float> d_solver;        // ... on the device
     // order 2: the previous step's prediction.  Two (B, T, 88) buffers, allocated on first use and used ping-pong (the
     // tail kernel's row tiles recompute a quad in different blocks: the one that stores must not overwrite what the
@@ -213,6 +218,10 @@ struct dr_engine {
     int hist_par = 0;
     // dr_step under order 2: what the history holds - the prediction of step hist_t of a (sampler, B, T) chain
     struct { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; } hist_key;
+    // option "start_step": the visited step a chain begins at (d_x on entry is x at that step); -1 = the chain's first
+    // visited step.  option "start_noise": 1 = d_x on entry to dr_sample is a clean roll, diffused to that step by the
+    // chain's first node (update.hip: diffuse_kernel)
+    int opt_start = -1, opt_start_noise = 0;
     dr::GuidanceInterval opt_guid;      // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack

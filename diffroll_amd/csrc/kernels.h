@@ -244,6 +244,10 @@ constexpr int window_idx(unsigned w) { return (int)(w & 0xFFFFu); }
 struct WindowTable { unsigned w[STACK_GROUPS]; };
 hipError_t launch_set_windows(unsigned* d_tab, const WindowTable& tab, int n, hipStream_t s);
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
+// option "start_noise": x = (coef[2] * x) + (coef[3] * z) in place (update.hip: diffuse_kernel).  Of UpdateArgs it reads x,
+// noise (z, or null: Philox), coef, t (the Philox counter word: timesteps + the start step), n, per_sample, seed /
+// first_sample (or dyn), win_H, win_tab, draw_n, draw_G
+hipError_t launch_diffuse(const UpdateArgs& a, hipStream_t s);
 
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->
 // classifier-free combine + posterior update -> input projection of the next step.  Same grid / grouping as the

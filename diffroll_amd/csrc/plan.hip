@@ -431,7 +431,8 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // the row says so and leaves this step's for the next (ping-pong); order 1 neither reads nor stores.
     if (e->opt_solver != 0 && family <= DR_COEF_DDIM_X0) {
         const bool hist = e->opt_solver == 2;
-        u.coef = e->d_solver + (size_t)t * 5; u.mode = 5;
+        // (option "start_step": the step it names is a chain's first - the copy of its row with c = 0, abi.hip: build_solver)
+        u.coef = e->d_solver + ((size_t)(t == e->opt_start ? e->S : 0) + t) * 5; u.mode = 5;
         u.hist_prev = hist ? (const float*)e->hist[e->hist_par] : nullptr;
         u.hist_next = hist && t > 0 ? (float*)e->hist[e->hist_par ^ 1] : nullptr;
         if (hist) e->hist_par ^= 1;

@@ -37,6 +37,53 @@ hipError_t launch_update(const UpdateArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Option "start_noise" (include/diffroll_amd.h): the forward diffusion of a clean roll to the step a chain starts at, in
+// place - x = (A * x0) + (Sm * z), A = coef[2] = sqrt_acp[t_s], Sm = coef[3] = sqrt_1m_acp[t_s] of the committed family-0
+// row, rounded as q_sample rounds (noise_mix_kernel below: each product once, then the sum, contraction off).  One float4
+// per lane; the last block is partial.  z is a.noise (row 0 of the injected noise, which no reverse step reads) or Philox
+// with counter word 2 = a.t = timesteps + t_s - no reverse step uses a word >= timesteps, so the draws are independent of
+// every step's z.  Sample key and quad: the noise-key rule of update_quad.h, the helpers update_quad itself uses - windows
+// whose x0 agree on the frames they share agree there after the diffusion, bit for bit.  HBM-bound: 8 bytes per element
+// (12 with injected noise), once per chain.
+__global__ __launch_bounds__(256) void diffuse_kernel(const UpdateArgs a) {
+#pragma clang fp contract(off)
+    const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i4 * 4 >= a.n) return;
+    const float A = a.coef[2], Sm = a.coef[3];
+    float z[4];
+    if (a.noise) {
+        const float4 zv = reinterpret_cast<const float4*>(a.noise)[i4];
+        z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+    } else {
+        const uint64_t seed = a.dyn ? a.dyn->seed : a.seed;
+        const int first_sample = a.dyn ? a.dyn->first_sample : a.first_sample;
+        long q, sk;
+        if (a.win_H > 0) {
+            const long e0 = i4 * 4;
+            const long smp = e0 / a.per_sample;
+            long rec, idx;
+            window_place(a, smp, rec, idx);
+            window_key(a, rec, idx, e0 - smp * a.per_sample, first_sample, q, sk);
+        } else clip_key(a, i4, first_sample, q, sk);
+        uint32_t rnd[4];
+        philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)a.t, (uint32_t)sk, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+        box_muller(rnd[0], rnd[1], z[0], z[1]);
+        box_muller(rnd[2], rnd[3], z[2], z[3]);
+    }
+    const float4 xv = reinterpret_cast<const float4*>(a.x)[i4];
+    const float x[4] = {xv.x, xv.y, xv.z, xv.w};
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (A * x[e]) + (Sm * z[e]);
+    reinterpret_cast<float4*>(a.x)[i4] = make_float4(o[0], o[1], o[2], o[3]);
+}
+hipError_t launch_diffuse(const UpdateArgs& a, hipStream_t s) {
+    if (!a.x || !a.coef || a.n <= 0 || (a.n & 3) || a.per_sample <= 0) return hipErrorInvalidValue;
+    const long n4 = a.n / 4;
+    hipLaunchKernelGGL(diffuse_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void fill_kernel(float* p, float v, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = v;

@@ -35,6 +35,37 @@ DR_DEVINL void box_muller(uint32_t u0, uint32_t u1, float& z0, float& z1) {
     z1 = rad * sn;
 }
 
+// THE NOISE-KEY RULE, stated once: which Philox (sample key sk, quad q) belongs to a float4 of the roll batch.  Used by
+// update_quad (the z of a reverse step, counter word 2 = t) and by diffuse_kernel (update.hip: the z of option
+// "start_noise", counter word 2 = timesteps + the start step).
+//   a window (a.win_H > 0) is window idx of recording rec of the batch - the table's word (options "window_break" /
+//   "draws": the draw is part of rec), else window smp of recording 0 - and is keyed by its recording and the element on
+//   that recording's canvas: two windows draw the same z on the frames they share;
+//   a clip is keyed by its row, or under option "draws" (a.draw_n > 0) as draw smp / n of clip smp % n.
+// (update_quad reads the table's word itself, inside its test for neighbouring windows: calling window_place there costs
+// the tail kernel one more scalar parked in a VGPR lane - profiles/start_kernel_resources.txt - so only the two key
+// functions are shared code; the word's meaning is window_rec / window_idx of kernels.h in both.)
+DR_DEVINL void window_place(const UpdateArgs& a, const long smp, long& rec, long& idx) {
+    rec = 0; idx = smp;
+    if (a.win_tab) {
+        const unsigned me = a.win_tab[smp];
+        rec = window_rec(me); idx = window_idx(me);
+    }
+}
+// within: the quad's first element inside its window
+DR_DEVINL void window_key(const UpdateArgs& a, const long rec, const long idx, const long within, const int first_sample,
+                          long& q, long& sk) {
+    sk = first_sample + rec;
+    q = (idx * a.win_H * 88 + within) >> 2;
+}
+DR_DEVINL void clip_key(const UpdateArgs& a, const long i4, const int first_sample, long& q, long& sk) {
+    const long e0 = i4 * 4;
+    const long smp = e0 / a.per_sample;
+    q = (e0 - smp * a.per_sample) >> 2;
+    // (option "draws": draw smp / n of clip smp % n)
+    sk = a.draw_n > 0 ? first_sample + smp % a.draw_n + (smp / a.draw_n) * a.draw_G : first_sample + smp;
+}
+
 // The guided prediction of one float4 (index i4) of the roll: (1 + w) x0c - w x0u, or x0c alone (task/diffusion.py:953).
 DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, const float g1pw, float (&y)[4]) {
 #pragma clang fp contract(off)
@@ -120,8 +151,7 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
 #pragma unroll
             for (int e = 0; e < 4; ++e) x0[e] = upper ? 0.5f * (x0[e] + yp[e]) : 0.5f * (yp[e] + x0[e]);
         }
-        key_smp = first_sample + rec;
-        key_q = (idx * a.win_H * 88 + within) >> 2;
+        window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
     if (pred) *pred = make_float4(x0[0], x0[1], x0[2], x0[3]);
     if (a.mode == 5) return solver_quad(a, i4, x0);
@@ -141,13 +171,7 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         } else {
             long within, sk;
             if (key_smp >= 0) { within = key_q; sk = key_smp; }
-            else {
-                const long e0 = i4 * 4;
-                const long smp = e0 / a.per_sample;
-                within = (e0 - smp * a.per_sample) >> 2;
-                // (option "draws": draw smp / n of clip smp % n)
-                sk = a.draw_n > 0 ? first_sample + smp % a.draw_n + (smp / a.draw_n) * a.draw_G : first_sample + smp;
-            }
+            else clip_key(a, i4, first_sample, within, sk);
             uint32_t rnd[4];
             philox4x32_10((uint32_t)within, (uint32_t)(within >> 32), (uint32_t)a.t,
                           (uint32_t)sk, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);

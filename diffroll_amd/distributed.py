@@ -167,7 +167,7 @@ def draw_major(rows: torch.Tensor, draws: int) -> torch.Tensor:
 
 
 def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noise: Optional[torch.Tensor],
-                 seed: int, rank: int, world_size: int, draws: int = 1) -> torch.Tensor:
+                 seed: int, rank: int, world_size: int, draws: int = 1, init: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The part of sample_sharded one rank computes: the chain of its contiguous shard of the GLOBAL batch,
     returned as (b_local, 1, T', 88) on the engine's device (b_local may be 0).  Philox noise is keyed by the
     global sample index (first_sample = lo), so the rolls do not depend on the world size.
@@ -175,7 +175,14 @@ def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noi
     every rank that is handed the same hparams runs the same steps guided.
     draws = D > 1: x_T / noise hold D draws of the B global clips, draw-major; the rank runs its clip shard x all draws in
     one chain with "draw_stride" = B - draw d of global clip c is keyed c + d * B on any world size - and returns
-    (D * b_local, 1, T', 88), draw-major over its shard."""
+    (D * b_local, 1, T', 88), draw-major over its shard.
+    init (x_T None): clean rolls to start the chains from (model.sample(init=...)), laid out and sharded like x_T; the
+    diffusion's Philox draws are keyed globally like the steps', so the result does not depend on the world size."""
+    more = {}
+    if init is not None:
+        if x_T is not None:
+            raise ValueError("pass either x_T or init=, not both")
+        x_T = init
     B = x_T.shape[0] // draws
     lo, hi = shard_bounds(B, rank, world_size)
     wav = None if waveform is None else waveform[lo:hi]
@@ -184,10 +191,15 @@ def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noi
         z = None if noise is None else noise.reshape((noise.shape[0], draws, B) + tuple(noise.shape[2:]))[:, :, lo:hi].reshape(
             (noise.shape[0], -1) + tuple(noise.shape[2:]))
         if hi > lo:
-            return model.sample(x_loc, wav, noise=z, seed=seed, first_sample=lo, draws=draws, draw_stride=B)[0]
+            if init is not None:
+                x_loc, more = None, {"init": x_loc}
+            return model.sample(x_loc, wav, noise=z, seed=seed, first_sample=lo, draws=draws, draw_stride=B, **more)[0]
     z = None if noise is None else noise[:, lo:hi]
     if hi > lo:
-        roll, _ = model.sample(x_T[lo:hi], wav, noise=z, seed=seed, first_sample=lo)
+        x_loc = x_T[lo:hi]
+        if init is not None:
+            x_loc, more = None, {"init": x_loc}
+        roll, _ = model.sample(x_loc, wav, noise=z, seed=seed, first_sample=lo, **more)
         return roll
     # more ranks than clips: an empty shard with the frame count the other ranks will produce (the model's own rule:
     # trim_spec_roll incl. the 641-frame learned spectrogram of condition='trainable_spec')
@@ -196,17 +208,19 @@ def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noi
 
 
 def sample_sharded(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None,
-                   seed: int = 0, group=None, draws: int = 1) -> torch.Tensor:
+                   seed: int = 0, group=None, draws: int = 1, init: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Every rank passes the SAME global batch (x_T (B,1,T,88), waveform (B,L), optional injected noise
     (S,B,1,T,88)); each runs its contiguous shard and all ranks return the full (B,1,T',88) result.
     Philox noise is keyed by the global sample index, so the result does not depend on the world size.
     draws = D > 1: x_T (D*B,1,T,88) and noise (S,D*B,1,T,88) are draw-major over the global batch, and so is the
-    (D*B,1,T',88) result: the shards travel through the gather one row per clip and are regrouped behind it."""
+    (D*B,1,T',88) result: the shards travel through the gather one row per clip and are regrouped behind it.
+    init (x_T None): the clean rolls of model.sample(init=...), sharded like x_T."""
     rank, ws = world()
-    roll = sample_shard(model, x_T, waveform, noise, seed, rank, ws, draws)
+    roll = sample_shard(model, x_T, waveform, noise, seed, rank, ws, draws, init)
+    n = (init if x_T is None else x_T).shape[0]
     if draws > 1:
-        return draw_major(gather_rolls_uneven(clip_major(roll, draws), x_T.shape[0] // draws, group), draws)
-    return gather_rolls_uneven(roll, x_T.shape[0], group)
+        return draw_major(gather_rolls_uneven(clip_major(roll, draws), n // draws, group), draws)
+    return gather_rolls_uneven(roll, n, group)
 
 
 def sample_sharded_sequential(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor],

@@ -46,12 +46,17 @@ _MIRRORED = {
     "draws": 1,                  # rolls per clip of one chain, draw-major
     "draw_stride": 0,            # Philox key distance of two draws (0 = the clips of the batch)
     "solver_order": 0,           # 0 = the sampler's own update
+    "start_step": -1,            # the visited step a chain begins at (-1 = its first)
+    "start_noise": 0,            # 1 = sample() takes a clean roll and diffuses it to the start step
     "blocked_accumulation": 2,   # 2 = every fp32 flavour that has a blocked form, 1 = single chain on 128-frame blocks
 }
 
 
 class Engine:
     """One engine handle per (device, stream).  Not re-entrant."""
+
+    # the library's defaults of options 'start_step' / 'start_noise', also for a subclass that does not run __init__
+    start_step, start_noise = _MIRRORED["start_step"], _MIRRORED["start_noise"]
 
     def __init__(self, *, residual_channels: int, residual_layers: int, kernel_size: int,
                  dilation_base: int, dilation_bound: int, n_mels: int, timesteps: int,
@@ -271,6 +276,8 @@ class Engine:
     def sample(self, sampler: str, x: torch.Tensor, noise: Optional[torch.Tensor], w: float = 0.0,
                seed: int = 0, first_sample: int = 0, use_graph: bool = True, check: bool = True) -> torch.Tensor:
         """Whole reverse chain in place on x (B, T, 88); noise (S, B, T, 88) or None (Philox).
+        Option 'start_step' = t_s: only the visited steps t <= t_s run and x is x at step t_s - or, under option 'start_noise'
+        (holding(start_noise=1)), a clean roll that the chain's first node diffuses to t_s (z: row 0 of noise, or Philox).
         check=True (default): synchronous and self-healing - returns only with the correct roll in x (a fused launch
         that timed out because something else held the device's CUs is detected and the chain re-run on the per-phase
         kernels, dr_sample_checked).  check=False: asynchronous on the current stream; call finish() before the
@@ -345,7 +352,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'start_step', 'start_noise' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -362,7 +369,7 @@ class Engine:
     def holding(self, **options):
         """Options held for one call and put back afterwards, also when the call raises: mirrored option names, and
         window_breaks = the marks.  An option that already has the value is not set at all - 'sampling_steps' would drop the
-        captured chain; 'draws', 'draw_stride' and the marks never do (they are part of its key or plain data), so a loop of
+        captured chain; 'draws', 'draw_stride', 'start_step', 'start_noise' and the marks never do (they are part of its key or plain data), so a loop of
         such calls replays one graph, and putting them back behind an asynchronous call touches nothing in flight."""
         def put(name, value):
             if name == "window_breaks":

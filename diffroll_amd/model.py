@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import check_guidance_interval, check_sampling_steps, check_solver_order, respaced_steps
+from .schedule import check_guidance_interval, check_sampling_steps, check_solver_order, check_start, respaced_steps
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
@@ -147,6 +147,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.solver_order = 1 / 2 integrates the x0 prediction with a multistep ODE solver (option
         # "solver_order": DPM-Solver++), the companion of sampling.steps; absent / None / 0 = the sampler's own update
         check_solver_order(sampling.get("solver_order"), sampling.type)
+        # an extension: sampling.start_step = t / sampling.strength = s start the chain at an intermediate visited step
+        # (options "start_step" / "start_noise"): refine or vary a given roll, resume a chain; absent / None = the whole chain
+        check_start(sampling.get("start_step"), sampling.get("strength"), respaced_steps(timesteps, sampling.get("steps") or 0))
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -240,6 +243,7 @@ class ClassifierFreeDiffRoll(nn.Module):
     def engine(self) -> Engine:
         interval = self.guidance_interval()               # (a malformed one raises here: before any GPU work)
         order = self.solver_order()                       # (likewise)
+        start = self.start_step()                         # (likewise)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
                                   fe_window=self.__dict__.get("_ckpt_window"), fe_fb=self.__dict__.get("_ckpt_fb"),
@@ -261,7 +265,23 @@ class ClassifierFreeDiffRoll(nn.Module):
             self._engine.set_guidance_interval(*interval)
         if self._engine.solver_order != order:            # (likewise part of the key)
             self._engine.set_option("solver_order", order)
+        if self._engine.start_step != start:              # (likewise part of the key)
+            self._engine.set_option("start_step", start)
         return self._engine
+
+    def start_configured(self):
+        """The hparams.sampling key that starts chains at an intermediate step - 'start_step' or 'strength' - or None."""
+        sampling = self.__dict__["hparams"].sampling
+        return next((k for k in ("start_step", "strength") if sampling.get(k) is not None), None)
+
+    def start_step(self) -> int:
+        """hparams.sampling.start_step / .strength as the engine's option "start_step" takes them (-1: the chain's first
+        step), or -1 while one of the reference's single-step methods runs.  Read at every use; a bad value raises
+        ValueError before any GPU work (schedule.check_start)."""
+        hp = self.__dict__["hparams"]
+        start = check_start(hp.sampling.get("start_step"), hp.sampling.get("strength"),
+                            respaced_steps(int(hp.timesteps), check_sampling_steps(hp.sampling.get("steps"), hp.timesteps)))
+        return -1 if self.__dict__.get("_stride1") else start
 
     def solver_order(self) -> int:
         """hparams.sampling.solver_order as the engine's option takes it (0: the sampler's own update), or 0 while one of
@@ -501,7 +521,8 @@ class ClassifierFreeDiffRoll(nn.Module):
 
     @torch.no_grad()
     def sample(self, x_T, waveform=None, noise=None, seed: int = 0, first_sample: int = 0,
-               use_graph: bool = True, check: bool = True, draws: int = 1, draw_stride: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+               use_graph: bool = True, check: bool = True, draws: int = 1, draw_stride: int = 0,
+               init=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The reverse chain t = timesteps-1 .. 0 (task/diffusion.py:528-534) - or, with hparams.sampling.steps = n,
         the n respaced steps of visited_steps() - on the device with no host round trip.  x_T (B,1,T,88); noise: None
         (on-device Philox keyed by seed, global sample index and step) or (timesteps, B, 1, T, 88) injected z's (row t
@@ -512,15 +533,26 @@ class ClassifierFreeDiffRoll(nn.Module):
         (n, L), draw-major (row b = draw b // n of clip b % n); the front-end and the conditioner tensors exist once per
         clip.  Returns (rolls (D*n,1,T',88), spec (n,n_mels,T')) - bit for bit the rolls of the waveform tiled D times.
         Philox keys row b by first_sample + b % n + (b // n) * draw_stride (0 = n: the tiled batch's first_sample + b).
+        With hparams.sampling.start_step = t_s or .strength = s (options "start_step" / "start_noise") only the visited steps
+        t <= t_s run.  init (B,1,T,88): a clean roll in the model's roll space - x_T must then be None; the roll is trimmed
+        like x_T and diffused to t_s by the chain's first node (z: row 0 of noise, or Philox keyed as the steps' draws with
+        step word timesteps + t_s); without a start configured it is diffused to the chain's first step.  Without init and
+        with a start configured, x_T is x AT step t_s (resume: a row of sample_trajectory).
         check=True (default): the call returns with the FINISHED, verified roll, as task/diffusion.py:528-538 does
         (synchronous; a fused-kernel time-out caused by another tenant of the device is healed by re-running the chain
         on the per-phase kernels - Engine.sample).  check=False: asynchronous; call engine.finish() before use."""
         eng = self.engine
         sampler = self.hparams.sampling.type
+        if (init is None) == (x_T is None):
+            raise ValueError("pass either x_T (x at the chain's first - or configured start - step) or init= (a clean roll to "
+                             "diffuse to it), not " + ("both" if init is not None else "neither"))
+        start_noise = 0 if init is None else 1
+        if init is not None:
+            x_T = init
         B, _, T, _ = x_T.shape
         draws = check_draws(draws)
         if B % draws:
-            raise ValueError(f"x_T holds {B} rolls: not a whole number of draws = {draws}")
+            raise ValueError(f"{'init' if start_noise else 'x_T'} holds {B} rolls: not a whole number of draws = {draws}")
         if draws > 1 and waveform is not None and waveform.shape[0] != B // draws:
             raise ValueError(f"{draws} draws of {B} rolls take the waveform of {B // draws} clips, got {waveform.shape[0]}")
         if sampler != "generation_ddpm_x0" and waveform is None:
@@ -535,14 +567,14 @@ class ClassifierFreeDiffRoll(nn.Module):
             z = noise.to(eng.device, torch.float32).reshape(S, B, T, 88)
             if Tm != T or not z.is_contiguous():
                 z = z[:, :, :Tm, :].contiguous()
-        with eng.holding(draws=draws, draw_stride=draw_stride):
+        with eng.holding(draws=draws, draw_stride=draw_stride, start_noise=start_noise):
             eng.sample(sampler, xb, z, self._guidance_weight(sampler), seed, first_sample, use_graph, check)
         return xb.unsqueeze(1), spec
 
     @torch.no_grad()
     def sample_long(self, waveform=None, frames: Optional[int] = None, overlap: int = 160, seed: int = 0,
                     recording: int = 0, x_T=None, noise=None, use_graph: bool = True, check: bool = True,
-                    draws: int = 1) -> torch.Tensor:
+                    draws: int = 1, init=None) -> torch.Tensor:
         """One recording of any length as jointly sampled 640-frame windows (diffroll_amd/longform.py; option
         "window_overlap" of include/diffroll_amd.h): returns the stitched roll (1, 1, T_out, 88) on the device.
         Conditional samplers take waveform (L,) (T_out = ceil(L / hop)); generation_ddpm_x0 takes frames = T_out.
@@ -550,12 +582,16 @@ class ClassifierFreeDiffRoll(nn.Module):
         (Philox keyed by seed, first_sample = recording and the canvas element) or a canvas tensor
         (timesteps, 1, 1, T_c, 88).  Every window is one row of ONE Engine.sample chain (check=True heals).
         draws = D > 1: D draws of the recording in that one chain, as sample_long_batch([waveform], draws=D) - returns
-        (D, 1, T_out, 88); x_T (D, 1, T_c, 88), noise (timesteps, D, 1, T_c, 88)."""
+        (D, 1, T_out, 88); x_T (D, 1, T_c, 88), noise (timesteps, D, 1, T_c, 88).
+        init: a clean roll of the recording in the shape this method RETURNS, (1, 1, T_out, 88) (or (D, 1, T_out, 88)) - a
+        roll it returned can be fed back - instead of x_T: zero-padded to the canvas, a single roll shared by all draws, and
+        diffused to the start step of hparams.sampling.start_step / .strength by the chain's first node (sample())."""
         from . import longform
         if check_draws(draws) > 1:
             return self.sample_long_batch(None if waveform is None else [waveform], None if frames is None else [frames],
                                           overlap, seed, recording, None if x_T is None else [x_T],
-                                          None if noise is None else [noise], use_graph, check, draws)[0]
+                                          None if noise is None else [noise], use_graph, check, draws,
+                                          None if init is None else [init])[0]
         sampler = self.hparams.sampling.type
         if sampler == "inpainting_ddpm_x0":
             raise ValueError("sample_long does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) are in "
@@ -577,6 +613,8 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise ValueError(f"{plan.n} windows of {plan.T} frames: one chain holds at most {longform.MAX_WINDOWS} "
                              f"(longform.MAX_WINDOWS); split the recording")
         S = int(self.hparams.timesteps)
+        if init is not None:
+            x_T = self._init_canvases([init], x_T, batch, 1)[0]
         if x_T is None:
             x_T = torch.randn(1, 1, plan.T_c, 88, generator=torch.Generator().manual_seed(int(seed)))
         if tuple(x_T.shape) != (1, 1, plan.T_c, 88):
@@ -584,15 +622,37 @@ class ClassifierFreeDiffRoll(nn.Module):
         if noise is not None and noise.numel() != S * plan.T_c * 88:
             raise ValueError(f"noise must be the canvas ({S}, 1, 1, {plan.T_c}, 88), got {tuple(noise.shape)}")
         xb = self._sample_windows(batch, None if waveform is None else [waveform], [x_T], None if noise is None else [noise],
-                                  1, seed, recording, use_graph, check)
+                                  1, seed, recording, use_graph, check, start_noise=0 if init is None else 1)
         return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
 
-    def _sample_windows(self, batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check, marks=None):
+    @staticmethod
+    def _init_canvases(init, x_T, batch, D):
+        """init= of sample_long / sample_long_batch -> the canvases that take x_T's place: one roll per recording in the shape
+        those methods return, (D or 1, 1, T_out, 88), zero-padded to the canvas's T_c frames, a single roll repeated for
+        every draw.  The windows gathered from a canvas agree on the frames they share - what the joint chain needs."""
+        if x_T is not None:
+            raise ValueError("pass either x_T (canvases at the chain's first - or configured start - step) or init= (clean "
+                             "rolls to diffuse to it), not both")
+        plans = batch.plans
+        if len(init) != len(plans) or any(r.dim() != 4 or r.shape[0] not in (1, D) or tuple(r.shape[1:]) != (1, p.T_out, 88)
+                                          for r, p in zip(init, plans)):
+            raise ValueError(f"init must be one roll ({D} or 1, 1, T_out, 88) per recording, T_out = {[p.T_out for p in plans]}, "
+                             f"got {[tuple(r.shape) for r in init]}")
+        out = []
+        for r, p in zip(init, plans):
+            canvas = torch.zeros(D, 1, p.T_c, 88, dtype=torch.float32, device=r.device)
+            canvas[:, :, :p.T_out] = r.to(torch.float32)       # (a single roll broadcasts over the draws)
+            out.append(canvas)
+        return out
+
+    def _sample_windows(self, batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check, marks=None,
+                        start_noise=0):
         """The one long-form chain: the recordings of `batch` (longform.plan_batch) as D draws of its windows.  waveforms: one
         (L,) host tensor per recording, or None (generation); x_T / noise: one canvas per recording, (D, 1, T_c, 88) /
         (timesteps, D, 1, T_c, 88), or noise None (Philox); marks: the window_break marks, the plan's unless given.  Options
         "window_overlap", "window_break", "draws" hold for the chain only.  Returns the window batch (D * n, T, 88) after the
-        chain: that of draw 0, then that of draw 1, ... (draw-major)."""
+        chain: that of draw 0, then that of draw 1, ... (draw-major).  start_noise = 1: the canvases are clean rolls (option
+        "start_noise": diffused to the chain's start step per recording and canvas element)."""
         from . import longform
         eng = self.engine
         sampler = self.hparams.sampling.type
@@ -608,13 +668,14 @@ class ClassifierFreeDiffRoll(nn.Module):
                          batch.plans[0].T)
             self._fe_key = None          # the engine's conditioner is the windows' now: sample() recomputes its own
         with eng.holding(window_overlap=batch.plans[0].overlap, window_breaks=batch.marks if marks is None else marks,
-                         draws=D, draw_stride=0):
+                         draws=D, draw_stride=0, start_noise=start_noise):
             eng.sample(sampler, xb, z, self._guidance_weight(sampler), seed, first_recording, use_graph, check)
         return xb
 
     @torch.no_grad()
     def sample_long_batch(self, waveforms=None, frames=None, overlap: int = 160, seed: int = 0, first_recording: int = 0,
-                          x_T=None, noise=None, use_graph: bool = True, check: bool = True, draws: int = 1) -> List[torch.Tensor]:
+                          x_T=None, noise=None, use_graph: bool = True, check: bool = True, draws: int = 1,
+                          init=None) -> List[torch.Tensor]:
         """Several recordings of any lengths in ONE chain (option "window_break" of include/diffroll_amd.h;
         longform.plan_batch): their windows fill one batch, a window shares frames only with windows of its own
         recording, and recording i draws the noise of first_sample = first_recording + i on its own canvas.  Returns one
@@ -627,7 +688,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         over ONE set of conditioner tensors, and draw d is the chain of first_recording + d * (number of recordings) on
         its own canvases.  Returns per recording (D, 1, T_out_i, 88); x_T / noise carry the draws in the canvases' batch
         dimension ((D, 1, T_c_i, 88) / (timesteps, D, 1, T_c_i, 88)); the default x_T are the first D canvases of
-        torch.Generator().manual_seed(seed) (draw 0 = the single-draw default)."""
+        torch.Generator().manual_seed(seed) (draw 0 = the single-draw default).
+        init: instead of x_T, one clean roll per recording in the shape this method returns ((D or 1, 1, T_out_i, 88));
+        see sample_long."""
         from . import longform
         D = check_draws(draws)
         sampler = self.hparams.sampling.type
@@ -651,13 +714,16 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise ValueError(f"{D * batch.n} windows in {len(batch.plans)} recordings ({D} draw(s)): one chain holds at most "
                              f"{longform.MAX_WINDOWS} (longform.MAX_WINDOWS); use fewer recordings per chain (longform.pack_chains)")
         R, S = len(batch.plans), int(self.hparams.timesteps)
+        if init is not None:
+            x_T = self._init_canvases(list(init), x_T, batch, D)
         if x_T is None:
             x_T = [torch.randn(D, 1, p.T_c, 88, generator=torch.Generator().manual_seed(int(seed))) for p in batch.plans]
         if len(x_T) != R or any(tuple(x.shape) != (D, 1, p.T_c, 88) for x, p in zip(x_T, batch.plans)):
             raise ValueError(f"x_T must be one canvas ({D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
         if noise is not None and (len(noise) != R or any(zr.numel() != S * D * p.T_c * 88 for zr, p in zip(noise, batch.plans))):
             raise ValueError(f"noise must be one canvas ({S}, {D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
-        xb = self._sample_windows(batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check)
+        xb = self._sample_windows(batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check,
+                                  start_noise=0 if init is None else 1)
         rolls = longform.stitch_batch(xb.reshape(D, batch.n, longform.WINDOW_FRAMES, 88), batch)
         return [r.reshape(D, 1, p.T_out, 88) for r, p in zip(rolls, batch.plans)]
 
@@ -666,10 +732,12 @@ class ClassifierFreeDiffRoll(nn.Module):
         row i = x after the i-th visited step - n = timesteps (t = timesteps-1-i), or hparams.sampling.steps - and spec).
         This is what the reference's sampling() collects as `noise_list` - on the host, with one D2H copy per step
         (task/diffusion.py:779-788) - for its animation; here it is an opt-in eager loop over dr_step (one launch sequence
-        per step, no graph), and the last row equals sample()'s result bit for bit."""
+        per step, no graph), and the last row equals sample()'s result bit for bit.
+        With hparams.sampling.start_step / .strength the rows are those of the visited steps t <= t_s, and x_T is x at t_s."""
         sampler = self.hparams.sampling.type
         x, rows, spec = x_T, [], None
-        for t in self.visited_steps():
+        steps, start = self.visited_steps(), self.start_step()
+        for t in steps[steps.index(start) if start >= 0 else 0:]:
             # no noise given: Philox keyed by (seed, global sample, step), the draws of sample(); step 0 takes none
             z = torch.zeros_like(x) if t == 0 else None if noise is None else noise[t]
             x, spec = self._one_step(sampler, x, waveform, t, z, respaced=True, philox=(seed, first_sample))
@@ -681,12 +749,25 @@ class ClassifierFreeDiffRoll(nn.Module):
         (B,1,T,88) (the reference returns nothing and writes figures/MIDI instead)."""
         noise, waveform = batch[0], batch[1]
         D = self.draws()
+        if self.start_configured():
+            # a chain that starts at an intermediate step starts FROM a roll: the batch's third element, (B,1,T,88) (one per
+            # clip, shared by the draws) - Gaussian x_T is never taken for x at the start step
+            init = self._batch_init(batch[2] if len(batch) > 2 else None)
+            rolls, _ = self.sample(None, waveform, seed=batch_idx, draws=D, init=init.repeat(D, 1, 1, 1))
+            return self._ensemble(rolls, D) if D > 1 else rolls
         if D > 1:      # draw 0 starts from the batch's x_T, the others from host-seeded ones; the mean roll is returned
             more = torch.randn((D - 1) * noise.shape[0], *noise.shape[1:], generator=torch.Generator().manual_seed(int(batch_idx)))
             rolls, _ = self.sample(torch.cat([noise.to("cpu", torch.float32), more], 0), waveform, seed=batch_idx, draws=D)
             return self._ensemble(rolls, D)
         roll, _ = self.sample(noise, waveform, seed=batch_idx)
         return roll
+
+    def _batch_init(self, init):
+        if init is None:
+            key = self.start_configured()
+            raise ValueError(f"hparams.sampling.{key} starts the chain at an intermediate step: the batch must carry the roll to "
+                             f"start from (a third element / the key 'init', (B, 1, T, 88)) - x_T is noise, not x at that step")
+        return torch.as_tensor(init).to(torch.float32)
 
     def _ensemble(self, rolls, D):
         """Mean roll of D draws per clip; the per-cell votes and spread stay in self.last_ensemble = (votes, std)."""
@@ -753,6 +834,11 @@ class ClassifierFreeDiffRoll(nn.Module):
         frame = batch["frame"]
         x_T = batch.get("x_T")
         D = self.draws()
+        if self.start_configured():      # (as predict_step: the roll to start from is batch['init'], never x_T)
+            init = self._batch_init(batch.get("init"))
+            rolls, spec = self.sample(None, batch["audio"], noise=batch.get("noise"), seed=batch_idx, draws=D,
+                                      init=init.repeat(D, 1, 1, 1))
+            return (self._ensemble(rolls, D) if D > 1 else rolls), spec
         if D > 1:
             # hparams.sampling.draws: D rolls per clip in one chain ('x_T' (D*B, 1, T, 88) / 'noise' (timesteps, D*B, 1, T, 88),
             # draw-major; x_T drawn on the host from a generator seeded with batch_idx when absent); the roll returned -

@@ -8,6 +8,7 @@ engine through dr_set_tables().
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List
 
 import torch
@@ -120,6 +121,33 @@ def check_solver_order(order, sampler: str = None) -> int:
         raise ValueError(f"solver_order = {order} integrates an x0 prediction ({', '.join(X0_SAMPLERS)}); '{sampler}' "
                          f"predicts epsilon")
     return order
+
+
+def check_start(start_step, strength, visited) -> int:
+    """Options "start_step" / "start_noise" (include/diffroll_amd.h) as hparams.sampling.start_step / .strength: where a
+    chain over the steps `visited` (chain order) begins.  The two keys are mutually exclusive.  strength s in (0, 1] runs
+    k = min(n, max(1, floor(s n + 0.5))) of the n visited steps - the start is visited[n - k]; start_step names the visited
+    step itself.  Returns the option's value: the step, or -1 for neither key and for k = n (the whole chain).  Anything
+    else raises ValueError."""
+    visited = [int(t) for t in visited]
+    n = len(visited)
+    if start_step is not None and strength is not None:
+        raise ValueError(f"start_step and strength are mutually exclusive (got start_step = {start_step!r}, strength = {strength!r})")
+    if strength is not None:
+        if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= 1.0:
+            raise ValueError(f"strength must be a number in (0, 1] (or None: the whole chain), got {strength!r}")
+        k = min(n, max(1, int(math.floor(float(strength) * n + 0.5))))
+        return -1 if k == n else visited[n - k]
+    if start_step is None:
+        return -1
+    if isinstance(start_step, bool) or not isinstance(start_step, int) or start_step not in visited:
+        near = ""
+        if isinstance(start_step, int) and not isinstance(start_step, bool) and visited[-1] < start_step < visited[0]:
+            near = (f": the visited steps on either side of it are {min(t for t in visited if t > start_step)} and "
+                    f"{max(t for t in visited if t < start_step)}")
+        raise ValueError(f"start_step must be one of the {n} steps the chain visits ({visited[0]} .. {visited[-1]}; or None: "
+                         f"the whole chain), got {start_step!r}{near}")
+    return start_step
 
 
 GUIDING_SAMPLERS = ("cfdg_ddpm_x0", "inpainting_ddpm_x0", "cfdg_ddim_x0")

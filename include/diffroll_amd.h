@@ -453,6 +453,40 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          chain's key, like "draws": setting it drops nothing, and a chain captured under another value
  *                          is never replayed.  Nothing is known about the quality of either order with this model
  *                          (INTEGRATION.md 3c).
+ *   "start_step"      [-1] t_s, -1 or 0 <= t_s < timesteps: START the reverse chain at an intermediate step.  dr_sample /
+ *                          dr_sample_checked run the visited steps t <= t_s in chain order, and d_x on entry is x at step
+ *                          t_s - a row of an earlier chain's trajectory (resume), or a roll diffused to t_s ("start_noise";
+ *                          SDEdit, Meng et al. 2022).  -1 = the chain's first visited step: off, bit-identical to an engine
+ *                          that never set the option.  Any other value -> DR_EINVAL at the set; a t_s that the chain does
+ *                          not visit (the full chain, or the steps of "sampling_steps") -> DR_EINVAL at the call, naming t_s
+ *                          and the visited steps on either side of it.  Nothing else moves: coefficient rows, the guidance
+ *                          interval test, Philox keys and injected-noise rows stay keyed by the real t, so a started chain
+ *                          draws exactly the z's the whole chain draws at those steps - a chain resumed from the whole
+ *                          chain's x at t_s ends in the whole chain's roll, bit for bit (orders 0 and 1).  Under
+ *                          "solver_order" 2 the started chain's first step is first order (c = 0) and starts a new
+ *                          history, as the whole chain's first step does - it reads a copy of its row with c = 0, kept
+ *                          beside the table, so no row that another captured chain reads is touched; the step into 0 stays
+ *                          first order; dr_step at t == t_s starts a history too.  dr_step, dr_forward, dr_forward_steps,
+ *                          dr_q_sample, dr_extract_x0 are otherwise unaffected.  Combines with "sampling_steps",
+ *                          "window_overlap" / "window_break", "draws" / "draw_stride", "guidance_t_min" / "guidance_t_max",
+ *                          both precisions and sharding (every rank sets the same step).  The effective start is part of
+ *                          a captured chain's key, like "draws": setting it drops nothing, and a chain captured under
+ *                          another start is never replayed.  Nothing is known about the quality of a started chain with
+ *                          this model.
+ *   "start_noise"      [0] 0 or 1.  1: d_x on entry to dr_sample / dr_sample_checked is a CLEAN roll x0 in the model's roll
+ *                          space, and the chain's first node diffuses it to the start step t_s ("start_step"; -1: the
+ *                          chain's first visited step) in place on the buffer the chain runs on: x = (A * x0) + (Sm * z),
+ *                          A = sqrt_acp[t_s], Sm = sqrt_1m_acp[t_s], the committed fp32 values (columns 2 and 3 of
+ *                          DR_COEF_DDPM_X0), rounded as dr_q_sample rounds - each product once, then the sum.  z is row 0
+ *                          of d_noise when that is given (no reverse step reads it), else Philox with the chain's seed and
+ *                          counter word 2 = timesteps + t_s (the steps use t < timesteps: the draws are independent of
+ *                          every step's z), sample key and element as the steps' own draws take them under "draws" /
+ *                          "draw_stride" / "window_overlap" / "window_break" - windows are keyed by recording and canvas
+ *                          element: if x0 agrees on the frames two windows share, so does x at t_s, bit for bit.  Under
+ *                          "solver_order" != 0 this is the one place that still draws.  dr_sample_checked keeps what the
+ *                          caller passed - x0 - so its re-run diffuses again with the same z.  dr_step ignores the
+ *                          option: it takes x at its step.  Any other value -> DR_EINVAL.  Part of a captured chain's key,
+ *                          like "draws".
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
