@@ -143,6 +143,14 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
             check_solver_order(cfg["task"]["sampling"]["solver_order"], cfg["task"]["sampling"]["type"])
         except ValueError as err:
             raise SystemExit(f"task.sampling.solver_order: {err}")
+    # task.sampling.solver_noise=1: the solver's stochastic form (option "solver_noise"); absent / null / 0 = deterministic
+    if cfg["task"]["sampling"].get("solver_noise") is not None:
+        from .schedule import check_solver_noise
+        try:
+            check_solver_noise(cfg["task"]["sampling"]["solver_noise"], cfg["task"]["sampling"]["type"],
+                               cfg["task"]["sampling"].get("solver_order"))
+        except ValueError as err:
+            raise SystemExit(f"task.sampling.solver_noise: {err}")
     # task.sampling.strength=S / task.sampling.start_step=T with task.sampling.init_dir=DIR: start every chain from the roll
     # DIR/roll_<stem>.npy (options "start_step" / "start_noise"); long-form only - the path that writes that file
     samp = cfg["task"]["sampling"]

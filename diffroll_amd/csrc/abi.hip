@@ -265,8 +265,12 @@ int chain_step(const dr_engine* e, int i) {
 //           c = h / (2 h_prev) for order 2 when t is not the chain's first step and t' != 0, else 0: the step into 0 is
 //           first order (lambda jumps between steps 1 and 0 of the linear schedule; extrapolating across it hurts short chains)
 //   t == 0: [0, 0, sqrt_acp[0], 0, 0]
+// option "solver_noise" (the stochastic form, SDE-DPM-Solver++), same c:
+//   t > 0:  [(sqrt_1m_acp[t'] / sqrt_1m_acp[t]) exp(-h), -sqrt_acp[t'] expm1(-2h), sqrt_acp[t], c, sqrt_1m_acp[t'] sqrt(-expm1(-2h))]
+// With sqrt_acp^2 + sqrt_1m_acp^2 = 1 column 4 is the sigma of the derived DR_COEF_DDPM_X0 row of build_respaced and column
+// 0 its sqrt(1 - acp' - sigma^2) / sqrt_1m_acp: first order is the ddpm_x0 update by another arithmetic route.
 // derived in double from the committed fp32 scalars (family 0, columns 2 and 3), rounded to fp32 once.  Rebuilt by
-// dr_commit and whenever "sampling_steps" or "solver_order" changes; the caller has made sure no chain is reading it.
+// dr_commit and whenever "sampling_steps", "solver_order" or "solver_noise" changes; the caller has made sure no chain is reading it.
 // Rows [S, 2 S) repeat rows [0, S) with c = 0: step t as a chain's FIRST step (option "start_step": a started chain has no
 // previous prediction).  run_step picks row S + t for the step the option names - no row is rewritten when the option
 // changes, so a chain captured under another start reads at replay what it read when it was captured.
@@ -284,8 +288,15 @@ int build_solver(dr_engine* e) {
         const int tp = chain_step(e, i + 1);
         const double Sm = h[(size_t)t * 5 + 3], Ap = h[(size_t)tp * 5 + 2], Smp = h[(size_t)tp * 5 + 3];
         const double hh = lambda(tp) - lambda(t);
-        row[0] = (float)(Smp / Sm);
-        row[1] = (float)(-Ap * std::expm1(-hh));
+        if (e->opt_solver_noise) {
+            const double g = -std::expm1(-2.0 * hh);      // 1 - exp(-2h) > 0: lambda increases along the chain
+            row[0] = (float)((Smp / Sm) * std::exp(-hh));
+            row[1] = (float)(Ap * g);
+            row[4] = (float)(Smp * std::sqrt(g));
+        } else {
+            row[0] = (float)(Smp / Sm);
+            row[1] = (float)(-Ap * std::expm1(-hh));
+        }
         if (e->opt_solver == 2 && i > 0 && tp != 0) row[3] = (float)(hh / (2.0 * (lambda(t) - lambda(chain_step(e, i - 1)))));
     }
     for (int t = 0; t < S; ++t) {
@@ -340,15 +351,15 @@ int run_diffuse(dr_engine* e, float* x, const float* d_noise, int B, int T, int 
     return DR_OK;
 }
 
-// order 2: the two history buffers, before anything is launched or captured (a chain that may still read them is waited for)
+// order 2: the history buffer (two halves), before anything is launched or captured (a chain that may still read them is waited for)
 int ensure_history(dr_engine* e, int B, int T, hipStream_t st) {
     if (e->opt_solver != 2) return DR_OK;
     const size_t per = (size_t)B * T * 88;
-    if (e->hist[0].fits(per) && e->hist[1].fits(per)) return DR_OK;
+    if (e->hist.fits(2 * per)) return DR_OK;
     HIPCHK(e, hipStreamSynchronize(st));
     if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
     e->hist_key.valid = false;
-    for (auto& b : e->hist) HIPCHK(e, b.ensure(per, true));
+    HIPCHK(e, e->hist.ensure(2 * per, true));
     return DR_OK;
 }
 
@@ -417,6 +428,18 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         e->opt_solver = value;
         e->hist_key.valid = false;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
+        return build_solver(e);
+    }
+    if (n == "solver_noise") {
+        // (as "solver_order": part of the chain's key, nothing is dropped; the table is rebuilt while an order is set - a
+        // chain captured under the other value is not replayed until the value, and with it the table, is back)
+        if (value != 0 && value != 1)
+            return fail(e, DR_EINVAL, "solver_noise is 0 (the deterministic solver) or 1 (its stochastic form, SDE-DPM-Solver++), got %d", value);
+        if (e->opt_solver_noise == value) return DR_OK;
+        if (e->opt_solver != 0) (void)hipDeviceSynchronize();      // a chain of the previous value may still be reading the table
+        e->opt_solver_noise = value;
+        e->hist_key.valid = false;
+        if (!e->committed || e->opt_solver == 0) return DR_OK;      // (dr_commit / "solver_order" builds it)
         return build_solver(e);
     }
     if (n == "start_step") {
@@ -808,7 +831,8 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
     key.draws = e->opt_draws; key.draw_G = e->opt_draws > 1 ? e->opt_draw_G : 0; key.fe_B = e->fe_B;
     if (NB == 2 * B) { key.g_lo = e->opt_guid.lo; key.g_hi = e->opt_guid.hi_eff(e->S); }
-    key.order = e->opt_solver; key.hist = e->opt_solver == 2 ? (const float*)e->hist[0] : nullptr;
+    key.order = e->opt_solver; key.hist = e->opt_solver == 2 ? (const float*)e->hist : nullptr;
+    key.solver_noise = e->opt_solver != 0 ? e->opt_solver_noise : 0;
     key.start = chain_step(e, i0); key.start_noise = e->opt_start_noise;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);

@@ -66,14 +66,15 @@ struct GraphKey {
     // ... and how the prediction is integrated: option "solver_order" (the update's mode, its table and the history
     // buffers' parity per node), like "draws" part of the key - setting it drops nothing
     int order = 0;
-    const float* hist = nullptr;      // the first history buffer (null: order < 2)
+    const float* hist = nullptr;      // the history buffer (null: order < 2)
+    int solver_noise = 0;             // option "solver_noise" (the effective value: 0 while order is 0), part of the key as well
     // ... and where the chain begins: options "start_step" (the effective step: the chain's first visited step when the
     // option is off) and "start_noise" (whether a diffusion node stands in front of the first step) - setting them drops nothing
     int start = -1, start_noise = 0;
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi &&
-               order == o.order && hist == o.hist && start == o.start && start_noise == o.start_noise;
+               order == o.order && hist == o.hist && solver_noise == o.solver_noise && start == o.start && start_noise == o.start_noise;
     }
 };
 
@@ -211,10 +212,13 @@ struct dr_engine {
                                         // zero), rows [S, 2 S) the same rows with c = 0 - step t as the FIRST step of a chain
                                         // (option "start_step"); a table of their own, so no row a captured chain reads moves
     drh::DevBuf<float> d_solver;        // ... on the device
-    // order 2: the previous step's prediction.  Two (B, T, 88) buffers, allocated on first use and used ping-pong (the
-    // tail kernel's row tiles recompute a quad in different blocks: the one that stores must not overwrite what the
-    // others still read); hist_par = the one the next step reads.  A captured chain bakes the parity per node.
-    drh::DevBuf<float> hist[2];
+    // option "solver_noise": 1 = the solver's stochastic form (SDE-DPM-Solver++): other rows 0 / 1 / 4, and mode 5 adds c4 z.
+    // Stored always, read only while opt_solver != 0
+    int opt_solver_noise = 0;
+    // order 2: the previous step's prediction.  One buffer of two (B, T, 88) halves, allocated on first use and used
+    // ping-pong (the tail kernel's row tiles recompute a quad in different blocks: the one that stores must not overwrite
+    // what the others still read); hist_par = the half the next step reads.  A captured chain bakes the parity per node.
+    drh::DevBuf<float> hist;
     int hist_par = 0;
     // dr_step under order 2: what the history holds - the prediction of step hist_t of a (sampler, B, T) chain
     struct { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; } hist_key;

@@ -195,10 +195,7 @@ struct UpdateArgs {
     float* x;              // (B, T, 88) in/out
     const float* x0c;      // (B, T, 88) conditional (or the only) prediction
     const float* x0u;      // unconditional prediction or null
-    union {
-        const float* noise;      // (B, T, 88) or null -> philox
-        const float* hist_prev;  // mode 5 (draws no noise): the previous step's prediction, see below
-    };
+    const float* noise;    // (B, T, 88) or null -> philox
     const float* coef;     // device pointer to this step's 5 coefficients
     int t;                 // step index
     int mode;              // coefficient family (DR_COEF_*): 0/1 x0 update, 2 eps ddpm, 3 eps ddim, 4 eps ddim2ddpm;
@@ -206,10 +203,7 @@ struct UpdateArgs {
     long n;                // B*T*88
     long per_sample;       // T*88
     float w, onepw;
-    union {
-        uint64_t seed;
-        float* hist_next;        // mode 5 (no Philox: the seed is not read): where this step's prediction goes, see below
-    };
+    uint64_t seed;
     int first_sample;
     const DynParams* dyn;  // non-null: w / onepw / seed / first_sample are read from here instead
     // Long-form windows (option "window_overlap" = O > 0; 0 = off): the B rolls are B consecutive windows of ONE
@@ -228,12 +222,19 @@ struct UpdateArgs {
     // first_sample + b % draw_n + (b / draw_n) * draw_G (draw_G = draw_n unless option "draw_stride" says otherwise).  Windows
     // (win_H > 0) carry the draw in their table word instead: win_tab is then always set.
     int draw_n, draw_G;
-    // Mode 5: the guided prediction (after the shared-frame mean) of the previous step, (B, T, 88), read only where this
-    // step's row has c != 0, and where this step's goes (null: no step follows / first order).  Two engine buffers used
-    // ping-pong - never the same one: the tail kernel's row tiles recompute a quad in different blocks.  The two pointers
-    // share the storage of `noise` and `seed` above, which mode 5 does not read: the argument block - SGPRs the tail
-    // kernel is short of (profiles/solver_kernel_resources.txt) - does not grow.
+    // Mode 5, order 2 (null: first order): the history - ONE engine buffer of two (B, T, 88) halves, n floats apart, used
+    // ping-pong.  Half hist_par holds the guided prediction (after the shared-frame mean) of the previous step, read only
+    // where this step's row has c != 0; this step's goes into the other half while t > 0 (a step follows) - never the same
+    // one: the tail kernel's row tiles recompute a quad in different blocks.  One pointer and one parity word instead of two
+    // pointers: under option "solver_noise" mode 5 reads `noise` and `seed` too, so the history can no longer share their
+    // storage, and the argument block - SGPRs the tail kernel is short of (profiles/solver_noise_kernel_resources.txt) -
+    // grows by three words instead of four.
+    float* hist;
+    int hist_par;
 };
+// (mode 5) the half the step reads / the half it writes, null where it stores nothing
+__host__ __device__ inline const float* hist_prev(const UpdateArgs& a) { return a.hist + (a.hist_par ? a.n : 0); }
+__host__ __device__ inline float* hist_next(const UpdateArgs& a) { return a.hist && a.t > 0 ? a.hist + (a.hist_par ? 0 : a.n) : nullptr; }
 // one word per window: Philox key offset of its recording (the ordinal in the batch; + draw x stride under option "draws":
 // < 65536) and index within the recording (< STACK_GROUPS)
 constexpr unsigned window_entry(unsigned rec, unsigned idx) { return (rec << 16) | idx; }

@@ -426,15 +426,15 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     u.seed = seed; u.first_sample = first_sample;
-    // option "solver_order" (the callers have refused the epsilon samplers): the solver's own row and update, no noise and
-    // no Philox - their fields hold the history pointers (kernels.h).  Order 2 reads the previous step's prediction where
-    // the row says so and leaves this step's for the next (ping-pong); order 1 neither reads nor stores.
+    // option "solver_order" (the callers have refused the epsilon samplers): the solver's own row and update.  Noise and
+    // seed are read only where the row's c4 is not 0 (option "solver_noise": the z of the DDPM updates at this step).  Order
+    // 2 reads the previous step's prediction where the row says so and leaves this step's for the next (the two halves of
+    // the history buffer, ping-pong); order 1 neither reads nor stores.
     if (e->opt_solver != 0 && family <= DR_COEF_DDIM_X0) {
         const bool hist = e->opt_solver == 2;
         // (option "start_step": the step it names is a chain's first - the copy of its row with c = 0, abi.hip: build_solver)
         u.coef = e->d_solver + ((size_t)(t == e->opt_start ? e->S : 0) + t) * 5; u.mode = 5;
-        u.hist_prev = hist ? (const float*)e->hist[e->hist_par] : nullptr;
-        u.hist_next = hist && t > 0 ? (float*)e->hist[e->hist_par ^ 1] : nullptr;
+        u.hist = hist ? (float*)e->hist : nullptr; u.hist_par = hist ? e->hist_par : 0;
         if (hist) e->hist_par ^= 1;
     }
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;

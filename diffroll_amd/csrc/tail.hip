@@ -141,7 +141,7 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
                         reinterpret_cast<float4*>(s.x_out)[i4] = v;
                         // (option "solver_order": this step's prediction for the next one, under the same guard - into the
                         // history buffer this launch does not read)
-                        if (s.u.mode == 5 && s.u.hist_next) reinterpret_cast<float4*>(s.u.hist_next)[i4] = y;
+                        if (s.u.mode == 5 && hist_next(s.u)) reinterpret_cast<float4*>(hist_next(s.u))[i4] = y;
                     }
                 }
                 DR_CHECK_LDS(XT + pl * 32 + fi, lds_off(XT), lds_off(XT) + 24u * 32u * 16u, 151);

@@ -10,7 +10,7 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
     if (i4 * 4 >= a.n) return;
     float4 y;
     reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4, &y);
-    if (a.mode == 5 && a.hist_next) reinterpret_cast<float4*>(a.hist_next)[i4] = y;      // (option "solver_order")
+    if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;      // (option "solver_order")
 }
 
 __global__ void set_dyn_kernel(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, unsigned epoch) {

@@ -87,12 +87,17 @@ DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, c
 // two values, added in the same order) - and the noise is keyed by the canvas element.
 // mode 5 (option "solver_order", x0-prediction samplers): the exponential integrator in lambda = log(sqrt_acp / sqrt_1m_acp)
 // of Lu et al. 2022 (DPM-Solver++), row [sqrt_1m_acp' / sqrt_1m_acp, -sqrt_acp' expm1(-h), sqrt_acp, c, 0] (abi.hip:
-// build_solver).  y is the guided prediction after the shared-frame mean, p the y of the previous step (a.hist_prev):
+// build_solver).  y is the guided prediction after the shared-frame mean, p the y of the previous step (hist_prev(a)):
 //   d = c != 0 ? y + c (y - p) : y      (2M; c = h / (2 h_prev), 0 = first order: p is not loaded)
 //   o = c0 x + c1 d;   t == 0: o = y / c2, the x0 samplers' own last step
-// One fp32 rounding per operation, no noise (deterministic).  The caller stores y to a.hist_next for the next step
+// One fp32 rounding per operation, no noise (deterministic).  The caller stores y to hist_next(a) for the next step
 // (update_quad hands it out): in the tail kernel several blocks recompute a quad and one of them stores.
-DR_DEVINL float4 solver_quad(const UpdateArgs& a, const long i4, const float (&y)[4]) {
+// Option "solver_noise" (SDE-DPM-Solver++, same paper): the row is [(sqrt_1m_acp' / sqrt_1m_acp) exp(-h), -sqrt_acp'
+// expm1(-2h), sqrt_acp, c, sqrt_1m_acp' sqrt(-expm1(-2h))] and o = (c0 x + c1 d) + c4 z at t > 0, z the step's noise_quad -
+// the z update_quad's DDPM modes draw at that step.  The deterministic rows have c4 = 0 exactly and take the expression
+// without the last term: the option at 0 changes no bit.
+DR_DEVINL float4 solver_quad(const UpdateArgs& a, const long i4, const float (&y)[4], const float (&x)[4], const bool noisy,
+                             const float (&z)[4]) {
 #pragma clang fp contract(off)
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c = a.coef[3];
     float o[4];
@@ -101,18 +106,41 @@ DR_DEVINL float4 solver_quad(const UpdateArgs& a, const long i4, const float (&y
         for (int e = 0; e < 4; ++e) o[e] = y[e] / c2;
         return make_float4(o[0], o[1], o[2], o[3]);
     }
-    const float4 xv = reinterpret_cast<const float4*>(a.x)[i4];
-    const float x[4] = {xv.x, xv.y, xv.z, xv.w};
     float d[4] = {y[0], y[1], y[2], y[3]};
     if (c != 0.f) {
-        const float4 pv = reinterpret_cast<const float4*>(a.hist_prev)[i4];
+        const float4 pv = reinterpret_cast<const float4*>(hist_prev(a))[i4];
         const float p[4] = {pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] = y[e] + c * (y[e] - p[e]);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = c0 * x[e] + c1 * d[e];
+    if (noisy) {
+        const float c4 = a.coef[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = o[e] + c4 * z[e];
+    }
     return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// The z of one float4 at step a.t: the quad of the injected noise, or Philox by the noise-key rule above (key_smp >= 0: the
+// window key update_quad has worked out; else the clip's).  Shared by every update that draws noise - the DDPM modes and
+// mode 5 under option "solver_noise".
+DR_DEVINL void noise_quad(const UpdateArgs& a, const long i4, const long key_smp, const long key_q, const int first_sample,
+                          const uint64_t seed, float (&z)[4]) {
+    if (a.noise) {
+        const float4 zv = reinterpret_cast<const float4*>(a.noise)[i4];
+        z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+    } else {
+        long within, sk;
+        if (key_smp >= 0) { within = key_q; sk = key_smp; }
+        else clip_key(a, i4, first_sample, within, sk);
+        uint32_t rnd[4];
+        philox4x32_10((uint32_t)within, (uint32_t)(within >> 32), (uint32_t)a.t,
+                      (uint32_t)sk, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+        box_muller(rnd[0], rnd[1], z[0], z[1]);
+        box_muller(rnd[2], rnd[3], z[2], z[3]);
+    }
 }
 
 // pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean (mode 5's history).
@@ -154,31 +182,18 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
     if (pred) *pred = make_float4(x0[0], x0[1], x0[2], x0[3]);
-    if (a.mode == 5) return solver_quad(a, i4, x0);
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];
-    // which updates draw noise at t > 0: x0 DDPM (0), eps ddpm (2), eps ddim2ddpm (4)
-    const bool noisy = (a.mode == 0 || a.mode == 2 || a.mode == 4) && a.t > 0;
+    // which updates draw noise at t > 0: x0 DDPM (0), eps ddpm (2), eps ddim2ddpm (4) - and the solver (5) where its row
+    // has c4 != 0 (option "solver_noise": a stochastic row has c4 > 0 at every t > 0 - abi.hip: build_solver)
+    const bool noisy = (a.mode == 0 || a.mode == 2 || a.mode == 4 || (a.mode == 5 && c4 != 0.f)) && a.t > 0;
     float x[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
     if (a.t > 0 || a.mode >= 2) {
         const float4 xv = reinterpret_cast<const float4*>(a.x)[i4];
         x[0] = xv.x; x[1] = xv.y; x[2] = xv.z; x[3] = xv.w;
     }
-    if (noisy) {
-        if (a.noise) {
-            const float4 zv = reinterpret_cast<const float4*>(a.noise)[i4];
-            z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-        } else {
-            long within, sk;
-            if (key_smp >= 0) { within = key_q; sk = key_smp; }
-            else clip_key(a, i4, first_sample, within, sk);
-            uint32_t rnd[4];
-            philox4x32_10((uint32_t)within, (uint32_t)(within >> 32), (uint32_t)a.t,
-                          (uint32_t)sk, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
-            box_muller(rnd[0], rnd[1], z[0], z[1]);
-            box_muller(rnd[2], rnd[3], z[2], z[3]);
-        }
-    }
+    if (noisy) noise_quad(a, i4, key_smp, key_q, first_sample, seed, z);
+    if (a.mode == 5) return solver_quad(a, i4, x0, x, noisy, z);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float y = x0[e];   // network output: x0 prediction (modes 0/1) or epsilon (modes 2-4)

@@ -24,7 +24,8 @@ import torch.nn as nn
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import check_guidance_interval, check_sampling_steps, check_solver_order, check_start, respaced_steps
+from .schedule import (check_guidance_interval, check_sampling_steps, check_solver_noise, check_solver_order, check_start,
+                       respaced_steps)
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
@@ -147,6 +148,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.solver_order = 1 / 2 integrates the x0 prediction with a multistep ODE solver (option
         # "solver_order": DPM-Solver++), the companion of sampling.steps; absent / None / 0 = the sampler's own update
         check_solver_order(sampling.get("solver_order"), sampling.type)
+        # an extension: sampling.solver_noise = 1 makes that solver stochastic (option "solver_noise": SDE-DPM-Solver++, the z's
+        # of the ddpm_x0 chain); absent / None / 0 = the deterministic solver
+        check_solver_noise(sampling.get("solver_noise"), sampling.type, sampling.get("solver_order"))
         # an extension: sampling.start_step = t / sampling.strength = s start the chain at an intermediate visited step
         # (options "start_step" / "start_noise"): refine or vary a given roll, resume a chain; absent / None = the whole chain
         check_start(sampling.get("start_step"), sampling.get("strength"), respaced_steps(timesteps, sampling.get("steps") or 0))
@@ -243,6 +247,7 @@ class ClassifierFreeDiffRoll(nn.Module):
     def engine(self) -> Engine:
         interval = self.guidance_interval()               # (a malformed one raises here: before any GPU work)
         order = self.solver_order()                       # (likewise)
+        snoise = self.solver_noise()                      # (likewise)
         start = self.start_step()                         # (likewise)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
@@ -265,6 +270,8 @@ class ClassifierFreeDiffRoll(nn.Module):
             self._engine.set_guidance_interval(*interval)
         if self._engine.solver_order != order:            # (likewise part of the key)
             self._engine.set_option("solver_order", order)
+        if self._engine.solver_noise != snoise:           # (likewise part of the key)
+            self._engine.set_option("solver_noise", snoise)
         if self._engine.start_step != start:              # (likewise part of the key)
             self._engine.set_option("start_step", start)
         return self._engine
@@ -290,6 +297,14 @@ class ClassifierFreeDiffRoll(nn.Module):
         hp = self.__dict__["hparams"]
         order = check_solver_order(hp.sampling.get("solver_order"), hp.sampling.type)
         return 0 if self.__dict__.get("_stride1") else order
+
+    def solver_noise(self) -> int:
+        """hparams.sampling.solver_noise as the engine's option takes it (0: the deterministic solver), or 0 while one of the
+        reference's single-step methods runs.  Read at every use; a bad value, a value set without solver_order or with an
+        epsilon sampler raises ValueError before any GPU work."""
+        hp = self.__dict__["hparams"]
+        value = check_solver_noise(hp.sampling.get("solver_noise"), hp.sampling.type, hp.sampling.get("solver_order"))
+        return 0 if self.__dict__.get("_stride1") else value
 
     def guidance_interval(self):
         """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain.  Read
@@ -527,7 +542,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         the n respaced steps of visited_steps() - on the device with no host round trip.  x_T (B,1,T,88); noise: None
         (on-device Philox keyed by seed, global sample index and step) or (timesteps, B, 1, T, 88) injected z's (row t
         is used at step t >= 1, also in a respaced chain).  With hparams.sampling.solver_order = 1 / 2 (option
-        "solver_order": DPM-Solver++ on the x0 prediction) the chain is deterministic: noise and seed are not used.
+        "solver_order": DPM-Solver++ on the x0 prediction) the chain is deterministic: noise and seed are not used - unless
+        hparams.sampling.solver_noise = 1 (option "solver_noise": the solver's stochastic form), which draws at every visited
+        step t >= 1 the z the ddpm_x0 chain draws there: noise and seed mean what they mean without a solver.
         Returns (roll (B,1,T',88), spec (B,n_mels,T')).
         draws = D > 1 (option "draws" of include/diffroll_amd.h): x_T (D*n,1,T,88) holds D draws of the n clips of waveform
         (n, L), draw-major (row b = draw b // n of clip b % n); the front-end and the conditioner tensors exist once per

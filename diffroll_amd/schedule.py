@@ -123,6 +123,25 @@ def check_solver_order(order, sampler: str = None) -> int:
     return order
 
 
+def check_solver_noise(value, sampler: str = None, order=None) -> int:
+    """Option "solver_noise" (include/diffroll_amd.h) as hparams.sampling.solver_noise: None / 0 / False = the deterministic
+    solver, 1 / True = its stochastic form (SDE-DPM-Solver++), which draws the z's of the ddpm_x0 chain.  `order` is the
+    configured solver_order.  Returns the option's value; any other value, or a set value while solver_order is absent / 0
+    or with a sampler that predicts epsilon, raises ValueError."""
+    if value is None:
+        return 0
+    if not isinstance(value, (bool, int)) or value not in (0, 1):
+        raise ValueError(f"solver_noise must be 0 / None (the deterministic solver) or 1 (its stochastic form), got {value!r}")
+    value = int(value)
+    if value and sampler is not None and sampler not in X0_SAMPLERS:
+        raise ValueError(f"solver_noise = 1 is the stochastic form of solver_order = 1 / 2, which integrates an x0 prediction "
+                         f"({', '.join(X0_SAMPLERS)}); '{sampler}' predicts epsilon")
+    if value and not check_solver_order(order):
+        raise ValueError(f"solver_noise = 1 is the stochastic form of solver_order = 1 / 2, but solver_order is {order!r} (the "
+                         f"sampler's own update): set solver_order too")
+    return value
+
+
 def check_start(start_step, strength, visited) -> int:
     """Options "start_step" / "start_noise" (include/diffroll_amd.h) as hparams.sampling.start_step / .strength: where a
     chain over the steps `visited` (chain order) begins.  The two keys are mutually exclusive.  strength s in (0, 1] runs

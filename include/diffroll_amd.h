@@ -437,7 +437,7 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          prediction and p that of the previous step: d = c != 0 ? y + c (y - p) : y, x' = c0 x + c1 d,
  *                          one fp32 rounding per operation; at t == 0 x' = y / c2, the x0 samplers' own last step.  The
  *                          chain is DETERMINISTIC: no noise is drawn, d_noise is ignored, and "draws" differ through x_T
- *                          only.  An epsilon sampler (DR_SAMPLER_* 6-8) with a non-zero order -> DR_EINVAL at dr_step /
+ *                          only - unless "solver_noise" is 1 (the stochastic form: see there).  An epsilon sampler (DR_SAMPLER_* 6-8) with a non-zero order -> DR_EINVAL at dr_step /
  *                          dr_sample / dr_sample_checked, naming both; any other value -> DR_EINVAL at the set.  Order 2
  *                          keeps p in two engine-owned (B, T, 88) buffers (allocated on first use).  dr_step: at the
  *                          chain's first visited step it starts a new history; at any other visited step the previous
@@ -453,6 +453,35 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          chain's key, like "draws": setting it drops nothing, and a chain captured under another value
  *                          is never replayed.  Nothing is known about the quality of either order with this model
  *                          (INTEGRATION.md 3c).
+ *   "solver_noise"     [0] 0 or 1: 1 makes the solver of "solver_order" 1 / 2 STOCHASTIC (SDE-DPM-Solver++ of the same paper,
+ *                          first order and 2M) - the second-order companion of the ddpm_x0 update for few-step chains
+ *                          ("sampling_steps").  Stored always; it takes effect only while "solver_order" is 1 or 2 (as
+ *                          "draw_stride" is inert while "draws" is 1; the epsilon samplers are refused under a non-zero
+ *                          order already).  In the notation of "solver_order" the row of a visited step t > 0 becomes
+ *                          [(Smp / Sm) exp(-h), Ap (-expm1(-2h)), A, c, Smp sqrt(-expm1(-2h))], c by the same rule; row 0
+ *                          stays [0, 0, A_0, 0, 0]; derived in double from the committed fp32 A and Sm and rounded to fp32
+ *                          once, in the same table.  The update is d = c != 0 ? y + c (y - p) : y,
+ *                          x' = (c0 x + c1 d) + c4 z at t > 0 and x' = y / c2 at t == 0, one fp32 rounding per operation.
+ *                          z is the z the DDPM-family updates draw at that step: row t of d_noise when that is given, else
+ *                          Philox keyed exactly as DR_SAMPLER_DDPM_X0 keys it - counter word 2 = the real t, sample key
+ *                          and element by clip, "draws" / "draw_stride", or recording and canvas element under
+ *                          "window_overlap" / "window_break".  So a stochastic solver chain draws exactly the z's the
+ *                          ddpm_x0 chain draws at those steps; frames shared by two windows stay bit-identical; draw d of
+ *                          clip c gets the same noise on any world size; dr_sample_checked's re-run reproduces the same
+ *                          chain; "start_noise" keeps its own, independent draw (counter word timesteps + t_s).  With
+ *                          A^2 + Sm^2 = 1 the first-order stochastic update IS the ddpm_x0 update of the derived
+ *                          "sampling_steps" row by another arithmetic route: c4^2 = Smp^2 (1 - exp(-2h)) =
+ *                          (Smp / Sm)^2 (1 - A^2 / Ap^2) = sigma^2 and c0 = sqrt(1 - Ap^2 - sigma^2) / Sm - as order 1
+ *                          without noise is ddim_x0 by another route; what the option adds is the second order.  The
+ *                          order-2 history rules of dr_step are unchanged; "start_step" resumes a first-order chain bit
+ *                          for bit, as it does without noise.  Combines with "sampling_steps", "window_overlap" /
+ *                          "window_break", "draws" / "draw_stride", "guidance_t_min" / "guidance_t_max", "start_step" /
+ *                          "start_noise", both precisions and sharding (every rank sets the same value).  0 = the
+ *                          deterministic solver, bit-identical to an engine that never set the option, in every mode.
+ *                          Any other value -> DR_EINVAL at the set.  The value is part of a captured chain's key, like
+ *                          "solver_order": setting it drops nothing, and a chain captured under another value is never
+ *                          replayed.  Nothing is known about the quality of the stochastic solver with this model: the
+ *                          one measurement is of the integrator on a Gaussian toy prior.
  *   "start_step"      [-1] t_s, -1 or 0 <= t_s < timesteps: START the reverse chain at an intermediate step.  dr_sample /
  *                          dr_sample_checked run the visited steps t <= t_s in chain order, and d_x on entry is x at step
  *                          t_s - a row of an earlier chain's trajectory (resume), or a roll diffused to t_s ("start_noise";
@@ -483,7 +512,8 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          every step's z), sample key and element as the steps' own draws take them under "draws" /
  *                          "draw_stride" / "window_overlap" / "window_break" - windows are keyed by recording and canvas
  *                          element: if x0 agrees on the frames two windows share, so does x at t_s, bit for bit.  Under
- *                          "solver_order" != 0 this is the one place that still draws.  dr_sample_checked keeps what the
+ *                          "solver_order" != 0 this is the one place that still draws (unless "solver_noise" is 1: the
+ *                          steps then draw their own z's, independent of this one).  dr_sample_checked keeps what the
  *                          caller passed - x0 - so its re-run diffuses again with the same z.  dr_step ignores the
  *                          option: it takes x at its step.  Any other value -> DR_EINVAL.  Part of a captured chain's key,
  *                          like "draws".
