@@ -7,7 +7,7 @@ import torch
 from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
 
-import guidance_ref as GR
+import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +31,7 @@ def test_checked_rerun_returns_the_per_phase_roll_of_the_same_interval():
     wav = 0.1 * torch.randn(B, T * 512, generator=g)
     x = torch.randn(B, 1, T, 88, generator=g)
     noise = torch.randn(S, B, 1, T, 88, generator=g)
-    ref = GR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, W, (4, 8))
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, w=W, interval=(4, 8))
     eng = m.engine
     eng.set_option("fused_stack", 0)
     per_phase, _ = m.sample(x, wav, noise=noise)
@@ -45,5 +45,5 @@ def test_checked_rerun_returns_the_per_phase_roll_of_the_same_interval():
     assert eng.fallbacks == 1 and eng.guidance_interval == (4, 8)
     assert eng.launch_state()["mode"] == "per_phase"
     assert torch.equal(roll, per_phase)
-    full = GR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, W, (0, S - 1))
+    full = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, w=W, interval=(0, S - 1))
     assert maxdiff(roll.cpu(), full) > 1e-5                    # ... not the fully guided chain: it would miss the tolerance

@@ -1,5 +1,5 @@
 """Option "solver_order" on the MI355X (hparams.sampling.solver_order): the HIP chain under the first-order exponential
-integrator and DPM-Solver++ (2M) against the CPU restatement of tests/dpmpp_ref.py - four x0 samplers, n in {2, 4, 20},
+integrator and DPM-Solver++ (2M) against the CPU restatement of tests/chain_ref.py - four x0 samplers, n in {2, 4, 20},
 both precisions - order 1 against the ddim_x0 respaced chain, the fused path at the geometry where the tail kernel's row
 tiles recompute the update (graph = eager = per-phase, no history across replays), dr_step over the visited steps, long-form
 windows, draws, a guidance interval, and order 0 as the engine that never set the option."""
@@ -10,8 +10,7 @@ from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
 from test_gpu_respaced import HOP, S, agree, hp_of, inputs
 
-import dpmpp_ref as DR
-import respaced_ref as RR
+import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +66,7 @@ def test_chain_vs_restatement(sampler):
     for order in (1, 2):
         for n in (2, 4, 20):
             m.hparams.sampling.steps, m.hparams.sampling.solver_order = n, order
-            ref = DR.sample_chain(p, hp, sampler, x, spec, n, order, w=w)
+            ref = CR.sample_chain(p, hp, sampler, x, spec, None, n, order=order, w=w)
             roll, _ = m.sample(x, wav, seed=3)
             ok, d = agree(roll, ref)
             print(f"\n{sampler} order {order} n {n}: max |d| {d:.3e}")
@@ -80,7 +79,7 @@ def test_split_bf16_vs_restatement():
     p = R.synthetic_params(hp, seed=72)
     m = solver_model(hp, p, "cfdg_ddpm_x0", 20, 2, precision="bf16x3")
     wav, x, _ = inputs(2, 40, 73)
-    ref = DR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), 20, 2, w=0.5)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), None, 20, order=2, w=0.5)
     roll, _ = m.sample(x, wav)
     ok, d = agree(roll, ref)
     print(f"\nbf16x3 order 2 n 20: max |d| {d:.3e}")
@@ -142,7 +141,7 @@ def test_fused_path_graph_eager_per_phase_and_no_history_across_replays():
     assert torch.equal(g2, fresh) and not torch.equal(g2, g)
     # the restatement of the first and the last clip (clips are independent: the others add CPU time, not coverage)
     sel = [0, 15]
-    ref = DR.sample_chain(p, hp, "cfdg_ddpm_x0", x[sel], R.frontend(wav[sel], hp, 125), 20, 2, w=0.5)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x[sel], R.frontend(wav[sel], hp, 125), None, 20, order=2, w=0.5)
     ok, d = agree(g[sel], ref)
     print(f"\nfused path order 2 n 20: max |d| {d:.3e}")
     assert ok, d
@@ -156,7 +155,7 @@ def test_dr_step_over_the_visited_steps_and_out_of_sequence():
     traj, _ = m.sample_trajectory(x, wav)
     roll, _ = m.sample(x, wav)
     assert traj.shape == (20,) + tuple(roll.shape) and torch.equal(traj[-1], roll)
-    ref = DR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), 20, 2, w=0.5, trajectory=True)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), None, 20, order=2, w=0.5, trajectory=True)
     d = maxdiff(traj.cpu(), ref)
     print(f"\ntrajectory order 2 n 20: max |d| {d:.3e}")
     assert d <= 1e-5
@@ -202,7 +201,7 @@ def test_sample_long_vs_restatement():
     x_T = torch.randn(1, 1, plan.T_c, 88, generator=g)
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    ref = DR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, 20, 2, w=0.5, plan=plan)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, None, 20, order=2, w=0.5, plan=plan)
     win = run_windows(m, plan, wav, x_T, None, seed=4, recording=1)
     assert_shared_frames_agree(win, plan)
     ok, d = agree(win, ref[:, 0])
@@ -232,12 +231,12 @@ def test_guidance_interval_vs_restatement():
     m.hparams.sampling.guidance_interval = [60, 140]
     wav, x, _ = inputs(2, 40, 86)
     spec = R.frontend(wav, hp, 40)
-    ref = DR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, 20, 2, w=0.5, guidance=(60, 140))
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, None, 20, order=2, w=0.5, interval=(60, 140))
     roll, _ = m.sample(x, wav)
     ok, d = agree(roll, ref)
     print(f"\nguidance [60, 140] order 2 n 20: max |d| {d:.3e}")
     assert ok, d
-    whole = DR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, 20, 2, w=0.5)
+    whole = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, None, 20, order=2, w=0.5)
     assert not agree(roll, whole)[0]                  # (the interval matters at this weight)
 
 

@@ -1,6 +1,6 @@
 """Guidance interval on the MI355X (options "guidance_t_min" / "guidance_t_max", hparams.sampling.guidance_interval):
 the HIP chain that runs the unconditional evaluation only at the steps lo <= t <= hi, against the CPU restatement of
-tests/guidance_ref.py (which evaluates both branches at every step) - the three guiding samplers, intervals with both
+tests/chain_ref.py (which evaluates both branches at every step) - the three guiding samplers, intervals with both
 transitions inside the chain / ending guided / starting guided, injected and Philox noise, split-bf16 once - and the bit
 identities the options promise: defaults = [0, S - 1] = an engine that never heard of them; fused stack + tail kernel across
 both transitions = per-phase launches = a dr_step loop that passes w or 0 itself; captured = eager under changing intervals;
@@ -19,8 +19,7 @@ from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
 from tuning_pins import pinned
 
-import guidance_ref as GR
-import respaced_ref as RR
+import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -127,9 +126,9 @@ def test_chain_vs_restatement(sampler, interval):
     m.hparams.sampling.guidance_interval = list(interval)
     wav, x, noise = inputs(B, T, 71)
     spec = R.frontend(wav, hp, T, inpainting_t=it)
-    zp = RR.philox_noise(9, 0, S, B, T)
+    zp = CR.philox_noise(9, 0, S, B, T)
     for z, kw in ((noise, dict(noise=noise)), (zp, dict(seed=9))):
-        ref = GR.sample_chain(p, hp, sampler, x, spec, z, 0, W, interval)
+        ref = CR.sample_chain(p, hp, sampler, x, spec, z, 0, w=W, interval=interval)
         roll, _ = m.sample(x, wav, **kw)
         assert m.engine.guidance_interval == interval
         ok, d = agree(roll, ref)
@@ -137,7 +136,7 @@ def test_chain_vs_restatement(sampler, interval):
         assert ok, (sampler, interval, "injected" if "noise" in kw else "philox", d)
     # the interval matters: the fully guided chain is a roll that this comparison tells from the interval's (with few late
     # steps unguided the two end close together - [0, 5] guides the last six steps - so the check is the rule itself)
-    full = RR.sample_chain(p, hp, sampler, x, spec, zp, 0, w=W)
+    full = CR.sample_chain(p, hp, sampler, x, spec, zp, 0, w=W)
     assert not agree(full, ref)[0], maxdiff(full, ref)
 
 
@@ -145,7 +144,7 @@ def test_split_bf16_vs_restatement():
     hp, p, m, _ = model_of("cfdg_ddpm_x0", precision="bf16x3")
     m.hparams.sampling.guidance_interval = [4, 8]
     wav, x, noise = inputs(B, T, 72)
-    ref = GR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, W, (4, 8))
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, w=W, interval=(4, 8))
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, ref)
     print(f"\nbf16x3 [4, 8]: max |d| = {d:.3g}")
@@ -249,7 +248,7 @@ def test_with_sampling_steps_vs_restatement():
     m.hparams.sampling.steps = 6
     m.hparams.sampling.guidance_interval = [4, 8]
     wav, x, noise = inputs(B, T, 76)
-    ref = GR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 6, W, (4, 8))
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 6, w=W, interval=(4, 8))
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, ref)
     assert ok, d
@@ -274,7 +273,7 @@ def test_with_window_overlap_vs_restatement():
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     zw = longform.gather_windows(noise.reshape(S, plan.T_c, 88), plan).unsqueeze(2)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    ref = GR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, zw, 0, W, (4, 8), plan=plan)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, zw, 0, w=W, interval=(4, 8), plan=plan)
     for use_graph in (True, False):
         win = run_windows(m, plan, wav, x_T, noise, use_graph=use_graph)
         assert_shared_frames_agree(win, plan)
@@ -292,7 +291,7 @@ def test_with_draws_equals_the_tiled_batch():
         ref, _ = m.sample(x, wav.repeat(2, 1), **kw)
         assert torch.equal(got, ref)
         assert not torch.equal(got[0], got[B])
-    want = GR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav.repeat(2, 1), hp, T), noise, 0, W, (4, 8))
+    want = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav.repeat(2, 1), hp, T), noise, 0, w=W, interval=(4, 8))
     got, _ = m.sample(x, wav, draws=2, noise=noise)
     ok, d = agree(got, want)
     assert ok, d
@@ -338,7 +337,7 @@ def test_full_depth_across_both_transitions():
     hp, p, m, _ = model_of("cfdg_ddpm_x0", hp=hp, seed=3)
     m.hparams.sampling.guidance_interval = [4, 8]
     wav, x, noise = inputs(B, T, 80)
-    ref = GR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, W, (4, 8))
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, T), noise, 0, w=W, interval=(4, 8))
     eng = m.engine
     eng.set_option("fused_stack", 2)
     try:

@@ -12,7 +12,7 @@ from oracle import diffroll_ref as R
 from oracle import philox
 from test_gpu_parity import make_model, maxdiff
 
-import respaced_ref as RR
+import chain_ref as CR
 
 from diffroll_amd import longform
 
@@ -32,7 +32,7 @@ def hp_of(layers=15, k=9, steps=4, channels=None):
 
 def oracle_long(p, hp, sampler, plan, wav, x_T, noise, w):
     """The joint chain on the CPU: windows of the canvas x_T / noise, one front-end per window crop, and the chain loop of
-    tests/respaced_ref.py over every step - the guided prediction of each window, the mean on shared frames, the posterior
+    tests/chain_ref.py over every step - the guided prediction of each window, the mean on shared frames, the posterior
     update.  Returns windows (n, 1, T, 88)."""
     S = int(hp["timesteps"])
     x = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
@@ -40,7 +40,7 @@ def oracle_long(p, hp, sampler, plan, wav, x_T, noise, w):
     spec = None
     if sampler != "generation_ddpm_x0":
         spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    return RR.sample_chain(p, hp, sampler, x, spec, zs, 0, w, plan=plan)
+    return CR.sample_chain(p, hp, sampler, x, spec, zs, 0, w=w, plan=plan)
 
 
 def run_windows(m, plan, wav, x_T, noise, seed=0, recording=0, use_graph=True):

@@ -1,5 +1,5 @@
 """Respaced sampling on the MI355X (option "sampling_steps", hparams.sampling.steps): the HIP chain on n of the S steps
-against the CPU restatement of tests/respaced_ref.py - one sampler per coefficient family, injected and Philox noise,
+against the CPU restatement of tests/chain_ref.py - one sampler per coefficient family, injected and Philox noise,
 n in {2, 20, 50}, a full-depth BASELINE config 2 guided batch, long-form windows, the trained proxy - and the bit
 identities the option promises (n = S is the full chain; graph = eager; fused stack + tail = per-phase; dr_step over the
 visited steps = dr_sample)."""
@@ -11,7 +11,7 @@ import torch
 from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
 
-import respaced_ref as RR
+import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +50,7 @@ def test_option_is_public_and_validated():
     m = make_model(hp, R.synthetic_params(hp, seed=1), sampler="generation_ddpm_x0")
     eng = m.engine
     eng.set_option("sampling_steps", 50)             # DR_ENAME (-> ValueError) before the option existed
-    assert eng.sampling_steps == 50 and eng.visited_steps() == RR.visited(S, 50)
+    assert eng.sampling_steps == 50 and eng.visited_steps() == CR.visited(S, 50)
     for bad in (1, -1, S + 1):
         with pytest.raises(ValueError):
             eng.set_option("sampling_steps", bad)
@@ -77,11 +77,11 @@ def test_respaced_chain_vs_restatement(sampler):
     wav, x, noise = inputs(B, Tn, 61)
     spec = R.frontend(wav, hp, Tn)
     w = 0.5 if sampler.startswith("cfdg") else 0.0
-    zp = RR.philox_noise(9, 0, S, B, Tn)
+    zp = CR.philox_noise(9, 0, S, B, Tn)
     for n in (2, 20, 50):
         m.hparams.sampling.steps = n
         for z, kw in ((noise, dict(noise=noise)), (zp, dict(seed=9))):
-            ref = RR.sample_chain(p, hp, sampler, x, spec, z, n, w=w)
+            ref = CR.sample_chain(p, hp, sampler, x, spec, z, n, w=w)
             roll, _ = m.sample(x, wav, **kw)
             ok, d = agree(roll, ref)
             assert ok, (n, "injected" if "noise" in kw else "philox", d)
@@ -93,7 +93,7 @@ def test_respaced_split_bf16_vs_restatement():
     m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5, precision="bf16x3")
     m.hparams.sampling.steps = 20
     wav, x, noise = inputs(2, 40, 63)
-    ref = RR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, w=0.5)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, w=0.5)
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, ref)
     assert ok, d
@@ -106,7 +106,7 @@ def test_full_depth_config2_guided_batch_at_50_steps():
     m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5)
     m.hparams.sampling.steps = 50
     wav, x, noise = inputs(2, 125, 64)
-    ref = RR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 125), noise, 50, w=0.5)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 125), noise, 50, w=0.5)
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, ref)
     assert ok, d
@@ -166,7 +166,7 @@ def test_dr_step_over_the_visited_steps_equals_dr_sample():
     traj, _ = m.sample_trajectory(x, wav, noise=noise)
     roll, _ = m.sample(x, wav, noise=noise)
     assert traj.shape == (20,) + tuple(roll.shape) and torch.equal(traj[-1], roll)
-    ref = RR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, w=0.5, trajectory=True)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, w=0.5, trajectory=True)
     assert maxdiff(traj.cpu(), ref) <= ATOL
     traj, _ = m.sample_trajectory(x, wav, seed=4, first_sample=1)
     roll, _ = m.sample(x, wav, seed=4, first_sample=1)
@@ -195,10 +195,10 @@ def test_sample_long_at_50_steps_vs_restatement():
     seed, rec = 21, 2
     z = {t: longform.gather_windows(torch.from_numpy(philox.step_noise(seed, rec, 1, plan.T_c * 88, t)).reshape(plan.T_c, 88),
                                     plan).unsqueeze(1)
-         for t in RR.visited(S, 50) if t > 0}
+         for t in CR.visited(S, 50) if t > 0}
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    ref = RR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, z, 50, w=0.5, plan=plan)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, z, 50, w=0.5, plan=plan)
     win = run_windows(m, plan, wav, x_T, None, seed=seed, recording=rec)
     assert_shared_frames_agree(win, plan)
     ok, d = agree(win, ref[:, 0])
@@ -221,7 +221,7 @@ def test_trained_proxy_thresholded_roll(golden_dir, n):
     wav, label = torch.from_numpy(gd["wav"]), torch.from_numpy(gd["label"])
     w = float(gd["w"])
     m = ClassifierFreeDiffRoll.load_from_checkpoint(_ckpt_path(golden_dir), sampling={"type": "cfdg_ddpm_x0", "w": w, "steps": n})
-    ref = RR.sample_chain(p, hp, "cfdg_ddpm_x0", x_T, R.frontend(wav, hp, x_T.shape[2]), noise, n, w=w)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x_T, R.frontend(wav, hp, x_T.shape[2]), noise, n, w=w)
     roll, _ = m.sample(x_T, wav, noise=noise)
     thr = float(gd["frame_threshold"])
     assert torch.equal(roll.cpu() > thr, ref > thr)

@@ -1,5 +1,5 @@
 """Option "solver_noise" on the MI355X (hparams.sampling.solver_noise): the HIP chain under the stochastic first-order
-solver and stochastic DPM-Solver++ (2M) against the CPU restatement of tests/solver_noise_ref.py - four x0 samplers,
+solver and stochastic DPM-Solver++ (2M) against the CPU restatement of tests/chain_ref.py - four x0 samplers,
 n in {2, 4, 20}, injected noise and the replayed Philox draws, both precisions - order 1 against the ddpm_x0 respaced chain,
 the fused path at the geometry where the tail kernel's row tiles recompute the update (graph = eager = per-phase, neither
 seed nor history across replays), seeds, long-form windows, draws, a guidance interval, a resumed chain, dr_step over the
@@ -11,8 +11,7 @@ from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
 from test_gpu_respaced import HOP, S, agree, hp_of, inputs
 
-import respaced_ref as RR
-import solver_noise_ref as SN
+import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -66,12 +65,12 @@ def test_chain_vs_restatement(sampler):
     spec = R.frontend(wav, hp, Tn)
     w = 0.5 if sampler.startswith("cfdg") else 0.0
     m = noisy_model(hp, p, sampler, 2, 1)
-    zp = RR.philox_noise(9, 0, S, B, Tn)
+    zp = CR.philox_noise(9, 0, S, B, Tn)
     for order in (1, 2):
         for n in (2, 4, 20):
             m.hparams.sampling.steps, m.hparams.sampling.solver_order = n, order
             for z, kw in ((noise, dict(noise=noise)), (zp, dict(seed=9))):
-                ref = SN.sample_chain(p, hp, sampler, x, spec, z, n, order, w=w)
+                ref = CR.sample_chain(p, hp, sampler, x, spec, z, n, order=order, solver_noise=1, w=w)
                 roll, _ = m.sample(x, wav, **kw)
                 ok, d = agree(roll, ref)
                 print(f"\n{sampler} order {order} n {n} {'injected' if 'noise' in kw else 'philox'}: max |d| {d:.3e}")
@@ -84,7 +83,7 @@ def test_split_bf16_vs_restatement():
     p = R.synthetic_params(hp, seed=72)
     m = noisy_model(hp, p, "cfdg_ddpm_x0", 20, 2, precision="bf16x3")
     wav, x, noise = inputs(2, 40, 73)
-    ref = SN.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, 2, w=0.5)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, order=2, solver_noise=1, w=0.5)
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, ref)
     print(f"\nbf16x3 order 2 n 20: max |d| {d:.3e}")
@@ -149,8 +148,8 @@ def test_fused_path_graph_eager_per_phase_and_nothing_across_replays():
     assert torch.equal(g2, fresh) and not torch.equal(g2, g)
     # the restatement of the first and the last clip (clips are independent: the others add CPU time, not coverage)
     sel = [0, 15]
-    z = SN.philox_rows(5, sel, S, 20, 125)
-    ref = SN.sample_chain(p, hp, "cfdg_ddpm_x0", x[sel], R.frontend(wav[sel], hp, 125), z, 20, 2, w=0.5)
+    z = CR.philox_rows(5, sel, S, 20, 125)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x[sel], R.frontend(wav[sel], hp, 125), z, 20, order=2, solver_noise=1, w=0.5)
     ok, d = agree(g[sel], ref)
     print(f"\nfused path stochastic order 2 n 20: max |d| {d:.3e}")
     assert ok, d
@@ -215,10 +214,10 @@ def test_sample_long_vs_restatement():
     seed, rec = 21, 2
     z = {t: longform.gather_windows(torch.from_numpy(philox.step_noise(seed, rec, 1, plan.T_c * 88, t)).reshape(plan.T_c, 88),
                                     plan).unsqueeze(1)
-         for t in RR.visited(S, 20) if t > 0}
+         for t in CR.visited(S, 20) if t > 0}
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    ref = SN.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, z, 20, 2, w=0.5, plan=plan)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, z, 20, order=2, solver_noise=1, w=0.5, plan=plan)
     win = run_windows(m, plan, wav, x_T, None, seed=seed, recording=rec)
     assert_shared_frames_agree(win, plan)
     ok, d = agree(win, ref[:, 0])
@@ -248,12 +247,12 @@ def test_guidance_interval_vs_restatement():
     m.hparams.sampling.guidance_interval = [60, 140]
     wav, x, noise = inputs(2, 40, 86)
     spec = R.frontend(wav, hp, 40)
-    ref = SN.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, 20, 2, w=0.5, guidance=(60, 140))
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, 20, order=2, solver_noise=1, w=0.5, interval=(60, 140))
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, ref)
     print(f"\nguidance [60, 140] stochastic order 2 n 20: max |d| {d:.3e}")
     assert ok, d
-    whole = SN.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, 20, 2, w=0.5)
+    whole = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, 20, order=2, solver_noise=1, w=0.5)
     assert not agree(roll, whole)[0]                  # (the interval matters at this weight)
 
 
@@ -284,7 +283,7 @@ def test_dr_step_over_the_visited_steps_ends_where_sample_ends():
     traj, _ = m.sample_trajectory(x, wav, noise=noise)
     roll, _ = m.sample(x, wav, noise=noise)
     assert traj.shape == (20,) + tuple(roll.shape) and torch.equal(traj[-1], roll)
-    ref = SN.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, 2, w=0.5, trajectory=True)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), noise, 20, order=2, solver_noise=1, w=0.5, trajectory=True)
     d = maxdiff(traj.cpu(), ref)
     print(f"\ntrajectory stochastic order 2 n 20: max |d| {d:.3e}")
     assert d <= 1e-5

@@ -12,8 +12,7 @@ from oracle import diffroll_ref as R
 from test_gpu_parity import make_model, maxdiff
 from test_gpu_respaced import ATOL, HOP, S, agree, hp_of, inputs
 
-import respaced_ref as RR
-import start_ref as SR
+import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
@@ -140,10 +139,10 @@ def test_start_noise_with_philox_vs_the_replayed_draws(seed, first):
     m = started(make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5), 105, 20)
     wav, _, _ = inputs(B, TN, 96)
     x0 = rolls(B, TN, 97)
-    z = SR.diffusion_noise(seed, first, S, B, TN, 105)
+    z = CR.diffusion_noise(seed, first, S, B, TN, 105)
     assert abs(float(z.std()) - 1.0) < 0.05 and abs(float(z.mean())) < 0.05
-    assert not torch.equal(z, torch.from_numpy(RR.philox.step_noise(seed, first, B, TN * 88, 105).reshape(B, 1, TN, 88)))
-    x = SR.diffuse(hp, x0, 105, z)
+    assert not torch.equal(z, torch.from_numpy(CR.philox.step_noise(seed, first, B, TN * 88, 105).reshape(B, 1, TN, 88)))
+    x = CR.diffuse(hp, x0, 105, z)
     for graph in (True, False):
         got, _ = m.sample(None, wav, seed=seed, first_sample=first, init=x0, use_graph=graph)
         want, _ = m.sample(x, wav, seed=seed, first_sample=first, use_graph=graph)
@@ -240,10 +239,10 @@ def test_long_form_refinement():
     assert m.engine.window_overlap == 0 and m.engine.start_noise == 0 and m.engine.start_step == t_s
     # the restatement: one canvas draw per recording for the diffusion and for each step run
     x0w = longform.gather_windows(canvas.reshape(plan.T_c, 88), plan).unsqueeze(1)
-    x = SR.diffuse(hp, x0w, t_s, SR.window_noise(seed, rec, S, plan, t_s))
-    zs = {t: SR.window_noise(seed, rec, 0, plan, t) for t in visited[10:] if t > 0}
+    x = CR.diffuse(hp, x0w, t_s, CR.window_noise(seed, rec, S, plan, t_s))
+    zs = {t: CR.window_noise(seed, rec, 0, plan, t) for t in visited[10:] if t > 0}
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    ref = SR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, zs, 20, t_s, w=0.5, plan=plan)
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, zs, 20, start=t_s, w=0.5, plan=plan)
     ok, d = agree(win, ref[:, 0])
     print(f"\nlong-form strength 0.5 n 20: max |d| {d:.3e}")
     assert ok, d
@@ -286,8 +285,9 @@ def test_solver_order_2_started_chain_and_dr_step():
     m.hparams.sampling.start_step = t_s
     wav, x, _ = inputs(B, TN, 86)
     spec = R.frontend(wav, hp, TN)
-    ref = SR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, None, 20, t_s, w=0.5, order=2, trajectory=True)
-    assert SR.rows_of(hp, "cfdg_ddpm_x0", 20, 2, t_s)[t_s][3] == 0 and SR.rows_of(hp, "cfdg_ddpm_x0", 20, 2, -1)[t_s][3] != 0
+    ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, None, 20, start=t_s, w=0.5, order=2, trajectory=True)
+    assert CR.chain_rows(hp, "cfdg_ddpm_x0", 20, order=2, start=t_s)[t_s][3] == 0
+    assert CR.chain_rows(hp, "cfdg_ddpm_x0", 20, order=2)[t_s][3] != 0
     for graph in (True, False):
         roll, _ = m.sample(x, wav, use_graph=graph)
         ok, d = agree(roll, ref[-1])
@@ -299,7 +299,7 @@ def test_solver_order_2_started_chain_and_dr_step():
     print(f"trajectory order 2 from {t_s}: max |d| {d:.3e}")
     assert d <= ATOL
     # the whole chain's step at t_s is second order: the started one is another number
-    whole = SR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, None, 20, t_s, w=0.5, order=1, trajectory=True)
+    whole = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, None, 20, start=t_s, w=0.5, order=1, trajectory=True)
     assert torch.equal(whole[0], ref[0]) and not torch.equal(whole[1], ref[1])
     eng = m.engine
     xb = x.squeeze(1).to(eng.device).contiguous()

@@ -1,6 +1,6 @@
 """Guidance interval (options "guidance_t_min" / "guidance_t_max", include/diffroll_amd.h) without a GPU: the options'
 names and value rules, the planner's per-step evaluation shapes (csrc/launch_plan.h compiled without HIP, as
-tests/test_launch_plan_cpu.py does), the restatement of tests/guidance_ref.py against tests/respaced_ref.py, the facade's
+tests/test_launch_plan_cpu.py does), the restatement of tests/chain_ref.py with an interval against itself without one, the facade's
 hparams.sampling.guidance_interval and the CLI's task.sampling.guidance_interval."""
 import os
 import re
@@ -12,8 +12,7 @@ import torch
 
 from oracle import diffroll_ref as R
 
-import guidance_ref as GR
-import respaced_ref as RR
+import chain_ref as CR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -127,7 +126,7 @@ def expected(steps, lo, hi):
 
 @pytest.mark.parametrize("n", [0, 6])
 def test_planner_sequence_over_an_interval(driver, n):
-    steps = RR.visited(S12, n)
+    steps = CR.visited(S12, n)
     if n == 6:
         assert steps == [11, 9, 7, 4, 2, 0]
     got = shapes(driver, steps, 4, 8)
@@ -144,7 +143,7 @@ def test_planner_sequence_over_an_interval(driver, n):
 def test_defaults_reproduce_todays_plan(driver, n):
     """Defaults: every step of a guiding sampler is the 2B dual step (w != 0) or the B conditional step (w == 0) - the
     rule run_step had; [0, S - 1] is the defaults field for field; the samplers that do not guide keep their shape."""
-    steps = RR.visited(S12, n)
+    steps = CR.visited(S12, n)
     nxt = lambda row: [row if t >= 0 else (0, 0, 0) for t in steps[1:] + [-1]]
     dflt = shapes(driver, steps, 0, -1)
     assert dflt == [(2 * B, B, 1) + m for m in nxt((2 * B, B, 1))]
@@ -174,14 +173,14 @@ def _reduced():
 def test_restatement_whole_chain_and_zero_weight(sampler):
     hp, p, x, spec, noise = _reduced()
     for n in (0, 6):
-        full = RR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.5)
-        assert torch.equal(GR.sample_chain(p, hp, sampler, x, spec, noise, n, 0.5, (0, S12 - 1)), full)
-        plain = RR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.0)
-        assert torch.equal(GR.sample_chain(p, hp, sampler, x, spec, noise, n, 0.0, (4, 8)), plain)
+        full = CR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.5)
+        assert torch.equal(CR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.5, interval=(0, S12 - 1)), full)
+        plain = CR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.0)
+        assert torch.equal(CR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.0, interval=(4, 8)), plain)
         # ... which is the chain of the conditional evaluation alone
-        alone = RR.sample_chain(p, hp, "ddpm_x0" if sampler == "cfdg_ddpm_x0" else "ddim_x0", x, spec, noise, n)
+        alone = CR.sample_chain(p, hp, "ddpm_x0" if sampler == "cfdg_ddpm_x0" else "ddim_x0", x, spec, noise, n)
         assert torch.equal(plain, alone)
-        mixed = GR.sample_chain(p, hp, sampler, x, spec, noise, n, 0.5, (4, 8))
+        mixed = CR.sample_chain(p, hp, sampler, x, spec, noise, n, w=0.5, interval=(4, 8))
         assert not torch.equal(mixed, full) and not torch.equal(mixed, plain)
 
 

@@ -5,7 +5,7 @@ import pytest
 
 from oracle import diffroll_ref as R
 
-import respaced_ref as RR
+import chain_ref as CR
 
 
 @pytest.mark.parametrize("S", [2, 3, 8, 50, 199, 200, 1000])
@@ -15,7 +15,7 @@ def test_visited_steps_rule(S):
     assert respaced_steps(S, 2) == [S - 1, 0]
     for n in range(2, min(S, 60) + 1):
         st = respaced_steps(S, n)
-        assert st == RR.visited(S, n)
+        assert st == CR.visited(S, n)
         assert len(st) == n and st[0] == S - 1 and st[-1] == 0
         assert all(a > b for a, b in zip(st, st[1:])), (S, n, st)
         # linspace(0, S - 1, n) rounded half up
@@ -39,12 +39,12 @@ def test_derived_rows_at_stride_one_restate_the_committed_rows():
     a few ulp where they are well conditioned, and up to 4.3e-4 relative (2.6e-6 absolute) near t = 1, where
     1 - (A / Ap)^2 = beta_t cancels."""
     hp = dict(R.DEFAULT_HP)
-    tab = RR.committed(hp)
+    tab = CR.committed(hp)
     S = int(hp["timesteps"])
     exact = [(f, k) for f in range(5) for k in range(5)
              if not ((f in (0, 4) and k in (1, 4)) or (f == 1 and k == 1) or (f == 2 and k in (0, 1, 3)))]
     for t in range(1, S):
-        d = RR.derived_rows(tab[0, t, 2], tab[0, t - 1, 2], tab[0, t, 3], tab[0, t - 1, 3]).astype(np.float64)
+        d = CR.derived_rows(tab[0, t, 2], tab[0, t - 1, 2], tab[0, t, 3], tab[0, t - 1, 3]).astype(np.float64)
         c = tab[:, t, :].astype(np.float64)
         for f, k in exact:
             assert d[f, k] == c[f, k], (t, f, k)
@@ -58,10 +58,10 @@ def test_derived_rows_at_stride_one_restate_the_committed_rows():
 
 def test_respaced_rows_keep_committed_rows_where_the_stride_is_one():
     hp = dict(R.DEFAULT_HP)
-    tab = RR.committed(hp)
+    tab = CR.committed(hp)
     for n in (2, 20, 50, 100, 150, 200):
-        st = RR.visited(200, n)
-        rows = RR.rows_for(tab, st)
+        st = CR.visited(200, n)
+        rows = CR.rows_for(tab, st)
         for i, t in enumerate(st):
             if t == 0 or st[i + 1] == t - 1:
                 assert np.array_equal(rows[t], tab[:, t, :])
@@ -89,9 +89,9 @@ def test_facade_hparams_sampling_steps():
     assert m.sampling_steps() == 0
     m = _model(sampling={"type": "ddim", "steps": 50})
     assert m.hparams.sampling.steps == 50 and m.sampling_steps() == 50
-    assert m.visited_steps() == RR.visited(200, 50)
+    assert m.visited_steps() == CR.visited(200, 50)
     m.hparams.sampling.steps = 20                     # read at every use, like the other hparams.sampling keys
-    assert m.visited_steps() == RR.visited(200, 20)
+    assert m.visited_steps() == CR.visited(200, 20)
     assert _model(sampling={"type": "ddim", "steps": 200}).visited_steps() == list(range(199, -1, -1))
     for bad in (1, 201, -3, 2.0, "50"):
         with pytest.raises(ValueError):

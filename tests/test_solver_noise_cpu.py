@@ -1,4 +1,4 @@
-"""Option "solver_noise" (include/diffroll_amd.h) without a GPU: the rows of tests/solver_noise_ref.py, its first order
+"""Option "solver_noise" (include/diffroll_amd.h) without a GPU: the rows of tests/chain_ref.py, its first order
 against the ddpm_x0 respaced update, what the second order buys on a Gaussian prior (exact covariance propagation in
 float64), the update's expression order, and the Python surface (check_solver_noise, hparams.sampling.solver_noise, the CLI,
 the checkpoint override)."""
@@ -9,9 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-import dpmpp_ref as DR
-import respaced_ref as RR
-import solver_noise_ref as SN
+import chain_ref as CR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = 200
@@ -36,17 +34,17 @@ def schedule64_exact():
 @pytest.mark.parametrize("order", [1, 2])
 def test_rows(n, order):
     hp = hp200()
-    steps = RR.visited(S, n)
-    AS = DR.scalars(hp)
+    steps = CR.visited(S, n)
+    AS = CR.scalars(hp)
     lam = np.log(AS[:, 0] / AS[:, 1])
-    rows, det = SN.rows(hp, n, order), DR.rows(hp, n, order)
+    rows, det = CR.solver_rows(hp, n, order, 1), CR.solver_rows(hp, n, order)
     assert set(rows) == set(steps)
     for i, t in enumerate(steps):
         r = rows[t]
         assert r.dtype == np.float32 and r.shape == (5,)
         assert r[3] == det[t][3]                      # c: today's rule, exactly
         if t == 0:
-            assert np.array_equal(r, np.array([0, 0, RR.committed(hp)[0, 0, 2], 0, 0], dtype=np.float32))
+            assert np.array_equal(r, np.array([0, 0, CR.committed(hp)[0, 0, 2], 0, 0], dtype=np.float32))
             continue
         (A, Sm), (Ap, Smp) = AS[t], AS[steps[i + 1]]
         h = lam[steps[i + 1]] - lam[t]
@@ -54,7 +52,7 @@ def test_rows(n, order):
         assert np.array_equal(r, want.astype(np.float32)), (n, t)
         assert r[4] > 0 and r[0] > 0 and r[1] > 0, (n, t)
     # the option at 0: the deterministic rows
-    off = SN.rows(hp, n, order, noise=0)
+    off = CR.solver_rows(hp, n, order, noise=0)
     assert all(np.array_equal(off[t], det[t]) for t in steps)
 
 
@@ -64,8 +62,8 @@ def test_first_order_is_the_ddpm_x0_update(n):
     - the derived DR_COEF_DDPM_X0 row of the "sampling_steps" entry - on the schedule evaluated in float64, where
     A^2 + Sm^2 = 1: sigma^2 = Smp^2 (1 - exp(-2h)) and sqrt(1 - Ap^2 - sigma^2) / Sm = (Smp / Sm) exp(-h)."""
     AS = schedule64_exact()
-    steps = RR.visited(S, n)
-    rows = SN.rows64(AS, steps, 1)
+    steps = CR.visited(S, n)
+    rows = CR.solver_rows64(AS, steps, 1, 1)
     g = np.random.default_rng(n)
     worst = 0.0
     for i, t in enumerate(steps):
@@ -86,9 +84,9 @@ def test_first_order_is_the_ddpm_x0_update(n):
 
 # ---------------------------------------------------------------------------------------------- 2. what order 2 buys
 def variance_errors(n, s2):
-    AS = DR.scalars(hp200())
-    steps = RR.visited(S, n)
-    return [SN.variance_error(AS, steps, order, s2) for order in (1, 2)]
+    AS = CR.scalars(hp200())
+    steps = CR.visited(S, n)
+    return [CR.variance_error(AS, steps, order, s2) for order in (1, 2)]
 
 
 @pytest.mark.parametrize("s2", [0.05, 0.25])
@@ -109,23 +107,23 @@ def test_second_order_is_closer_at_the_ends(n, s2):
 
 
 def test_variance_propagation_is_the_chain():
-    """The closed form against the chain itself: 200000 scalar chains of solver_noise_ref.update in float64."""
-    AS = DR.scalars(hp200())
+    """The closed form against the chain itself: 200000 scalar chains of chain_ref.solver_update in float64."""
+    AS = CR.scalars(hp200())
     n, s2 = 20, 0.25
-    steps = RR.visited(S, n)
+    steps = CR.visited(S, n)
     k = AS[:, 0] * s2 / (AS[:, 0] ** 2 * s2 + AS[:, 1] ** 2)
     g = torch.Generator().manual_seed(5)
     N = 200000
     for order in (1, 2):
-        rw = SN.rows64(AS, steps, order)
+        rw = CR.solver_rows64(AS, steps, order, 1)
         x = torch.randn(N, generator=g, dtype=torch.float64) * float(np.sqrt(AS[steps[0], 0] ** 2 * s2 + AS[steps[0], 1] ** 2))
         p = None
         for t in steps:
             y = float(k[t]) * x
-            x = SN.update(t, rw[t], x, y, p, torch.randn(N, generator=g, dtype=torch.float64))
+            x = CR.solver_update(t, rw[t], x, y, p, torch.randn(N, generator=g, dtype=torch.float64))
             p = y
         mc = abs(float(x.var()) / s2 - 1.0)
-        exact = SN.variance_error(AS, steps, order, s2)
+        exact = CR.variance_error(AS, steps, order, s2)
         print(f"\norder {order}: closed form {exact:.4e}, {N} chains {mc:.4e}")
         assert abs(mc - exact) < 5.0 * np.sqrt(2.0 / N)      # five standard errors of a sample variance's relative error
 
@@ -136,14 +134,14 @@ def test_update_expression():
     x, y, p, z = (torch.randn(5, 88, generator=g) for _ in range(4))
     row = np.array([0.9, 0.2, 0.99, 0.4, 0.3], dtype=np.float32)
     c0, c1, c2, c, c4 = (torch.tensor(float(v)) for v in row)
-    assert torch.equal(SN.update(7, row, x, y, p, z), (c0 * x + c1 * (y + c * (y - p))) + c4 * z)
+    assert torch.equal(CR.solver_update(7, row, x, y, p, z), (c0 * x + c1 * (y + c * (y - p))) + c4 * z)
     row[3] = 0
-    assert torch.equal(SN.update(7, row, x, y, None, z), (c0 * x + c1 * y) + c4 * z)       # the history is not touched
-    assert torch.equal(SN.update(0, row, x, y, None, None), y / c2)                      # ... nor the noise at t == 0
-    row[4] = 0                                         # a deterministic row: dpmpp_ref's update, the noise is not touched
-    assert torch.equal(SN.update(7, row, x, y, None, None), DR.update(7, row, x, y, None))
+    assert torch.equal(CR.solver_update(7, row, x, y, None, z), (c0 * x + c1 * y) + c4 * z)       # the history is not touched
+    assert torch.equal(CR.solver_update(0, row, x, y, None, None), y / c2)                      # ... nor the noise at t == 0
+    row[4] = 0                                         # a deterministic row: the update without a z, the noise is not touched
+    assert torch.equal(CR.solver_update(7, row, x, y, None, None), CR.solver_update(7, row, x, y, None))
     row[3] = 0.4
-    assert torch.equal(SN.update(7, row, x, y, p, None), DR.update(7, row, x, y, p))
+    assert torch.equal(CR.solver_update(7, row, x, y, p, None), CR.solver_update(7, row, x, y, p))
 
 
 # ---------------------------------------------------------------------------------------------- 4. Python surface

@@ -1,7 +1,7 @@
 """Options "start_step" / "start_noise" (include/diffroll_amd.h) without a GPU: the strength -> step rule, the header and the
 public names, the facade's conversation with a stand-in engine (init xor x_T, trimming, start_noise held for the call only,
 the drivers' refusal of a batch without a roll to start from), the CLI's keys and exits, sharding over two gloo ranks, and
-the identity the restatement of tests/start_ref.py must have itself: a chain resumed from a row of the whole chain's
+the identity the restatement of tests/chain_ref.py must have itself: a chain resumed from a row of the whole chain's
 trajectory ends in the whole chain's roll."""
 import math
 import os
@@ -12,9 +12,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
-import dpmpp_ref as DR
-import respaced_ref as RR
-import start_ref as SR
+import chain_ref as CR
 from test_facade_cpu import MELS, RecordingEngine, clip, eq, facade, sample_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -376,43 +374,44 @@ def tiny():
 def test_the_restatement_resumes_its_own_trajectory(order):
     hp, p, x, spec, noise = tiny()
     n = 6
-    steps = RR.visited(12, n)
-    whole = RR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, n, 0.5, trajectory=True, order=order)
-    assert torch.equal(whole, SR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, n, -1, w=0.5, trajectory=True, order=order))
+    steps = CR.visited(12, n)
+    whole = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, n, w=0.5, trajectory=True, order=order)
+    assert torch.equal(whole, CR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, noise, n, start=CR.start_of(12, n, -1), w=0.5, trajectory=True,
+                                             order=order))
     for i in (0, 2, n - 2):
         t_s = steps[i + 1]
-        got = SR.sample_chain(p, hp, "cfdg_ddpm_x0", whole[i], spec, noise, n, t_s, w=0.5, order=order)
-        rows = SR.rows_of(hp, "cfdg_ddpm_x0", n, order, t_s)
+        got = CR.sample_chain(p, hp, "cfdg_ddpm_x0", whole[i], spec, noise, n, start=t_s, w=0.5, order=order)
+        rows = CR.chain_rows(hp, "cfdg_ddpm_x0", n, order=order, start=t_s)
         assert list(rows) == steps[i + 1:]
         if order < 2:
             assert torch.equal(got, whole[-1]), (order, i)
         else:
             assert rows[t_s][3] == 0                              # the first started row is first order ...
-            second = DR.rows(hp, n, 2)[t_s][3] != 0               # ... where the whole chain's row is second order
+            second = CR.solver_rows(hp, n, 2)[t_s][3] != 0               # ... where the whole chain's row is second order
             assert torch.equal(got, whole[-1]) != second, (i, t_s)
-    assert any(DR.rows(hp, n, 2)[steps[i + 1]][3] != 0 for i in (0, 2, n - 2))
+    assert any(CR.solver_rows(hp, n, 2)[steps[i + 1]][3] != 0 for i in (0, 2, n - 2))
 
 
 def test_the_restatements_diffusion():
     hp, p, x, spec, noise = tiny()
     x0 = torch.rand(2, 1, 8, 88)
-    tab = RR.committed(hp)
-    z = SR.diffusion_noise(7, 3, 12, 2, 8, 5)
+    tab = CR.committed(hp)
+    z = CR.diffusion_noise(7, 3, 12, 2, 8, 5)
     assert z.shape == (2, 1, 8, 88) and abs(float(z.std()) - 1) < 0.1
     from oracle import philox
     assert np.array_equal(z.numpy().reshape(2, -1), philox.step_noise(7, 3, 2, 8 * 88, 12 + 5))
     assert not np.array_equal(z.numpy().reshape(2, -1), philox.step_noise(7, 3, 2, 8 * 88, 5))
-    got = SR.diffuse(hp, x0, 5, z)
+    got = CR.diffuse(hp, x0, 5, z)
     assert torch.equal(got, torch.tensor(tab[0, 5, 2]) * x0 + torch.tensor(tab[0, 5, 3]) * z)
     # windows: one canvas draw per recording, so shared frames carry the same z
     from diffroll_amd import longform
     plan = longform.plan_windows(40, None, T=16, overlap=4)
-    zw = SR.window_noise(7, 3, 12, plan, 5)
+    zw = CR.window_noise(7, 3, 12, plan, 5)
     assert zw.shape == (plan.n, 1, 16, 88)
     for b in range(plan.n - 1):
         assert torch.equal(zw[b, 0, plan.stride:], zw[b + 1, 0, :plan.overlap])
-    t_s = RR.visited(12, 6)[2]
-    z = SR.diffusion_noise(7, 3, 12, 2, 8, t_s)
-    a = SR.refine_chain(p, hp, "cfdg_ddpm_x0", x0, spec, noise, 6, t_s, z, w=0.5)
-    b = SR.sample_chain(p, hp, "cfdg_ddpm_x0", SR.diffuse(hp, x0, t_s, z), spec, noise, 6, t_s, w=0.5)
+    t_s = CR.visited(12, 6)[2]
+    z = CR.diffusion_noise(7, 3, 12, 2, 8, t_s)
+    a = CR.refine_chain(p, hp, "cfdg_ddpm_x0", x0, spec, noise, 6, t_s, z, w=0.5)
+    b = CR.sample_chain(p, hp, "cfdg_ddpm_x0", CR.diffuse(hp, x0, t_s, z), spec, noise, 6, start=t_s, w=0.5)
     assert torch.equal(a, b)
