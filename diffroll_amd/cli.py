@@ -151,6 +151,14 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
                                cfg["task"]["sampling"].get("solver_order"))
         except ValueError as err:
             raise SystemExit(f"task.sampling.solver_noise: {err}")
+    # task.sampling.x0_clip=1: clamp the x0 prediction to the roll's range model.args.norm_args (option "x0_clip"); absent /
+    # null / 0 = off
+    if cfg["task"]["sampling"].get("x0_clip") is not None:
+        from .schedule import check_x0_clip
+        try:
+            check_x0_clip(cfg["task"]["sampling"]["x0_clip"], cfg["task"]["sampling"]["type"], cfg["model"]["args"].get("norm_args"))
+        except ValueError as err:
+            raise SystemExit(f"task.sampling.x0_clip: {err}")
     # task.sampling.strength=S / task.sampling.start_step=T with task.sampling.init_dir=DIR: start every chain from the roll
     # DIR/roll_<stem>.npy (options "start_step" / "start_noise"); long-form only - the path that writes that file
     samp = cfg["task"]["sampling"]

@@ -317,6 +317,13 @@ int check_solver(dr_engine* e, int sampler) {
                                   "solver_order 0 for the sampler's own update", sampler, e->opt_solver);
     return DR_OK;
 }
+// option "x0_clip" clamps an x0 prediction (DR_SAMPLER_* 0-5); the epsilon samplers have none and refuse it
+int check_x0_clamp(dr_engine* e, int sampler) {
+    if (e->opt_x0_clamp != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
+        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d clamps an x0 prediction (samplers 0-5); set "
+                                  "x0_clip 0 for this sampler", sampler, e->opt_x0_clamp);
+    return DR_OK;
+}
 // option "start_step": the chain position of the step a chain begins at - 0 when the option is off; a step the chain does
 // not visit is refused, naming the visited steps on either side of it
 int start_position(dr_engine* e, int& i0) {
@@ -454,6 +461,15 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value != 0 && value != 1)
             return fail(e, DR_EINVAL, "start_noise is 0 (x on entry is x at the start step) or 1 (a clean roll, diffused to it), got %d", value);
         e->opt_start_noise = value;
+        return DR_OK;
+    }
+    if (n == "x0_clip") {      // (part of the chain's key too: nothing is dropped, a chain captured under another value is not replayed)
+        if (value < 0 || value > 2)
+            return fail(e, DR_EINVAL, "x0_clip is 0 (off), 1 (clamp the x0 prediction to [0, 1]) or 2 (to [-1, 1]), got %d", value);
+        // (under "solver_order" 2 the history holds the prediction as the previous step clamped it: a dr_step sequence does
+        // not continue across a change - the next step that is not a chain's first is refused, as for "solver_noise")
+        if (e->opt_x0_clamp != value) e->hist_key.valid = false;
+        e->opt_x0_clamp = value;
         return DR_OK;
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
@@ -739,6 +755,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = check_solver(e, sampler))) return rc;
+    if ((rc = check_x0_clamp(e, sampler))) return rc;
     if ((rc = check_guidance(e, B, NB))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     if ((rc = ensure_history(e, B, T, (hipStream_t)stream))) return rc;
@@ -781,6 +798,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     int NB, n_cond;
     if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
     if ((rc = check_solver(e, sampler))) return rc;
+    if ((rc = check_x0_clamp(e, sampler))) return rc;
     if ((rc = check_guidance(e, B, NB))) return rc;
     int i0 = 0;      // option "start_step": the chain position of the first step this call runs
     if ((rc = start_position(e, i0))) return rc;
@@ -834,6 +852,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     key.order = e->opt_solver; key.hist = e->opt_solver == 2 ? (const float*)e->hist : nullptr;
     key.solver_noise = e->opt_solver != 0 ? e->opt_solver_noise : 0;
     key.start = chain_step(e, i0); key.start_noise = e->opt_start_noise;
+    key.x0_clamp = e->opt_x0_clamp;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

@@ -71,10 +71,13 @@ struct GraphKey {
     // ... and where the chain begins: options "start_step" (the effective step: the chain's first visited step when the
     // option is off) and "start_noise" (whether a diffusion node stands in front of the first step) - setting them drops nothing
     int start = -1, start_noise = 0;
+    // ... and whether the update clamps its prediction: option "x0_clip" (UpdateArgs::clamp_lo / clamp_hi of every node), part of the key too
+    int x0_clamp = 0;
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi &&
-               order == o.order && hist == o.hist && solver_noise == o.solver_noise && start == o.start && start_noise == o.start_noise;
+               order == o.order && hist == o.hist && solver_noise == o.solver_noise && start == o.start && start_noise == o.start_noise &&
+               x0_clamp == o.x0_clamp;
     }
 };
 
@@ -226,6 +229,9 @@ struct dr_engine {
     // visited step.  option "start_noise": 1 = d_x on entry to dr_sample is a clean roll, diffused to that step by the
     // chain's first node (update.hip: diffuse_kernel)
     int opt_start = -1, opt_start_noise = 0;
+    // option "x0_clip": 0 = off; 1 / 2 = the x0-prediction samplers clamp the prediction their update consumes to [0, 1] /
+    // [-1, 1] (update_quad.h: clamp_quad); the epsilon samplers refuse a non-zero value (abi.hip: check_x0_clamp)
+    int opt_x0_clamp = 0;
     dr::GuidanceInterval opt_guid;      // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack

@@ -231,6 +231,11 @@ struct UpdateArgs {
     // grows by three words instead of four.
     float* hist;
     int hist_par;
+    // Option "x0_clip" (0 = off): the prediction the update consumes - guided, after the shared-frame mean - is clamped to
+    // [clamp_lo, clamp_hi] in front of everything that reads it (update_quad.h: clamp_quad); x0 samplers only (mode 0 / 1 / 5).
+    // On where clamp_lo < clamp_hi: a zero-initialised block is off.  The bounds themselves, not the option's code: of the forms
+    // tried this one parks the fewest scalars of the tail kernel in VGPR lanes (profiles/clip_kernel_resources.txt).
+    float clamp_lo, clamp_hi;
 };
 // (mode 5) the half the step reads / the half it writes, null where it stores nothing
 __host__ __device__ inline const float* hist_prev(const UpdateArgs& a) { return a.hist + (a.hist_par ? a.n : 0); }

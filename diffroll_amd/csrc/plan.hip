@@ -437,6 +437,8 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         u.hist = hist ? (float*)e->hist : nullptr; u.hist_par = hist ? e->hist_par : 0;
         if (hist) e->hist_par ^= 1;
     }
+    // option "x0_clip" (the callers have refused the epsilon samplers): the update clamps the prediction it consumes
+    if (e->opt_x0_clamp != 0 && family <= DR_COEF_DDIM_X0) { u.clamp_lo = e->opt_x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f; }
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
     u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
     // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)

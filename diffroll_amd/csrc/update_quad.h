@@ -143,7 +143,19 @@ DR_DEVINL void noise_quad(const UpdateArgs& a, const long i4, const long key_smp
     }
 }
 
-// pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean (mode 5's history).
+// Option "x0_clip" (a.clamp_lo < a.clamp_hi: [0, 1] or [-1, 1]; else off): the static clamp of the prediction the update
+// consumes ("clip_denoised" of the DDPM code bases, the static thresholding DPM-Solver++ was published with).
+// Compare-and-select, not fminf(fmaxf()): both comparisons are false for a NaN, which stays a NaN as under torch.clamp.
+// Everything behind it reads the clamped value: both terms of modes 0 / 1, y / c2 of the last step (the final roll lies in
+// [lo / c2, hi / c2]), mode 5's d = y + c (y - p) and its history p (d itself is not clamped), an unguided step's c alone;
+// two windows clamp the same mean.
+DR_DEVINL void clamp_quad(const float lo, const float hi, float (&y)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = y[e] < lo ? lo : (y[e] > hi ? hi : y[e]);
+}
+
+// pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean and the clamp of
+// option "x0_clip" (mode 5's history).
 DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr) {
 #pragma clang fp contract(off)
     float x0[4];
@@ -181,6 +193,7 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         }
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
+    if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, x0);
     if (pred) *pred = make_float4(x0[0], x0[1], x0[2], x0[3]);
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];

@@ -49,6 +49,7 @@ _MIRRORED = {
     "solver_noise": 0,           # 1 = the solver's stochastic form (inert while solver_order is 0)
     "start_step": -1,            # the visited step a chain begins at (-1 = its first)
     "start_noise": 0,            # 1 = sample() takes a clean roll and diffuses it to the start step
+    "x0_clip": 0,                # 1 / 2 = the updates clamp the x0 prediction they consume to [0, 1] / [-1, 1]
     "blocked_accumulation": 2,   # 2 = every fp32 flavour that has a blocked form, 1 = single chain on 128-frame blocks
 }
 
@@ -56,8 +57,9 @@ _MIRRORED = {
 class Engine:
     """One engine handle per (device, stream).  Not re-entrant."""
 
-    # the library's defaults of options 'start_step' / 'start_noise' / 'solver_noise', also for a subclass that does not run __init__
+    # the library's defaults of options 'start_step' / 'start_noise' / 'solver_noise' / 'x0_clip', also for a subclass that does not run __init__
     start_step, start_noise, solver_noise = _MIRRORED["start_step"], _MIRRORED["start_noise"], _MIRRORED["solver_noise"]
+    x0_clip = _MIRRORED["x0_clip"]
 
     def __init__(self, *, residual_channels: int, residual_layers: int, kernel_size: int,
                  dilation_base: int, dilation_bound: int, n_mels: int, timesteps: int,
@@ -353,7 +355,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -370,7 +372,7 @@ class Engine:
     def holding(self, **options):
         """Options held for one call and put back afterwards, also when the call raises: mirrored option names, and
         window_breaks = the marks.  An option that already has the value is not set at all - 'sampling_steps' would drop the
-        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise' and the marks never do (they are part of its key or plain data), so a loop of
+        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip' and the marks never do (they are part of its key or plain data), so a loop of
         such calls replays one graph, and putting them back behind an asynchronous call touches nothing in flight."""
         def put(name, value):
             if name == "window_breaks":

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import (check_guidance_interval, check_sampling_steps, check_solver_noise, check_solver_order, check_start,
+from .schedule import (check_guidance_interval, check_sampling_steps, check_solver_noise, check_solver_order, check_start, check_x0_clip,
                        respaced_steps)
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
@@ -154,6 +154,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.start_step = t / sampling.strength = s start the chain at an intermediate visited step
         # (options "start_step" / "start_noise"): refine or vary a given roll, resume a chain; absent / None = the whole chain
         check_start(sampling.get("start_step"), sampling.get("strength"), respaced_steps(timesteps, sampling.get("steps") or 0))
+        # an extension: sampling.x0_clip = 1 clamps the x0 prediction every update consumes to the roll's range norm_args[0] ..
+        # norm_args[1] (option "x0_clip": the static "clip_denoised"); absent / None / 0 = the prediction as it comes out
+        check_x0_clip(sampling.get("x0_clip"), sampling.type, norm_args)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -249,6 +252,7 @@ class ClassifierFreeDiffRoll(nn.Module):
         order = self.solver_order()                       # (likewise)
         snoise = self.solver_noise()                      # (likewise)
         start = self.start_step()                         # (likewise)
+        clip = self.x0_clip()                             # (likewise)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
                                   fe_window=self.__dict__.get("_ckpt_window"), fe_fb=self.__dict__.get("_ckpt_fb"),
@@ -274,6 +278,8 @@ class ClassifierFreeDiffRoll(nn.Module):
             self._engine.set_option("solver_noise", snoise)
         if self._engine.start_step != start:              # (likewise part of the key)
             self._engine.set_option("start_step", start)
+        if self._engine.x0_clip != clip:                  # (likewise part of the key)
+            self._engine.set_option("x0_clip", clip)
         return self._engine
 
     def start_configured(self):
@@ -304,6 +310,14 @@ class ClassifierFreeDiffRoll(nn.Module):
         epsilon sampler raises ValueError before any GPU work."""
         hp = self.__dict__["hparams"]
         value = check_solver_noise(hp.sampling.get("solver_noise"), hp.sampling.type, hp.sampling.get("solver_order"))
+        return 0 if self.__dict__.get("_stride1") else value
+
+    def x0_clip(self) -> int:
+        """hparams.sampling.x0_clip as the engine's option takes it (0: off, 1: the range (0, 1) of hparams.norm_args, 2:
+        (-1, 1)), or 0 while one of the reference's single-step methods runs.  Read at every use; a bad value, a range the
+        engine has no code for or an epsilon sampler raises ValueError before any GPU work."""
+        hp = self.__dict__["hparams"]
+        value = check_x0_clip(hp.sampling.get("x0_clip"), hp.sampling.type, hp.norm_args)
         return 0 if self.__dict__.get("_stride1") else value
 
     def guidance_interval(self):

@@ -142,6 +142,33 @@ def check_solver_noise(value, sampler: str = None, order=None) -> int:
     return value
 
 
+X0_CLIP_RANGES = {(0.0, 1.0): 1, (-1.0, 1.0): 2}      # the range the rolls were normalised to -> the option's code
+
+
+def check_x0_clip(value, sampler: str = None, norm_args=(0, 1)) -> int:
+    """Option "x0_clip" (include/diffroll_amd.h) as hparams.sampling.x0_clip: None / 0 / False = off, 1 / True = clamp the
+    x0 prediction every update consumes to the range the rolls were normalised to, norm_args[0] .. norm_args[1].  Returns
+    the option's value - 1 for the range (0, 1), 2 for (-1, 1), 0 for off; any other value, a range the engine has no code
+    for, or a set value with a sampler that predicts epsilon (it has no x0 prediction to clamp) raises ValueError."""
+    if value is None:
+        return 0
+    if not isinstance(value, (bool, int)) or value not in (0, 1):
+        raise ValueError(f"x0_clip must be 0 / None (off) or 1 (clamp the x0 prediction to the roll's range), got {value!r}")
+    if not value:
+        return 0
+    if sampler is not None and sampler not in X0_SAMPLERS:
+        raise ValueError(f"x0_clip = 1 clamps an x0 prediction ({', '.join(X0_SAMPLERS)}); '{sampler}' predicts epsilon")
+    try:
+        rng = (float(norm_args[0]), float(norm_args[1])) if isinstance(norm_args, (list, tuple)) else None
+    except (TypeError, ValueError, IndexError):
+        rng = None
+    if rng not in X0_CLIP_RANGES:
+        shown = list(norm_args[:2]) if isinstance(norm_args, (list, tuple)) else norm_args
+        raise ValueError(f"x0_clip = 1 clamps to the roll's range norm_args[0] .. norm_args[1], which must be 0 .. 1 or -1 .. 1, "
+                         f"got {shown!r}")
+    return X0_CLIP_RANGES[rng]
+
+
 def check_start(start_step, strength, visited) -> int:
     """Options "start_step" / "start_noise" (include/diffroll_amd.h) as hparams.sampling.start_step / .strength: where a
     chain over the steps `visited` (chain order) begins.  The two keys are mutually exclusive.  strength s in (0, 1] runs

@@ -517,6 +517,33 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          caller passed - x0 - so its re-run diffuses again with the same z.  dr_step ignores the
  *                          option: it takes x at its step.  Any other value -> DR_EINVAL.  Part of a captured chain's key,
  *                          like "draws".
+ *   "x0_clip"          [0] 0, 1 or 2: CLAMP the x0 prediction every update consumes to the range the rolls were normalised
+ *                          to - 1 = [0, 1] (every released config), 2 = [-1, 1] - the static "clip_denoised" of the DDPM
+ *                          code bases and the static thresholding DPM-Solver++ was published with (Lu et al. 2022), the
+ *                          companion of strong guidance and short chains: under guidance the prediction (1 + w) c - w u
+ *                          is an extrapolation and leaves that range.  0 = off, bit-identical to an engine that never set
+ *                          the option, on every path.  The clamp applies to exactly one value: the step's prediction y
+ *                          after the classifier-free combine and after the shared-frame mean of "window_overlap",
+ *                          y = y < lo ? lo : (y > hi ? hi : y) (a NaN stays a NaN).  Everything behind it reads the
+ *                          clamped y: both terms of the x0 samplers' own update; the last step's x' = y / c2, so a
+ *                          finished roll lies in [lo / c2, hi / c2]; under "solver_order" d = y + c (y - p) is formed
+ *                          from the clamped y and the history p holds the clamped prediction, while d itself is not
+ *                          clamped (the published thresholded 2M), with or without "solver_noise"; a step outside
+ *                          "guidance_t_min" / "guidance_t_max" clamps the conditional prediction alone; two windows clamp
+ *                          the same mean, so the frames they share stay bit-identical.  The diffusion of "start_noise",
+ *                          dr_forward, dr_forward_steps, dr_q_sample and dr_extract_x0 are unaffected; dr_sample_checked's
+ *                          re-run uses the same value.  A change of the value ends a dr_step history of "solver_order" 2
+ *                          (p would be clamped by another rule than y): the next dr_step that is not a chain's first ->
+ *                          DR_ESTATE.  An epsilon sampler (DR_SAMPLER_* 6-8) has no x0 prediction to
+ *                          clamp: a non-zero value with one -> DR_EINVAL at dr_step / dr_sample / dr_sample_checked,
+ *                          naming both; any other value -> DR_EINVAL at the set.  Combines with "sampling_steps",
+ *                          "window_overlap" / "window_break", "draws" / "draw_stride", "guidance_t_min" / "guidance_t_max",
+ *                          "solver_order" / "solver_noise", "start_step" / "start_noise", both precisions and sharding
+ *                          (every rank sets the same value).  The value is part of a captured chain's key, like
+ *                          "solver_order": setting it drops nothing, and a chain captured under another value is never
+ *                          replayed.  Static only: dynamic (percentile) thresholding needs a reduction over each roll
+ *                          between the network and the update and is not offered.  Nothing is known about the quality of
+ *                          clamped chains with this model.
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
