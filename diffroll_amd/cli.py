@@ -159,6 +159,14 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
             check_x0_clip(cfg["task"]["sampling"]["x0_clip"], cfg["task"]["sampling"]["type"], cfg["model"]["args"].get("norm_args"))
         except ValueError as err:
             raise SystemExit(f"task.sampling.x0_clip: {err}")
+    # task.sampling.x0_threshold=0.995: dynamic thresholding at that quantile (option "x0_threshold"), with
+    # task.sampling.x0_clip=1; absent / null / 0 = off
+    if cfg["task"]["sampling"].get("x0_threshold") is not None:
+        from .schedule import check_x0_threshold
+        try:
+            check_x0_threshold(cfg["task"]["sampling"]["x0_threshold"], cfg["task"]["sampling"]["type"], cfg["task"]["sampling"].get("x0_clip"))
+        except ValueError as err:
+            raise SystemExit(f"task.sampling.x0_threshold: {err}")
     # task.sampling.strength=S / task.sampling.start_step=T with task.sampling.init_dir=DIR: start every chain from the roll
     # DIR/roll_<stem>.npy (options "start_step" / "start_noise"); long-form only - the path that writes that file
     samp = cfg["task"]["sampling"]

@@ -318,7 +318,14 @@ int check_solver(dr_engine* e, int sampler) {
     return DR_OK;
 }
 // option "x0_clip" clamps an x0 prediction (DR_SAMPLER_* 0-5); the epsilon samplers have none and refuse it
+// option "x0_threshold" refines "x0_clip", which names the range: refused without it
 int check_x0_clamp(dr_engine* e, int sampler) {
+    if (e->opt_x0_thresh != 0 && e->opt_x0_clamp == 0)
+        return fail(e, DR_EINVAL, "x0_threshold = %d needs x0_clip: the range the rolls were normalised to (x0_clip 1 = [0, 1], 2 = "
+                                  "[-1, 1]) is what the threshold is compared with, and x0_clip is 0", e->opt_x0_thresh);
+    if (e->opt_x0_thresh != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
+        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d and x0_threshold = %d act on an x0 prediction (samplers "
+                                  "0-5); set both 0 for this sampler", sampler, e->opt_x0_clamp, e->opt_x0_thresh);
     if (e->opt_x0_clamp != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
         return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d clamps an x0 prediction (samplers 0-5); set "
                                   "x0_clip 0 for this sampler", sampler, e->opt_x0_clamp);
@@ -367,6 +374,41 @@ int ensure_history(dr_engine* e, int B, int T, hipStream_t st) {
     if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
     e->hist_key.valid = false;
     HIPCHK(e, e->hist.ensure(2 * per, true));
+    return DR_OK;
+}
+
+// option "x0_threshold": the work buffer of the threshold launches, before anything is launched or captured (as ensure_history)
+int ensure_threshold(dr_engine* e, int B, hipStream_t st) {
+    if (e->opt_x0_thresh == 0 || e->thresh_work.fits(thresh_work_words(B))) return DR_OK;
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
+    HIPCHK(e, e->thresh_work.ensure(thresh_work_words(B), true));      // (tickets and counts start at zero: armed)
+    return DR_OK;
+}
+
+// dr_debug_threshold: the threshold launches of a step on the caller's tensors, then the groups' {q, s} gathered into d_out
+int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
+    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
+    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
+    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
+    DeviceGuard guard(e->cfg.device);
+    if (e->opt_x0_thresh == 0) return fail(e, DR_EINVAL, "dr_debug_threshold: x0_threshold is 0 (off)");
+    int rc = check_x0_clamp(e, DR_SAMPLER_DDPM_X0);
+    if (rc) return rc;
+    if (B % e->opt_draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt_draws, B);
+    if ((rc = check_windows(e, B, T))) return rc;
+    if ((rc = ensure_threshold(e, B, st))) return rc;
+    if ((rc = write_windows(e, B, false, st))) return rc;
+    UpdateArgs u{};
+    u.x0c = d_x0c; u.x0u = d_x0u;
+    u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
+    u.w = w; u.onepw = (float)(1.0 + (double)w);
+    u.clamp_lo = e->opt_x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f;
+    u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
+    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (!e->win_marks.empty() || e->opt_draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    const ThreshArgs ta = thresh_args(e, u);
+    HIPCHK(e, launch_threshold(ta, B, st));
+    HIPCHK(e, launch_thresh_gather(ta, B, d_out, st));
     return DR_OK;
 }
 
@@ -470,6 +512,14 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // not continue across a change - the next step that is not a chain's first is refused, as for "solver_noise")
         if (e->opt_x0_clamp != value) e->hist_key.valid = false;
         e->opt_x0_clamp = value;
+        return DR_OK;
+    }
+    if (n == "x0_threshold") {      // (stored like "solver_noise": nothing is dropped; part of the chain's key)
+        if (value != 0 && (value < 5000 || value > 10000))
+            return fail(e, DR_EINVAL, "x0_threshold is 0 (off) or the percentile in units of 1 / 10000, 5000 .. 10000 (9950 = 99.5 %%), got %d", value);
+        // (the history of "solver_order" 2 holds the prediction as the previous step thresholded it, as for "x0_clip")
+        if (e->opt_x0_thresh != value) e->hist_key.valid = false;
+        e->opt_x0_thresh = value;
         return DR_OK;
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
@@ -759,6 +809,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if ((rc = check_guidance(e, B, NB))) return rc;
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     if ((rc = ensure_history(e, B, T, (hipStream_t)stream))) return rc;
+    if ((rc = ensure_threshold(e, B, (hipStream_t)stream))) return rc;
     if (e->opt_solver == 2) {
         // the history is engine state: the chain's first step starts one, every other step continues the one the previous
         // dr_step left - the preceding visited step of the same (sampler, B, T)
@@ -805,6 +856,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if ((rc = ensure_workspace(e, NB, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_history(e, B, T, st))) return rc;
+    if ((rc = ensure_threshold(e, B, st))) return rc;
     e->hist_key.valid = false;      // (a whole chain uses the history buffers: a dr_step sequence does not continue across it)
     if (e->tuning_epoch != tuning_epoch().load()) {      // a tune.* knob changed (any engine, any thread): the cached chain is stale
         if ((rc = drop_chain(e))) return rc;
@@ -853,6 +905,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     key.solver_noise = e->opt_solver != 0 ? e->opt_solver_noise : 0;
     key.start = chain_step(e, i0); key.start_noise = e->opt_start_noise;
     key.x0_clamp = e->opt_x0_clamp;
+    key.x0_thresh = e->opt_x0_thresh; key.thresh_work = e->opt_x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

@@ -73,11 +73,15 @@ struct GraphKey {
     int start = -1, start_noise = 0;
     // ... and whether the update clamps its prediction: option "x0_clip" (UpdateArgs::clamp_lo / clamp_hi of every node), part of the key too
     int x0_clamp = 0;
+    // ... and thresholds it: option "x0_threshold" (the threshold launches and the update's other form are nodes of the chain)
+    // and the work buffer their arguments point into - a buffer that grew since is another chain
+    int x0_thresh = 0;
+    const unsigned* thresh_work = nullptr;
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi &&
                order == o.order && hist == o.hist && solver_noise == o.solver_noise && start == o.start && start_noise == o.start_noise &&
-               x0_clamp == o.x0_clamp;
+               x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && thresh_work == o.thresh_work;
     }
 };
 
@@ -232,6 +236,11 @@ struct dr_engine {
     // option "x0_clip": 0 = off; 1 / 2 = the x0-prediction samplers clamp the prediction their update consumes to [0, 1] /
     // [-1, 1] (update_quad.h: clamp_quad); the epsilon samplers refuse a non-zero value (abi.hip: check_x0_clamp)
     int opt_x0_clamp = 0;
+    // option "x0_threshold": 0 = off; 5000 .. 10000 = the percentile (1 / 10000) of dynamic thresholding, a refinement of
+    // "x0_clip" (refused without it: abi.hip: check_x0_clamp).  A thresholded step offers no tail plan: the stack launch, the
+    // head projections, the threshold launches (threshold.hip) and update_thresh_kernel (plan.hip: run_step)
+    int opt_x0_thresh = 0;
+    drh::DevBuf<unsigned> thresh_work;  // its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
     dr::GuidanceInterval opt_guid;      // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
@@ -337,6 +346,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab
 void set_kfd_root(const char* root);                                      // dr_debug_kfd_root
 int build_respaced(dr_engine* e);       // option "sampling_steps": rs_steps and d_coef_rs from opt_steps and h_coef
 int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_solver from the chain's steps and h_coef
+int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);      // dr_debug_threshold
 
 // ---- pack.hip
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);
@@ -373,6 +383,8 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
                 hipStream_t st, bool zero_spec = false, const int* tsel = nullptr, TailPlan* tail = nullptr);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& zero_spec);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond);
+// option "x0_threshold": the arguments of a step's threshold launches, from the update they precede
+ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u);
 struct ChainState {
     bool inproj_ready = false;
     StepEval ready{};          // the shape inproj_ready holds for (TailPlan::primed of the next step)

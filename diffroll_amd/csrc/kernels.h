@@ -255,6 +255,41 @@ hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
 // first_sample (or dyn), win_H, win_tab, draw_n, draw_G
 hipError_t launch_diffuse(const UpdateArgs& a, hipStream_t s);
 
+// Option "x0_threshold" (include/diffroll_amd.h): dynamic thresholding of the prediction the update consumes.  One q - the
+// exact v / 10000 quantile of |y - m| - is taken over each GROUP of the batch: a clip's roll, or under "window_overlap" a
+// recording's canvas, every canvas frame counted once (a window that is not its recording's first contributes frames [O, T)).
+// The threshold launches (threshold.hip) leave {q, s = max(q, r)} of a group in the record of the group's FIRST row; the
+// update's thresholding form reads s from there.
+// The engine's work buffer: [0] the ticket of the multi-launch form (zero between launches), then one record of
+// THRESH_ROW_WORDS words per row of the batch at THRESH_HEAD + row * THRESH_ROW_WORDS:
+//   [0, 256) the digit counts of the running pass (zero between launches), [256] the pattern bits selected so far,
+//   [257] the rank still sought among the elements that carry them, [258] elements in the selected bin, [259] ~(the smallest
+//   pattern above a[k]) (zero between launches: armed), [260] rem, [264] q, [265] s.
+// The words that must be zero sit at the same offsets whatever B a call has, so one buffer serves every batch that fits.
+constexpr int THRESH_HEAD = 4, THRESH_ROW_WORDS = 272, THRESH_SEL = 256, THRESH_QS = 264;
+inline size_t thresh_work_words(int B) { return (size_t)THRESH_HEAD + (size_t)B * THRESH_ROW_WORDS; }
+struct ThreshArgs {
+    UpdateArgs u;          // read: x0c, x0u, w / onepw (or dyn), n, per_sample, win_H, win_tab - what forms y (threshold_quad.h: pred_quad)
+    float m, r;            // centre and half-width of the range "x0_clip" names
+    int v;                 // the percentile, 1 / 10000
+    int pass;              // multi-launch form: 0-3 the radix passes (8, 8, 8, 7 bits from the top), 4 the successor pass
+    unsigned* work;        // the buffer above, thresh_work_words(B) words
+};
+// What the update's thresholding form needs beside UpdateArgs (a second kernel argument: UpdateArgs, embedded in TailArgs,
+// does not grow): the q / s pair of row 0's record - row b's is THRESH_ROW_WORDS floats further per row - and m, r.
+struct ThreshUpd {
+    const float* qs;
+    float m, r;
+};
+// every launch of one step's selection: one launch of one workgroup per roll (clips of at most THRESH_ROLL_MAX elements), or
+// five launches over all rows (windows, longer clips)
+constexpr long THRESH_ROLL_MAX = 65536;
+hipError_t launch_threshold(ThreshArgs a, int B, hipStream_t s);
+// update_kernel's thresholding form (update.hip: update_thresh_kernel)
+hipError_t launch_update_thresh(const UpdateArgs& a, const ThreshUpd& th, hipStream_t s);
+// (dr_debug_threshold) out (G, 2) = {q, s} of the batch's groups in row / recording order
+hipError_t launch_thresh_gather(const ThreshArgs& a, int B, float* out, hipStream_t s);
+
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->
 // classifier-free combine + posterior update -> input projection of the next step.  Same grid / grouping as the
 // stack_kernel launch it follows: NB samples (first `dual` conditional, next `dual` unconditional when dual > 0) x

@@ -455,7 +455,10 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     plan.skip_inproj = chain && chain->inproj_ready;
     if (chain) plan.primed = chain->ready;
     // (x and the tail kernel's output buffer must differ: a caller that hands us xalt itself gets the unfused tail)
-    TailPlan* offer = (result && x != xalt) ? &plan : nullptr;
+    // option "x0_threshold": the selection sits between the network and the update, so the step offers no tail plan - the
+    // evaluation keeps its fused stack launch, the head projections write e->x0buf, the rest are ordinary launches
+    const bool thresh = e->opt_x0_thresh != 0 && u.clamp_lo < u.clamp_hi;
+    TailPlan* offer = (result && x != xalt && !thresh) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
@@ -465,8 +468,24 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         return DR_OK;
     }
     if (result) *result = x;
+    if (thresh) {
+        const ThreshArgs ta = thresh_args(e, u);
+        HIPCHK(e, launch_threshold(ta, B, st));
+        HIPCHK(e, launch_update_thresh(u, ThreshUpd{reinterpret_cast<const float*>(ta.work + THRESH_HEAD + THRESH_QS), ta.m, ta.r}, st));
+        return DR_OK;
+    }
     HIPCHK(e, launch_update(u, st));
     return DR_OK;
+}
+
+ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u) {
+    ThreshArgs a{};
+    a.u = u;
+    // m = (lo + hi) / 2, r = (hi - lo) / 2 of the range "x0_clip" names: [0, 1] or [-1, 1], both exact
+    a.m = 0.5f * (u.clamp_lo + u.clamp_hi); a.r = 0.5f * (u.clamp_hi - u.clamp_lo);
+    a.v = e->opt_x0_thresh;
+    a.work = e->thresh_work;
+    return a;
 }
 
 void drop_graph(dr_engine* e) {

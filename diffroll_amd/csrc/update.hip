@@ -1,7 +1,7 @@
 // gfx950 (MI355X, CDNA4): the small HBM-bound kernels around the network - posterior update of all nine samplers +
 // classifier-free combine + Philox noise (task/diffusion.py:804-1055), q_sample / extract_x0 (:31-64), frame confusion
 // counts (:381-383), the roll -> note-run scan (:1185-1233).
-#include "update_quad.h"
+#include "threshold_quad.h"
 
 namespace dr {
 
@@ -11,6 +11,16 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
     float4 y;
     reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4, &y);
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;      // (option "solver_order")
+}
+
+// Option "x0_threshold": the same update with thresh_quad in place of the clamp (threshold_quad.h).  The selection's result
+// travels as a second argument; UpdateArgs is the block every other launch passes.
+__global__ __launch_bounds__(256) void update_thresh_kernel(const UpdateArgs a, const ThreshUpd th) {
+    const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i4 * 4 >= a.n) return;
+    float4 y;
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad<true>(a, i4, &y, &th);
+    if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
 }
 
 __global__ void set_dyn_kernel(DynParams* d, unsigned long long seed, int first_sample, float w, float onepw, unsigned epoch) {
@@ -34,6 +44,13 @@ hipError_t launch_set_windows(unsigned* d_tab, const WindowTable& tab, int n, hi
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s) {
     const long n4 = a.n / 4;
     hipLaunchKernelGGL(update_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_thresh(const UpdateArgs& a, const ThreshUpd& th, hipStream_t s) {
+    if (!th.qs) return hipErrorInvalidValue;
+    const long n4 = a.n / 4;
+    hipLaunchKernelGGL(update_thresh_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a, th);
     return hipGetLastError();
 }
 

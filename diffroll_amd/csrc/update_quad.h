@@ -154,9 +154,15 @@ DR_DEVINL void clamp_quad(const float lo, const float hi, float (&y)[4]) {
     for (int e = 0; e < 4; ++e) y[e] = y[e] < lo ? lo : (y[e] > hi ? hi : y[e]);
 }
 
+// Option "x0_threshold": what the update's thresholding form does in place of the clamp - defined in threshold_quad.h, which
+// the units that instantiate that form include behind this header.
+DR_DEVINL void thresh_quad(const UpdateArgs& a, const ThreshUpd& th, const long i4, float (&y)[4]);
+
 // pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean and the clamp of
-// option "x0_clip" (mode 5's history).
-DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr) {
+// option "x0_clip" (mode 5's history).  TH: update_kernel's thresholding form (option "x0_threshold"; th is set) - the
+// tail kernel instantiates TH = false, the text it always had.
+template <bool TH = false>
+DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr, const ThreshUpd* th = nullptr) {
 #pragma clang fp contract(off)
     float x0[4];
     // per-call scalars: by value (eager launches) or from the device block (captured chain)
@@ -193,7 +199,10 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         }
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
-    if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, x0);
+    if constexpr (TH) thresh_quad(a, *th, i4, x0);
+    else {
+        if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, x0);
+    }
     if (pred) *pred = make_float4(x0[0], x0[1], x0[2], x0[3]);
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];

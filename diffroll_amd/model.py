@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import (check_guidance_interval, check_sampling_steps, check_solver_noise, check_solver_order, check_start, check_x0_clip,
+from .schedule import (check_guidance_interval, check_sampling_steps, check_solver_noise, check_solver_order, check_start, check_x0_clip, check_x0_threshold,
                        respaced_steps)
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
@@ -157,6 +157,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         # an extension: sampling.x0_clip = 1 clamps the x0 prediction every update consumes to the roll's range norm_args[0] ..
         # norm_args[1] (option "x0_clip": the static "clip_denoised"); absent / None / 0 = the prediction as it comes out
         check_x0_clip(sampling.get("x0_clip"), sampling.type, norm_args)
+        # an extension: sampling.x0_threshold = 0.995 rescales instead of clamping wherever that quantile of |y - m| over the
+        # roll exceeds the range's half-width (option "x0_threshold": dynamic thresholding); needs x0_clip; absent / None / 0 = off
+        check_x0_threshold(sampling.get("x0_threshold"), sampling.type, sampling.get("x0_clip"))
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -253,6 +256,7 @@ class ClassifierFreeDiffRoll(nn.Module):
         snoise = self.solver_noise()                      # (likewise)
         start = self.start_step()                         # (likewise)
         clip = self.x0_clip()                             # (likewise)
+        thresh = self.x0_threshold()                      # (likewise)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
                                   fe_window=self.__dict__.get("_ckpt_window"), fe_fb=self.__dict__.get("_ckpt_fb"),
@@ -280,6 +284,8 @@ class ClassifierFreeDiffRoll(nn.Module):
             self._engine.set_option("start_step", start)
         if self._engine.x0_clip != clip:                  # (likewise part of the key)
             self._engine.set_option("x0_clip", clip)
+        if self._engine.x0_threshold != thresh:           # (likewise part of the key)
+            self._engine.set_option("x0_threshold", thresh)
         return self._engine
 
     def start_configured(self):
@@ -318,6 +324,14 @@ class ClassifierFreeDiffRoll(nn.Module):
         engine has no code for or an epsilon sampler raises ValueError before any GPU work."""
         hp = self.__dict__["hparams"]
         value = check_x0_clip(hp.sampling.get("x0_clip"), hp.sampling.type, hp.norm_args)
+        return 0 if self.__dict__.get("_stride1") else value
+
+    def x0_threshold(self) -> int:
+        """hparams.sampling.x0_threshold as the engine's option takes it (0: off, else the percentile in units of 1 / 10000),
+        or 0 while one of the reference's single-step methods runs.  Read at every use; a bad value, a value without
+        hparams.sampling.x0_clip or an epsilon sampler raises ValueError before any GPU work."""
+        hp = self.__dict__["hparams"]
+        value = check_x0_threshold(hp.sampling.get("x0_threshold"), hp.sampling.type, hp.sampling.get("x0_clip"))
         return 0 if self.__dict__.get("_stride1") else value
 
     def guidance_interval(self):

@@ -169,6 +169,25 @@ def check_x0_clip(value, sampler: str = None, norm_args=(0, 1)) -> int:
     return X0_CLIP_RANGES[rng]
 
 
+def check_x0_threshold(value, sampler: str = None, x0_clip=None) -> int:
+    """Option "x0_threshold" (include/diffroll_amd.h) as hparams.sampling.x0_threshold: None / 0 / False = off, a float p
+    with 0.5 <= p <= 1 = dynamic thresholding at that quantile of |y - m| over each roll (0.995 is Imagen's 99.5 %).  Returns
+    the option's value round(p * 10000) - 5000 .. 10000, or 0 for off; x0_clip is hparams.sampling.x0_clip, which the
+    threshold refines: a set value without it, any other value, or a sampler that predicts epsilon raises ValueError."""
+    if value is None or value is False or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0):
+        return 0
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.5 <= value <= 1.0:
+        raise ValueError(f"x0_threshold must be 0 / None (off) or a quantile p with 0.5 <= p <= 1 (0.995 = the 99.5th percentile), "
+                         f"got {value!r}")
+    if sampler is not None and sampler not in X0_SAMPLERS:
+        raise ValueError(f"x0_threshold = {value!r} and x0_clip act on an x0 prediction ({', '.join(X0_SAMPLERS)}); '{sampler}' "
+                         f"predicts epsilon")
+    if not x0_clip:
+        raise ValueError(f"x0_threshold = {value!r} needs x0_clip = 1: the threshold is compared with the roll's range, which x0_clip "
+                         f"names, got x0_clip = {x0_clip!r}")
+    return int(round(float(value) * 10000))
+
+
 def check_start(start_step, strength, visited) -> int:
     """Options "start_step" / "start_noise" (include/diffroll_amd.h) as hparams.sampling.start_step / .strength: where a
     chain over the steps `visited` (chain order) begins.  The two keys are mutually exclusive.  strength s in (0, 1] runs

@@ -541,9 +541,48 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          "solver_order" / "solver_noise", "start_step" / "start_noise", both precisions and sharding
  *                          (every rank sets the same value).  The value is part of a captured chain's key, like
  *                          "solver_order": setting it drops nothing, and a chain captured under another value is never
- *                          replayed.  Static only: dynamic (percentile) thresholding needs a reduction over each roll
- *                          between the network and the update and is not offered.  Nothing is known about the quality of
- *                          clamped chains with this model.
+ *                          replayed.  The dynamic (percentile) form is "x0_threshold" below, which refines this
+ *                          option.  Nothing is known about the quality of clamped chains with this model
+ *                          (INTEGRATION.md 3c).
+ *   "x0_threshold"     [0] 0, or 5000 .. 10000: DYNAMIC THRESHOLDING of the same prediction (Saharia et al. 2022, Imagen;
+ *                          the thresholding DPM-Solver++ was published with) at the percentile value / 10000 - 9950 is
+ *                          Imagen's 99.5 %, 10000 the maximum.  It refines "x0_clip", which keeps naming the range
+ *                          [lo, hi]; m = (lo + hi) / 2, r = (hi - lo) / 2.  With y the value "x0_clip" clamps (guided,
+ *                          after the shared-frame mean), every line rounded once in fp32:
+ *                              u = y - m;  a = |u| of every element of the GROUP, ascending (as bit patterns with the sign
+ *                              cleared: -0 == +0, inf above every finite value, NaN last)
+ *                              num = value (N - 1) (64-bit; N = elements of the group), k = num / 10000, rem = num % 10000
+ *                              q = rem == 0 ? a[k] : a[k] + f (a[k + 1] - a[k]),  f = (float)((double)rem / 10000.0)
+ *                              s = q > r ? q : r      (a NaN q gives s = r)
+ *                              y' = s > r ? m + (clamp(u, -s, s) r) / s : clamp(y, lo, hi)
+ *                          clamp = the compare-and-select of "x0_clip" (a NaN stays a NaN).  q is the linear-interpolation
+ *                          quantile (torch.quantile), selected EXACTLY - no sampling, no bins - and deterministically:
+ *                          integer counts only, the same bits on every launch geometry and replay.  A step whose q does
+ *                          not exceed r is bit-identical to the "x0_clip" step.  Everything behind y' reads y', exactly as
+ *                          it reads the clamped y under "x0_clip".  THE GROUP one q is taken over: a clip's roll, T * 88
+ *                          elements (every draw of "draws" is a roll of its own); under "window_overlap" the RECORDING'S
+ *                          CANVAS, every canvas frame counted once - a recording's first window contributes all its
+ *                          frames, every other one frames [O, T); "window_break" and draws delimit recordings as they do
+ *                          for the noise keys; N = ((n_r - 1) H + T) * 88 - so all windows of a recording use the same s
+ *                          on the same mean and the frames they share stay bit-identical.  A group never spans ranks: a
+ *                          sharded run gives every roll the same result on any world size.  WHERE IT RUNS: the selection
+ *                          sits between the network and the update, so a thresholded step does not use the tail kernel.
+ *                          The evaluation keeps its fused stack launch where it has one; the head projections, the
+ *                          threshold launches (one per roll-sized clip batch, five for windows and longer clips) and the
+ *                          update are ordinary launches: dr_launch_state reports DR_MODE_FUSED_STACK for such a step and
+ *                          tail_launches does not move (cost: profiles/thresh_sweep.txt).  A non-zero value with
+ *                          "x0_clip" = 0 -> DR_EINVAL at dr_step / dr_sample / dr_sample_checked, naming both; an
+ *                          epsilon sampler is refused by the rule of "x0_clip"; any value but 0 and 5000 .. 10000 ->
+ *                          DR_EINVAL at the set, naming the value.  dr_forward, dr_forward_steps, dr_q_sample,
+ *                          dr_extract_x0 and the diffusion of "start_noise" are unaffected; dr_sample_checked's re-run
+ *                          uses the same value.  A change of the value ends a dr_step history of "solver_order" 2, as a
+ *                          change of "x0_clip" does.  Combines with "sampling_steps", "window_overlap" / "window_break",
+ *                          "draws" / "draw_stride", "guidance_t_min" / "guidance_t_max" (an unguided step thresholds the
+ *                          conditional prediction alone), "solver_order" / "solver_noise", "start_step" / "start_noise",
+ *                          both precisions and sharding.  Stored like "solver_noise": setting it drops nothing; the value
+ *                          is part of a captured chain's key, and the chain replays with no host help (the kernels re-arm
+ *                          their own work words).  0 = off: every path is byte-identical to an engine that never set it.
+ *                          Nothing is known about quality with real weights.
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */

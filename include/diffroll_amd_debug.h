@@ -96,6 +96,14 @@ int dr_debug_ticks(dr_engine* e, int64_t* loop_ticks, int64_t* block_ticks);
  * the second, also across the ends of a guidance interval. */
 int dr_debug_launch_counts(dr_engine* e, int64_t* out2);
 
+/* Option "x0_threshold" on its own: exactly the threshold launches a reverse step runs between the network and the update
+ * (csrc/threshold.hip), on the caller's tensors instead of the network's outputs - d_x0c (B, T, 88) the conditional (or the
+ * only) prediction, d_x0u the unconditional one or NULL, combined with weight w as a step combines them - under the
+ * engine's current "x0_clip", "x0_threshold", "window_overlap", "window_break" and "draws".  d_out receives (G, 2) floats
+ * {q, s}: the quantile of |y - m| and s = max(q, r) of each group of the batch, in row / recording order - G = B clips, or
+ * the recordings of a window batch (per draw).  Either option at 0 -> DR_EINVAL.  Asynchronous on `stream`. */
+int dr_debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
