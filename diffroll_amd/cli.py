@@ -124,61 +124,24 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
     draws = cfg["task"]["sampling"].get("draws")
     if draws is not None and (isinstance(draws, bool) or not isinstance(draws, int) or draws < 1):
         raise SystemExit(f"task.sampling.draws must be an integer >= 1 (or null: one roll per clip), got {draws!r}")
-    # task.sampling.guidance_interval=[lo,hi]: guide the steps lo <= t <= hi only (options "guidance_t_min" / "guidance_t_max");
-    # absent / null = the whole chain
-    interval = cfg["task"]["sampling"].get("guidance_interval")
-    if interval is not None:
-        from .schedule import check_guidance_interval
-        try:
-            if not isinstance(S, int):
-                raise ValueError(f"task.timesteps = {S!r}")
-            check_guidance_interval(interval, S, cfg["task"]["sampling"]["type"])
-        except ValueError as err:
-            raise SystemExit(f"task.sampling.guidance_interval: {err}")
-    # task.sampling.solver_order=N: integrate the x0 prediction with a multistep solver (option "solver_order"); absent /
-    # null / 0 = the sampler's own update
-    if cfg["task"]["sampling"].get("solver_order") is not None:
-        from .schedule import check_solver_order
-        try:
-            check_solver_order(cfg["task"]["sampling"]["solver_order"], cfg["task"]["sampling"]["type"])
-        except ValueError as err:
-            raise SystemExit(f"task.sampling.solver_order: {err}")
-    # task.sampling.solver_noise=1: the solver's stochastic form (option "solver_noise"); absent / null / 0 = deterministic
-    if cfg["task"]["sampling"].get("solver_noise") is not None:
-        from .schedule import check_solver_noise
-        try:
-            check_solver_noise(cfg["task"]["sampling"]["solver_noise"], cfg["task"]["sampling"]["type"],
-                               cfg["task"]["sampling"].get("solver_order"))
-        except ValueError as err:
-            raise SystemExit(f"task.sampling.solver_noise: {err}")
-    # task.sampling.x0_clip=1: clamp the x0 prediction to the roll's range model.args.norm_args (option "x0_clip"); absent /
-    # null / 0 = off
-    if cfg["task"]["sampling"].get("x0_clip") is not None:
-        from .schedule import check_x0_clip
-        try:
-            check_x0_clip(cfg["task"]["sampling"]["x0_clip"], cfg["task"]["sampling"]["type"], cfg["model"]["args"].get("norm_args"))
-        except ValueError as err:
-            raise SystemExit(f"task.sampling.x0_clip: {err}")
-    # task.sampling.x0_threshold=0.995: dynamic thresholding at that quantile (option "x0_threshold"), with
-    # task.sampling.x0_clip=1; absent / null / 0 = off
-    if cfg["task"]["sampling"].get("x0_threshold") is not None:
-        from .schedule import check_x0_threshold
-        try:
-            check_x0_threshold(cfg["task"]["sampling"]["x0_threshold"], cfg["task"]["sampling"]["type"], cfg["task"]["sampling"].get("x0_clip"))
-        except ValueError as err:
-            raise SystemExit(f"task.sampling.x0_threshold: {err}")
-    # task.sampling.strength=S / task.sampling.start_step=T with task.sampling.init_dir=DIR: start every chain from the roll
-    # DIR/roll_<stem>.npy (options "start_step" / "start_noise"); long-form only - the path that writes that file
+    # the other task.sampling keys - guidance_interval=[lo,hi], solver_order=N, solver_noise=1, strength=S / start_step=T,
+    # x0_clip=1 (to the roll's range model.args.norm_args), x0_threshold=0.995 - are read as the model reads them
+    # (schedule.sampling_options: each key's validator and the engine option it becomes); absent / null = off
+    from .schedule import sampling_options
     samp = cfg["task"]["sampling"]
     start_key = next((k for k in ("strength", "start_step") if samp.get(k) is not None), None)
+    try:
+        needs_S = next((k for k in ("guidance_interval", start_key) if k and samp.get(k) is not None), None)
+        if needs_S and not isinstance(S, int):      # (the two keys that are read against the schedule's length)
+            bad = ValueError(f"task.timesteps = {S!r}")
+            bad.key = needs_S
+            raise bad
+        sampling_options(samp, S, cfg["model"]["args"].get("norm_args"))
+    except ValueError as err:
+        raise SystemExit(f"task.sampling.{err.key}: {err}")
+    # strength / start_step with task.sampling.init_dir=DIR: start every chain from the roll DIR/roll_<stem>.npy (options
+    # "start_step" / "start_noise"); long-form only - the path that writes that file
     if start_key is not None:
-        from .schedule import check_start, respaced_steps
-        try:
-            if not isinstance(S, int):
-                raise ValueError(f"task.timesteps = {S!r}")
-            check_start(samp.get("start_step"), samp.get("strength"), respaced_steps(S, steps or 0))
-        except ValueError as err:
-            raise SystemExit(f"task.sampling.{start_key}: {err}")
         if not isinstance(samp.get("init_dir"), str):
             raise SystemExit(f"task.sampling.{start_key} starts every chain from a given roll: task.sampling.init_dir=DIR (the "
                              f"folder holding roll_<stem>.npy for every input file) is required")

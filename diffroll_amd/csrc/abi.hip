@@ -62,9 +62,14 @@ void forget_fused_slot(dr_engine* e) {
     }
     s.cv.notify_all();
 }
+// the captured chain may still be running, on the stream it was last launched on: wait for it
+int wait_chain(dr_engine* e) {
+    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
+    return DR_OK;
+}
 // the launch mode changed (a FusedMode transition returned true) or a tuning knob did: the captured chain is stale
 int drop_chain(dr_engine* e) {
-    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));      // it may still be running
+    if (int rc = wait_chain(e)) return rc;
     drop_graph(e);
     return DR_OK;
 }
@@ -148,7 +153,7 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
         if (rc) return rc;
     }
     // option "draws": the B rolls are D draws of B / D clips, and the front-end ran on the clips
-    const int D = e->opt_draws;
+    const int D = e->opt.draws;
     if (B % D) return fail(e, DR_EINVAL, "B=%d rolls are not a whole number of draws (option draws = %d)", B, D);
     if (sampler != DR_SAMPLER_GENERATION_DDPM_X0 && (e->fe_B != B / D || e->fe_T != T)) {
         if (D > 1)
@@ -160,21 +165,18 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
     return DR_OK;
 }
 
-// options "guidance_t_min" / "guidance_t_max": the samplers that guide need lo <= hi (the others ignore both)
-int check_guidance(dr_engine* e, int B, int NB) {
-    if (NB == 2 * B && e->opt_guid.empty(e->S))
-        return fail(e, DR_EINVAL, "guidance interval is empty: guidance_t_min = %d exceeds guidance_t_max = %d", e->opt_guid.lo,
-                    e->opt_guid.hi_eff(e->S));
-    return DR_OK;
-}
-
+// The options, against what only a call knows - sampler, batch and frames; NB (out) is the sampler's evaluation batch.
 // option "window_overlap": at most two windows share a frame (O <= T / 2)
 // option "window_break": every mark names a window of this batch (marks are ignored while "window_overlap" is 0)
-int check_windows(dr_engine* e, int B, int T) {
-    if (2 * e->opt_win_O > T)
-        return fail(e, DR_EINVAL, "window_overlap %d exceeds half the window (T = %d frames)", e->opt_win_O, T);
-    const int D = e->opt_draws, n = B / D;      // (option "draws": the marks are those of one draw and repeat per draw)
-    if (e->opt_win_O > 0 && !e->win_marks.empty()) {
+// options "solver_order", "x0_clip" and "x0_threshold" act on an x0 prediction (DR_SAMPLER_* 0-5): the epsilon samplers
+// refuse them; "x0_threshold" refines "x0_clip", which names the range, and is refused without it
+// options "guidance_t_min" / "guidance_t_max": the samplers that guide need lo <= hi (the others ignore both)
+int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
+    const ChainOptions& o = e->opt;
+    if (2 * o.win_O > T)
+        return fail(e, DR_EINVAL, "window_overlap %d exceeds half the window (T = %d frames)", o.win_O, T);
+    const int D = o.draws, n = B / D;      // (option "draws": the marks are those of one draw and repeat per draw)
+    if (o.win_O > 0 && !e->win_marks.empty()) {
         if (e->win_marks.back() >= n) {
             if (D > 1)
                 return fail(e, DR_EINVAL, "window_break %d is not a window of one draw (B = %d windows in %d draws of %d)", e->win_marks.back(), B, D, n);
@@ -183,13 +185,31 @@ int check_windows(dr_engine* e, int B, int T) {
         if (B > STACK_GROUPS)
             return fail(e, DR_EINVAL, "window_break: a batch with recording boundaries holds at most %d windows, got B = %d", STACK_GROUPS, B);
     }
-    if (e->opt_win_O > 0 && D > 1) {
+    if (o.win_O > 0 && D > 1) {
         if (B > STACK_GROUPS)
             return fail(e, DR_EINVAL, "draws: a window batch of several draws holds at most %d windows, got B = %d", STACK_GROUPS, B);
-        const long R = (long)e->win_marks.size() + 1, G = e->opt_draw_G > 0 ? e->opt_draw_G : R;
+        const long R = (long)e->win_marks.size() + 1, G = o.draw_G > 0 ? o.draw_G : R;
         if ((D - 1) * G + R > 65536)
             return fail(e, DR_EINVAL, "draws: %d draws at key stride %ld do not fit the window table (sample key offsets < 65536)", D, G);
     }
+    int n_cond;
+    if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
+    const bool eps = !predicts_x0(sampler);
+    if (o.solver != 0 && eps)
+        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: solver_order = %d integrates an x0 prediction (samplers 0-5); set "
+                                  "solver_order 0 for the sampler's own update", sampler, o.solver);
+    if (o.x0_thresh != 0 && o.x0_clamp == 0)
+        return fail(e, DR_EINVAL, "x0_threshold = %d needs x0_clip: the range the rolls were normalised to (x0_clip 1 = [0, 1], 2 = "
+                                  "[-1, 1]) is what the threshold is compared with, and x0_clip is 0", o.x0_thresh);
+    if (o.x0_thresh != 0 && eps)
+        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d and x0_threshold = %d act on an x0 prediction (samplers "
+                                  "0-5); set both 0 for this sampler", sampler, o.x0_clamp, o.x0_thresh);
+    if (o.x0_clamp != 0 && eps)
+        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d clamps an x0 prediction (samplers 0-5); set "
+                                  "x0_clip 0 for this sampler", sampler, o.x0_clamp);
+    if (NB == 2 * B && o.guid.empty(e->S))
+        return fail(e, DR_EINVAL, "guidance interval is empty: guidance_t_min = %d exceeds guidance_t_max = %d", o.guid.lo,
+                    o.guid.hi_eff(e->S));
     return DR_OK;
 }
 
@@ -197,12 +217,12 @@ int check_windows(dr_engine* e, int B, int T) {
 // that read it: an eager sequence with marks, and every launch of a captured chain (force: its graph holds the table's
 // address whether or not marks were set when it was captured).  Without marks: window b of recording 0.
 int write_windows(dr_engine* e, int B, bool force, hipStream_t st) {
-    if (e->opt_win_O <= 0 || B > STACK_GROUPS || (!force && e->win_marks.empty() && e->opt_draws <= 1)) return DR_OK;
+    if (e->opt.win_O <= 0 || B > STACK_GROUPS || (!force && e->win_marks.empty() && e->opt.draws <= 1)) return DR_OK;
     WindowTable tab;
     // option "draws": every draw starts new recordings, and draw d of recording r is keyed first_sample + r + d * stride
     // (the recordings of one draw, or option "draw_stride")
-    const int n = B / e->opt_draws;
-    const size_t stride = e->opt_draw_G > 0 ? (size_t)e->opt_draw_G : e->win_marks.size() + 1;
+    const int n = B / e->opt.draws;
+    const size_t stride = e->opt.draw_G > 0 ? (size_t)e->opt.draw_G : e->win_marks.size() + 1;
     size_t m = 0;
     for (int b = 0, first = 0; b < B; ++b) {
         const int j = b % n;
@@ -219,7 +239,7 @@ int write_windows(dr_engine* e, int B, bool force, hipStream_t st) {
 // gets a row derived in double precision from the committed fp32 sqrt_acp / sqrt_1m_acp of t and t' (family 0, columns
 // 2 and 3) and rounded to fp32 once, in the column order update_quad.h reads.  Rebuilt by dr_commit and by the option.
 int build_respaced(dr_engine* e) {
-    const int S = e->S, n = e->opt_steps;
+    const int S = e->S, n = e->opt.steps;
     e->rs_steps.clear();
     e->d_coef_rs.reset();
     if (n == 0 || n == S) return DR_OK;       // the full chain: committed rows
@@ -277,7 +297,7 @@ int chain_step(const dr_engine* e, int i) {
 int build_solver(dr_engine* e) {
     const int S = e->S, n = chain_steps(e);
     e->h_solver.assign((size_t)2 * S * 5, 0.f);
-    if (e->opt_solver == 0) return DR_OK;
+    if (e->opt.solver == 0) return DR_OK;
     const float* h = e->h_coef.data();
     auto lambda = [&](int t) { return std::log((double)h[(size_t)t * 5 + 2] / (double)h[(size_t)t * 5 + 3]); };
     for (int i = 0; i < n; ++i) {
@@ -288,7 +308,7 @@ int build_solver(dr_engine* e) {
         const int tp = chain_step(e, i + 1);
         const double Sm = h[(size_t)t * 5 + 3], Ap = h[(size_t)tp * 5 + 2], Smp = h[(size_t)tp * 5 + 3];
         const double hh = lambda(tp) - lambda(t);
-        if (e->opt_solver_noise) {
+        if (e->opt.solver_noise) {
             const double g = -std::expm1(-2.0 * hh);      // 1 - exp(-2h) > 0: lambda increases along the chain
             row[0] = (float)((Smp / Sm) * std::exp(-hh));
             row[1] = (float)(Ap * g);
@@ -297,7 +317,7 @@ int build_solver(dr_engine* e) {
             row[0] = (float)(Smp / Sm);
             row[1] = (float)(-Ap * std::expm1(-hh));
         }
-        if (e->opt_solver == 2 && i > 0 && tp != 0) row[3] = (float)(hh / (2.0 * (lambda(t) - lambda(chain_step(e, i - 1)))));
+        if (e->opt.solver == 2 && i > 0 && tp != 0) row[3] = (float)(hh / (2.0 * (lambda(t) - lambda(chain_step(e, i - 1)))));
     }
     for (int t = 0; t < S; ++t) {
         const float* row = e->h_solver.data() + (size_t)t * 5;
@@ -310,32 +330,11 @@ int build_solver(dr_engine* e) {
     return DR_OK;
 }
 
-// option "solver_order" applies to the x0-prediction samplers (DR_SAMPLER_* 0-5); the epsilon samplers refuse it
-int check_solver(dr_engine* e, int sampler) {
-    if (e->opt_solver != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
-        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: solver_order = %d integrates an x0 prediction (samplers 0-5); set "
-                                  "solver_order 0 for the sampler's own update", sampler, e->opt_solver);
-    return DR_OK;
-}
-// option "x0_clip" clamps an x0 prediction (DR_SAMPLER_* 0-5); the epsilon samplers have none and refuse it
-// option "x0_threshold" refines "x0_clip", which names the range: refused without it
-int check_x0_clamp(dr_engine* e, int sampler) {
-    if (e->opt_x0_thresh != 0 && e->opt_x0_clamp == 0)
-        return fail(e, DR_EINVAL, "x0_threshold = %d needs x0_clip: the range the rolls were normalised to (x0_clip 1 = [0, 1], 2 = "
-                                  "[-1, 1]) is what the threshold is compared with, and x0_clip is 0", e->opt_x0_thresh);
-    if (e->opt_x0_thresh != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
-        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d and x0_threshold = %d act on an x0 prediction (samplers "
-                                  "0-5); set both 0 for this sampler", sampler, e->opt_x0_clamp, e->opt_x0_thresh);
-    if (e->opt_x0_clamp != 0 && sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS)
-        return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d clamps an x0 prediction (samplers 0-5); set "
-                                  "x0_clip 0 for this sampler", sampler, e->opt_x0_clamp);
-    return DR_OK;
-}
 // option "start_step": the chain position of the step a chain begins at - 0 when the option is off; a step the chain does
 // not visit is refused, naming the visited steps on either side of it
 int start_position(dr_engine* e, int& i0) {
     i0 = 0;
-    const int ts = e->opt_start;
+    const int ts = e->opt.start;
     if (ts < 0) return DR_OK;
     const int n = chain_steps(e);
     for (int i = 0; i < n; ++i) {
@@ -343,7 +342,7 @@ int start_position(dr_engine* e, int& i0) {
         if (t == ts) { i0 = i; return DR_OK; }
         if (t < ts)       // (the steps decrease strictly and end at 0; the first one is S - 1 >= ts: i > 0 here)
             return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits (option sampling_steps = %d): the visited steps "
-                                      "on either side of it are %d and %d", ts, e->opt_steps, chain_step(e, i - 1), t);
+                                      "on either side of it are %d and %d", ts, e->opt.steps, chain_step(e, i - 1), t);
     }
     return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits", ts);      // (unreachable: step 0 is always visited)
 }
@@ -351,38 +350,23 @@ int start_position(dr_engine* e, int& i0) {
 // z is row 0 of the injected noise (no reverse step reads it: step 0 draws none), else Philox with counter word S + ts,
 // keyed as run_step keys the updates of this chain (plan.hip).
 int run_diffuse(dr_engine* e, float* x, const float* d_noise, int B, int T, int ts, uint64_t seed, int first_sample, hipStream_t st) {
-    UpdateArgs u{};
+    UpdateArgs u = update_base(e, B, T);
     u.x = x; u.noise = d_noise;
     u.coef = e->d_coef + (size_t)ts * 5;      // family 0: [.., .., sqrt_acp[ts], sqrt_1m_acp[ts], ..], the committed row
     u.t = e->S + ts;
-    u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.seed = seed; u.first_sample = first_sample;
-    u.dyn = e->use_dyn ? e->d_dyn : nullptr;
-    u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
-    if (e->opt_draws > 1) { u.draw_n = B / e->opt_draws; u.draw_G = e->opt_draw_G > 0 ? e->opt_draw_G : u.draw_n; }
-    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt_draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
     HIPCHK(e, launch_diffuse(u, st));
     return DR_OK;
 }
 
-// order 2: the history buffer (two halves), before anything is launched or captured (a chain that may still read them is waited for)
-int ensure_history(dr_engine* e, int B, int T, hipStream_t st) {
-    if (e->opt_solver != 2) return DR_OK;
-    const size_t per = (size_t)B * T * 88;
-    if (e->hist.fits(2 * per)) return DR_OK;
+// A buffer the chain's launches point into (the history of solver order 2, the threshold launches' work words) grows to n
+// zeroed elements before anything is launched or captured: what may still read the old one is waited for
+template <class V>
+int grow_chain_buffer(dr_engine* e, DevBuf<V>& buf, size_t n, hipStream_t st) {
+    if (buf.fits(n)) return DR_OK;
     HIPCHK(e, hipStreamSynchronize(st));
-    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
-    e->hist_key.valid = false;
-    HIPCHK(e, e->hist.ensure(2 * per, true));
-    return DR_OK;
-}
-
-// option "x0_threshold": the work buffer of the threshold launches, before anything is launched or captured (as ensure_history)
-int ensure_threshold(dr_engine* e, int B, hipStream_t st) {
-    if (e->opt_x0_thresh == 0 || e->thresh_work.fits(thresh_work_words(B))) return DR_OK;
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
-    HIPCHK(e, e->thresh_work.ensure(thresh_work_words(B), true));      // (tickets and counts start at zero: armed)
+    if (int rc = wait_chain(e)) return rc;
+    HIPCHK(e, buf.ensure(n, true));
     return DR_OK;
 }
 
@@ -392,20 +376,16 @@ int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B,
     if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
     if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
     DeviceGuard guard(e->cfg.device);
-    if (e->opt_x0_thresh == 0) return fail(e, DR_EINVAL, "dr_debug_threshold: x0_threshold is 0 (off)");
-    int rc = check_x0_clamp(e, DR_SAMPLER_DDPM_X0);
-    if (rc) return rc;
-    if (B % e->opt_draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt_draws, B);
-    if ((rc = check_windows(e, B, T))) return rc;
-    if ((rc = ensure_threshold(e, B, st))) return rc;
+    if (e->opt.x0_thresh == 0) return fail(e, DR_EINVAL, "dr_debug_threshold: x0_threshold is 0 (off)");
+    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
+    int rc, NB;
+    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
+    if ((rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
     if ((rc = write_windows(e, B, false, st))) return rc;
-    UpdateArgs u{};
+    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
     u.x0c = d_x0c; u.x0u = d_x0u;
-    u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
-    u.clamp_lo = e->opt_x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f;
-    u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
-    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (!e->win_marks.empty() || e->opt_draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    u.clamp_lo = e->opt.x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f;
     const ThreshArgs ta = thresh_args(e, u);
     HIPCHK(e, launch_threshold(ta, B, st));
     HIPCHK(e, launch_thresh_gather(ta, B, d_out, st));
@@ -432,8 +412,8 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (n == "fused_tail") { if (e->opt_tail != value) drop(); e->opt_tail = value; return DR_OK; }
     if (n == "window_overlap") {      // (O <= T / 2 is checked by dr_step / dr_sample, which know T)
         if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
-        if (e->opt_win_O != value) drop();
-        e->opt_win_O = value;
+        if (e->opt.win_O != value) drop();
+        e->opt.win_O = value;
         return DR_OK;
     }
     // (a mark >= B is refused by dr_step / dr_sample, which know B; no captured chain is dropped: the table is data)
@@ -448,23 +428,23 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // (no captured chain is dropped: the value is part of the chain's key - GraphKey - so a chain captured under
         // another value is simply not replayed, and one captured under this value still is)
         if (value < 1) return fail(e, DR_EINVAL, "draws is >= 1 (1 = every roll its own clip), got %d", value);
-        if (e->opt_draws != value) e->hist_key.valid = false;
-        e->opt_draws = value;
+        if (e->opt.draws != value) e->hist_key.valid = false;
+        e->opt.draws = value;
         return DR_OK;
     }
     if (n == "draw_stride") {
         if (value < 0) return fail(e, DR_EINVAL, "draw_stride is >= 0 (0 = the clips of the batch), got %d", value);
-        e->opt_draw_G = value;
+        e->opt.draw_G = value;
         return DR_OK;
     }
     if (n == "sampling_steps") {
         if (value != 0 && (value < 2 || value > e->S))
             return fail(e, DR_EINVAL, "sampling_steps is 0 (off) or in [2, timesteps = %d], got %d", e->S, value);
-        if (e->opt_steps == value) return DR_OK;
+        if (e->opt.steps == value) return DR_OK;
         drop();
-        e->opt_steps = value;
+        e->opt.steps = value;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
-        if (int rc = build_respaced(e)) { e->opt_steps = 0; return rc; }
+        if (int rc = build_respaced(e)) { e->opt.steps = 0; return rc; }
         return build_solver(e);               // (its rows belong to the steps this chain visits)
     }
     if (n == "solver_order") {
@@ -472,9 +452,9 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // under this value reads the table at replay, and the table is this value's whenever that chain is replayed.)
         if (value < 0 || value > 2)
             return fail(e, DR_EINVAL, "solver_order is 0 (the sampler's own update), 1 or 2 (DPM-Solver++ 2M), got %d", value);
-        if (e->opt_solver == value) return DR_OK;
+        if (e->opt.solver == value) return DR_OK;
         (void)hipDeviceSynchronize();         // a chain of the previous order may still be reading the table
-        e->opt_solver = value;
+        e->opt.solver = value;
         e->hist_key.valid = false;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         return build_solver(e);
@@ -484,11 +464,11 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // chain captured under the other value is not replayed until the value, and with it the table, is back)
         if (value != 0 && value != 1)
             return fail(e, DR_EINVAL, "solver_noise is 0 (the deterministic solver) or 1 (its stochastic form, SDE-DPM-Solver++), got %d", value);
-        if (e->opt_solver_noise == value) return DR_OK;
-        if (e->opt_solver != 0) (void)hipDeviceSynchronize();      // a chain of the previous value may still be reading the table
-        e->opt_solver_noise = value;
+        if (e->opt.solver_noise == value) return DR_OK;
+        if (e->opt.solver != 0) (void)hipDeviceSynchronize();      // a chain of the previous value may still be reading the table
+        e->opt.solver_noise = value;
         e->hist_key.valid = false;
-        if (!e->committed || e->opt_solver == 0) return DR_OK;      // (dr_commit / "solver_order" builds it)
+        if (!e->committed || e->opt.solver == 0) return DR_OK;      // (dr_commit / "solver_order" builds it)
         return build_solver(e);
     }
     if (n == "start_step") {
@@ -496,13 +476,13 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // the chain visits the step is checked by dr_sample, which knows the chain)
         if (value < -1 || value >= e->S)
             return fail(e, DR_EINVAL, "start_step is -1 (the chain's first step) or in [0, timesteps = %d), got %d", e->S, value);
-        e->opt_start = value;
+        e->opt.start = value;
         return DR_OK;
     }
     if (n == "start_noise") {      // (part of the chain's key too)
         if (value != 0 && value != 1)
             return fail(e, DR_EINVAL, "start_noise is 0 (x on entry is x at the start step) or 1 (a clean roll, diffused to it), got %d", value);
-        e->opt_start_noise = value;
+        e->opt.start_noise = value;
         return DR_OK;
     }
     if (n == "x0_clip") {      // (part of the chain's key too: nothing is dropped, a chain captured under another value is not replayed)
@@ -510,16 +490,16 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
             return fail(e, DR_EINVAL, "x0_clip is 0 (off), 1 (clamp the x0 prediction to [0, 1]) or 2 (to [-1, 1]), got %d", value);
         // (under "solver_order" 2 the history holds the prediction as the previous step clamped it: a dr_step sequence does
         // not continue across a change - the next step that is not a chain's first is refused, as for "solver_noise")
-        if (e->opt_x0_clamp != value) e->hist_key.valid = false;
-        e->opt_x0_clamp = value;
+        if (e->opt.x0_clamp != value) e->hist_key.valid = false;
+        e->opt.x0_clamp = value;
         return DR_OK;
     }
     if (n == "x0_threshold") {      // (stored like "solver_noise": nothing is dropped; part of the chain's key)
         if (value != 0 && (value < 5000 || value > 10000))
             return fail(e, DR_EINVAL, "x0_threshold is 0 (off) or the percentile in units of 1 / 10000, 5000 .. 10000 (9950 = 99.5 %%), got %d", value);
         // (the history of "solver_order" 2 holds the prediction as the previous step thresholded it, as for "x0_clip")
-        if (e->opt_x0_thresh != value) e->hist_key.valid = false;
-        e->opt_x0_thresh = value;
+        if (e->opt.x0_thresh != value) e->hist_key.valid = false;
+        e->opt.x0_thresh = value;
         return DR_OK;
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
@@ -529,7 +509,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (!guidance_value_ok(is_max, value, e->S))
             return fail(e, DR_EINVAL, is_max ? "guidance_t_max is -1 (= timesteps - 1) or in [0, timesteps = %d), got %d"
                                              : "guidance_t_min is in [0, timesteps = %d), got %d", e->S, value);
-        (is_max ? e->opt_guid.hi : e->opt_guid.lo) = value;
+        (is_max ? e->opt.guid.hi : e->opt.guid.lo) = value;
         return DR_OK;
     }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
@@ -559,6 +539,32 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         return DR_OK;
     }
     return fail(e, DR_ENAME, "unknown option '%s'", name);
+}
+
+// The opening dr_step and dr_sample share: the engine is ready for (sampler, B, T), the options are ones this call can run
+// under, and the buffers its launches point into exist before anything is launched or captured.  step: dr_step's t, checked
+// in its place; null for dr_sample, whose i0 is then the chain position option "start_step" names.  NB: the sampler's batch.
+int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, int& NB, int& i0, hipStream_t st) {
+    int rc = check_ready(e, sampler, B, T);
+    if (rc) return rc;
+    if (step) {
+        const int t = *step;
+        if (t < 0 || t >= e->S) return fail(e, DR_EINVAL, "step %d out of range", t);
+        if (!e->rs_steps.empty() && std::find(e->rs_steps.begin(), e->rs_steps.end(), t) == e->rs_steps.end())
+            return fail(e, DR_EINVAL, "step %d is not visited by the respaced chain (option sampling_steps = %d)", t, e->opt.steps);
+    }
+    if ((rc = check_options(e, sampler, B, NB, T))) return rc;
+    i0 = 0;
+    if (!step && (rc = start_position(e, i0))) return rc;
+    if ((rc = ensure_workspace(e, NB, T))) return rc;
+    if (e->opt.solver == 2) {      // order 2: the history buffer (two halves)
+        const size_t need = 2 * (size_t)B * T * 88;
+        if (!e->hist.fits(need)) e->hist_key.valid = false;
+        if ((rc = grow_chain_buffer(e, e->hist, need, st))) return rc;
+    }
+    // option "x0_threshold": the work buffer of the threshold launches (tickets and counts start at zero: armed)
+    if (e->opt.x0_thresh != 0 && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
+    return DR_OK;
 }
 
 }  // namespace drh
@@ -796,27 +802,16 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
             int first_sample, void* stream) {
     if (!e || !d_x) return fail(e, DR_EINVAL, "null argument");
     DeviceGuard guard(e->cfg.device);
-    int rc = check_ready(e, sampler, B, T);
+    int NB, i0;
+    int rc = open_chain_call(e, sampler, B, T, &t, NB, i0, (hipStream_t)stream);
     if (rc) return rc;
-    if (t < 0 || t >= e->S) return fail(e, DR_EINVAL, "step %d out of range", t);
-    if (!e->rs_steps.empty() && std::find(e->rs_steps.begin(), e->rs_steps.end(), t) == e->rs_steps.end())
-        return fail(e, DR_EINVAL, "step %d is not visited by the respaced chain (option sampling_steps = %d)", t, e->opt_steps);
-    if ((rc = check_windows(e, B, T))) return rc;
-    int NB, n_cond;
-    if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
-    if ((rc = check_solver(e, sampler))) return rc;
-    if ((rc = check_x0_clamp(e, sampler))) return rc;
-    if ((rc = check_guidance(e, B, NB))) return rc;
-    if ((rc = ensure_workspace(e, NB, T))) return rc;
-    if ((rc = ensure_history(e, B, T, (hipStream_t)stream))) return rc;
-    if ((rc = ensure_threshold(e, B, (hipStream_t)stream))) return rc;
-    if (e->opt_solver == 2) {
+    if (e->opt.solver == 2) {
         // the history is engine state: the chain's first step starts one, every other step continues the one the previous
         // dr_step left - the preceding visited step of the same (sampler, B, T)
         // (option "start_step": the step it names starts a history too - its row has c = 0, run_step)
         const int first = chain_step(e, 0);
         auto& k = e->hist_key;
-        if (t != first && t != e->opt_start) {
+        if (t != first && t != e->opt.start) {
             const bool same = k.valid && k.sampler == sampler && k.B == B && k.T == T;
             int expect = first;
             if (same)
@@ -835,7 +830,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if ((rc = run_step(e, sampler, d_x, d_noise, B, T, t, w, seed, first_sample, (hipStream_t)stream, &res))) return rc;
     if (res != d_x)      // the fused step wrote x_{t-1} into the engine's buffer: hand it back in place
         HIPCHK(e, hipMemcpyAsync(d_x, res, (size_t)B * T * 88 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (e->opt_solver == 2 && t > 0) { auto& k = e->hist_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
+    if (e->opt.solver == 2 && t > 0) { auto& k = e->hist_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
     return DR_OK;
 }
 
@@ -843,20 +838,10 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
               int first_sample, int use_graph, void* stream) {
     if (!e || !d_x) return fail(e, DR_EINVAL, "null argument");
     DeviceGuard guard(e->cfg.device);
-    int rc = check_ready(e, sampler, B, T);
-    if (rc) return rc;
-    if ((rc = check_windows(e, B, T))) return rc;
-    int NB, n_cond;
-    if (sampler_shape(sampler, B, NB, n_cond)) return fail(e, DR_EINVAL, "unknown sampler %d", sampler);
-    if ((rc = check_solver(e, sampler))) return rc;
-    if ((rc = check_x0_clamp(e, sampler))) return rc;
-    if ((rc = check_guidance(e, B, NB))) return rc;
-    int i0 = 0;      // option "start_step": the chain position of the first step this call runs
-    if ((rc = start_position(e, i0))) return rc;
-    if ((rc = ensure_workspace(e, NB, T))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = ensure_history(e, B, T, st))) return rc;
-    if ((rc = ensure_threshold(e, B, st))) return rc;
+    int NB, i0;      // i0: the chain position of the first step this call runs (option "start_step")
+    int rc = open_chain_call(e, sampler, B, T, nullptr, NB, i0, st);
+    if (rc) return rc;
     e->hist_key.valid = false;      // (a whole chain uses the history buffers: a dr_step sequence does not continue across it)
     if (e->tuning_epoch != tuning_epoch().load()) {      // a tune.* knob changed (any engine, any thread): the cached chain is stale
         if ((rc = drop_chain(e))) return rc;
@@ -874,7 +859,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         float* cur = xbuf;
         e->hist_par = 0;      // (option "solver_order": the first step reads no history - its row has c = 0)
         // option "start_noise": xbuf holds a clean roll - diffuse it to the first step, in place, in front of everything
-        if (e->opt_start_noise)
+        if (e->opt.start_noise)
             if (int r = run_diffuse(e, xbuf, d_noise, B, T, chain_step(e, i0), seed, first_sample, st)) return r;
         // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows) - from
         // position i0 on (option "start_step"; 0: the whole chain)
@@ -899,13 +884,10 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
 
     GraphKey key;
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
-    key.draws = e->opt_draws; key.draw_G = e->opt_draws > 1 ? e->opt_draw_G : 0; key.fe_B = e->fe_B;
-    if (NB == 2 * B) { key.g_lo = e->opt_guid.lo; key.g_hi = e->opt_guid.hi_eff(e->S); }
-    key.order = e->opt_solver; key.hist = e->opt_solver == 2 ? (const float*)e->hist : nullptr;
-    key.solver_noise = e->opt_solver != 0 ? e->opt_solver_noise : 0;
-    key.start = chain_step(e, i0); key.start_noise = e->opt_start_noise;
-    key.x0_clamp = e->opt_x0_clamp;
-    key.x0_thresh = e->opt_x0_thresh; key.thresh_work = e->opt_x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
+    key.opt = effective(e->opt, NB == 2 * B, e->S, chain_step(e, i0));
+    key.fe_B = e->fe_B;
+    key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
+    key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
     for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
         drop_graph(e);
         if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

@@ -98,7 +98,7 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     if (layer < 0 || layer >= e->L || t < 0 || t >= e->S || n_cond < 0 || n_cond > NB)
         return fail(e, DR_EINVAL, "bad argument");
     // (option "draws": the conditional rows are draws x the clips of the last dr_frontend, read modulo fe_B)
-    if (n_cond > 0 && ((long)e->fe_B * e->opt_draws < n_cond || e->fe_T != T)) return fail(e, DR_ESTATE, "dr_frontend needed for n_cond > 0");
+    if (n_cond > 0 && ((long)e->fe_B * e->opt.draws < n_cond || e->fe_T != T)) return fail(e, DR_ESTATE, "dr_frontend needed for n_cond > 0");
     DeviceGuard guard(e->cfg.device);
     int rc = ensure_workspace(e, NB, T);
     if (rc) return rc;

@@ -47,6 +47,52 @@ struct LayerW {
     int dil = 1;
 };
 
+// The value options a chain is run under (dr_set_option; each name's accepted values and what setting it drops or rebuilds:
+// abi.hip, set_option).  dr_engine::opt holds them as set; a captured chain's key holds effective() of them.
+struct ChainOptions {
+    int steps = 0;                      // option "sampling_steps": n of a respaced chain; 0 (and S) = every step
+    int win_O = 0;                      // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
+                                        // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
+    int draws = 1;                      // option "draws": D > 1 = the B rolls are D draws of the B / D clips of the last dr_frontend, draw-major
+    int draw_G = 0;                     // option "draw_stride": Philox key distance between two draws of a clip; 0 = the clips of the batch
+    dr::GuidanceInterval guid;          // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
+    // option "solver_order": 0 = the sampler's own update; 1 / 2 = the x0-prediction samplers integrate their prediction
+    // with the first-order exponential integrator in lambda / DPM-Solver++ (2M) (update_quad.h: solver_quad)
+    int solver = 0;
+    // option "solver_noise": 1 = the solver's stochastic form (SDE-DPM-Solver++): other rows 0 / 1 / 4, and mode 5 adds c4 z.
+    // Stored always, read only while solver != 0
+    int solver_noise = 0;
+    // option "start_step": the visited step a chain begins at (d_x on entry is x at that step); -1 = the chain's first
+    // visited step.  option "start_noise": 1 = d_x on entry to dr_sample is a clean roll, diffused to that step by the
+    // chain's first node (update.hip: diffuse_kernel)
+    int start = -1, start_noise = 0;
+    // option "x0_clip": 0 = off; 1 / 2 = the x0-prediction samplers clamp the prediction their update consumes to [0, 1] /
+    // [-1, 1] (update_quad.h: clamp_quad); the epsilon samplers refuse a non-zero value (abi.hip: check_options)
+    int x0_clamp = 0;
+    // option "x0_threshold": 0 = off; 5000 .. 10000 = the percentile (1 / 10000) of dynamic thresholding, a refinement of
+    // "x0_clip" (refused without it: abi.hip: check_options).  A thresholded step offers no tail plan: the stack launch, the
+    // head projections, the threshold launches (threshold.hip) and update_thresh_kernel (plan.hip: run_step)
+    int x0_thresh = 0;
+    bool operator==(const ChainOptions& o) const {
+        return steps == o.steps && win_O == o.win_O && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
+               guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
+               start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh;
+    }
+};
+// The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
+// under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
+// a solver order, the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
+// step the chain visits first (abi.hip: start_position).
+inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t) {
+    if (o.draws <= 1) o.draw_G = 0;
+    if (o.solver == 0) o.solver_noise = 0;
+    o.guid = guiding ? dr::GuidanceInterval{o.guid.lo, o.guid.hi_eff(S)} : dr::GuidanceInterval{};
+    o.start = start_t;
+    return o;
+}
+// the samplers whose network output is the x0 prediction (DR_SAMPLER_* 0-5); the others predict epsilon
+inline bool predicts_x0(int sampler) { return !(sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS); }
+
 // What a captured chain bakes in: sampler, shape, the engine's work buffer and the injected-noise address (test
 // mode).  Seed, batch offset and guidance weight live in the DynParams device block; the caller's roll buffer
 // is copied into / out of the work buffer around the launch.
@@ -55,33 +101,19 @@ struct GraphKey {
     float* x = nullptr;
     const float* noise = nullptr;
     bool w_zero = false;        // guidance weight 0 captures a different (conditional-only) chain
+    // ... and the effective options: the draw layout of the update's Philox keys, which steps run the unconditional
+    // evaluation, how the prediction is integrated, clamped and thresholded, where the chain begins.  Setting one of them
+    // drops nothing ("sampling_steps" and "window_overlap" apart): a chain captured under another value is simply not
+    // replayed, and a façade that sets them around every call replays one graph.
+    ChainOptions opt;
     // A captured chain also bakes the clip count of the conditioner tensors (GemmArgs::c_n and the per-layer offsets
-    // l * fe_B * 2 Cp T) and the draw layout of the update's Philox keys (UpdateArgs::draw_n / draw_G): options "draws" /
-    // "draw_stride" do not drop the chain, they are part of its key (a façade that sets them around every call replays
-    // one graph), and so is fe_B - dr_frontend drops the chain when it changes, the key keeps that from being load-bearing.
-    int draws = 1, draw_G = 0, fe_B = 0;
-    // ... and which steps run the unconditional evaluation: options "guidance_t_min" / "guidance_t_max" (the effective pair)
-    // are part of the key too - a chain captured under another interval is never replayed
-    int g_lo = 0, g_hi = 0;
-    // ... and how the prediction is integrated: option "solver_order" (the update's mode, its table and the history
-    // buffers' parity per node), like "draws" part of the key - setting it drops nothing
-    int order = 0;
-    const float* hist = nullptr;      // the history buffer (null: order < 2)
-    int solver_noise = 0;             // option "solver_noise" (the effective value: 0 while order is 0), part of the key as well
-    // ... and where the chain begins: options "start_step" (the effective step: the chain's first visited step when the
-    // option is off) and "start_noise" (whether a diffusion node stands in front of the first step) - setting them drops nothing
-    int start = -1, start_noise = 0;
-    // ... and whether the update clamps its prediction: option "x0_clip" (UpdateArgs::clamp_lo / clamp_hi of every node), part of the key too
-    int x0_clamp = 0;
-    // ... and thresholds it: option "x0_threshold" (the threshold launches and the update's other form are nodes of the chain)
-    // and the work buffer their arguments point into - a buffer that grew since is another chain
-    int x0_thresh = 0;
-    const unsigned* thresh_work = nullptr;
+    // l * fe_B * 2 Cp T): dr_frontend drops the chain when fe_B changes, the key keeps that from being load-bearing.
+    int fe_B = 0;
+    const float* hist = nullptr;              // the history buffer of solver order 2 (null: order < 2; the parity is baked per node)
+    const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
-               draws == o.draws && draw_G == o.draw_G && fe_B == o.fe_B && g_lo == o.g_lo && g_hi == o.g_hi &&
-               order == o.order && hist == o.hist && solver_noise == o.solver_noise && start == o.start && start_noise == o.start_noise &&
-               x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && thresh_work == o.thresh_work;
+               opt == o.opt && fe_B == o.fe_B && hist == o.hist && thresh_work == o.thresh_work;
     }
 };
 
@@ -196,8 +228,7 @@ struct dr_engine {
     drh::StackSync sync;                // group counters, XCC tags, time-out flags, window ready words
     int opt_tail = 1;                   // fused step: layer 0's shared conv inside the stack launch + the tail kernel
     int64_t tail_launches = 0;
-    int opt_win_O = 0;                  // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
-                                        // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
+    drh::ChainOptions opt;              // the value options of dr_set_option a chain is run under
     std::vector<int> win_marks;         // option "window_break", ascending: the windows that start a new recording (window 0 always does)
     // The per-window table behind UpdateArgs::win_tab (kernels.h: window_entry).  A one-block kernel rewrites it on the
     // call's stream in front of every launch sequence / graph launch that reads it, as launch_set_dyn rewrites d_dyn; its
@@ -206,22 +237,13 @@ struct dr_engine {
     // stream, so the rewrite starts only when every launch of the earlier chain has finished - and an engine is used
     // from one stream at a time (diffroll_amd.h), as d_dyn, xwork and the activation workspace already require.
     drh::DevBuf<unsigned> d_wintab;
-    int opt_draws = 1;                  // option "draws": D > 1 = the B rolls are D draws of the B / D clips of the last dr_frontend, draw-major
-    int opt_draw_G = 0;                 // option "draw_stride": Philox key distance between two draws of a clip; 0 = the clips of the batch
-    int opt_steps = 0;                  // option "sampling_steps": n of a respaced chain; 0 (and S) = every step
     std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
     drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor
                                         // is not t - 1 replaced by the respaced row (build_respaced); empty when rs_steps is
-    // option "solver_order": 0 = the sampler's own update; 1 / 2 = the x0-prediction samplers integrate their prediction
-    // with the first-order exponential integrator in lambda / DPM-Solver++ (2M) (update_quad.h: solver_quad)
-    int opt_solver = 0;
-    std::vector<float> h_solver;        // (2 S, 5): rows [0, S) of the chain's visited steps (build_solver; unvisited rows are
+    std::vector<float> h_solver;        // option "solver_order", (2 S, 5): rows [0, S) of the chain's visited steps (build_solver; unvisited rows are
                                         // zero), rows [S, 2 S) the same rows with c = 0 - step t as the FIRST step of a chain
                                         // (option "start_step"); a table of their own, so no row a captured chain reads moves
     drh::DevBuf<float> d_solver;        // ... on the device
-    // option "solver_noise": 1 = the solver's stochastic form (SDE-DPM-Solver++): other rows 0 / 1 / 4, and mode 5 adds c4 z.
-    // Stored always, read only while opt_solver != 0
-    int opt_solver_noise = 0;
     // order 2: the previous step's prediction.  One buffer of two (B, T, 88) halves, allocated on first use and used
     // ping-pong (the tail kernel's row tiles recompute a quad in different blocks: the one that stores must not overwrite
     // what the others still read); hist_par = the half the next step reads.  A captured chain bakes the parity per node.
@@ -229,19 +251,7 @@ struct dr_engine {
     int hist_par = 0;
     // dr_step under order 2: what the history holds - the prediction of step hist_t of a (sampler, B, T) chain
     struct { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; } hist_key;
-    // option "start_step": the visited step a chain begins at (d_x on entry is x at that step); -1 = the chain's first
-    // visited step.  option "start_noise": 1 = d_x on entry to dr_sample is a clean roll, diffused to that step by the
-    // chain's first node (update.hip: diffuse_kernel)
-    int opt_start = -1, opt_start_noise = 0;
-    // option "x0_clip": 0 = off; 1 / 2 = the x0-prediction samplers clamp the prediction their update consumes to [0, 1] /
-    // [-1, 1] (update_quad.h: clamp_quad); the epsilon samplers refuse a non-zero value (abi.hip: check_x0_clamp)
-    int opt_x0_clamp = 0;
-    // option "x0_threshold": 0 = off; 5000 .. 10000 = the percentile (1 / 10000) of dynamic thresholding, a refinement of
-    // "x0_clip" (refused without it: abi.hip: check_x0_clamp).  A thresholded step offers no tail plan: the stack launch, the
-    // head projections, the threshold launches (threshold.hip) and update_thresh_kernel (plan.hip: run_step)
-    int opt_x0_thresh = 0;
-    drh::DevBuf<unsigned> thresh_work;  // its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
-    dr::GuidanceInterval opt_guid;      // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
+    drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
@@ -344,7 +354,7 @@ struct Range {
 int clear_stack_timeout(dr_engine* e);
 int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab: the names of dr_debug_set_option too
 void set_kfd_root(const char* root);                                      // dr_debug_kfd_root
-int build_respaced(dr_engine* e);       // option "sampling_steps": rs_steps and d_coef_rs from opt_steps and h_coef
+int build_respaced(dr_engine* e);       // option "sampling_steps": rs_steps and d_coef_rs from opt.steps and h_coef
 int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_solver from the chain's steps and h_coef
 int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);      // dr_debug_threshold
 
@@ -383,6 +393,8 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
                 hipStream_t st, bool zero_spec = false, const int* tsel = nullptr, TailPlan* tail = nullptr);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& zero_spec);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond);
+// the layout half of an update's arguments for B rolls of T frames: n, per_sample, dyn, win_H, draw_n / draw_G, win_tab
+UpdateArgs update_base(const dr_engine* e, int B, int T);
 // option "x0_threshold": the arguments of a step's threshold launches, from the update they precede
 ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u);
 struct ChainState {

@@ -402,6 +402,20 @@ int sampler_shape(int sampler, int B, int& NB, int& n_cond) {
     return sampler_shape(sampler, B, NB, n_cond, fam, z);
 }
 
+UpdateArgs update_base(const dr_engine* e, int B, int T) {
+    UpdateArgs u{};
+    u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
+    u.dyn = e->use_dyn ? e->d_dyn : nullptr;
+    u.win_H = e->opt.win_O > 0 ? T - e->opt.win_O : 0;
+    // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)
+    if (e->opt.draws > 1) { u.draw_n = B / e->opt.draws; u.draw_G = e->opt.draw_G > 0 ? e->opt.draw_G : u.draw_n; }
+    // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
+    // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
+    // (the table has STACK_GROUPS words: a larger batch is one recording - check_options refuses marks there)
+    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt.draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    return u;
+}
+
 // One reverse step.  The result is written in place on x - or, when the fused step ran (tail kernel), into e->xalt (or
 // chain->x_out): *result tells which; chain (optional) carries "h / hd of this step are already there" from step to step.
 int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int T, int t, float w, uint64_t seed,
@@ -414,39 +428,30 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // outside the guidance interval (options "guidance_t_min" / "guidance_t_max") is that step, whatever the caller's w;
     // w == 0 is the empty interval (launch_plan.h: plan_step).
     const bool guiding = NB == 2 * B;
-    const StepShapes shapes = plan_step(NB, n_cond, B, e->opt_guid, e->S, w == 0.f, t, chain ? chain->next_t : -1);
+    const StepShapes shapes = plan_step(NB, n_cond, B, e->opt.guid, e->S, w == 0.f, t, chain ? chain->next_t : -1);
     NB = shapes.now.NB; n_cond = shapes.now.n_cond;
     if (guiding && !shapes.now.dual) w = 0.f;
-    UpdateArgs u{};
+    UpdateArgs u = update_base(e, B, T);
     u.x = x; u.x0c = e->x0buf; u.x0u = (NB == 2 * B) ? e->x0buf + (size_t)B * T * 88 : nullptr;
     // row t of the family's table: the committed one, or under option "sampling_steps" the row for t's successor in the
     // respaced chain (build_respaced; unvisited rows are never read)
     const float* coef = e->rs_steps.empty() ? e->d_coef : e->d_coef_rs;
     u.noise = noise; u.coef = coef + ((size_t)family * e->S + t) * 5; u.t = t; u.mode = family;
-    u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     u.seed = seed; u.first_sample = first_sample;
     // option "solver_order" (the callers have refused the epsilon samplers): the solver's own row and update.  Noise and
     // seed are read only where the row's c4 is not 0 (option "solver_noise": the z of the DDPM updates at this step).  Order
     // 2 reads the previous step's prediction where the row says so and leaves this step's for the next (the two halves of
     // the history buffer, ping-pong); order 1 neither reads nor stores.
-    if (e->opt_solver != 0 && family <= DR_COEF_DDIM_X0) {
-        const bool hist = e->opt_solver == 2;
+    if (e->opt.solver != 0 && predicts_x0(sampler)) {
+        const bool hist = e->opt.solver == 2;
         // (option "start_step": the step it names is a chain's first - the copy of its row with c = 0, abi.hip: build_solver)
-        u.coef = e->d_solver + ((size_t)(t == e->opt_start ? e->S : 0) + t) * 5; u.mode = 5;
+        u.coef = e->d_solver + ((size_t)(t == e->opt.start ? e->S : 0) + t) * 5; u.mode = 5;
         u.hist = hist ? (float*)e->hist : nullptr; u.hist_par = hist ? e->hist_par : 0;
         if (hist) e->hist_par ^= 1;
     }
     // option "x0_clip" (the callers have refused the epsilon samplers): the update clamps the prediction it consumes
-    if (e->opt_x0_clamp != 0 && family <= DR_COEF_DDIM_X0) { u.clamp_lo = e->opt_x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f; }
-    u.dyn = e->use_dyn ? e->d_dyn : nullptr;
-    u.win_H = e->opt_win_O > 0 ? T - e->opt_win_O : 0;
-    // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)
-    if (e->opt_draws > 1) { u.draw_n = B / e->opt_draws; u.draw_G = e->opt_draw_G > 0 ? e->opt_draw_G : u.draw_n; }
-    // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
-    // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
-    // (the table has STACK_GROUPS words: a larger batch is one recording - check_windows refuses marks there)
-    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt_draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    if (e->opt.x0_clamp != 0 && predicts_x0(sampler)) { u.clamp_lo = e->opt.x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f; }
     float* const xalt = chain && chain->x_out ? chain->x_out : e->xalt;
     TailPlan plan;
     plan.u = u; plan.x_out = xalt; plan.u_B = B;
@@ -457,7 +462,7 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // (x and the tail kernel's output buffer must differ: a caller that hands us xalt itself gets the unfused tail)
     // option "x0_threshold": the selection sits between the network and the update, so the step offers no tail plan - the
     // evaluation keeps its fused stack launch, the head projections write e->x0buf, the rest are ordinary launches
-    const bool thresh = e->opt_x0_thresh != 0 && u.clamp_lo < u.clamp_hi;
+    const bool thresh = e->opt.x0_thresh != 0 && u.clamp_lo < u.clamp_hi;
     TailPlan* offer = (result && x != xalt && !thresh) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
@@ -483,7 +488,7 @@ ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u) {
     a.u = u;
     // m = (lo + hi) / 2, r = (hi - lo) / 2 of the range "x0_clip" names: [0, 1] or [-1, 1], both exact
     a.m = 0.5f * (u.clamp_lo + u.clamp_hi); a.r = 0.5f * (u.clamp_hi - u.clamp_lo);
-    a.v = e->opt_x0_thresh;
+    a.v = e->opt.x0_thresh;
     a.work = e->thresh_work;
     return a;
 }

@@ -58,9 +58,8 @@ _MIRRORED = {
 class Engine:
     """One engine handle per (device, stream).  Not re-entrant."""
 
-    # the library's defaults of options 'start_step' / 'start_noise' / 'solver_noise' / 'x0_clip', also for a subclass that does not run __init__
-    start_step, start_noise, solver_noise = _MIRRORED["start_step"], _MIRRORED["start_noise"], _MIRRORED["solver_noise"]
-    x0_clip, x0_threshold = _MIRRORED["x0_clip"], _MIRRORED["x0_threshold"]
+    # the library's defaults of the mirrored options are class attributes too, for a subclass that does not run __init__
+    locals().update(_MIRRORED)
 
     def __init__(self, *, residual_channels: int, residual_layers: int, kernel_size: int,
                  dilation_base: int, dilation_bound: int, n_mels: int, timesteps: int,

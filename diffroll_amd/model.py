@@ -24,8 +24,7 @@ import torch.nn as nn
 
 from .engine import Engine
 from .ensemble import aggregate, check_draws
-from .schedule import (check_guidance_interval, check_sampling_steps, check_solver_noise, check_solver_order, check_start, check_x0_clip, check_x0_threshold,
-                       respaced_steps)
+from .schedule import respaced_steps, sampling_options
 
 _SAMPLERS = ("ddpm_x0", "cfdg_ddpm_x0", "generation_ddpm_x0", "inpainting_ddpm_x0",
              "ddim_x0", "cfdg_ddim_x0", "ddpm", "ddim", "ddim2ddpm")
@@ -136,30 +135,10 @@ class ClassifierFreeDiffRoll(nn.Module):
         spec_args = _attr(dict(spec_args))
         if sampling.type not in _SAMPLERS:
             raise AttributeError(sampling.type)                               # getattr at task/diffusion.py:255
-        # an extension: sampling.steps = n runs the chain on n respaced steps (option "sampling_steps"); absent / None in
-        # the reference's configs = every step
-        check_sampling_steps(sampling.get("steps"), timesteps)
-        # an extension: sampling.draws = D samples D rolls per clip in one chain (option "draws") and scores / exports their
-        # mean (diffroll_amd/ensemble.py); absent / None / 1 = one roll per clip
-        check_draws(sampling.get("draws"))
-        # an extension: sampling.guidance_interval = [lo, hi] guides the steps lo <= t <= hi only (options "guidance_t_min" /
-        # "guidance_t_max"); absent / None = the whole chain, the reference's behaviour
-        check_guidance_interval(sampling.get("guidance_interval"), timesteps, sampling.type)
-        # an extension: sampling.solver_order = 1 / 2 integrates the x0 prediction with a multistep ODE solver (option
-        # "solver_order": DPM-Solver++), the companion of sampling.steps; absent / None / 0 = the sampler's own update
-        check_solver_order(sampling.get("solver_order"), sampling.type)
-        # an extension: sampling.solver_noise = 1 makes that solver stochastic (option "solver_noise": SDE-DPM-Solver++, the z's
-        # of the ddpm_x0 chain); absent / None / 0 = the deterministic solver
-        check_solver_noise(sampling.get("solver_noise"), sampling.type, sampling.get("solver_order"))
-        # an extension: sampling.start_step = t / sampling.strength = s start the chain at an intermediate visited step
-        # (options "start_step" / "start_noise"): refine or vary a given roll, resume a chain; absent / None = the whole chain
-        check_start(sampling.get("start_step"), sampling.get("strength"), respaced_steps(timesteps, sampling.get("steps") or 0))
-        # an extension: sampling.x0_clip = 1 clamps the x0 prediction every update consumes to the roll's range norm_args[0] ..
-        # norm_args[1] (option "x0_clip": the static "clip_denoised"); absent / None / 0 = the prediction as it comes out
-        check_x0_clip(sampling.get("x0_clip"), sampling.type, norm_args)
-        # an extension: sampling.x0_threshold = 0.995 rescales instead of clamping wherever that quantile of |y - m| over the
-        # roll exceeds the range's half-width (option "x0_threshold": dynamic thresholding); needs x0_clip; absent / None / 0 = off
-        check_x0_threshold(sampling.get("x0_threshold"), sampling.type, sampling.get("x0_clip"))
+        # extensions, absent / None in the reference's configs (each key, its validator and the engine option it becomes:
+        # schedule.sampling_options): steps, draws, guidance_interval, solver_order, solver_noise, start_step / strength,
+        # x0_clip, x0_threshold
+        sampling_options(sampling, timesteps, norm_args)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
             n_mels=n_mels, norm_args=list(norm_args), residual_layers=residual_layers,
@@ -251,12 +230,7 @@ class ClassifierFreeDiffRoll(nn.Module):
 
     @property
     def engine(self) -> Engine:
-        interval = self.guidance_interval()               # (a malformed one raises here: before any GPU work)
-        order = self.solver_order()                       # (likewise)
-        snoise = self.solver_noise()                      # (likewise)
-        start = self.start_step()                         # (likewise)
-        clip = self.x0_clip()                             # (likewise)
-        thresh = self.x0_threshold()                      # (likewise)
+        options = self.sampling_options()                 # (a bad value raises here: before any GPU work)
         if self._engine is None:
             self._engine = Engine(device=self._device, betas=self._betas(), norm_mode=str(self.hparams.norm_args[2]),
                                   fe_window=self.__dict__.get("_ckpt_window"), fe_fb=self.__dict__.get("_ckpt_fb"),
@@ -271,21 +245,14 @@ class ClassifierFreeDiffRoll(nn.Module):
         want = 1 if self.accumulation == "single_chain" else 2
         if self._engine.blocked_accumulation != want:
             self._engine.set_option("blocked_accumulation", want)
-        steps = self.sampling_steps()
-        if self._engine.sampling_steps != steps:          # (a change drops the engine's captured chain)
-            self._engine.set_option("sampling_steps", steps)
-        if self._engine.guidance_interval != interval:    # (part of the captured chain's key: nothing is dropped)
-            self._engine.set_guidance_interval(*interval)
-        if self._engine.solver_order != order:            # (likewise part of the key)
-            self._engine.set_option("solver_order", order)
-        if self._engine.solver_noise != snoise:           # (likewise part of the key)
-            self._engine.set_option("solver_noise", snoise)
-        if self._engine.start_step != start:              # (likewise part of the key)
-            self._engine.set_option("start_step", start)
-        if self._engine.x0_clip != clip:                  # (likewise part of the key)
-            self._engine.set_option("x0_clip", clip)
-        if self._engine.x0_threshold != thresh:           # (likewise part of the key)
-            self._engine.set_option("x0_threshold", thresh)
+        # (a change of "sampling_steps" drops the engine's captured chain; the others are part of its key: nothing is dropped)
+        for name, value in options.items():
+            if name == "draws" or getattr(self._engine, name) == value:      # ("draws" is set around the calls that sample them)
+                continue
+            if name == "guidance_interval":
+                self._engine.set_guidance_interval(*value)
+            else:
+                self._engine.set_option(name, value)
         return self._engine
 
     def start_configured(self):
@@ -293,64 +260,48 @@ class ClassifierFreeDiffRoll(nn.Module):
         sampling = self.__dict__["hparams"].sampling
         return next((k for k in ("start_step", "strength") if sampling.get(k) is not None), None)
 
-    def start_step(self) -> int:
-        """hparams.sampling.start_step / .strength as the engine's option "start_step" takes them (-1: the chain's first
-        step), or -1 while one of the reference's single-step methods runs.  Read at every use; a bad value raises
-        ValueError before any GPU work (schedule.check_start)."""
+    def sampling_options(self) -> Dict[str, Any]:
+        """hparams.sampling as the engine's options take it, by option name (schedule.sampling_options).  Read at every use; a
+        bad value raises ValueError before any GPU work.  While one of the reference's single-step methods runs, the options
+        that shape the chain's steps and updates read as off; which steps guide and how many rolls a clip gets stay."""
         hp = self.__dict__["hparams"]
-        start = check_start(hp.sampling.get("start_step"), hp.sampling.get("strength"),
-                            respaced_steps(int(hp.timesteps), check_sampling_steps(hp.sampling.get("steps"), hp.timesteps)))
-        return -1 if self.__dict__.get("_stride1") else start
+        options = sampling_options(hp.sampling, hp.timesteps, hp.norm_args)
+        if self.__dict__.get("_stride1"):
+            off = sampling_options({}, hp.timesteps)
+            options = {k: v if k in ("guidance_interval", "draws") else off[k] for k, v in options.items()}
+        return options
+
+    def start_step(self) -> int:
+        """hparams.sampling.start_step / .strength as option "start_step" takes them (-1: the chain's first step)."""
+        return self.sampling_options()["start_step"]
 
     def solver_order(self) -> int:
-        """hparams.sampling.solver_order as the engine's option takes it (0: the sampler's own update), or 0 while one of
-        the reference's single-step methods runs.  Read at every use; a bad value or an epsilon sampler raises ValueError
-        before any GPU work."""
-        hp = self.__dict__["hparams"]
-        order = check_solver_order(hp.sampling.get("solver_order"), hp.sampling.type)
-        return 0 if self.__dict__.get("_stride1") else order
+        """hparams.sampling.solver_order as the engine's option takes it (0: the sampler's own update)."""
+        return self.sampling_options()["solver_order"]
 
     def solver_noise(self) -> int:
-        """hparams.sampling.solver_noise as the engine's option takes it (0: the deterministic solver), or 0 while one of the
-        reference's single-step methods runs.  Read at every use; a bad value, a value set without solver_order or with an
-        epsilon sampler raises ValueError before any GPU work."""
-        hp = self.__dict__["hparams"]
-        value = check_solver_noise(hp.sampling.get("solver_noise"), hp.sampling.type, hp.sampling.get("solver_order"))
-        return 0 if self.__dict__.get("_stride1") else value
+        """hparams.sampling.solver_noise as the engine's option takes it (0: the deterministic solver)."""
+        return self.sampling_options()["solver_noise"]
 
     def x0_clip(self) -> int:
-        """hparams.sampling.x0_clip as the engine's option takes it (0: off, 1: the range (0, 1) of hparams.norm_args, 2:
-        (-1, 1)), or 0 while one of the reference's single-step methods runs.  Read at every use; a bad value, a range the
-        engine has no code for or an epsilon sampler raises ValueError before any GPU work."""
-        hp = self.__dict__["hparams"]
-        value = check_x0_clip(hp.sampling.get("x0_clip"), hp.sampling.type, hp.norm_args)
-        return 0 if self.__dict__.get("_stride1") else value
+        """hparams.sampling.x0_clip as the engine's option takes it (0: off, 1: the range (0, 1) of hparams.norm_args, 2: (-1, 1))."""
+        return self.sampling_options()["x0_clip"]
 
     def x0_threshold(self) -> int:
-        """hparams.sampling.x0_threshold as the engine's option takes it (0: off, else the percentile in units of 1 / 10000),
-        or 0 while one of the reference's single-step methods runs.  Read at every use; a bad value, a value without
-        hparams.sampling.x0_clip or an epsilon sampler raises ValueError before any GPU work."""
-        hp = self.__dict__["hparams"]
-        value = check_x0_threshold(hp.sampling.get("x0_threshold"), hp.sampling.type, hp.sampling.get("x0_clip"))
-        return 0 if self.__dict__.get("_stride1") else value
+        """hparams.sampling.x0_threshold as the engine's option takes it (0: off, else the percentile in units of 1 / 10000)."""
+        return self.sampling_options()["x0_threshold"]
 
     def guidance_interval(self):
-        """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain.  Read
-        at every use, like the other hparams.sampling keys; raises ValueError for a malformed interval or a sampler that
-        does not guide - before any GPU work (every sampling method reaches the engine through here)."""
-        hp = self.__dict__["hparams"]
-        return check_guidance_interval(hp.sampling.get("guidance_interval"), hp.timesteps, hp.sampling.type)
+        """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain."""
+        return self.sampling_options()["guidance_interval"]
 
     def sampling_steps(self) -> int:
-        """n of hparams.sampling.steps (0: every step), or 0 while one of the reference's single-step methods runs."""
-        if self.__dict__.get("_stride1"):
-            return 0
-        hp = self.__dict__["hparams"]
-        return check_sampling_steps(hp.sampling.get("steps"), hp.timesteps)
+        """n of hparams.sampling.steps (0: every step)."""
+        return self.sampling_options()["sampling_steps"]
 
     def draws(self) -> int:
         """D of hparams.sampling.draws: the rolls predict_step / sampling / test_step sample per clip (1: one)."""
-        return check_draws(self.__dict__["hparams"].sampling.get("draws"))
+        return self.sampling_options()["draws"]
 
     def visited_steps(self):
         """The diffusion steps sample() visits, in chain order (timesteps-1 .. 0, or hparams.sampling.steps of them)."""

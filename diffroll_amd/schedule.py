@@ -246,6 +246,35 @@ def respaced_steps(timesteps: int, n: int) -> List[int]:
     return [(2 * i * (S - 1) + (n - 1)) // (2 * (n - 1)) for i in range(n - 1, -1, -1)]
 
 
+def sampling_options(sampling, timesteps, norm_args=(0, 1)) -> Dict[str, object]:
+    """hparams.sampling (the CLI's task.sampling) read once: every key above through its validator, in this order, and the
+    values the engine's options take, by option name - "guidance_interval" is the pair of "guidance_t_min" / "guidance_t_max",
+    "start_step" comes from the keys start_step / strength.  A refusal is the validator's own ValueError, with the key it
+    belongs to as its attribute `key`."""
+    from .ensemble import check_draws
+    get, sampler = sampling.get, sampling.get("type")
+    started = get("start_step") is not None or get("strength") is not None      # (the visited steps are only needed then)
+    checks = (
+        ("sampling_steps", "steps", lambda: check_sampling_steps(get("steps"), timesteps)),
+        ("draws", "draws", lambda: check_draws(get("draws"))),
+        ("guidance_interval", "guidance_interval", lambda: check_guidance_interval(get("guidance_interval"), timesteps, sampler)),
+        ("solver_order", "solver_order", lambda: check_solver_order(get("solver_order"), sampler)),
+        ("solver_noise", "solver_noise", lambda: check_solver_noise(get("solver_noise"), sampler, get("solver_order"))),
+        ("start_step", "start_step" if get("strength") is None else "strength",
+         lambda: check_start(get("start_step"), get("strength"), respaced_steps(timesteps, get("steps") or 0) if started else ())),
+        ("x0_clip", "x0_clip", lambda: check_x0_clip(get("x0_clip"), sampler, norm_args)),
+        ("x0_threshold", "x0_threshold", lambda: check_x0_threshold(get("x0_threshold"), sampler, get("x0_clip"))),
+    )
+    options = {}
+    for option, key, check in checks:
+        try:
+            options[option] = check()
+        except ValueError as err:
+            err.key = key
+            raise
+    return options
+
+
 def sampler_coef_tables(sch: Dict[str, torch.Tensor]) -> torch.Tensor:
     """(5, S, 5) fp32: one table of per-step scalars per coefficient family (DR_COEF_* in
     include/diffroll_amd.h), each scalar evaluated with the reference's own torch expression:

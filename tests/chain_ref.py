@@ -186,7 +186,7 @@ def shared_mean(y: torch.Tensor, plan) -> torch.Tensor:
 
 def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, w: float = 0.0,
                  plan=None, trajectory: bool = False, interval=None, order: int = 0, solver_noise: int = 0,
-                 start: Optional[int] = None):
+                 start: Optional[int] = None, hook: Optional[Callable] = None):
     """THE chain loop of the tests: predict -> shared-frame mean -> update, over the rows of chain_rows - the n visited steps
     (0: all) from `start` on (None: all of them).  x (B, 1, T, 88) is x at the step the chain starts at, spec_c
     (B, n_mels, T) (conditional samplers), noise (S, B, 1, T, 88) or a dict t -> (B, 1, T, 88): noise[t] is the z of visited
@@ -197,6 +197,8 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
     (1 + w_t) c - w_t u, so this is the reference's arithmetic, not the engine's shortcut.
     order = 1 / 2: option "solver_order" - solver_rows and solver_update on the x0 prediction, the previous step's
     prediction carried along, noise drawn only under solver_noise = 1; 0: the sampler's own rows and update.
+    hook(t, y) -> y: what an option does to the prediction behind the shared-frame mean (clip_ref, thresh_ref); the update
+    and the solver's history see what it returns.
     Returns the final roll, or the roll after every step run (steps, B, 1, T, 88) with trajectory=True."""
     S = int(hp["timesteps"])
     family = SAMPLERS[sampler][0]
@@ -209,6 +211,8 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
             y = prediction(params, hp, sampler, x, spec_c, t, w if lo <= t <= hi else 0.0, table)
             if plan is not None:
                 y = shared_mean(y, plan)
+            if hook is not None:
+                y = hook(t, y)
             z = noise[t] if draws and t > 0 else None
             x = solver_update(t, row, x, y, prev, z) if order else update(family, t, row, x, y, z)
             prev = y

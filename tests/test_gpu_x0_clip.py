@@ -266,6 +266,40 @@ def test_fused_path_graph_eager_per_phase_and_nothing_stale_is_replayed():
     assert CC.in_range(g, hp, 1) and CC.in_range(g2, hp, 1) and not CC.in_range(off, hp, 1)
 
 
+@pytest.mark.parametrize("sampler,w,inert", [
+    ("cfdg_ddpm_x0", 3.0, {"solver_noise": 1}),                      # ... while solver_order is 0
+    ("cfdg_ddpm_x0", 3.0, {"draw_stride": 7}),                       # ... while draws is 1
+    ("ddpm_x0", 0.0, {"guidance_t_min": 1, "guidance_t_max": 2}),    # ... on a sampler that does not guide
+], ids=["solver_noise-without-order", "draw_stride-without-draws", "interval-without-guidance"])
+def test_inert_option_values_replay_the_captured_chain(sampler, w, inert):
+    """A value that is inert under the other options is not part of a captured chain's key: setting it replays the chain -
+    the same roll bit for bit, and no launch counted (captured launches count once, at capture).  Control: "x0_clip" 0 -> 1
+    is part of the key and captures again; back at 0 the first roll comes back.  Four steps: the shortest chain with a
+    second-order step and a step into 0."""
+    hp, p, wav, x, _, _ = CC.setup()
+    m = make_model(hp, p, sampler=sampler, w=w)
+    m.hparams.sampling.steps = 4
+    eng = m.engine
+    eng.frontend(wav, CC.TN)
+    x_T = x.squeeze(1).to(eng.device).contiguous()
+
+    def run():
+        return eng.sample(sampler, x_T.clone(), None, w=w, seed=CC.PHILOX_SEED)
+
+    first, c0 = run(), eng.launch_counts()
+    assert sum(c0) > 0                                # (the capture was counted: the counter sees this chain)
+    for name, value in inert.items():
+        eng.set_option(name, value)
+    again = run()
+    assert torch.equal(again, first)
+    assert eng.launch_counts() == c0, (c0, eng.launch_counts())
+    eng.set_option("x0_clip", 1)
+    run()
+    assert eng.launch_counts() != c0
+    eng.set_option("x0_clip", 0)
+    assert torch.equal(run(), first)
+
+
 # ---------------------------------------------------------------------------------------------- 7. dr_step
 def test_dr_step_over_the_visited_steps_ends_where_sample_ends():
     """Order 2: the history the steps hand on is the clamped prediction."""

@@ -1,14 +1,11 @@
 """Option "x0_threshold" (include/diffroll_amd.h) restated on the CPU - test infrastructure, in two parts: the option's
 seven lines with torch.sort (group_stats / threshold: per roll, or per recording's canvas through the window groups), and the
-chain loop of clip_ref.sample_chain with the thresholding in place of the clamp line (sample_chain), composed from
-chain_ref's pieces.  Every line rounds once in fp32, as the header states it; beside the roll the chain returns, per step
+chain loop of chain_ref.sample_chain with the thresholding as its hook, in place of clip_ref's clamp (sample_chain).  Every line rounds once in fp32, as the header states it; beside the roll the chain returns, per step
 and group, q and whether s > r, so that a test can tell whether its inputs threshold at all."""
 from typing import List, Optional
 
 import numpy as np
 import torch
-
-from oracle import diffroll_ref as R
 
 import chain_ref as CR
 import clip_ref as CL
@@ -91,32 +88,20 @@ def threshold(y: torch.Tensor, code: int, v: int, groups):
 
 
 def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, code: int, v: int,
-                 w: float = 0.0, plan=None, trajectory: bool = False, interval=None, order: int = 0, solver_noise: int = 0,
-                 start: Optional[int] = None):
+                 plan=None, **kw):
     """clip_ref.sample_chain's arguments and v, the option's value (0: the clipped chain).  Returns (the final roll - or the
     trajectory -, {t: (G, 2) {q, s}} over the steps run, r)."""
-    S = int(hp["timesteps"])
-    family = CR.SAMPLERS[sampler][0]
-    assert family <= 1 and code, "the threshold refines x0_clip on an x0 prediction"
-    draws = solver_noise if order else family in (0, 2, 4)
-    lo, hi = (0, S - 1) if interval is None else interval
-    table = R.build_embedding(S)
+    assert CR.SAMPLERS[sampler][0] <= 1 and code, "the threshold refines x0_clip on an x0 prediction"
     groups = clip_groups(x.shape[0]) if plan is None else window_groups(plan.n, plan.overlap)
-    prev, traj, stats = None, [], {}
-    with torch.no_grad():
-        for t, row in CR.chain_rows(hp, sampler, n, order, solver_noise, start).items():
-            y = CR.prediction(params, hp, sampler, x, spec_c, t, w if lo <= t <= hi else 0.0, table)
-            if plan is not None:
-                y = CR.shared_mean(y, plan)
-            if v:
-                y, stats[t] = threshold(y, code, v, groups)               # THE line in place of the clamp
-            else:
-                y = y.clamp(*CL.BOUNDS[code])
-            z = noise[t] if draws and t > 0 else None
-            x = CR.solver_update(t, row, x, y, prev, z) if order else CR.update(family, t, row, x, y, z)
-            prev = y
-            traj.append(x)
-    return (torch.stack(traj, 0) if trajectory else x), stats, centre(code)[1]
+    stats = {}
+
+    def hook(t, y):
+        if not v:
+            return y.clamp(*CL.BOUNDS[code])
+        y, stats[t] = threshold(y, code, v, groups)               # in place of the clamp
+        return y
+
+    return CR.sample_chain(params, hp, sampler, x, spec_c, noise, n, plan=plan, hook=hook, **kw), stats, centre(code)[1]
 
 
 def active(stats, r) -> List[bool]:
