@@ -20,7 +20,8 @@ torchaudio 0.11's windowed-sinc kernel (diffroll_amd/audio.py).
 
 Long-form: ``dataset=Custom dataset.args.max_segment_samples=null`` transcribes every file whole (the reference
 documents None as "get the full audio", utils/custom_dataset.py:21, but crashes on it): each recording is one chain of
-jointly sampled 640-frame windows overlapping by ``task.window_overlap`` frames (default 160; diffroll_amd/longform.py),
+jointly sampled 640-frame windows overlapping by ``task.window_overlap`` frames (default 160; diffroll_amd/longform.py;
+``task.window_blend=linear`` / ``nearest`` cross-fades the windows over those frames or hands over in their middle),
 written as ``roll_<stem>.npy`` (1, 1, ceil(L / hop), 88), ``raw_midi_<stem>.mid`` and ``clean_midi_<stem>.mid``.  With
 ``gpus=N`` every rank takes the files round-robin and writes its own outputs.
 
@@ -164,6 +165,12 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
         overlap = cfg["task"].get("window_overlap", DEFAULT_WINDOW_OVERLAP)
         if not isinstance(overlap, int) or not 1 <= overlap <= 320:
             raise SystemExit(f"task.window_overlap must be an integer in [1, 320] (half the 640-frame window), got {overlap!r}")
+        # task.window_blend=linear: what the frames two windows share take of their predictions (option "window_blend")
+        from .longform import check_window_blend
+        try:
+            check_window_blend(cfg["task"].get("window_blend"))
+        except ValueError as err:
+            raise SystemExit(f"task.window_blend: {err}")
     return cfg
 
 
@@ -215,6 +222,8 @@ def transcribe_long_form(cfg: Dict[str, Any], model, rank: int, world: int) -> L
     written = []
     D = int(cfg["task"]["sampling"].get("draws") or 1)
     more = {"draws": D} if D > 1 else {}
+    if cfg["task"].get("window_blend") is not None:
+        more["blend"] = cfg["task"]["window_blend"]
     init_dir = cfg["task"]["sampling"].get("init_dir")
 
     def init_roll(path, wav):

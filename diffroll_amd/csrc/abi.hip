@@ -175,6 +175,8 @@ int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     const ChainOptions& o = e->opt;
     if (2 * o.win_O > T)
         return fail(e, DR_EINVAL, "window_overlap %d exceeds half the window (T = %d frames)", o.win_O, T);
+    if (o.win_O > 0 && T >= (1 << WIN_BLEND_SHIFT))
+        return fail(e, DR_EINVAL, "window_overlap: windows hold fewer than %d frames, got T = %d", 1 << WIN_BLEND_SHIFT, T);
     const int D = o.draws, n = B / D;      // (option "draws": the marks are those of one draw and repeat per draw)
     if (o.win_O > 0 && !e->win_marks.empty()) {
         if (e->win_marks.back() >= n) {
@@ -414,6 +416,15 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
         if (e->opt.win_O != value) drop();
         e->opt.win_O = value;
+        return DR_OK;
+    }
+    if (n == "window_blend") {      // (part of the chain's key while "window_overlap" is set: nothing is dropped)
+        if (value < 0 || value > 2)
+            return fail(e, DR_EINVAL, "window_blend is 0 (the mean of the two windows' predictions), 1 (linear cross-fade) or 2 (hand-over "
+                                      "at the middle of the overlap), got %d", value);
+        // (under "solver_order" 2 the history holds the prediction as the previous step blended it, as for "x0_clip")
+        if (e->opt.win_blend != value) e->hist_key.valid = false;
+        e->opt.win_blend = value;
         return DR_OK;
     }
     // (a mark >= B is refused by dr_step / dr_sample, which know B; no captured chain is dropped: the table is data)

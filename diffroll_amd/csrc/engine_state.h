@@ -52,7 +52,9 @@ struct LayerW {
 struct ChainOptions {
     int steps = 0;                      // option "sampling_steps": n of a respaced chain; 0 (and S) = every step
     int win_O = 0;                      // option "window_overlap": > 0 = the B rolls of dr_step / dr_sample are consecutive windows of
-                                        // one recording sharing that many frames (UpdateArgs::win_H); 0 = independent clips
+                                        // one recording sharing that many frames (UpdateArgs::win); 0 = independent clips
+    int win_blend = 0;                  // option "window_blend": what a frame shared by two windows takes of their predictions - 0 the mean,
+                                        // 1 the linear cross-fade, 2 the hand-over (update_quad.h: blend_quad); read only while win_O > 0
     int draws = 1;                      // option "draws": D > 1 = the B rolls are D draws of the B / D clips of the last dr_frontend, draw-major
     int draw_G = 0;                     // option "draw_stride": Philox key distance between two draws of a clip; 0 = the clips of the batch
     dr::GuidanceInterval guid;          // options "guidance_t_min" / "guidance_t_max": the steps a guiding sampler guides (launch_plan.h)
@@ -74,18 +76,19 @@ struct ChainOptions {
     // head projections, the threshold launches (threshold.hip) and update_thresh_kernel (plan.hip: run_step)
     int x0_thresh = 0;
     bool operator==(const ChainOptions& o) const {
-        return steps == o.steps && win_O == o.win_O && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
+        return steps == o.steps && win_O == o.win_O && win_blend == o.win_blend && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
                guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
                start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh;
     }
 };
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
-// a solver order, the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
+// a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
 // step the chain visits first (abi.hip: start_position).
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
+    if (o.win_O <= 0) o.win_blend = 0;
     o.guid = guiding ? dr::GuidanceInterval{o.guid.lo, o.guid.hi_eff(S)} : dr::GuidanceInterval{};
     o.start = start_t;
     return o;
@@ -393,7 +396,7 @@ int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, in
                 hipStream_t st, bool zero_spec = false, const int* tsel = nullptr, TailPlan* tail = nullptr);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& zero_spec);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond);
-// the layout half of an update's arguments for B rolls of T frames: n, per_sample, dyn, win_H, draw_n / draw_G, win_tab
+// the layout half of an update's arguments for B rolls of T frames: n, per_sample, dyn, win, draw_n / draw_G, win_tab
 UpdateArgs update_base(const dr_engine* e, int B, int T);
 // option "x0_threshold": the arguments of a step's threshold launches, from the update they precede
 ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u);

@@ -211,7 +211,12 @@ struct UpdateArgs {
     // 2 O <= T.  A frame shared by windows b and b + 1 (frames [win_H, T) of b = frames [0, O) of b + 1) uses the mean
     // 0.5 (y_b + y_b+1) of the two windows' guided predictions, and Philox is keyed by (seed, first_sample = the
     // recording, t, canvas element / 4): both windows compute the same x_{t-1} there, bit for bit.
-    int win_H;
+    // Option "window_blend" travels in the same word: win = win_H | blend << 28 (win_H < 2^28; read them with win_H() /
+    // win_blend() below) - how a shared frame combines the two predictions: 0 the mean above, 1 the linear cross-fade, 2 the
+    // hand-over at the middle of the overlap (update_quad.h: blend_quad).  Spare bits of this word and not a word of its
+    // own: the argument block does not grow, and tail_kernel parks no more scalars than it did
+    // (profiles/blend_kernel_resources.txt).  A zero-initialised block is off in both.
+    int win;
     // Recording boundaries inside the window batch (option "window_break"): null = one recording (the definition above);
     // else the engine's per-window table, win_tab[b] = window_entry(r, i): window b is window i of recording r of the batch.
     // Windows b and b + 1 share frames only when b + 1 is not the first window of a recording (i(b + 1) > 0), the canvas
@@ -240,6 +245,10 @@ struct UpdateArgs {
 // (mode 5) the half the step reads / the half it writes, null where it stores nothing
 __host__ __device__ inline const float* hist_prev(const UpdateArgs& a) { return a.hist + (a.hist_par ? a.n : 0); }
 __host__ __device__ inline float* hist_next(const UpdateArgs& a) { return a.hist && a.t > 0 ? a.hist + (a.hist_par ? 0 : a.n) : nullptr; }
+// the two fields of UpdateArgs::win: the windows' stride H = T - O (0: independent clips) and the mode of option "window_blend"
+constexpr int WIN_BLEND_SHIFT = 28;
+__host__ __device__ inline int win_H(const UpdateArgs& a) { return a.win & ((1 << WIN_BLEND_SHIFT) - 1); }
+__host__ __device__ inline int win_blend(const UpdateArgs& a) { return a.win >> WIN_BLEND_SHIFT; }
 // one word per window: Philox key offset of its recording (the ordinal in the batch; + draw x stride under option "draws":
 // < 65536) and index within the recording (< STACK_GROUPS)
 constexpr unsigned window_entry(unsigned rec, unsigned idx) { return (rec << 16) | idx; }
@@ -252,7 +261,7 @@ hipError_t launch_set_windows(unsigned* d_tab, const WindowTable& tab, int n, hi
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
 // option "start_noise": x = (coef[2] * x) + (coef[3] * z) in place (update.hip: diffuse_kernel).  Of UpdateArgs it reads x,
 // noise (z, or null: Philox), coef, t (the Philox counter word: timesteps + the start step), n, per_sample, seed /
-// first_sample (or dyn), win_H, win_tab, draw_n, draw_G
+// first_sample (or dyn), win (its win_H), win_tab, draw_n, draw_G
 hipError_t launch_diffuse(const UpdateArgs& a, hipStream_t s);
 
 // Option "x0_threshold" (include/diffroll_amd.h): dynamic thresholding of the prediction the update consumes.  One q - the
@@ -269,7 +278,7 @@ hipError_t launch_diffuse(const UpdateArgs& a, hipStream_t s);
 constexpr int THRESH_HEAD = 4, THRESH_ROW_WORDS = 272, THRESH_SEL = 256, THRESH_QS = 264;
 inline size_t thresh_work_words(int B) { return (size_t)THRESH_HEAD + (size_t)B * THRESH_ROW_WORDS; }
 struct ThreshArgs {
-    UpdateArgs u;          // read: x0c, x0u, w / onepw (or dyn), n, per_sample, win_H, win_tab - what forms y (threshold_quad.h: pred_quad)
+    UpdateArgs u;          // read: x0c, x0u, w / onepw (or dyn), n, per_sample, win, win_tab - what forms y (threshold_quad.h: pred_quad)
     float m, r;            // centre and half-width of the range "x0_clip" names
     int v;                 // the percentile, 1 / 10000
     int pass;              // multi-launch form: 0-3 the radix passes (8, 8, 8, 7 bits from the top), 4 the successor pass
@@ -324,7 +333,7 @@ struct TailArgs {
     long long* dbg;                           // optional: block 0 writes s_memtime at the start and after T1, its barrier, T2, its
                                               // barrier, T3, its barrier, T4 (8 marks)
     unsigned *bar, *pbar, *err, *derr;        // counters as in StackArgs (own arrays), time-out flags (shared with the stack)
-    // long-form windows (u.win_H > 0): T3 of window b reads the x0 that windows b - 1 / b + 1 wrote in their T2.  After
+    // long-form windows (win_H(u) > 0): T3 of window b reads the x0 that windows b - 1 / b + 1 wrote in their T2.  After
     // its pair barrier, window b publishes ready[b] = epoch and waits for its neighbours' words to reach it.  The words
     // only ever grow (epoch = (u.dyn ? u.dyn->epoch : 0) + this launch's epoch, a per-engine count of tail launches):
     // a replayed graph and a neighbour that has already left the launch are both seen correctly.

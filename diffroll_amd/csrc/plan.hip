@@ -406,13 +406,14 @@ UpdateArgs update_base(const dr_engine* e, int B, int T) {
     UpdateArgs u{};
     u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
-    u.win_H = e->opt.win_O > 0 ? T - e->opt.win_O : 0;
+    // (option "window_blend" rides in the word's spare bits - kernels.h: win_H / win_blend; check_options keeps T below them)
+    u.win = e->opt.win_O > 0 ? (T - e->opt.win_O) | (e->opt.win_blend << WIN_BLEND_SHIFT) : 0;
     // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)
     if (e->opt.draws > 1) { u.draw_n = B / e->opt.draws; u.draw_G = e->opt.draw_G > 0 ? e->opt.draw_G : u.draw_n; }
     // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
     // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
     // (the table has STACK_GROUPS words: a larger batch is one recording - check_options refuses marks there)
-    u.win_tab = (u.win_H > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt.draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    u.win_tab = (u.win > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt.draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
     return u;
 }
 

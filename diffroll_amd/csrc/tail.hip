@@ -19,7 +19,7 @@ DR_BOUNDS_TU(tail)
 //   --  group barrier (+ L1 invalidate: T2 reads tmp with plain loads)
 //   T2  output projection -> x0 in the (B, T, 88) roll layout.  Items = 32-frame chunks (pw_body<1>; 88 rows: three
 //       of the four waves).  Output write-through.
-//   --  pair barrier (group barrier without guidance) + L1 invalidate; long-form windows (UpdateArgs::win_H) also wait for
+//   --  pair barrier (group barrier without guidance) + L1 invalidate; long-form windows (UpdateArgs::win) also wait for
 //       the neighbouring windows' T2 (neighbour_wait) - T3 reads their x0 on the shared frames; only neighbours of the
 //       same recording count (UpdateArgs::win_tab)
 //   T3  per item (128-row tile of the input projection, 32-frame chunk) of the pair's clip: the classifier-free
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(512) void tail_kernel(const TailArgs s) {
     mark();
     if (paired) group_barrier<true>(pctr, 2u * gsize + DR_FAULT_EXTRA(s), s.err, s.derr);
     else group_barrier<true>(ctr, 2u * (gsize + DR_FAULT_EXTRA(s)), s.err, s.derr);
-    if (s.u.win_H > 0) {
+    if (win_H(s.u) > 0) {
         // long-form windows: T3 reads the neighbouring windows' x0 on the shared frames (neighbour_wait, persistent.h)
         if (threadIdx.x == 0) {
             const unsigned epoch = (s.u.dyn ? s.u.dyn->epoch : 0u) + s.epoch;
@@ -248,8 +248,8 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
     // (a guided successor pairs row b with row b + u_B: the rolls of this launch, one per pair / single group)
     if (s.dual_next < 0 || (s.dual_next > 0 && (s.dual_next != s.u_B || s.u_B != (s.dual > 0 ? s.dual : s.NB)))) return hipErrorInvalidValue;
     if (!s.x_out || s.x_out == s.u.x) return hipErrorInvalidValue;
-    if (s.u.win_H > 0 && (!s.ready || s.u_B > STACK_GROUPS || 2 * s.u.win_H < s.T || s.u.win_H >= s.T)) return hipErrorInvalidValue;
-    if (s.u.win_tab && s.u.win_H <= 0) return hipErrorInvalidValue;      // (a table of u_B <= STACK_GROUPS words: windows only)
+    if (win_H(s.u) > 0 && (!s.ready || s.u_B > STACK_GROUPS || 2 * win_H(s.u) < s.T || win_H(s.u) >= s.T)) return hipErrorInvalidValue;
+    if (s.u.win_tab && win_H(s.u) <= 0) return hipErrorInvalidValue;      // (a table of u_B <= STACK_GROUPS words: windows only)
     const int tps = (s.T + s.BN - 1) / s.BN, MT = s.Cp >> 6;
     TailArgs b = s;
     const int NBp = xcd_padded_groups(s.NB, MT * tps, &b.xcd_n);       // idle padding groups, as launch_stack

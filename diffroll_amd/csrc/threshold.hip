@@ -235,7 +235,7 @@ hipError_t launch_threshold(ThreshArgs a, int B, hipStream_t s) {
     if (!u.x0c || !a.work || B < 1 || u.per_sample < 4 || (u.per_sample & 3) || u.n != (long)B * u.per_sample ||
         u.n >= (1l << 31) || a.v < 5000 || a.v > 10000 || !(a.r > 0.f))
         return hipErrorInvalidValue;
-    if (u.win_H == 0 && u.per_sample <= THRESH_ROLL_MAX) {
+    if (win_H(u) == 0 && u.per_sample <= THRESH_ROLL_MAX) {
         hipLaunchKernelGGL(thresh_roll_kernel, dim3((unsigned)B), dim3(512), 0, s, a);
         return hipGetLastError();
     }
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void thresh_gather_kernel(const ThreshArgs a, 
         thresh_place(a.u, b, first, f_lo);
         if (first != b) continue;
         long g = b;
-        if (a.u.win_H > 0) {
+        if (win_H(a.u) > 0) {
             g = 0;
             if (a.u.win_tab)
                 for (long j = 0; j < b; ++j) g += window_idx(a.u.win_tab[j]) == 0;

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void diffuse_kernel(const UpdateArgs a) {
         const uint64_t seed = a.dyn ? a.dyn->seed : a.seed;
         const int first_sample = a.dyn ? a.dyn->first_sample : a.first_sample;
         long q, sk;
-        if (a.win_H > 0) {
+        if (win_H(a) > 0) {
             const long e0 = i4 * 4;
             const long smp = e0 / a.per_sample;
             long rec, idx;

@@ -38,7 +38,7 @@ DR_DEVINL void box_muller(uint32_t u0, uint32_t u1, float& z0, float& z1) {
 // THE NOISE-KEY RULE, stated once: which Philox (sample key sk, quad q) belongs to a float4 of the roll batch.  Used by
 // update_quad (the z of a reverse step, counter word 2 = t) and by diffuse_kernel (update.hip: the z of option
 // "start_noise", counter word 2 = timesteps + the start step).
-//   a window (a.win_H > 0) is window idx of recording rec of the batch - the table's word (options "window_break" /
+//   a window (win_H(a) > 0) is window idx of recording rec of the batch - the table's word (options "window_break" /
 //   "draws": the draw is part of rec), else window smp of recording 0 - and is keyed by its recording and the element on
 //   that recording's canvas: two windows draw the same z on the frames they share;
 //   a clip is keyed by its row, or under option "draws" (a.draw_n > 0) as draw smp / n of clip smp % n.
@@ -56,7 +56,7 @@ DR_DEVINL void window_place(const UpdateArgs& a, const long smp, long& rec, long
 DR_DEVINL void window_key(const UpdateArgs& a, const long rec, const long idx, const long within, const int first_sample,
                           long& q, long& sk) {
     sk = first_sample + rec;
-    q = (idx * a.win_H * 88 + within) >> 2;
+    q = (idx * win_H(a) * 88 + within) >> 2;
 }
 DR_DEVINL void clip_key(const UpdateArgs& a, const long i4, const int first_sample, long& q, long& sk) {
     const long e0 = i4 * 4;
@@ -82,9 +82,10 @@ DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, c
 // Classifier-free combine + x0-prediction posterior update of ONE float4 (4 consecutive elements, index i4) of the
 // roll.  Same operation order as task/diffusion.py:953 and :957-967; contraction off so that no FMA is formed where
 // the reference rounds twice.  Shared by update_kernel and the tail kernel (identical arithmetic).
-// Long-form windows (a.win_H > 0, UpdateArgs): on a frame shared with a neighbouring window of the same recording the prediction is the mean
+// Long-form windows (win_H(a) > 0, UpdateArgs): on a frame shared with a neighbouring window of the same recording the prediction is the mean
 // 0.5f * (y_lower + y_upper) of both windows' guided predictions - the same bits in both (the operands are the same
-// two values, added in the same order) - and the noise is keyed by the canvas element.
+// two values, added in the same order) - or what option "window_blend" makes of the two (blend_quad below) - and the noise
+// is keyed by the canvas element.
 // mode 5 (option "solver_order", x0-prediction samplers): the exponential integrator in lambda = log(sqrt_acp / sqrt_1m_acp)
 // of Lu et al. 2022 (DPM-Solver++), row [sqrt_1m_acp' / sqrt_1m_acp, -sqrt_acp' expm1(-h), sqrt_acp, c, 0] (abi.hip:
 // build_solver).  y is the guided prediction after the shared-frame mean, p the y of the previous step (hist_prev(a)):
@@ -158,6 +159,30 @@ DR_DEVINL void clamp_quad(const float lo, const float hi, float (&y)[4]) {
 // the units that instantiate that form include behind this header.
 DR_DEVINL void thresh_quad(const UpdateArgs& a, const ThreshUpd& th, const long i4, float (&y)[4]);
 
+// Option "window_blend" (win_blend() of UpdateArgs::win): what a frame shared by windows b and b + 1 takes of the two guided predictions
+// lo (window b's, its frame H + j) and up (window b + 1's, its frame j), j = 0 .. O - 1 the position within the overlap:
+//   0  the mean 0.5f * (lo + up)
+//   1  the linear cross-fade lo + wu * (up - lo), wu = (float)(j + 1) / (float)(O + 1): subtraction, product and sum each
+//      rounded once (contraction off), the IEEE division; lo == up gives that value exactly
+//   2  the hand-over: lo for j < (O + 1) / 2, else up - a select; the lower window takes the odd frame
+// Both windows call it with the lower window's value first: the frames they share stay bit-identical.  y may be lo or up
+// (element e is read before it is written).  Shared by update_quad and pred_quad (threshold_quad.h).
+DR_DEVINL void blend_quad(const int mode, const int j, const int O, const float (&lo)[4], const float (&up)[4], float (&y)[4]) {
+#pragma clang fp contract(off)
+    if (mode == 1) {
+        const float wu = (float)(j + 1) / (float)(O + 1);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[e] = lo[e] + wu * (up[e] - lo[e]);
+    } else if (mode == 2) {
+        const bool lower = j < (O + 1) / 2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[e] = lower ? lo[e] : up[e];
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) y[e] = 0.5f * (lo[e] + up[e]);
+    }
+}
+
 // pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean and the clamp of
 // option "x0_clip" (mode 5's history).  TH: update_kernel's thresholding form (option "x0_threshold"; th is set) - the
 // tail kernel instantiates TH = false, the text it always had.
@@ -171,12 +196,12 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
     const int first_sample = a.dyn ? a.dyn->first_sample : a.first_sample;
     guided_quad(a, i4, gw, g1pw, x0);
     long key_smp = -1, key_q = 0;             // Philox sample / quad key of a window (win_H > 0): canvas coordinates
-    if (a.win_H > 0) {
+    if (win_H(a) > 0) {
         const long e0 = i4 * 4;
         const long smp = e0 / a.per_sample;
         const long within = e0 - smp * a.per_sample;
         const int f = (int)(within / 88);
-        const long o4 = a.per_sample / 4 - (long)a.win_H * 22;      // O frames x 22 quads: window b's frame f <-> b + 1's f - H
+        const long o4 = a.per_sample / 4 - (long)win_H(a) * 22;      // O frames x 22 quads: window b's frame f <-> b + 1's f - H
         long p4 = -1;
         bool upper = false;                                        // the partner is the upper window (b + 1)
         // which neighbours exist, and this window's place on its canvas: one recording (rec 0, window smp of it), or the
@@ -189,13 +214,14 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
             has_lo = idx > 0;
             has_up = has_up && window_idx(a.win_tab[smp + 1]) > 0;
         }
-        if (f >= a.win_H && has_up) { p4 = i4 + o4; upper = true; }
+        if (f >= win_H(a) && has_up) { p4 = i4 + o4; upper = true; }
         else if (f < (int)(o4 / 22) && has_lo) p4 = i4 - o4;
         if (p4 >= 0) {
             float yp[4];
             guided_quad(a, p4, gw, g1pw, yp);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x0[e] = upper ? 0.5f * (x0[e] + yp[e]) : 0.5f * (yp[e] + x0[e]);
+            // (the lower window's value first in both windows: the same operands in the same order, the same bits)
+            if (upper) blend_quad(win_blend(a), f - win_H(a), (int)(o4 / 22), x0, yp, x0);
+            else blend_quad(win_blend(a), f, (int)(o4 / 22), yp, x0, x0);
         }
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }

@@ -42,6 +42,7 @@ def _clamp_range(r: Optional[Sequence[int]], n: int) -> Tuple[int, int]:
 # Options whose last value set is readable as the attribute of the same name, with the library's defaults
 _MIRRORED = {
     "window_overlap": 0,         # frames two neighbouring windows share (0 = off)
+    "window_blend": 0,           # shared frames: 0 = the mean of the two windows' predictions, 1 = linear cross-fade, 2 = hand-over
     "sampling_steps": 0,         # steps of the respaced chain (0 = every step)
     "draws": 1,                  # rolls per clip of one chain, draw-major
     "draw_stride": 0,            # Philox key distance of two draws (0 = the clips of the batch)
@@ -355,7 +356,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'window_blend', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -372,7 +373,7 @@ class Engine:
     def holding(self, **options):
         """Options held for one call and put back afterwards, also when the call raises: mirrored option names, and
         window_breaks = the marks.  An option that already has the value is not set at all - 'sampling_steps' would drop the
-        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold' and the marks never do (they are part of its key or plain data), so a loop of
+        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'window_blend' and the marks never do (they are part of its key or plain data), so a loop of
         such calls replays one graph, and putting them back behind an asynchronous call touches nothing in flight."""
         def put(name, value):
             if name == "window_breaks":

@@ -9,7 +9,8 @@ Definitions (include/diffroll_amd.h, option "window_overlap"):
     spectrogram, normalisation and conditioner are those of dr_frontend for that clip.
   * joint step: on a frame shared by windows b and b + 1 (frames [H, T) of b = frames [0, O) of b + 1) both windows use
     0.5f * (y_b + y_b+1), the mean of their guided x0 predictions, before the posterior update; noise is drawn per
-    canvas frame.  If x_T agrees on shared frames, every x_t does, bit for bit, so the stitched roll is a plain gather
+    canvas frame.  Option "window_blend" (check_window_blend below) replaces the mean by a linear cross-fade over the
+    overlap or by a hand-over at its middle; both windows still take the same value.  If x_T agrees on shared frames, every x_t does, bit for bit, so the stitched roll is a plain gather
     from the canvas (stitch), sliced to T_out.
   * several recordings in one chain (option "window_break", plan_batch): the windows of the recordings one after another;
     a window shares frames only with windows of its own recording, and recording r of the batch draws the noise of
@@ -27,6 +28,22 @@ DEFAULT_OVERLAP = 160
 # windows one chain can hold: the engine's fused launches keep counters for 512 evaluations (launch_plan.h STACK_GROUPS),
 # i.e. 256 guided windows (about 65 minutes of audio at the default overlap)
 MAX_WINDOWS = 256
+# option "window_blend": what a frame shared by windows b and b + 1 takes of their two guided predictions
+WINDOW_BLENDS = {"mean": 0, "linear": 1, "nearest": 2}
+
+
+def check_window_blend(blend) -> int:
+    """blend= of sample_long / sample_long_batch and the CLI's task.window_blend -> the value of option "window_blend":
+    None or "mean" = 0, the mean of the two predictions; "linear" = 1, the cross-fade y_lo + wu (y_up - y_lo) with
+    wu = (j + 1) / (O + 1) at position j of the overlap; "nearest" = 2, the hand-over at the middle of the overlap - every
+    canvas frame from the window whose centre is nearer.  The integers 0 / 1 / 2 themselves pass.  Anything else: ValueError."""
+    if blend is None:
+        return 0
+    if isinstance(blend, str) and blend in WINDOW_BLENDS:
+        return WINDOW_BLENDS[blend]
+    if isinstance(blend, int) and not isinstance(blend, bool) and blend in (0, 1, 2):
+        return blend
+    raise ValueError(f"window blend is None, 'mean', 'linear', 'nearest' or 0 / 1 / 2, got {blend!r}")
 
 
 @dataclass(frozen=True)

@@ -570,7 +570,7 @@ class ClassifierFreeDiffRoll(nn.Module):
     @torch.no_grad()
     def sample_long(self, waveform=None, frames: Optional[int] = None, overlap: int = 160, seed: int = 0,
                     recording: int = 0, x_T=None, noise=None, use_graph: bool = True, check: bool = True,
-                    draws: int = 1, init=None) -> torch.Tensor:
+                    draws: int = 1, init=None, blend=None) -> torch.Tensor:
         """One recording of any length as jointly sampled 640-frame windows (diffroll_amd/longform.py; option
         "window_overlap" of include/diffroll_amd.h): returns the stitched roll (1, 1, T_out, 88) on the device.
         Conditional samplers take waveform (L,) (T_out = ceil(L / hop)); generation_ddpm_x0 takes frames = T_out.
@@ -581,13 +581,17 @@ class ClassifierFreeDiffRoll(nn.Module):
         (D, 1, T_out, 88); x_T (D, 1, T_c, 88), noise (timesteps, D, 1, T_c, 88).
         init: a clean roll of the recording in the shape this method RETURNS, (1, 1, T_out, 88) (or (D, 1, T_out, 88)) - a
         roll it returned can be fed back - instead of x_T: zero-padded to the canvas, a single roll shared by all draws, and
-        diffused to the start step of hparams.sampling.start_step / .strength by the chain's first node (sample())."""
+        diffused to the start step of hparams.sampling.start_step / .strength by the chain's first node (sample()).
+        blend: what a frame shared by two windows takes of their predictions at every step (option "window_blend",
+        longform.check_window_blend): None / "mean" = their mean, "linear" = a cross-fade over the overlap, "nearest" = each
+        frame from the window whose centre is nearer."""
         from . import longform
+        blend = longform.check_window_blend(blend)
         if check_draws(draws) > 1:
             return self.sample_long_batch(None if waveform is None else [waveform], None if frames is None else [frames],
                                           overlap, seed, recording, None if x_T is None else [x_T],
                                           None if noise is None else [noise], use_graph, check, draws,
-                                          None if init is None else [init])[0]
+                                          None if init is None else [init], blend)[0]
         sampler = self.hparams.sampling.type
         if sampler == "inpainting_ddpm_x0":
             raise ValueError("sample_long does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) are in "
@@ -618,7 +622,7 @@ class ClassifierFreeDiffRoll(nn.Module):
         if noise is not None and noise.numel() != S * plan.T_c * 88:
             raise ValueError(f"noise must be the canvas ({S}, 1, 1, {plan.T_c}, 88), got {tuple(noise.shape)}")
         xb = self._sample_windows(batch, None if waveform is None else [waveform], [x_T], None if noise is None else [noise],
-                                  1, seed, recording, use_graph, check, start_noise=0 if init is None else 1)
+                                  1, seed, recording, use_graph, check, start_noise=0 if init is None else 1, blend=blend)
         return longform.stitch(xb, plan).reshape(1, 1, plan.T_out, 88)
 
     @staticmethod
@@ -642,11 +646,11 @@ class ClassifierFreeDiffRoll(nn.Module):
         return out
 
     def _sample_windows(self, batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check, marks=None,
-                        start_noise=0):
+                        start_noise=0, blend=0):
         """The one long-form chain: the recordings of `batch` (longform.plan_batch) as D draws of its windows.  waveforms: one
         (L,) host tensor per recording, or None (generation); x_T / noise: one canvas per recording, (D, 1, T_c, 88) /
         (timesteps, D, 1, T_c, 88), or noise None (Philox); marks: the window_break marks, the plan's unless given.  Options
-        "window_overlap", "window_break", "draws" hold for the chain only.  Returns the window batch (D * n, T, 88) after the
+        "window_overlap", "window_blend" (blend), "window_break", "draws" hold for the chain only.  Returns the window batch (D * n, T, 88) after the
         chain: that of draw 0, then that of draw 1, ... (draw-major).  start_noise = 1: the canvases are clean rolls (option
         "start_noise": diffused to the chain's start step per recording and canvas element)."""
         from . import longform
@@ -663,7 +667,7 @@ class ClassifierFreeDiffRoll(nn.Module):
             eng.frontend(torch.cat([longform.window_audio(wv, p, eng.hop_length) for wv, p in zip(waveforms, batch.plans)]),
                          batch.plans[0].T)
             self._fe_key = None          # the engine's conditioner is the windows' now: sample() recomputes its own
-        with eng.holding(window_overlap=batch.plans[0].overlap, window_breaks=batch.marks if marks is None else marks,
+        with eng.holding(window_overlap=batch.plans[0].overlap, window_blend=blend, window_breaks=batch.marks if marks is None else marks,
                          draws=D, draw_stride=0, start_noise=start_noise):
             eng.sample(sampler, xb, z, self._guidance_weight(sampler), seed, first_recording, use_graph, check)
         return xb
@@ -671,7 +675,7 @@ class ClassifierFreeDiffRoll(nn.Module):
     @torch.no_grad()
     def sample_long_batch(self, waveforms=None, frames=None, overlap: int = 160, seed: int = 0, first_recording: int = 0,
                           x_T=None, noise=None, use_graph: bool = True, check: bool = True, draws: int = 1,
-                          init=None) -> List[torch.Tensor]:
+                          init=None, blend=None) -> List[torch.Tensor]:
         """Several recordings of any lengths in ONE chain (option "window_break" of include/diffroll_amd.h;
         longform.plan_batch): their windows fill one batch, a window shares frames only with windows of its own
         recording, and recording i draws the noise of first_sample = first_recording + i on its own canvas.  Returns one
@@ -686,9 +690,10 @@ class ClassifierFreeDiffRoll(nn.Module):
         dimension ((D, 1, T_c_i, 88) / (timesteps, D, 1, T_c_i, 88)); the default x_T are the first D canvases of
         torch.Generator().manual_seed(seed) (draw 0 = the single-draw default).
         init: instead of x_T, one clean roll per recording in the shape this method returns ((D or 1, 1, T_out_i, 88));
-        see sample_long."""
+        see sample_long.  blend: option "window_blend" for the chain, as in sample_long."""
         from . import longform
         D = check_draws(draws)
+        blend = longform.check_window_blend(blend)
         sampler = self.hparams.sampling.type
         if sampler == "inpainting_ddpm_x0":
             raise ValueError("sample_long_batch does not support inpainting_ddpm_x0: its masks (inpainting_t / inpainting_f) "
@@ -719,7 +724,7 @@ class ClassifierFreeDiffRoll(nn.Module):
         if noise is not None and (len(noise) != R or any(zr.numel() != S * D * p.T_c * 88 for zr, p in zip(noise, batch.plans))):
             raise ValueError(f"noise must be one canvas ({S}, {D}, 1, T_c, 88) per recording, T_c = {[p.T_c for p in batch.plans]}")
         xb = self._sample_windows(batch, waveforms, x_T, noise, D, seed, first_recording, use_graph, check,
-                                  start_noise=0 if init is None else 1)
+                                  start_noise=0 if init is None else 1, blend=blend)
         rolls = longform.stitch_batch(xb.reshape(D, batch.n, longform.WINDOW_FRAMES, 88), batch)
         return [r.reshape(D, 1, p.T_out, 88) for r, p in zip(rolls, batch.plans)]
 

@@ -361,6 +361,30 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          data of a captured chain, not part of it: setting them does NOT drop it, and a new
  *                          segmentation at the same (sampler, B, T) replays the same graph.  dr_sample_checked's re-run
  *                          uses the same marks; dr_forward / dr_forward_steps are unaffected.
+ *   "window_blend"     [0] 0, 1 or 2: WHAT A SHARED FRAME TAKES of the two windows' predictions under "window_overlap"
+ *                          (ignored while that is 0).  With O the overlap, H = T - O and j = 0 .. O - 1 the position within
+ *                          the overlap, frame H + j of the lower window b is frame j of the upper window b + 1; y_lo and
+ *                          y_up are the two windows' guided predictions of it.  0 = the mean 0.5f * (y_lo + y_up), the
+ *                          definition above: not a bit changes.  1 = LINEAR CROSS-FADE: wu = (float)(j + 1) / (float)(O + 1),
+ *                          y = y_lo + wu * (y_up - y_lo) - subtraction, product and sum each rounded once, in that order
+ *                          (no FMA); where y_lo == y_up the result is that value exactly.  Each window's weight falls
+ *                          towards its own edge, where its dilated convolutions see zero padding instead of context (the
+ *                          tapered window weights of tiled diffusion).  2 = HAND-OVER: y = j < (O + 1) / 2 ? y_lo : y_up
+ *                          (integer division), a select: every canvas frame from the window whose centre is nearer, the
+ *                          lower window taking the odd frame.  Both windows evaluate the same expression on the same
+ *                          operands, lower first, so the frames they share stay bit-identical in every mode and the
+ *                          stitched roll stays a plain gather.  Whatever read the mean reads the blended value: both
+ *                          terms of every update (the epsilon samplers blend their epsilon), the clamp of "x0_clip", the
+ *                          selection and the update of "x0_threshold" (every canvas frame still counted once), the d and
+ *                          the history of "solver_order", the last step.  "window_break" is respected - only windows of
+ *                          one recording blend - and "draws" blends per draw; noise keys, the diffusion of "start_noise",
+ *                          dr_forward and dr_forward_steps are untouched.  Modes 1 and 2 keep the tail kernel of
+ *                          "fused_tail" (cost: profiles/blend_sweep.txt).  Any other value -> DR_EINVAL at the set.  While
+ *                          "window_overlap" is set the value is part of a captured chain's key, like "x0_clip": setting
+ *                          it drops nothing, and a chain captured under another value is never replayed; while the
+ *                          overlap is 0 it is inert and makes no other chain.  A change of the value ends a dr_step
+ *                          history of "solver_order" 2, as a change of "x0_clip" does.  Nothing is known about what the
+ *                          modes do to quality with real weights.
  *   "sampling_steps"   [0] n, 2 <= n < timesteps (S): a RESPACED reverse chain of n network steps instead of S.  Visited
  *                          steps t_i = (2 i (S - 1) + (n - 1)) / (2 (n - 1)) in integer arithmetic (linspace rounded half
  *                          up), i = n-1 .. 0: strictly decreasing from S - 1 to 0; t' = the next visited step.  The row of
