@@ -148,8 +148,8 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
                                     "same time? call dr_finish (or dr_stack_status) to clear the condition and recompute - "
                                     "dr_finish also switches this engine to per-phase launches; dr_sample_checked does all of that");
     if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
-    if (e->prec && !e->s3_ready) {       // (a commit after dr_set_precision, or a packing build that failed: never launch without them)
-        int rc = ensure_s3(e);
+    if (e->prec && !(e->prec == 2 ? e->bf16_ready : e->s3_ready)) {       // (a commit after dr_set_precision, or a packing build that failed: never launch without them)
+        int rc = ensure_packings(e, e->prec);
         if (rc) return rc;
     }
     // option "draws": the B rolls are D draws of B / D clips, and the front-end ran on the clips
@@ -1088,13 +1088,13 @@ int dr_set_spec_norm(dr_engine* e, int mode) {
 
 int dr_set_precision(dr_engine* e, int mode) {
     if (!e) return DR_EINVAL;
-    if (mode != DR_PRECISION_F32 && mode != DR_PRECISION_BF16X3) return fail(e, DR_EINVAL, "unknown precision mode %d", mode);
+    if (mode != DR_PRECISION_F32 && mode != DR_PRECISION_BF16X3 && mode != DR_PRECISION_BF16) return fail(e, DR_EINVAL, "unknown precision mode %d", mode);
     if (mode != e->prec) {
         DeviceGuard guard(e->cfg.device);     // the graph may still be executing on the ENGINE's device
         (void)hipDeviceSynchronize();
         drop_graph(e);
-        if (mode) {           // the mode changes only once its packings exist (520 MB of uploads: the build can fail)
-            int rc = ensure_s3(e);
+        if (mode) {           // the mode changes only once its own packings exist (bf16x3: 520 MB of uploads, bf16: a third - the build can fail)
+            int rc = ensure_packings(e, mode);
             if (rc) return rc;
         }
         e->prec = mode;

@@ -55,7 +55,7 @@ static void host_extent(const void* p, size_t bytes, const char* what, const cha
     }
 }
 static void check_gemm_extents(const GemmArgs& a, int epi, int prec, const char* kernel) {
-    const size_t slab = prec ? 24576 : 16384;
+    const size_t slab = prec == 2 ? 8192 : prec ? 24576 : 16384;
     const int mts = a.mt0 + a.MT;
     host_extent(a.Wp, (size_t)mts * a.kchunks * a.taps * slab, "packed weights", kernel);
     host_extent(a.bias, (size_t)mts * 128 * 4, "bias", kernel);
@@ -107,6 +107,7 @@ hipError_t init_frontend_kernels();
 
 struct AF4 { float4 v[4]; };                         // fp32 A fragments of one K step (32 channels): one per 8-channel group
 struct AF6 { uint4 v[6]; };                          // split-bf16 A fragments of one K step: [g16 * 3 + piece]
+struct AF2 { uint4 v[2]; };                          // one-pass bf16 A fragments of one K step: [g16]
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // allow the whole 160 KiB of dynamic LDS for every kernel given; stops at the first error
@@ -174,6 +175,25 @@ DR_DEVINL void store_s3_quad(float* dst, const float (&v)[4], int row0, int t, i
         *reinterpret_cast<uint2*>(q) = w;
     }
 }
+// One-pass bf16 (precision "bf16"): piece 0 of the split alone - the round-to-nearest-even bf16 of the value - in a tensor
+// of ONE plane set, [batch][plane8 = channel/8][frame][8 bf16].  The quad is the low (half = 0) or high 8 bytes of its
+// plane8 unit; COH / write_through as store_s3_quad.
+template <int COH = 0>
+DR_DEVINL void store_bf16_quad(float* dst, const float (&v)[4], int row0, int t, int T, const int write_through = 0) {
+    uint2 w;
+    w.x = (bf16_rne_bits(v[0]) >> 16) | bf16_rne_bits(v[1]);
+    w.y = (bf16_rne_bits(v[2]) >> 16) | bf16_rne_bits(v[3]);
+    char* q = reinterpret_cast<char*>(dst) + ((long)(row0 >> 3) * T + t) * 16 + ((row0 >> 2) & 1) * 8;
+    if constexpr (COH && DR_FAULT != 2) {
+        if (write_through) {       // wave-uniform
+            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+            const u32x2 d = {w.x, w.y};
+            asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" ::"v"(q), "v"(d) : "memory");
+            return;
+        }
+    }
+    *reinterpret_cast<uint2*>(q) = w;
+}
 DR_DEVINL f32x16 mma_bf16(const uint4 a, const uint4 b, const f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -193,6 +213,16 @@ DR_DEVINL void sgb_mix() {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         if constexpr (V > 0) __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);
         sgb_mix<N - 1, (V > 0 ? V - 1 : 0)>();
+    }
+}
+// N x (1 MFMA, 1 LDS read [, 1 vector-memory read for the first V]): the one-pass bf16 K step, one fragment read per MFMA
+template <int N, int V>
+DR_DEVINL void sgb_mix1() {
+    if constexpr (N > 0) {
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        if constexpr (V > 0) __builtin_amdgcn_sched_group_barrier(0x20, 1, 0);
+        sgb_mix1<N - 1, (V > 0 ? V - 1 : 0)>();
     }
 }
 // (x + residual) / math.sqrt(2.0) (model/diffwave.py:151) is an IEEE fp32 division by fp32(sqrt 2) in ATen.

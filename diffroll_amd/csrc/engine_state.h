@@ -40,6 +40,11 @@ struct LayerW {
     float* conv_b_z = nullptr;   // ... for spec == 0 samples (cfdg_ddim_x0's second branch): b_conv + bc
     float* conv_w3 = nullptr;    // split-bf16 ("S3") packing of conv_w  [MTc][kch][k] slabs of 24 KiB
     float* out_w3 = nullptr;     // split-bf16 packing of out_w
+    float* conv_wb = nullptr;    // one-pass bf16 packing of conv_w  [MTc][kch][k] slabs of 8 KiB
+    float* out_wb = nullptr;     // one-pass bf16 packing of out_w
+    // the packing of the two hot GEMMs that precision `prec` contracts
+    const float* conv_w_of(int prec) const { return prec == 2 ? conv_wb : prec ? conv_w3 : conv_w; }
+    const float* out_w_of(int prec) const { return prec == 2 ? out_wb : prec ? out_w3 : out_w; }
     float* out_w = nullptr;      // packed (natural halves) 1x1
     float* out_b = nullptr;
     float* cond_w = nullptr;     // packed (paired rows) conditioner 1x1
@@ -194,8 +199,9 @@ struct dr_engine {
     drh::DevBuf<float> h, hd, g, skip, tmp, x0buf;
     drh::DevBuf<float> xwork;              // the captured chain runs in place on this roll buffer (not the caller's)
     drh::DevBuf<float> hd3, g3;            // split-bf16 (S3) versions of hd and g: 1.5x the fp32 size
-    int prec = 0;                          // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3, 6 products)
+    int prec = 0;                          // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3, 6 products), 2: one-pass bf16 (1 product)
     bool s3_ready = false;                 // the split-bf16 packings exist (built on first use: ensure_s3)
+    bool bf16_ready = false;               // the one-pass bf16 packings exist (built on first use: ensure_bf16)
     double t_pack_s = 0.0, t_upload_s = 0.0, t_tables_s = 0.0, t_capture_s = 0.0;      // dr_cold_times
     int norm_framewise = 0;                // spectrogram normalisation: 0 imagewise, 1 framewise (norm_args[2])
     // conditioner tensors of the last dr_frontend: [L][fe_B][2Cp/4][fe_T][4]
@@ -365,6 +371,8 @@ int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B,
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);
 size_t expected_numel(const dr_engine* e, const std::string& name);
 int ensure_s3(dr_engine* e);            // the split-bf16 packings, built on first use
+int ensure_bf16(dr_engine* e);          // the one-pass bf16 packings, built on first use (independent of ensure_s3)
+int ensure_packings(dr_engine* e, int prec);      // what precision `prec` needs beyond the fp32 packings (nothing for 0)
 int commit(dr_engine* e, hipStream_t st);
 
 // ---- plan.hip

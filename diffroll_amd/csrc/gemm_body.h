@@ -1,5 +1,5 @@
 // The three GEMM bodies every contraction of the path is made of (device code, templates): gemm_body (LDS-staged X,
-// 32x32x2 fp32 / 32x32x16 split-bf16 MFMA), pw_body (1x1, both operands straight from L2) and gemm16_body (16x16x4 MFMA,
+// 32x32x2 fp32 / 32x32x16 split-bf16 or one-pass bf16 MFMA), pw_body (1x1, both operands straight from L2) and gemm16_body (16x16x4 MFMA,
 // 96 / 160-frame blocks).  Included by gemm.hip (one launch per phase), stack.hip and tail.hip (persistent kernels): the
 // same device code everywhere, which is what makes the fused kernels bit-identical to the per-phase launches.
 // What the bodies have in common is written once, in front of them: the epilogue arithmetic on register quads
@@ -59,11 +59,14 @@ DR_DEVINL void hd_quad(const float (&h)[4], const float4 d, float (&o)[4]) {
 }
 // ... and its store for rows p0..p0+3, frame t of sample b: split-bf16 (a.out_s3 & 2) or fp32 P4.  COH3 / COH4: that
 // flavour's store is write-through when a.wt_store says so (tensors handed to other workgroups of a fused launch), else plain.
-template <int COH3, int COH4>
+// BF: the one-pass bf16 tensor (precision "bf16": the bodies with PREC = 2 write nothing else)
+template <int COH3, int COH4, int BF = 0>
 DR_DEVINL void store_y2(const GemmArgs& a, const int b, const float (&o)[4], const float4 d, const int p0, const int t) {
     float o2[4];
     hd_quad(o, d, o2);
-    if (a.out_s3 & 2) {
+    if constexpr (BF) {
+        store_bf16_quad<COH3>(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.wt_store);
+    } else if (a.out_s3 & 2) {
         store_s3_quad<COH3>(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3, a.wt_store);
     } else {
         float* dst2 = a.Y2 + (long)b * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
@@ -115,12 +118,13 @@ DR_DEVINL void dma_tile(float4* Rs, PlaneOf plane_of, const int T, const int t0,
 //   staging.  Producers therefore issue a handful of instructions per chunk and no longer steal
 //   issue slots from the consumers' MFMA stream (measured: 70.7 -> 66 ticks per MFMA when idle).
 //   PREC = 1: the X tile rows are the split-bf16 planes [(sub*2 + g)*6 + piece*2 + kq] (see gemm_body).
+//   PREC = 2: the one-pass bf16 planes [(sub*2 + g)*2 + kq] = four consecutive plane8 units per 32 channels.
 //   AUX = 16: sc1 loads (COH bodies: X was written by other workgroups of the same launch).
 // ---------------------------------------------------------------------------------------------
 template <int KS, int PREC, int AUX, int RBN>
 DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw, const int lane, const int mt, const int b, const int t0,
                         const int halo, const int FW, const int c0, const int c1, const int code_x, const int code_r) {
-    constexpr int XP = (PREC ? 12 : 8) * KS;            // 16-byte rows per X tile
+    constexpr int XP = (PREC == 2 ? 4 : PREC ? 12 : 8) * KS;            // 16-byte rows per X tile
     const int bx = a.x_bmod ? (b % a.x_bmod) : b;
     const float* Xg = a.X + (long)bx * a.x_bs;
     const int last_plane = a.x_planes - 1;
@@ -133,7 +137,10 @@ DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw,
             const int f = seg * 64 + lane;
             // planes beyond Cin (K padding) re-read the last valid plane: finite data x zero weights
             const float* src;
-            if constexpr (PREC) {
+            if constexpr (PREC == 2) {
+                const int pc = min(chunk * (4 * KS) + pl, last_plane);                // plane8: rows are [(sub*2 + g)*2 + kq]
+                src = Xg + (long)pc * a.x_ps;
+            } else if constexpr (PREC) {
                 const int sg = pl / 6, rem = pl - sg * 6, pce = rem >> 1, kq = rem & 1;
                 const int pc = min(chunk * (4 * KS) + sg * 2 + kq, last_plane);       // plane8
                 src = Xg + (long)pce * a.x_piece + (long)pc * a.x_ps;
@@ -201,6 +208,9 @@ DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw,
 //   PREC = 1 ("S3"): the X input and the weights are split-bf16 (see above): X tile rows are
 //   [(sub*2 + g)*6 + piece*2 + kq] (16 channels per group g, 8 per kq half), the consumers run 6
 //   v_mfma_f32_32x32x16_bf16 per (group, row tile, frame tile) instead of 8 fp32 MFMAs per 16 channels.
+//   PREC = 2 ("bf16"): the X input and the weights are piece 0 of that split alone - each value rounded once to bf16 - in one
+//   plane set: X tile rows [(sub*2 + g)*2 + kq], ONE v_mfma_f32_32x32x16_bf16 per (group, row tile, frame tile) and K step;
+//   the EPI_GATE output and the second output Y2 are written in the same form (store_bf16_quad).
 //   COH = 1 (the fused residual-stack kernel only): the tensors this body exchanges with OTHER workgroups of the
 //   same launch - its X input (hd) and its EPI_GATE output (g) - are read with sc1 loads and written with sc1
 //   (write-through) stores, the placement-independent hand-off form of MI355X_MICROARCH.md "inter-workgroup
@@ -230,7 +240,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     constexpr int BN = 32 * NW;
     static_assert(NI == 1 || NI == 2 || ((NI == 3 || NI == 5) && EPI == EPI_GATE && PREC == 0 && KS == 1 && FOLDP == 1),
                   "block widths: 64, 128; 96, 160 (conv)");
-    constexpr int XP = (PREC ? 12 : 8) * KS;      // 16-byte rows per X tile
+    constexpr int XP = (PREC == 2 ? 4 : PREC ? 12 : 8) * KS;      // 16-byte rows per X tile
     // Consumer wave arrangement: 4 (M) x 1 (N) - every wave owns 32 distinct rows x all 64*NI frames of the
     // block, so no two waves issue the same A-fragment loads (a CU's vector-memory path is the stressed
     // resource: with 2 x 2 the two N-waves fetched identical fragments); the X tile is shared through LDS.
@@ -308,7 +318,84 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // a branch + s_waitcnt vmcnt(0) per quad), the EPI_RES_SKIP read-modify-write tile waits in LDS (Rs).
     float4 eop[NW][4];
 
-    if constexpr (PREC == 1) {
+    if constexpr (PREC == 2) {
+        // One-pass bf16: both operands rounded once to bf16 (piece 0 of the split), ONE v_mfma_f32_32x32x16_bf16 per
+        // (group, row tile, frame tile) and K step.  A slab = 8 KiB, [g16 2][kq 2][row 128][8 bf16]; X tile rows
+        // [(sub*2 + g)*2 + kq].  A K step is only 2*NW MFMAs of 32 cycles, shorter than an L2 round trip: the A fragments
+        // are refreshed in place TWO steps ahead (two register sets, roles alternate statically), each load right behind
+        // the MFMAs that consumed its registers; every MFMA has one B-fragment read (the wave tile is 32 rows: a
+        // fragment is used once), issued one group ahead in the shadow of the previous MFMA.
+        const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)(a.Wp + (long)mt * NS * 2048), 0, (unsigned)NS * 8192u, 0x00020000);
+        const int wvo = (hi * 128 + wave * 32 + r) * 16;
+        auto load_ag = [&](int slab, int g) -> uint4 {
+            DR_CHECK(slab >= 0 && wvo + slab * 8192 + g * 4096 + 16 <= NS * 8192, 113, slab, NS);
+            return buffer_load_u4(wrsrc, wvo, slab * 8192 + g * 4096);
+        };
+        const int s0 = c0 * KS * a.taps;
+        AF2 wA, wB;
+        wA.v[0] = load_ag(s0, 0); wA.v[1] = load_ag(s0, 1);
+        wB.v[0] = load_ag(min(s0 + 1, NS - 1), 0); wB.v[1] = load_ag(min(s0 + 1, NS - 1), 1);
+        const int cen = (a.taps - 1) >> 1;
+        const int per_chunk = a.taps * KS;
+        const uint4* Xsb = reinterpret_cast<const uint4*>(Xs);
+        struct BF1 { uint4 v[NW]; };              // B fragments of one 16-channel group: NW 32-frame tiles
+        BF1 b0, b1;
+        auto xaddr = [&](int chunk, int q) -> const uint4* {
+            const int j = q / KS, sub = q - j * KS;
+            return Xsb + (((chunk - c0) & 1) * XP + sub * 4 + hi) * FW + halo + (j - cen) * a.dil + r;
+        };
+        auto rd1 = [&](const uint4* Xb, int g) -> BF1 {
+            BF1 o;
+#pragma unroll
+            for (int ni = 0; ni < NW; ++ni) {
+                DR_CHECK_LDS(Xb + g * 2 * FW + ni * 32, xs0, xs1, 114);
+                o.v[ni] = Xb[g * 2 * FW + ni * 32];
+            }
+            return o;
+        };
+        auto mma1 = [&](auto FIRST, const uint4 af, const BF1& bf) {
+            constexpr bool kFirst = FOLD && decltype(FIRST)::value;      // the chunk's first products: C = 0 (a new chain)
+#pragma unroll
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(af, bf.v[ni], kFirst ? zero16 : acc[ni]);
+        };
+        auto step = [&](auto ROLE, auto FIRST, int slab, int chunk, int q) {
+            constexpr bool kB = decltype(ROLE)::value;
+            const uint4* Xb = xaddr(chunk, q);
+            const int nx = min(slab + 2, NS - 1);
+            b1 = rd1(Xb, 1);
+            mma1(FIRST, kB ? wB.v[0] : wA.v[0], b0);
+            if constexpr (kB) wB.v[0] = load_ag(nx, 0);
+            else wA.v[0] = load_ag(nx, 0);
+            b0 = rd1(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
+            mma1(std::false_type{}, kB ? wB.v[1] : wA.v[1], b1);
+            if constexpr (kB) wB.v[1] = load_ag(nx, 1);
+            else wA.v[1] = load_ag(nx, 1);
+            sgb<0x100, 1>();
+            sgb_mix1<NW - 1, 0>(); sgb<0x8, 1>(); sgb<0x20, 1>();
+            sgb<0x100, 1>();
+            sgb_mix1<NW - 1, 0>(); sgb<0x8, 1>(); sgb<0x20, 1>();
+        };
+        using T_ = std::true_type;
+        using F_ = std::false_type;
+        for (int chunk = c0; chunk < c1; ++chunk) {
+            auto at = [&](auto R, auto FIRST, int q) {
+                const int j = q / KS, sub = q - j * KS;
+                step(R, FIRST, (chunk * KS + sub) * a.taps + j, chunk, q);
+            };
+            __syncthreads();              // X tile #chunk staged by the producers (matches their hand-over barrier)
+            b0 = rd1(xaddr(chunk, 0), 0);
+            fold();                       // the previous chunk's chain joins the outer sum (zeros the first time)
+            at(F_{}, T_{}, 0);
+            int q = 1;
+            for (; q + 2 <= per_chunk; q += 2) {
+                at(T_{}, F_{}, q);
+                at(F_{}, F_{}, q + 1);
+            }
+            if (q < per_chunk) at(T_{}, F_{}, q);
+            else { const AF2 t = wA; wA = wB; wB = t; }      // (an odd number of steps: the next step's fragments sit in set B)
+        }
+    } else if constexpr (PREC == 1) {
         // A fragments through buffer loads with scalar per-step offsets (see the fp32 path): slab = 24 KiB,
         // [g16 2][piece 3][kq 2][row 128][8 bf16]
         const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -688,7 +775,9 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = v0[e] * v0[e] + v1[e] * v1[e];
                     }
-                    if (a.out_s3 & 1) {   // g for the split-bf16 1x1 kernel
+                    if constexpr (PREC == 2) {   // g for the one-pass bf16 1x1 kernel
+                        store_bf16_quad<COH>(a.Y + (long)be * a.y_bs, o, c0, t, a.T, a.wt_store);
+                    } else if (a.out_s3 & 1) {   // g for the split-bf16 1x1 kernel
                         store_s3_quad<COH>(a.Y + (long)be * a.y_bs, o, c0, t, a.T, a.y_rows >> 3, a.wt_store);
                     } else {
                         float* dst = a.Y + (long)be * a.y_bs + (long)(c0 >> 2) * a.y_ps + (long)t * a.y_fs;
@@ -706,7 +795,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                             float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
                             residual_quad(v, ebias[q], eop[ni][q], o);
                             *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                            if (a.Y2) store_y2<COH, 0>(a, be, o, ed2[q], p0, t);
+                            if (a.Y2) store_y2<COH, 0, PREC == 2>(a, be, o, ed2[q], p0, t);
                         } else {
                             float* dst = a.skip + (long)be * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
                             skip_quad(v, ebias[q], eop[ni][q], a.skip_init, o);

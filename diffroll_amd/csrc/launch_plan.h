@@ -41,7 +41,7 @@ inline size_t gemm_lds_bytes(int NI, int KS, int taps, int dil, int prec, int ep
     const int halo = ((taps - 1) / 2) * dil;
     const int BN = gemm_block_frames(NI);
     const int FW = BN + 2 * halo;
-    return (size_t)2 * (prec ? 12 : 8) * KS * FW * 16 + (epi == EPI_RES_SKIP ? (size_t)32 * BN * 16 : 0);
+    return (size_t)2 * (prec == 2 ? 4 : prec ? 12 : 8) * KS * FW * 16 + (epi == EPI_RES_SKIP ? (size_t)32 * BN * 16 : 0);
 }
 
 // THE split-K decision of gemm_kernel launches (the launcher takes it; the engine's tile choice prices a launch with it,
@@ -76,8 +76,9 @@ inline KSplitPlan plan_ksplit(const PlanKnobs& k, long tiles, int nchunks, int k
 // 64 / 128 / 160 frames.
 inline int stack_tile_frames(int FL) { return FL == 5 ? 160 : 64 * FL; }
 // split-bf16 flavour: max over its two phase bodies (conv: S3 X tiles; 1x1: 128-channel S3 X tiles + the 64-frame h / skip tile)
-inline size_t stack3_lds_bytes(int FL, int taps, int max_dil) {
-    return std::max(gemm_lds_bytes(FL, 1, taps, max_dil, 1, EPI_GATE), gemm_lds_bytes(1, 4, 1, 1, 1, EPI_RES_SKIP)) + 16;
+// (prec = 2: the one-pass bf16 flavour - the same two bodies on X tiles of a third the rows)
+inline size_t stack3_lds_bytes(int FL, int taps, int max_dil, int prec = 1) {
+    return std::max(gemm_lds_bytes(FL, 1, taps, max_dil, prec, EPI_GATE), gemm_lds_bytes(1, 4, 1, 1, prec, EPI_RES_SKIP)) + 16;
 }
 // blocks of one clip evaluation (= one barrier group): M tiles x frame tiles
 inline int stack_group_blocks(int FL, int Cp, int T) {
@@ -185,7 +186,7 @@ inline Tile pick_pointwise_tile(const PlanKnobs& k, int MT, int NB, int T, int p
 struct NetShape {
     int NB, n_cond, bmod, T;
     int Cp, L, K, max_dil;      // padded channels, residual layers, kernel size, largest dilation
-    int prec;                   // 0 exact fp32, 1 split-bf16
+    int prec;                   // 0 exact fp32, 1 split-bf16, 2 one-pass bf16
     int n_cus;                  // CUs of the device (0: unknown - never fused)
     int fuse;                   // FusedMode::active(): 0 one launch per phase, 1 fused where the cost model likes it, 2 fused regardless
     int opt_blocked, opt_tail;  // options "blocked_accumulation" and "fused_tail"
@@ -211,7 +212,8 @@ inline NetPlan plan_network(const NetShape& s, const PlanKnobs& k) {
     int stack_from = -1;                   // first phase run by the fused kernel (-1: none)
     int stack_ni = 0, stack_chunks = 1;    // flavour, and how many sample chunks the evaluation is launched in
     bool fused_step = false;
-    // (the split-bf16 precision has its own flavour of the kernel: 128-channel S3 chunks in the 1x1 phases need Cp % 128 == 0)
+    // (the split-bf16 and one-pass bf16 precisions have their own flavours of the kernel: 128-channel chunks in the 1x1 phases
+    // need Cp % 128 == 0)
     const int stack3 = k.stack3;
     const int fuse = s.fuse;
     if (fuse && (prec == 0 || (stack3 && Cp % 128 == 0)) && L <= DR_STACK_MAX_LAYERS && s.n_cus > 0) {
@@ -245,7 +247,7 @@ inline NetPlan plan_network(const NetShape& s, const PlanKnobs& k) {
             const int bn = stack_tile_frames(fl);
             const long gsize = stack_group_blocks(fl, Cp, T);                           // blocks per sample
             const long cap = std::min<long>(s.n_cus, 1024) / gsize;                     // samples per launch
-            if (cap < 1 || (prec ? stack3_lds_bytes(fl, s.K, s.max_dil) : stack_lds_bytes(fl, s.K, s.max_dil)) > 160 * 1024) continue;
+            if (cap < 1 || (prec ? stack3_lds_bytes(fl, s.K, s.max_dil, prec) : stack_lds_bytes(fl, s.K, s.max_dil)) > 160 * 1024) continue;
             const long chunks = (NB + cap - 1) / cap;
             if ((NB + chunks - 1) / chunks > STACK_GROUPS) continue;
             // (what fusing saves is per-launch overhead, which the per-phase launches amortise over their rounds:

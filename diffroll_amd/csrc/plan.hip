@@ -93,10 +93,15 @@ struct Eval {
     const int* tsel;               // (device, NB ints): per-sample diffusion steps; null: step t for all
 };
 
-// S3 input description of an activation tensor with Cp channels
-static void s3_in(GemmArgs& a, const float* X, int Cp, int T) {
+// per-sample size (4-byte units) of the reduced-precision form of an activation tensor with Cp channels: the three bf16
+// pieces of S3 (prec = 1) or the one bf16 plane set (prec = 2)
+static long lowp_bs(int prec, int Cp, int T) {
     const long act_bs = (long)Cp * T;
-    a.X = X; a.x_bs = act_bs + act_bs / 2; a.x_piece = (long)(Cp / 8) * T * 4; a.x_ps = (long)T * 4; a.x_fs = 4;
+    return prec == 2 ? act_bs / 2 : act_bs + act_bs / 2;
+}
+// S3 / one-pass bf16 input description of an activation tensor with Cp channels
+static void s3_in(GemmArgs& a, const float* X, int Cp, int T, int prec) {
+    a.X = X; a.x_bs = lowp_bs(prec, Cp, T); a.x_piece = (long)(Cp / 8) * T * 4; a.x_ps = (long)T * 4; a.x_fs = 4;
     a.x_planes = Cp / 8; a.kchunks = Cp / 32;
 }
 
@@ -127,10 +132,12 @@ static int launch_inproj(const Eval& v, const PlanKnobs& k) {
     // hd = h + d_0 (model/diffwave.py:138-139), fp32 P4 or split-bf16 for the first dilated conv
     a.d2 = e->d_dtab + (v.tsel ? 0 : (size_t)v.t * e->L * Cp);
     a.tsel = v.tsel; a.d2_ts = (long)e->L * Cp;
-    if (e->prec) { a.Y2 = e->hd3; a.y2_bs = act_bs + act_bs / 2; a.out_s3 = 2; }
+    if (e->prec == 1) { a.Y2 = e->hd3; a.y2_bs = act_bs + act_bs / 2; a.out_s3 = 2; }
     else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     allow_splitk(e, a);
     HIPCHK(e, launch_gemm(a, EPI_RELU, pick_ni(k, a.MT, v.NB, T, 1, 1), v.st));
+    // (one-pass bf16: this fp32 kernel leaves hd in P4; the first conv's operand is its rounding)
+    if (e->prec == 2) HIPCHK(e, launch_round_bf16(e->hd, e->hd3, v.NB, Cp, T, v.st));
     e->inproj_launches += 1;
     return DR_OK;
 }
@@ -145,7 +152,7 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
         const int nb = v.NB / p.stack_chunks + (ck < v.NB % p.stack_chunks ? 1 : 0);      // balanced chunk sizes
         StackArgs sa{};
         sa.h = e->h + b0 * act_n; sa.hd = e->hd + b0 * act_n; sa.g = e->g + b0 * act_n; sa.skip = e->skip + b0 * act_n;
-        if (prec) { sa.hd = e->hd3 + b0 * (act_n + act_n / 2); sa.g = e->g3 + b0 * (act_n + act_n / 2); }      // the S3 tensors
+        if (prec) { sa.hd = e->hd3 + b0 * lowp_bs(prec, Cp, T); sa.g = e->g3 + b0 * lowp_bs(prec, Cp, T); }      // the S3 / bf16 tensors
         sa.d2 = e->d_dtab + (v.tsel ? 0 : (size_t)v.t * L * Cp);
         sa.tsel = v.tsel ? v.tsel + b0 : nullptr; sa.d2_ts = (long)L * Cp;
         sa.zero = zero_vec();
@@ -165,13 +172,13 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
         for (int l = 0; l < L; ++l) {
             const LayerW& w = e->layers[l];
             StackLayer& y = sa.layer[l];
-            y.conv_w = prec ? w.conv_w3 : w.conv_w; y.conv_b = w.conv_b;
+            y.conv_w = w.conv_w_of(prec); y.conv_b = w.conv_b;
             y.conv_b2 = v.zero_spec ? w.conv_b_z : w.conv_b_u;
             y.cond2 = nullptr;
             if (e->cond_tr && !v.zero_spec) { y.cond2 = e->cond_tr + (size_t)l * 2 * Cp * T; y.conv_b2 = w.conv_b; }
             // (a chunk without conditional samples keeps a readable pointer: the kernel prefetches, then ignores it)
             y.cond = e->cond ? e->cond + (size_t)l * e->fe_B * 2 * Cp * T : e->cond_dummy;
-            y.out_w = prec ? w.out_w3 : w.out_w; y.out_b = w.out_b; y.dil = w.dil;
+            y.out_w = w.out_w_of(prec); y.out_b = w.out_b; y.dil = w.dil;
         }
         int rc = profiled(e, v.st, true, [&]() -> int {
             HIPCHK(e, launch_stack(sa, p.stack_fl, e->max_dil, v.st, prec));
@@ -187,7 +194,8 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
                            std::to_string(e->K) + " + conditioner + gate and 1x1 + residual/skip, phases " +
                            std::to_string(p0) + ".." + std::to_string(p1 - 1) + " of " + std::to_string(2 * L) +
                            (p.stack_chunks > 1 ? ", " + std::to_string(p.stack_chunks) + " sample chunks" : "") +
-                           (prec ? (p.fold ? ", split-bf16, blocked accumulation" : ", split-bf16, one chain per output")
+                           (prec == 2 ? (p.fold ? ", bf16, blocked accumulation" : ", bf16, one chain per output")
+                            : prec ? (p.fold ? ", split-bf16, blocked accumulation" : ", split-bf16, one chain per output")
                                  : (p.fold ? ", blocked accumulation" : ", one fp32 chain per output")) + ")";
         });
         if (rc) return rc;
@@ -201,8 +209,8 @@ static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int 
     dr_engine* e = v.e;
     const int Cp = e->Cp, L = e->L, T = v.T, NB = v.NB, bmod = v.bmod, prec = e->prec;
     const LayerW& w = e->layers[l];
-    GemmArgs a = p4_gemm(prec ? w.conv_w3 : w.conv_w, w.conv_b, Cp / 64, e->hd, Cp / 4, NB, T);
-    if (prec) s3_in(a, e->hd3, Cp, T);
+    GemmArgs a = p4_gemm(w.conv_w_of(prec), w.conv_b, Cp / 64, e->hd, Cp / 4, NB, T);
+    if (prec) s3_in(a, e->hd3, Cp, T, prec);
     a.bias2 = v.zero_spec ? w.conv_b_z : w.conv_b_u;     // samples >= n_cond: spec == 0 or spec == -1
     if (e->cond_tr && !v.zero_spec) {                    // ... or the learned unconditional spectrogram
         a.cond2 = e->cond_tr + (size_t)l * 2 * Cp * T;
@@ -215,7 +223,7 @@ static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int 
     a.c_n = e->fe_B;        // (option "draws": conditional row b reads clip b % fe_B)
     a.n_cond = v.n_cond;
     p4_out(a, e->g, Cp / 4, T, Cp);
-    if (prec) { const long act_bs = (long)Cp * T; a.Y = e->g3; a.y_bs = act_bs + act_bs / 2; a.out_s3 = 1; }
+    if (prec) { a.Y = e->g3; a.y_bs = lowp_bs(prec, Cp, T); a.out_s3 = 1; }
     allow_splitk(e, a);
     // Classifier-free guidance evaluates the same x_t twice (samples b and b + bmod): in the first layer
     // both halves convolve the same h + d_0, so the contraction is done once per pair and the epilogue
@@ -245,13 +253,13 @@ static int launch_res_skip(const Eval& v, const PlanKnobs& k, int l) {
     const int Cp = e->Cp, L = e->L, T = v.T, NB = v.NB, prec = e->prec;
     const long act_bs = (long)Cp * T;
     const LayerW& w = e->layers[l];
-    GemmArgs a = p4_gemm(prec ? w.out_w3 : w.out_w, w.out_b, Cp / 64, e->g, Cp / 4, NB, T);
-    if (prec) s3_in(a, e->g3, Cp, T);
+    GemmArgs a = p4_gemm(w.out_w_of(prec), w.out_b, Cp / 64, e->g, Cp / 4, NB, T);
+    if (prec) s3_in(a, e->g3, Cp, T, prec);
     p4_out(a, e->h, Cp / 4, T, Cp);
     if (l + 1 < L) {
         a.d2 = e->d_dtab + ((v.tsel ? 0 : (size_t)v.t * L) + l + 1) * Cp;
         a.tsel = v.tsel; a.d2_ts = (long)L * Cp;
-        if (prec) { a.Y2 = e->hd3; a.y2_bs = act_bs + act_bs / 2; a.out_s3 = 2; }
+        if (prec) { a.Y2 = e->hd3; a.y2_bs = lowp_bs(prec, Cp, T); a.out_s3 = 2; }
         else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     }
     a.skip = e->skip; a.s_bs = (long)Cp * T; a.skip_init = (l == 0);

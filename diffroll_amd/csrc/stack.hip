@@ -22,6 +22,8 @@ DR_BOUNDS_TU(stack)
 // EPI_RES_SKIP, 1>) on the block's 64-frame tile(s), which re-reads its h / skip tile from global every layer (nothing is
 // LDS-resident here: the S3 X tiles of a 128-channel 1x1 chunk need the space); same device code as the per-phase launches
 // of that precision: bit-identical to them.  Needs Cp % 128 == 0.
+// PREC = 2: the one-pass bf16 precision - the same phase structure on the one-plane-set bf16 tensors ([sample][channel/8][frame]
+// [8 bf16]: a third of an S3 tensor) and gemm_body<.., PREC = 2>.
 template <int FL, int FOLDP = 1, int PREC = 0>
 __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -128,14 +130,14 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
         a.x_bs = act_bs; a.x_ps = (long)s.T * 4; a.x_fs = 4; a.x_planes = P; a.kchunks = s.Cp >> 5;
         a.y_bs = act_bs; a.y_ps = (long)s.T * 4; a.y_fs = 4; a.y_rows = s.Cp;
         if constexpr (PREC) {
-            const long s3_bs = act_bs + act_bs / 2;          // per-sample size of an S3 tensor (4-byte units)
+            const long s3_bs = PREC == 2 ? act_bs / 2 : act_bs + act_bs / 2;      // per-sample size of an S3 / bf16 tensor (4-byte units)
             if ((p & 1) == 0) {
                 a.Wp = ly.conv_w; a.bias = ly.conv_b; a.bias2 = ly.conv_b2;
                 a.X = s.hd; a.x_bs = s3_bs; a.x_piece = (long)(s.Cp >> 3) * s.T * 4; a.x_planes = s.Cp >> 3;
                 a.taps = s.taps; a.dil = ly.dil;
                 a.cond = ly.cond; a.cond2 = ly.cond2; a.c_bs = s.c_bs; a.c_b0 = s.c_b0; a.c_n = s.c_n; a.n_cond = s.n_cond;
                 a.Y = s.g; a.y_bs = s3_bs; a.out_s3 = 1;
-                gemm_body<FL, 1, EPI_GATE, 1, 1, FOLDP>(a, smem, mt, nt, 0);
+                gemm_body<FL, 1, EPI_GATE, PREC, 1, FOLDP>(a, smem, mt, nt, 0);
             } else {
                 a.Wp = ly.out_w; a.bias = ly.out_b;
                 a.X = s.g; a.x_bs = s3_bs; a.x_piece = (long)(s.Cp >> 3) * s.T * 4; a.x_planes = s.Cp >> 3;
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         __syncthreads();
                     }
-                    if (!idle && t64 < tps64) gemm_body<1, 4, EPI_RES_SKIP, 1, 1>(a, smem, mt, b_ * tps64 + t64, 0);
+                    if (!idle && t64 < tps64) gemm_body<1, 4, EPI_RES_SKIP, PREC, 1>(a, smem, mt, b_ * tps64 + t64, 0);
                 }
             }
         } else
@@ -280,7 +282,7 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
     if (prec && ((s.Cp & 127) || FL == 5)) return hipErrorInvalidValue;
     if (s.L < 1 || s.L > DR_STACK_MAX_LAYERS || s.p0 < 0 || s.p1 > 2 * s.L || s.p0 >= s.p1 || (s.Cp & 63)) return hipErrorInvalidValue;
     const int BN = stack_tile_frames(FL), MT = s.Cp >> 6, gsize = stack_group_blocks(FL, s.Cp, s.T);
-    const size_t lds = prec ? stack3_lds_bytes(FL, s.taps, max_dil) : stack_lds_bytes(FL, s.taps, max_dil);
+    const size_t lds = prec ? stack3_lds_bytes(FL, s.taps, max_dil, prec) : stack_lds_bytes(FL, s.taps, max_dil);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     StackArgs b = s;
     b.rs_off = (int)(lds - 16 - (size_t)32 * BN * 16);
@@ -302,6 +304,13 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
 #endif
     (void)MT;
     const dim3 grid((unsigned)(gsize * NBp));
+    if (prec < 0 || prec > 2) return hipErrorInvalidValue;
+    if (prec == 2) {
+        if (FL == 1) hipLaunchKernelGGL((stack_kernel<1, 1, 2>), grid, dim3(512), lds, st, b);
+        else if (s.fold128) hipLaunchKernelGGL((stack_kernel<2, 1, 2>), grid, dim3(512), lds, st, b);
+        else hipLaunchKernelGGL((stack_kernel<2, 0, 2>), grid, dim3(512), lds, st, b);
+        return hipGetLastError();
+    }
     if (prec) {
         if (FL == 1) hipLaunchKernelGGL((stack_kernel<1, 1, 1>), grid, dim3(512), lds, st, b);
         else if (s.fold128) hipLaunchKernelGGL((stack_kernel<2, 1, 1>), grid, dim3(512), lds, st, b);
@@ -317,7 +326,8 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
 }
 hipError_t init_stack_kernels() {
     return allow_max_lds(&stack_kernel<1>, &stack_kernel<2, 0>, &stack_kernel<5>, &stack_kernel<2, 1>,
-                         &stack_kernel<1, 1, 1>, &stack_kernel<2, 0, 1>, &stack_kernel<2, 1, 1>);
+                         &stack_kernel<1, 1, 1>, &stack_kernel<2, 0, 1>, &stack_kernel<2, 1, 1>,
+                         &stack_kernel<1, 1, 2>, &stack_kernel<2, 0, 2>, &stack_kernel<2, 1, 2>);
 }
 
 }  // namespace dr

@@ -82,10 +82,21 @@ enum {
 /* arithmetic of the two hot contractions (dilated conv, 1x1 output projection); everything else is fp32 */
 enum {
     DR_PRECISION_F32 = 0,     /* exact fp32 MFMA (v_mfma_f32_32x32x2_f32): the default                     */
-    DR_PRECISION_BF16X3 = 1   /* opt-in: each fp32 operand is split EXACTLY into three bf16 pieces and a
+    DR_PRECISION_BF16X3 = 1,  /* opt-in: each fp32 operand is split EXACTLY into three bf16 pieces and a
                                  product is formed from the six piece products with i + j <= 2 on the bf16
                                  MFMA with fp32 accumulation (drops terms <= 2^-24 |ab|); fp32-level error
                                  at 2.67x the matrix rate                                                  */
+    DR_PRECISION_BF16 = 2     /* opt-in: ordinary one-pass bf16.  Rounding happens at exactly the operands
+                                 BF16X3 splits - the input x + diffusion_projection and the weights of each
+                                 layer's dilated conv, the gated activation sigmoid * tanh and the weights of
+                                 each layer's output projection - each rounded ONCE to bf16, round to nearest
+                                 even (piece 0 of that split); products are exact (one bf16 MFMA per K step),
+                                 accumulation is fp32.  Biases, the conditioner term, the residual stream,
+                                 the skip sum and everything outside the residual stack (front-end, embedding,
+                                 input / skip / head projections, update) stay fp32 as in BF16X3; nothing is
+                                 truncated and no bf16 value is stored where BF16X3 stores fp32.  One sixth
+                                 of BF16X3's matrix work, one third of its operand bytes; about 1e-3 rms
+                                 error per evaluation on unit-scale activations (README.md)                */
 };
 
 /* which spectrogram a dr_forward evaluation sees (model/diffwave.py:656-660) */
@@ -307,7 +318,8 @@ int dr_extract_x0(dr_engine* e, const float* d_x_t, const float* d_epsilon, cons
 int dr_set_spec_norm(dr_engine* e, int mode);
 
 /* Select DR_PRECISION_* for subsequent dr_forward / dr_step / dr_sample calls (default F32).
- * Drops a captured chain. */
+ * Drops a captured chain.  BF16X3 and BF16 each build their own weight packing the first time they are
+ * selected (neither builds the other's); the mode changes only once that packing exists. */
 int dr_set_precision(dr_engine* e, int mode);
 
 /*
