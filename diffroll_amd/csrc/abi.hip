@@ -600,6 +600,8 @@ int dr_create(dr_engine** out, const dr_config* cfg) {
         cfg->n_fft <= 0 || cfg->n_fft % 32 || cfg->hop_length <= 0 || cfg->hop_length % 4 ||
         cfg->dilation_base <= 0 || cfg->dilation_bound <= 0)
         return fail(nullptr, DR_EINVAL, "unsupported configuration");
+    if (cfg->n_fft > (1 << 16) || cfg->residual_channels > (1 << 15))
+        return fail(nullptr, DR_EINVAL, "configuration too large");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, DR_EHIP, "no HIP device available: the engine has no CPU fallback");
@@ -621,8 +623,6 @@ int dr_create(dr_engine** out, const dr_config* cfg) {
             return fail(nullptr, DR_EHIP, "allocating the zero vector failed");
         g_zero_vecs[cfg->device] = (const float*)z;
     }
-    if (cfg->n_fft > (1 << 16) || cfg->residual_channels > (1 << 15))
-        return fail(nullptr, DR_EINVAL, "configuration too large");
     dr_engine* e = new dr_engine();
     e->cfg = *cfg;
     e->C = cfg->residual_channels;
