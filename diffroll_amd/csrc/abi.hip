@@ -220,133 +220,43 @@ int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
 // address whether or not marks were set when it was captured).  Without marks: window b of recording 0.
 int write_windows(dr_engine* e, int B, bool force, hipStream_t st) {
     if (e->opt.win_O <= 0 || B > STACK_GROUPS || (!force && e->win_marks.empty() && e->opt.draws <= 1)) return DR_OK;
-    WindowTable tab;
-    // option "draws": every draw starts new recordings, and draw d of recording r is keyed first_sample + r + d * stride
-    // (the recordings of one draw, or option "draw_stride")
-    const int n = B / e->opt.draws;
-    const size_t stride = e->opt.draw_G > 0 ? (size_t)e->opt.draw_G : e->win_marks.size() + 1;
-    size_t m = 0;
-    for (int b = 0, first = 0; b < B; ++b) {
-        const int j = b % n;
-        if (j == 0) { m = 0; first = b; }
-        if (m < e->win_marks.size() && e->win_marks[m] == j) { ++m; first = b; }
-        tab.w[b] = window_entry((unsigned)((size_t)(b / n) * stride + m), (unsigned)(b - first));
-    }
-    HIPCHK(e, launch_set_windows(e->d_wintab, tab, B, st));
+    HIPCHK(e, launch_set_windows(e->d_wintab, window_table(e->win_marks, B, e->opt.draws, e->opt.draw_G), B, st));
     return DR_OK;
 }
 
-// option "sampling_steps" (include/diffroll_amd.h): n visited steps t_i = round-half-up(i (S - 1) / (n - 1)), i = n-1 .. 0,
-// in integer arithmetic.  A visited t whose successor t' is t - 1 (or t == 0) keeps the committed row; every other one
-// gets a row derived in double precision from the committed fp32 sqrt_acp / sqrt_1m_acp of t and t' (family 0, columns
-// 2 and 3) and rounded to fp32 once, in the column order update_quad.h reads.  Rebuilt by dr_commit and by the option.
+// option "sampling_steps": the chain's steps and, for a respaced chain, its coefficient table on the device (chain_tables.h:
+// ChainSteps, respaced_table).  Rebuilt by dr_commit and by the option.
 int build_respaced(dr_engine* e) {
-    const int S = e->S, n = e->opt.steps;
-    e->rs_steps.clear();
+    e->steps = ChainSteps(e->S, 0);
     e->d_coef_rs.reset();
-    if (n == 0 || n == S) return DR_OK;       // the full chain: committed rows
-    std::vector<int> steps(n);
-    for (int i = n - 1; i >= 0; --i)
-        steps[n - 1 - i] = (int)((2LL * i * (S - 1) + (n - 1)) / (2LL * (n - 1)));
-    std::vector<float> tab(e->h_coef);
-    const float* h = e->h_coef.data();        // family 0 row t: [.., .., sqrt_acp[t], sqrt_1m_acp[t], ..]
-    for (int i = 0; i + 1 < n; ++i) {
-        const int t = steps[i], tp = steps[i + 1];
-        if (tp == t - 1) continue;
-        const double A = h[(size_t)t * 5 + 2], Sm = h[(size_t)t * 5 + 3], Ap = h[(size_t)tp * 5 + 2], Smp = h[(size_t)tp * 5 + 3];
-        const double r2 = (A / Ap) * (A / Ap);                       // alpha of the stride: acp[t] / acp[t']
-        const double sigma = (Smp / Sm) * std::sqrt(1.0 - r2);
-        const double dir = std::sqrt(std::max(0.0, 1.0 - Ap * Ap - sigma * sigma));   // (>= 0 exactly; clamps rounding)
-        const double beta = 1.0 - r2;
-        const double rows[DR_COEF_FAMILIES][5] = {
-            {Ap, dir, A, Sm, sigma},                                  // ddpm_x0 family
-            {Ap, std::sqrt(1.0 - Ap * Ap), A, Sm, 0.0},               // ddim_x0 family
-            {Ap / A, beta, Sm, std::sqrt(beta * Smp * Smp / (Sm * Sm)), 0.0},   // ddpm (epsilon)
-            {Ap, Smp, A, Sm, 0.0},                                    // ddim (epsilon)
-            {Ap, dir, A, Sm, sigma}};                                 // ddim2ddpm (epsilon)
-        for (int f = 0; f < DR_COEF_FAMILIES; ++f)
-            for (int c = 0; c < 5; ++c) tab[((size_t)f * S + t) * 5 + c] = (float)rows[f][c];
-    }
+    const ChainSteps steps(e->S, e->opt.steps);
+    if (!steps.respaced()) return DR_OK;      // the full chain: committed rows
+    const std::vector<float> tab = respaced_table(e->h_coef, steps);
     HIPCHK(e, e->d_coef_rs.ensure(tab.size(), false));
     HIPCHK(e, hipMemcpy(e->d_coef_rs, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    e->rs_steps = std::move(steps);
+    e->steps = steps;
     return DR_OK;
 }
 
-// the chain's steps: position i (0 = the first step, S - 1 or t_{n-1}) -> diffusion step t; -1 past the end
-int chain_steps(const dr_engine* e) { return e->rs_steps.empty() ? e->S : (int)e->rs_steps.size(); }
-int chain_step(const dr_engine* e, int i) {
-    if (i >= chain_steps(e)) return -1;
-    return e->rs_steps.empty() ? e->S - 1 - i : e->rs_steps[i];
-}
-
-// option "solver_order" (include/diffroll_amd.h): the (S, 5) rows solver_quad reads (update_quad.h), for the steps the chain
-// visits - all of them, or those of option "sampling_steps".  With lambda_t = log(sqrt_acp[t] / sqrt_1m_acp[t]), t' the
-// successor of t and t'' its predecessor in the chain, h = lambda_t' - lambda_t and h_prev = lambda_t - lambda_t'':
-//   t > 0:  [sqrt_1m_acp[t'] / sqrt_1m_acp[t], -sqrt_acp[t'] expm1(-h), sqrt_acp[t], c, 0]
-//           c = h / (2 h_prev) for order 2 when t is not the chain's first step and t' != 0, else 0: the step into 0 is
-//           first order (lambda jumps between steps 1 and 0 of the linear schedule; extrapolating across it hurts short chains)
-//   t == 0: [0, 0, sqrt_acp[0], 0, 0]
-// option "solver_noise" (the stochastic form, SDE-DPM-Solver++), same c:
-//   t > 0:  [(sqrt_1m_acp[t'] / sqrt_1m_acp[t]) exp(-h), -sqrt_acp[t'] expm1(-2h), sqrt_acp[t], c, sqrt_1m_acp[t'] sqrt(-expm1(-2h))]
-// With sqrt_acp^2 + sqrt_1m_acp^2 = 1 column 4 is the sigma of the derived DR_COEF_DDPM_X0 row of build_respaced and column
-// 0 its sqrt(1 - acp' - sigma^2) / sqrt_1m_acp: first order is the ddpm_x0 update by another arithmetic route.
-// derived in double from the committed fp32 scalars (family 0, columns 2 and 3), rounded to fp32 once.  Rebuilt by
-// dr_commit and whenever "sampling_steps", "solver_order" or "solver_noise" changes; the caller has made sure no chain is reading it.
-// Rows [S, 2 S) repeat rows [0, S) with c = 0: step t as a chain's FIRST step (option "start_step": a started chain has no
-// previous prediction).  run_step picks row S + t for the step the option names - no row is rewritten when the option
-// changes, so a chain captured under another start reads at replay what it read when it was captured.
+// option "solver_order": the solver's rows for the steps the chain visits (chain_tables.h: solver_table), on the host and -
+// while an order is set - on the device.  Rebuilt by dr_commit and whenever "sampling_steps", "solver_order" or
+// "solver_noise" changes; the caller has made sure no chain is reading it.
 int build_solver(dr_engine* e) {
-    const int S = e->S, n = chain_steps(e);
-    e->h_solver.assign((size_t)2 * S * 5, 0.f);
+    e->h_solver = solver_table(e->h_coef, e->steps, e->opt.solver, e->opt.solver_noise);
     if (e->opt.solver == 0) return DR_OK;
-    const float* h = e->h_coef.data();
-    auto lambda = [&](int t) { return std::log((double)h[(size_t)t * 5 + 2] / (double)h[(size_t)t * 5 + 3]); };
-    for (int i = 0; i < n; ++i) {
-        const int t = chain_step(e, i);
-        float* row = e->h_solver.data() + (size_t)t * 5;
-        row[2] = h[(size_t)t * 5 + 2];
-        if (t == 0) continue;
-        const int tp = chain_step(e, i + 1);
-        const double Sm = h[(size_t)t * 5 + 3], Ap = h[(size_t)tp * 5 + 2], Smp = h[(size_t)tp * 5 + 3];
-        const double hh = lambda(tp) - lambda(t);
-        if (e->opt.solver_noise) {
-            const double g = -std::expm1(-2.0 * hh);      // 1 - exp(-2h) > 0: lambda increases along the chain
-            row[0] = (float)((Smp / Sm) * std::exp(-hh));
-            row[1] = (float)(Ap * g);
-            row[4] = (float)(Smp * std::sqrt(g));
-        } else {
-            row[0] = (float)(Smp / Sm);
-            row[1] = (float)(-Ap * std::expm1(-hh));
-        }
-        if (e->opt.solver == 2 && i > 0 && tp != 0) row[3] = (float)(hh / (2.0 * (lambda(t) - lambda(chain_step(e, i - 1)))));
-    }
-    for (int t = 0; t < S; ++t) {
-        const float* row = e->h_solver.data() + (size_t)t * 5;
-        float* first = e->h_solver.data() + ((size_t)S + t) * 5;
-        std::copy(row, row + 5, first);
-        first[3] = 0.f;
-    }
     HIPCHK(e, e->d_solver.ensure(e->h_solver.size(), false));
     HIPCHK(e, hipMemcpy(e->d_solver, e->h_solver.data(), e->h_solver.size() * sizeof(float), hipMemcpyHostToDevice));
     return DR_OK;
 }
 
-// option "start_step": the chain position of the step a chain begins at - 0 when the option is off; a step the chain does
-// not visit is refused, naming the visited steps on either side of it
+// option "start_step": the chain position of the step a chain begins at (chain_tables.h: start_position); a step the chain
+// does not visit is refused, naming the visited steps on either side of it
 int start_position(dr_engine* e, int& i0) {
-    i0 = 0;
-    const int ts = e->opt.start;
-    if (ts < 0) return DR_OK;
-    const int n = chain_steps(e);
-    for (int i = 0; i < n; ++i) {
-        const int t = chain_step(e, i);
-        if (t == ts) { i0 = i; return DR_OK; }
-        if (t < ts)       // (the steps decrease strictly and end at 0; the first one is S - 1 >= ts: i > 0 here)
-            return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits (option sampling_steps = %d): the visited steps "
-                                      "on either side of it are %d and %d", ts, e->opt.steps, chain_step(e, i - 1), t);
-    }
-    return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits", ts);      // (unreachable: step 0 is always visited)
+    const StartPosition p = dr::start_position(e->steps, e->opt.start);
+    i0 = std::max(p.pos, 0);
+    if (p.pos >= 0) return DR_OK;
+    return fail(e, DR_EINVAL, "start_step %d is not a step this chain visits (option sampling_steps = %d): the visited steps "
+                              "on either side of it are %d and %d", e->opt.start, e->opt.steps, p.above, p.below);
 }
 // option "start_noise": the chain's first node - the clean roll in x becomes x at step ts (update.hip: diffuse_kernel).
 // z is row 0 of the injected noise (no reverse step reads it: step 0 draws none), else Philox with counter word S + ts,
@@ -561,7 +471,7 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
     if (step) {
         const int t = *step;
         if (t < 0 || t >= e->S) return fail(e, DR_EINVAL, "step %d out of range", t);
-        if (!e->rs_steps.empty() && std::find(e->rs_steps.begin(), e->rs_steps.end(), t) == e->rs_steps.end())
+        if (e->steps.position(t) < 0)
             return fail(e, DR_EINVAL, "step %d is not visited by the respaced chain (option sampling_steps = %d)", t, e->opt.steps);
     }
     if ((rc = check_options(e, sampler, B, NB, T))) return rc;
@@ -630,6 +540,7 @@ int dr_create(dr_engine** out, const dr_config* cfg) {
     e->L = cfg->residual_layers;
     e->K = cfg->kernel_size;
     e->S = cfg->timesteps;
+    e->steps = ChainSteps(e->S, 0);
     e->NM = cfg->n_mels;
     e->n_bins = cfg->n_fft / 2 + 1;
     e->bins_p = round_up(e->n_bins, 64);
@@ -817,22 +728,13 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     int rc = open_chain_call(e, sampler, B, T, &t, NB, i0, (hipStream_t)stream);
     if (rc) return rc;
     if (e->opt.solver == 2) {
-        // the history is engine state: the chain's first step starts one, every other step continues the one the previous
-        // dr_step left - the preceding visited step of the same (sampler, B, T)
-        // (option "start_step": the step it names starts a history too - its row has c = 0, run_step)
-        const int first = chain_step(e, 0);
-        auto& k = e->hist_key;
-        if (t != first && t != e->opt.start) {
-            const bool same = k.valid && k.sampler == sampler && k.B == B && k.T == T;
-            int expect = first;
-            if (same)
-                for (int i = 0, n = chain_steps(e); i + 1 < n; ++i)
-                    if (chain_step(e, i) == k.t) expect = chain_step(e, i + 1);
-            if (!same || expect != t)
-                return fail(e, DR_ESTATE, "solver_order = 2: dr_step at step %d continues no history - the step expected next is %d "
-                                          "(the chain's first step starts a new history; every other step follows its predecessor)", t, expect);
-        } else e->hist_par = 0;
-        k.valid = false;      // (until the step has been issued)
+        // the history is engine state: t starts one or continues the one the previous dr_step left (chain_tables.h: history_step)
+        const HistoryVerdict v = history_step(e->hist_key, sampler, B, T, t, e->steps, e->opt.start);
+        if (v.what == HistoryStep::REFUSED)
+            return fail(e, DR_ESTATE, "solver_order = 2: dr_step at step %d continues no history - the step expected next is %d "
+                                      "(the chain's first step starts a new history; every other step follows its predecessor)", t, v.expect);
+        if (v.what == HistoryStep::STARTS) e->hist_par = 0;
+        e->hist_key.valid = false;      // (until the step has been issued)
     }
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
@@ -871,14 +773,14 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         e->hist_par = 0;      // (option "solver_order": the first step reads no history - its row has c = 0)
         // option "start_noise": xbuf holds a clean roll - diffuse it to the first step, in place, in front of everything
         if (e->opt.start_noise)
-            if (int r = run_diffuse(e, xbuf, d_noise, B, T, chain_step(e, i0), seed, first_sample, st)) return r;
+            if (int r = run_diffuse(e, xbuf, d_noise, B, T, e->steps.at(i0), seed, first_sample, st)) return r;
         // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows) - from
         // position i0 on (option "start_step"; 0: the whole chain)
-        for (int i = i0, n = chain_steps(e); i < n; ++i) {
-            const int t = chain_step(e, i);
+        for (int i = i0, n = e->steps.count(); i < n; ++i) {
+            const int t = e->steps.at(i);
             // row t of the injected noise is the z of step t; t == 0 draws none (task/diffusion.py:957-960)
             const float* z = d_noise ? d_noise + (size_t)t * per : nullptr;
-            cs.next_t = chain_step(e, i + 1);
+            cs.next_t = e->steps.at(i + 1);
             cs.x_out = cur == e->xalt ? xbuf : e->xalt;      // (the previous step left the roll in the engine's buffer: back into xbuf)
             float* res = nullptr;
             if (int r = run_step(e, sampler, cur, z, B, T, t, w, seed, first_sample, st, &res, &cs)) return r;
@@ -895,7 +797,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
 
     GraphKey key;
     key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
-    key.opt = effective(e->opt, NB == 2 * B, e->S, chain_step(e, i0));
+    key.opt = effective(e->opt, NB == 2 * B, e->S, e->steps.at(i0));
     key.fe_B = e->fe_B;
     key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
     key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;

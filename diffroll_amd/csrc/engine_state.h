@@ -3,6 +3,7 @@
 //   pack.hip       weight packing, staged uploads, dr_set_param / dr_set_tables / dr_commit (+ the split-bf16 packings)
 //   plan.hip       the launch sequences of one evaluation and one reverse step (their planning: launch_plan.h)
 //   abi.hip        the C-ABI of include/diffroll_amd.h: life cycle, front-end, forward / step / sample (hipGraph), time-outs
+//                  (the chain's steps, coefficient rows, start position, history rule and window table: chain_tables.h)
 //   debug_abi.hip  measurement and checker entry points (dr_bench_*, dr_debug_*, dr_profile_*)
 // Not part of the public ABI.
 #pragma once
@@ -24,6 +25,7 @@
 #include <vector>
 
 #include "../../include/diffroll_amd_debug.h"      // (includes the boundary, diffroll_amd.h)
+#include "chain_tables.h"
 #include "device_buffer.h"
 #include "fused_mode.h"
 #include "kernels.h"
@@ -89,7 +91,7 @@ struct ChainOptions {
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
-// step the chain visits first (abi.hip: start_position).
+// step the chain visits first (chain_tables.h: start_position).
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
@@ -239,17 +241,17 @@ struct dr_engine {
     int64_t tail_launches = 0;
     drh::ChainOptions opt;              // the value options of dr_set_option a chain is run under
     std::vector<int> win_marks;         // option "window_break", ascending: the windows that start a new recording (window 0 always does)
-    // The per-window table behind UpdateArgs::win_tab (kernels.h: window_entry).  A one-block kernel rewrites it on the
+    // The per-window table behind UpdateArgs::win_tab (chain_tables.h: window_table).  A one-block kernel rewrites it on the
     // call's stream in front of every launch sequence / graph launch that reads it, as launch_set_dyn rewrites d_dyn; its
     // address is what a captured chain bakes in, so new marks at the same (sampler, B, T) replay the same graph.
     // Overwriting it is safe while an earlier chain is still running: that chain and the rewriting kernel are on the same
     // stream, so the rewrite starts only when every launch of the earlier chain has finished - and an engine is used
     // from one stream at a time (diffroll_amd.h), as d_dyn, xwork and the activation workspace already require.
     drh::DevBuf<unsigned> d_wintab;
-    std::vector<int> rs_steps;          // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order; empty: every step
+    dr::ChainSteps steps;               // the visited steps S-1 = t_{n-1} > ... > t_0 = 0 in chain order (chain_tables.h); every step unless respaced
     drh::DevBuf<float> d_coef_rs;       // (DR_COEF_FAMILIES, S, 5): d_coef with the row of each visited t whose successor
-                                        // is not t - 1 replaced by the respaced row (build_respaced); empty when rs_steps is
-    std::vector<float> h_solver;        // option "solver_order", (2 S, 5): rows [0, S) of the chain's visited steps (build_solver; unvisited rows are
+                                        // is not t - 1 replaced by the respaced row (respaced_table); empty unless respaced
+    std::vector<float> h_solver;        // option "solver_order", (2 S, 5): rows [0, S) of the chain's visited steps (solver_table; unvisited rows are
                                         // zero), rows [S, 2 S) the same rows with c = 0 - step t as the FIRST step of a chain
                                         // (option "start_step"); a table of their own, so no row a captured chain reads moves
     drh::DevBuf<float> d_solver;        // ... on the device
@@ -258,8 +260,7 @@ struct dr_engine {
     // what the others still read); hist_par = the half the next step reads.  A captured chain bakes the parity per node.
     drh::DevBuf<float> hist;
     int hist_par = 0;
-    // dr_step under order 2: what the history holds - the prediction of step hist_t of a (sampler, B, T) chain
-    struct { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; } hist_key;
+    dr::HistoryKey hist_key;            // dr_step under order 2: what the history holds (chain_tables.h)
     drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
@@ -363,7 +364,7 @@ struct Range {
 int clear_stack_timeout(dr_engine* e);
 int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab: the names of dr_debug_set_option too
 void set_kfd_root(const char* root);                                      // dr_debug_kfd_root
-int build_respaced(dr_engine* e);       // option "sampling_steps": rs_steps and d_coef_rs from opt.steps and h_coef
+int build_respaced(dr_engine* e);       // option "sampling_steps": steps and d_coef_rs from opt.steps and h_coef
 int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_solver from the chain's steps and h_coef
 int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);      // dr_debug_threshold
 

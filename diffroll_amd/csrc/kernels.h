@@ -6,6 +6,7 @@
 
 #include <atomic>
 
+#include "chain_tables.h"     // window_entry / window_rec / window_idx, WindowTable
 #include "launch_plan.h"      // Epilogue, tile / split-K / fused-stack planning
 
 namespace dr {
@@ -254,14 +255,7 @@ __host__ __device__ inline float* hist_next(const UpdateArgs& a) { return a.hist
 constexpr int WIN_BLEND_SHIFT = 28;
 __host__ __device__ inline int win_H(const UpdateArgs& a) { return a.win & ((1 << WIN_BLEND_SHIFT) - 1); }
 __host__ __device__ inline int win_blend(const UpdateArgs& a) { return a.win >> WIN_BLEND_SHIFT; }
-// one word per window: Philox key offset of its recording (the ordinal in the batch; + draw x stride under option "draws":
-// < 65536) and index within the recording (< STACK_GROUPS)
-constexpr unsigned window_entry(unsigned rec, unsigned idx) { return (rec << 16) | idx; }
-constexpr int window_rec(unsigned w) { return (int)(w >> 16); }
-constexpr int window_idx(unsigned w) { return (int)(w & 0xFFFFu); }
-// The table travels to the device BY VALUE in the kernel arguments of a one-block launch (2 KiB: no host buffer has to
-// outlive the call), stream-ordered like launch_set_dyn.
-struct WindowTable { unsigned w[STACK_GROUPS]; };
+// (the words of the per-window table and the table itself: chain_tables.h)
 hipError_t launch_set_windows(unsigned* d_tab, const WindowTable& tab, int n, hipStream_t s);
 hipError_t launch_update(const UpdateArgs& a, hipStream_t s);
 // option "start_noise": x = (coef[2] * x) + (coef[3] * z) in place (update.hip: diffuse_kernel).  Of UpdateArgs it reads x,

@@ -416,7 +416,7 @@ UpdateArgs update_base(const dr_engine* e, int B, int T) {
     u.dyn = e->use_dyn ? e->d_dyn : nullptr;
     // (option "window_blend" rides in the word's spare bits - kernels.h: win_H / win_blend; check_options keeps T below them)
     u.win = e->opt.win_O > 0 ? (T - e->opt.win_O) | (e->opt.win_blend << WIN_BLEND_SHIFT) : 0;
-    // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (write_windows)
+    // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (chain_tables.h: window_table)
     if (e->opt.draws > 1) { u.draw_n = B / e->opt.draws; u.draw_G = e->opt.draw_G > 0 ? e->opt.draw_G : u.draw_n; }
     // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
     // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
@@ -443,8 +443,8 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     UpdateArgs u = update_base(e, B, T);
     u.x = x; u.x0c = e->x0buf; u.x0u = (NB == 2 * B) ? e->x0buf + (size_t)B * T * 88 : nullptr;
     // row t of the family's table: the committed one, or under option "sampling_steps" the row for t's successor in the
-    // respaced chain (build_respaced; unvisited rows are never read)
-    const float* coef = e->rs_steps.empty() ? e->d_coef : e->d_coef_rs;
+    // respaced chain (chain_tables.h: respaced_table; unvisited rows are never read)
+    const float* coef = e->steps.respaced() ? e->d_coef_rs : e->d_coef;
     u.noise = noise; u.coef = coef + ((size_t)family * e->S + t) * 5; u.t = t; u.mode = family;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     u.seed = seed; u.first_sample = first_sample;
@@ -454,7 +454,7 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // the history buffer, ping-pong); order 1 neither reads nor stores.
     if (e->opt.solver != 0 && predicts_x0(sampler)) {
         const bool hist = e->opt.solver == 2;
-        // (option "start_step": the step it names is a chain's first - the copy of its row with c = 0, abi.hip: build_solver)
+        // (option "start_step": the step it names is a chain's first - the copy of its row with c = 0, chain_tables.h: solver_table)
         u.coef = e->d_solver + ((size_t)(t == e->opt.start ? e->S : 0) + t) * 5; u.mode = 5;
         u.hist = hist ? (float*)e->hist : nullptr; u.hist_par = hist ? e->hist_par : 0;
         if (hist) e->hist_par ^= 1;

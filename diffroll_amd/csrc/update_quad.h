@@ -87,8 +87,8 @@ DR_DEVINL void guided_quad(const UpdateArgs& a, const long i4, const float gw, c
 // two values, added in the same order) - or what option "window_blend" makes of the two (blend_quad below) - and the noise
 // is keyed by the canvas element.
 // mode 5 (option "solver_order", x0-prediction samplers): the exponential integrator in lambda = log(sqrt_acp / sqrt_1m_acp)
-// of Lu et al. 2022 (DPM-Solver++), row [sqrt_1m_acp' / sqrt_1m_acp, -sqrt_acp' expm1(-h), sqrt_acp, c, 0] (abi.hip:
-// build_solver).  y is the guided prediction after the shared-frame mean, p the y of the previous step (hist_prev(a)):
+// of Lu et al. 2022 (DPM-Solver++), row [sqrt_1m_acp' / sqrt_1m_acp, -sqrt_acp' expm1(-h), sqrt_acp, c, 0] (chain_tables.h:
+// solver_table).  y is the guided prediction after the shared-frame mean, p the y of the previous step (hist_prev(a)):
 //   d = c != 0 ? y + c (y - p) : y      (2M; c = h / (2 h_prev), 0 = first order: p is not loaded)
 //   o = c0 x + c1 d;   t == 0: o = y / c2, the x0 samplers' own last step
 // One fp32 rounding per operation, no noise (deterministic).  The caller stores y to hist_next(a) for the next step
@@ -233,7 +233,7 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];
     // which updates draw noise at t > 0: x0 DDPM (0), eps ddpm (2), eps ddim2ddpm (4) - and the solver (5) where its row
-    // has c4 != 0 (option "solver_noise": a stochastic row has c4 > 0 at every t > 0 - abi.hip: build_solver)
+    // has c4 != 0 (option "solver_noise": a stochastic row has c4 > 0 at every t > 0 - chain_tables.h: solver_table)
     const bool noisy = (a.mode == 0 || a.mode == 2 || a.mode == 4 || (a.mode == 5 && c4 != 0.f)) && a.t > 0;
     float x[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f};
     if (a.t > 0 || a.mode >= 2) {
