@@ -62,16 +62,18 @@ void forget_fused_slot(dr_engine* e) {
     }
     s.cv.notify_all();
 }
-// the captured chain may still be running, on the stream it was last launched on: wait for it
-int wait_chain(dr_engine* e) {
-    if (e->gexec && e->graph_stream_set) HIPCHK(e, hipStreamSynchronize(e->graph_stream));
-    return DR_OK;
-}
-// the launch mode changed (a FusedMode transition returned true) or a tuning knob did: the captured chain is stale
+// "The captured chain is stale" has three spellings, by what is waited for first: drop_graph (plan.hip) waits for nothing,
+// drop_chain for the stream the chain was last launched on, drop_after_device_sync for the whole device.
+// the launch mode changed (a FusedMode transition returned true) or a tuning knob did
 int drop_chain(dr_engine* e) {
-    if (int rc = wait_chain(e)) return rc;
+    HIPCHK(e, e->chain.wait());
     drop_graph(e);
     return DR_OK;
+}
+// an option or the precision changed what the chain's launches read: whatever stream it, or anything else, still runs on
+void drop_after_device_sync(dr_engine* e) {
+    (void)hipDeviceSynchronize();
+    drop_graph(e);
 }
 // Another process on this GPU (tenants.h)?  Asked at creation and in front of a chain, at most every 250 ms (a scan is
 // ~0.1 ms of sysfs reads: 0.4 % of a single-clip chain if it ran every time; force: now - behind a graph capture).
@@ -277,7 +279,7 @@ template <class V>
 int grow_chain_buffer(dr_engine* e, DevBuf<V>& buf, size_t n, hipStream_t st) {
     if (buf.fits(n)) return DR_OK;
     HIPCHK(e, hipStreamSynchronize(st));
-    if (int rc = wait_chain(e)) return rc;
+    HIPCHK(e, e->chain.wait());
     HIPCHK(e, buf.ensure(n, true));
     return DR_OK;
 }
@@ -309,22 +311,18 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (!e || !name) return fail(e, DR_EINVAL, "null argument");
     const std::string n = name;
     DeviceGuard guard(e->cfg.device);
-    auto drop = [&]() {
-        (void)hipDeviceSynchronize();
-        drop_graph(e);
-    };
-    if (n == "fused_stack") { if (e->fused.set_option(value)) drop(); return DR_OK; }      // (forgets a pending yield or heal)
+    if (n == "fused_stack") { if (e->fused.set_option(value)) drop_after_device_sync(e); return DR_OK; }      // (forgets a pending yield or heal)
     if (n == "fused_rearm") { e->fused.rearm_after = value; return DR_OK; }
     if (n == "blocked_accumulation") {
         if (value != 1 && value != 2) return fail(e, DR_EINVAL, "blocked_accumulation is 1 or 2");
-        if (e->opt_blocked != value) drop();
+        if (e->opt_blocked != value) drop_after_device_sync(e);
         e->opt_blocked = value;
         return DR_OK;
     }
-    if (n == "fused_tail") { if (e->opt_tail != value) drop(); e->opt_tail = value; return DR_OK; }
+    if (n == "fused_tail") { if (e->opt_tail != value) drop_after_device_sync(e); e->opt_tail = value; return DR_OK; }
     if (n == "window_overlap") {      // (O <= T / 2 is checked by dr_step / dr_sample, which know T)
         if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
-        if (e->opt.win_O != value) drop();
+        if (e->opt.win_O != value) drop_after_device_sync(e);
         e->opt.win_O = value;
         return DR_OK;
     }
@@ -362,7 +360,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value != 0 && (value < 2 || value > e->S))
             return fail(e, DR_EINVAL, "sampling_steps is 0 (off) or in [2, timesteps = %d], got %d", e->S, value);
         if (e->opt.steps == value) return DR_OK;
-        drop();
+        drop_after_device_sync(e);
         e->opt.steps = value;
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         if (int rc = build_respaced(e)) { e->opt.steps = 0; return rc; }
@@ -434,17 +432,17 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         return DR_OK;
     }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
-    if (n == "fused_stack_xcd") { if (e->opt_stack_xcd != value) drop(); e->opt_stack_xcd = value; return DR_OK; }
-    if (n == "fused_stack_warm") { if (e->opt_stack_warm != value) drop(); e->opt_stack_warm = value; return DR_OK; }
+    if (n == "fused_stack_xcd") { if (e->opt_stack_xcd != value) drop_after_device_sync(e); e->opt_stack_xcd = value; return DR_OK; }
+    if (n == "fused_stack_warm") { if (e->opt_stack_warm != value) drop_after_device_sync(e); e->opt_stack_warm = value; return DR_OK; }
 #ifdef DR_FAULT_HOOK
-    if (n == "stack_fault_test") { if (e->opt_stack_fault != value) drop(); e->opt_stack_fault = value; return DR_OK; }
+    if (n == "stack_fault_test") { if (e->opt_stack_fault != value) drop_after_device_sync(e); e->opt_stack_fault = value; return DR_OK; }
 #endif
-    if (n == "stack_ticks") { if (e->stack_dbg_on != value) drop(); e->stack_dbg_on = value; return DR_OK; }
+    if (n == "stack_ticks") { if (e->stack_dbg_on != value) drop_after_device_sync(e); e->stack_dbg_on = value; return DR_OK; }
     if (n.compare(0, 5, "tune.") == 0) {      // A/B knobs of planners and launchers: PROCESS-wide (kernels.h: Tuning)
         Tuning& t = tuning();
         const std::string f = n.substr(5);
         if (f == "ksplit_blocks") {
-            if (t.ksplit_blocks.load() != value) { t.ksplit_blocks.store(value); tuning_epoch().fetch_add(1); drop(); }
+            if (t.ksplit_blocks.load() != value) { t.ksplit_blocks.store(value); tuning_epoch().fetch_add(1); drop_after_device_sync(e); }
             return DR_OK;
         }
         std::atomic<int>* field = f == "pack_threads" ? &t.pack_threads : f == "tile" ? &t.tile : f == "pw" ? &t.pw : f == "pw_nw" ? &t.pw_nw
@@ -455,7 +453,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (field->load() != value) {
             field->store(value);
             tuning_epoch().fetch_add(1);      // every engine drops its captured chain at its next dr_sample
-            drop();
+            drop_after_device_sync(e);
         }
         return DR_OK;
     }
@@ -486,6 +484,47 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
     // option "x0_threshold": the work buffer of the threshold launches (tickets and counts start at zero: armed)
     if (e->opt.x0_thresh != 0 && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
     return DR_OK;
+}
+
+// What dr_sample was asked for; i0: the chain position of the first step it runs (option "start_step")
+struct ChainCall { int sampler; const float* noise; int B, T; float w; uint64_t seed; int first_sample; int i0; };
+
+// The reverse chain of one call, in place on xbuf, as launches on st - the caller's stream (eager) or the stream of a capture
+int run_chain(dr_engine* e, const ChainCall& c, float* xbuf, hipStream_t st) {
+    const size_t per = (size_t)c.B * c.T * 88;
+    // the roll ping-pongs between xbuf and e->xalt while the fused step runs (its tail kernel cannot update in
+    // place), and each tail also computes the next step's input projection
+    ChainState cs;
+    float* cur = xbuf;
+    e->hist_par = 0;      // (option "solver_order": the first step reads no history - its row has c = 0)
+    // option "start_noise": xbuf holds a clean roll - diffuse it to the first step, in place, in front of everything
+    if (e->opt.start_noise)
+        if (int r = run_diffuse(e, xbuf, c.noise, c.B, c.T, e->steps.at(c.i0), c.seed, c.first_sample, st)) return r;
+    // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows) - from
+    // position i0 on (option "start_step"; 0: the whole chain)
+    for (int i = c.i0, n = e->steps.count(); i < n; ++i) {
+        const int t = e->steps.at(i);
+        // row t of the injected noise is the z of step t; t == 0 draws none (task/diffusion.py:957-960)
+        const float* z = c.noise ? c.noise + (size_t)t * per : nullptr;
+        cs.next_t = e->steps.at(i + 1);
+        cs.x_out = cur == e->xalt ? xbuf : e->xalt;      // (the previous step left the roll in the engine's buffer: back into xbuf)
+        float* res = nullptr;
+        if (int r = run_step(e, c.sampler, cur, z, c.B, c.T, t, c.w, c.seed, c.first_sample, st, &res, &cs)) return r;
+        cur = res;
+    }
+    if (cur != xbuf) HIPCHK(e, hipMemcpyAsync(xbuf, cur, per * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return DR_OK;
+}
+
+// What the capture of this call's chain bakes in (engine_state.h: GraphKey); NB: the sampler's evaluation batch
+GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
+    GraphKey key;
+    key.sampler = c.sampler; key.B = c.B; key.T = c.T; key.x = e->xwork; key.noise = c.noise; key.w_zero = (c.w == 0.f);
+    key.opt = effective(e->opt, NB == 2 * c.B, e->S, e->steps.at(c.i0));
+    key.fe_B = e->fe_B;
+    key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
+    key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
+    return key;
 }
 
 }  // namespace drh
@@ -573,7 +612,7 @@ void dr_destroy(dr_engine* e) {
     DeviceGuard guard(dev);
     (void)hipDeviceSynchronize();
     forget_fused_slot(e);
-    delete e;       // (~dr_engine and the members' destructors release everything it holds)
+    delete e;       // (the members' destructors release everything it holds, the captured chain first)
     if (g_engines[dev].fetch_sub(1) == 1) release_stager(dev);
 }
 
@@ -764,63 +803,21 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if (e->fused.may_fuse() && (rc = fused_look(e, shared_with_another_process(e)))) return rc;
     FusedTurn turn(e, st);      // (released - event recorded on `st` - when this call returns, behind the chain's launches)
     if (turn.rc) return turn.rc;
-    const size_t per = (size_t)B * T * 88;
-    auto chain = [&](float* xbuf) -> int {
-        // the roll ping-pongs between xbuf and e->xalt while the fused step runs (its tail kernel cannot update in
-        // place), and each tail also computes the next step's input projection
-        ChainState cs;
-        float* cur = xbuf;
-        e->hist_par = 0;      // (option "solver_order": the first step reads no history - its row has c = 0)
-        // option "start_noise": xbuf holds a clean roll - diffuse it to the first step, in place, in front of everything
-        if (e->opt.start_noise)
-            if (int r = run_diffuse(e, xbuf, d_noise, B, T, e->steps.at(i0), seed, first_sample, st)) return r;
-        // every step t = S-1 .. 0, or the visited steps of option "sampling_steps" (run_step reads their rows) - from
-        // position i0 on (option "start_step"; 0: the whole chain)
-        for (int i = i0, n = e->steps.count(); i < n; ++i) {
-            const int t = e->steps.at(i);
-            // row t of the injected noise is the z of step t; t == 0 draws none (task/diffusion.py:957-960)
-            const float* z = d_noise ? d_noise + (size_t)t * per : nullptr;
-            cs.next_t = e->steps.at(i + 1);
-            cs.x_out = cur == e->xalt ? xbuf : e->xalt;      // (the previous step left the roll in the engine's buffer: back into xbuf)
-            float* res = nullptr;
-            if (int r = run_step(e, sampler, cur, z, B, T, t, w, seed, first_sample, st, &res, &cs)) return r;
-            cur = res;
-        }
-        if (cur != xbuf) HIPCHK(e, hipMemcpyAsync(xbuf, cur, per * sizeof(float), hipMemcpyDeviceToDevice, st));
-        return DR_OK;
-    };
-    if (!use_graph || e->prof) {
+    const ChainCall call{sampler, d_noise, B, T, w, seed, first_sample, i0};
+    if (!use_graph || e->prof.on) {
         Range range("dr_sample: eager chain");
         if ((rc = write_windows(e, B, false, st))) return rc;
-        return chain(d_x);
+        return run_chain(e, call, d_x, st);
     }
 
-    GraphKey key;
-    key.sampler = sampler; key.B = B; key.T = T; key.x = e->xwork; key.noise = d_noise; key.w_zero = (w == 0.f);
-    key.opt = effective(e->opt, NB == 2 * B, e->S, e->steps.at(i0));
-    key.fe_B = e->fe_B;
-    key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
-    key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
-    for (int attempt = 0; attempt < 2 && (!e->gexec || !(key == e->gkey)); ++attempt) {
+    const GraphKey key = chain_key(e, call, NB);
+    for (int attempt = 0; attempt < 2 && !e->chain.holds(key); ++attempt) {
         drop_graph(e);
-        if (!e->cap_stream) HIPCHK(e, hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
-        hipStream_t user = st;
-        st = e->cap_stream;   // chain() launches on `st`
         Range range("dr_sample: capture + instantiate the chain graph");
-        const double tc0 = now_s();
-        HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        e->use_dyn = true;
-        rc = chain(e->xwork);
-        e->use_dyn = false;
-        hipGraph_t gr = nullptr;
-        hipError_t ce = hipStreamEndCapture(st, &gr);
-        st = user;
-        if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
-        if (ce != hipSuccess) return fail(e, DR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
-        e->graph = gr;
-        HIPCHK(e, hipGraphInstantiate(&e->gexec, e->graph, nullptr, nullptr, 0));
-        e->t_capture_s = now_s() - tc0;
-        e->gkey = key;
+        const auto cap = e->chain.capture(key, [&](hipStream_t cs) { return run_chain(e, call, e->xwork, cs); });
+        if (cap.failed == Chain::Step::RECORD) return cap.rc;      // (the error text is the failing launch's own)
+        if (cap.failed == Chain::Step::END) return fail(e, DR_EHIP, "%s failed: %s", cap.call, hipGetErrorString(cap.hip));
+        if (!cap) return fail(e, DR_EHIP, "%s failed: %s (%s:%d)", cap.call, hipGetErrorString(cap.hip), __FILE__, __LINE__);
         e->tuning_epoch = tuning_epoch().load();
         // capture + instantiation took tens of milliseconds: look again before a chain of persistent launches goes out
         if (attempt == 0 && e->fused.active() && turn.held) {
@@ -828,16 +825,16 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         }
     }
     Range range("dr_sample: launch the chain graph");
+    const size_t bytes = (size_t)B * T * 88 * sizeof(float);
     // the graph owns no caller address: x_T is copied in, the finished roll copied out (0.7 MB each way)
-    HIPCHK(e, hipMemcpyAsync(e->xwork, d_x, per * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(e->xwork, d_x, bytes, hipMemcpyDeviceToDevice, st));
     // (the chain's tail launches publish epochs in win_epoch + 1 .. win_epoch + S, one per step: TailArgs::ready)
     HIPCHK(e, launch_set_dyn(e->d_dyn, seed, first_sample, w, (float)(1.0 + (double)w), e->win_epoch, st));
     if ((rc = write_windows(e, B, true, st))) return rc;      // (the captured chain reads the table of THIS call's marks)
     e->win_epoch += (unsigned)e->S;
-    HIPCHK(e, hipGraphLaunch(e->gexec, st));
-    e->graph_stream = st; e->graph_stream_set = true;
+    HIPCHK(e, e->chain.launch(st));
     if (e->stack_launches || e->tail_launches) { e->unverified = true; e->fused_stream = st; }      // (the captured chain may hold persistent launches)
-    HIPCHK(e, hipMemcpyAsync(d_x, e->xwork, per * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(d_x, e->xwork, bytes, hipMemcpyDeviceToDevice, st));
     return DR_OK;
 }
 
@@ -993,8 +990,7 @@ int dr_set_precision(dr_engine* e, int mode) {
     if (mode != DR_PRECISION_F32 && mode != DR_PRECISION_BF16X3 && mode != DR_PRECISION_BF16) return fail(e, DR_EINVAL, "unknown precision mode %d", mode);
     if (mode != e->prec) {
         DeviceGuard guard(e->cfg.device);     // the graph may still be executing on the ENGINE's device
-        (void)hipDeviceSynchronize();
-        drop_graph(e);
+        drop_after_device_sync(e);
         if (mode) {           // the mode changes only once its own packings exist (bf16x3: 520 MB of uploads, bf16: a third - the build can fail)
             int rc = ensure_packings(e, mode);
             if (rc) return rc;

@@ -21,10 +21,8 @@ int dr_debug_kfd_root(const char* kfd_root) {
 
 int dr_cold_times(dr_engine* e, double* out5) {
     if (!e || !out5) return DR_EINVAL;
-    out5[0] = e->t_pack_s; out5[1] = e->t_upload_s; out5[2] = e->t_tables_s; out5[3] = e->t_capture_s;
-    size_t nodes = 0;
-    if (e->graph && hipGraphGetNodes(e->graph, nullptr, &nodes) != hipSuccess) nodes = 0;
-    out5[4] = (double)nodes;
+    out5[0] = e->t_pack_s; out5[1] = e->t_upload_s; out5[2] = e->t_tables_s; out5[3] = e->chain.capture_seconds();
+    out5[4] = (double)e->chain.nodes();
     return DR_OK;
 }
 
@@ -51,13 +49,13 @@ int dr_stack_status(dr_engine* e, int32_t* timed_out, int64_t* launches, int64_t
 int dr_profile_enable(dr_engine* e, int on) {
     if (!e) return DR_EINVAL;
     DeviceGuard guard(e->cfg.device);
-    e->prof = on != 0;
-    if (e->prof && e->prof_events.empty()) {
+    e->prof.on = on != 0;
+    if (e->prof.on && e->prof.events.empty()) {
         const size_t n = (size_t)e->S * e->L;
-        e->prof_events.resize(n);
-        for (auto& p : e->prof_events) { HIPCHK(e, hipEventCreate(&p.first)); HIPCHK(e, hipEventCreate(&p.second)); }
+        e->prof.events.resize(n);
+        for (auto& p : e->prof.events) HIPCHK(e, p.create());
     }
-    e->prof_used = 0;
+    e->prof.used = 0;
     return DR_OK;
 }
 
@@ -65,30 +63,30 @@ int dr_profile_read(dr_engine* e, int64_t* launches, double* total_ms, int reset
     if (!e) return DR_EINVAL;
     DeviceGuard guard(e->cfg.device);
     HIPCHK(e, hipDeviceSynchronize());
-    for (size_t i = 0; i < e->prof_used; ++i) {
+    for (size_t i = 0; i < e->prof.used; ++i) {
         float ms = 0.f;
-        HIPCHK(e, hipEventElapsedTime(&ms, e->prof_events[i].first, e->prof_events[i].second));
-        e->prof_ms += ms;
-        e->prof_launches += 1;
+        HIPCHK(e, hipEventElapsedTime(&ms, e->prof.events[i].first, e->prof.events[i].second));
+        e->prof.ms += ms;
+        e->prof.launches += 1;
     }
-    e->prof_used = 0;
-    if (launches) *launches = e->prof_launches;
-    if (total_ms) *total_ms = e->prof_ms;
-    if (reset) { e->prof_launches = 0; e->prof_ms = 0.0; }
+    e->prof.used = 0;
+    if (launches) *launches = e->prof.launches;
+    if (total_ms) *total_ms = e->prof.ms;
+    if (reset) { e->prof.launches = 0; e->prof.ms = 0.0; }
     return DR_OK;
 }
 
 int dr_profile_read_ex(dr_engine* e, int64_t* launches, double* total_ms, double* total_flops, char* name, size_t name_len,
                        int reset) {
     if (!e) return DR_EINVAL;
-    const double fl = e->prof_flops;
+    const double fl = e->prof.flops;
     int rc = dr_profile_read(e, launches, total_ms, reset);
     if (rc) return rc;
     if (total_flops) *total_flops = fl;
     if (name && name_len) {
-        snprintf(name, name_len, "%s", e->prof_name.c_str());
+        snprintf(name, name_len, "%s", e->prof.name.c_str());
     }
-    if (reset) e->prof_flops = 0.0;
+    if (reset) e->prof.flops = 0.0;
     return DR_OK;
 }
 

@@ -3,7 +3,8 @@
 //   pack.hip       weight packing, staged uploads, dr_set_param / dr_set_tables / dr_commit (+ the split-bf16 packings)
 //   plan.hip       the launch sequences of one evaluation and one reverse step (their planning: launch_plan.h)
 //   abi.hip        the C-ABI of include/diffroll_amd.h: life cycle, front-end, forward / step / sample (hipGraph), time-outs
-//                  (the chain's steps, coefficient rows, start position, history rule and window table: chain_tables.h)
+//                  (the chain's steps, coefficient rows, start position, history rule and window table: chain_tables.h;
+//                  the owner of the captured chain - graph, executable, key, capture stream: captured_chain.h)
 //   debug_abi.hip  measurement and checker entry points (dr_bench_*, dr_debug_*, dr_profile_*)
 // Not part of the public ABI.
 #pragma once
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "../../include/diffroll_amd_debug.h"      // (includes the boundary, diffroll_amd.h)
+#include "captured_chain.h"
 #include "chain_tables.h"
 #include "device_buffer.h"
 #include "fused_mode.h"
@@ -126,6 +128,7 @@ struct GraphKey {
                opt == o.opt && fe_B == o.fe_B && hist == o.hist && thresh_work == o.thresh_work;
     }
 };
+using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
 
 // The synchronisation words of the persistent kernels (stack_kernel, tail kernel) in one device allocation, plus the
 // time-out flag in host-mapped memory: every later API call sees it without a synchronisation and fails loudly instead of
@@ -168,6 +171,30 @@ struct StackSync {
     }
 };
 
+// dr_profile_*: the launches of the dominant kernel are bracketed by pairs of events, one pair per timed launch
+struct EventPair {
+    hipEvent_t first = nullptr, second = nullptr;
+    EventPair() = default;
+    ~EventPair() {
+        if (first) (void)hipEventDestroy(first);
+        if (second) (void)hipEventDestroy(second);
+    }
+    EventPair(EventPair&& o) noexcept : first(o.first), second(o.second) { o.first = o.second = nullptr; }      // (move-only)
+    hipError_t create() {
+        hipError_t st = hipEventCreate(&first);
+        return st == hipSuccess ? hipEventCreate(&second) : st;
+    }
+};
+struct Profile {
+    bool on = false;
+    std::vector<EventPair> events;      // created by the first dr_profile_enable: one pair per (step, layer)
+    size_t used = 0;                    // pairs recorded since the last dr_profile_read
+    int64_t launches = 0;
+    double ms = 0.0;
+    double flops = 0.0;                 // algorithmic FLOPs of the timed launches
+    std::string name;
+};
+
 }  // namespace drh
 
 struct dr_engine {
@@ -204,7 +231,7 @@ struct dr_engine {
     int prec = 0;                          // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3, 6 products), 2: one-pass bf16 (1 product)
     bool s3_ready = false;                 // the split-bf16 packings exist (built on first use: ensure_s3)
     bool bf16_ready = false;               // the one-pass bf16 packings exist (built on first use: ensure_bf16)
-    double t_pack_s = 0.0, t_upload_s = 0.0, t_tables_s = 0.0, t_capture_s = 0.0;      // dr_cold_times
+    double t_pack_s = 0.0, t_upload_s = 0.0, t_tables_s = 0.0;      // dr_cold_times (the capture's seconds: chain)
     int norm_framewise = 0;                // spectrogram normalisation: 0 imagewise, 1 framewise (norm_args[2])
     // conditioner tensors of the last dr_frontend: [L][fe_B][2Cp/4][fe_T][4]
     int fe_B = 0, fe_T = 0;
@@ -216,17 +243,11 @@ struct dr_engine {
     // front-end workspace
     drh::DevBuf<float> wav_pad, power, logmel, specP4, mm;
 
-    // graph cache
-    drh::GraphKey gkey;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t gexec = nullptr;
     drh::DevBuf<long long> dbg_ticks;   // dr_bench_layer measurement hook
     drh::DevBuf<unsigned long long> d_counts;   // dr_frame_counts: result words, ticket, per-block partials (update.hip)
     size_t mm_scratch_off = 0;                // floats into `mm` where the multi-block min-max keeps its partials / tickets
-    hipStream_t cap_stream = nullptr;   // capture happens here (the caller's stream may be the null stream)
     drh::DevBuf<dr::DynParams> d_dyn;   // per-call scalars of the captured chain (seed, batch offset, guidance weight)
     drh::DevBuf<int> d_tsel;            // per-sample steps of dr_forward_steps
-    bool use_dyn = false;               // set while the chain is being captured: run_step points the update at d_dyn
 
     // fused residual stack (stack_kernel): one persistent launch for the residual layers when every block of the
     // launch is resident at once; fused.active() 0 = one launch per phase (options fused_stack / fused_rearm, yields,
@@ -268,11 +289,9 @@ struct dr_engine {
     drh::DevBuf<float> xalt;            // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
     int last_mode = 0;                  // DR_MODE_* of the most recently planned evaluation (dr_launch_state)
-    unsigned tuning_epoch = 0;          // tuning_epoch() when the cached chain was captured
+    unsigned tuning_epoch = 0;          // tuning_epoch() when the cached chain was captured (dr_sample waits for a chain of another epoch, then drops it)
     long kfd_gpu_id = -1;               // the driver's id of this GPU in /sys/class/kfd (tenants.h); -1: unknown, no scans
     double last_tenant_scan_s = -1.0;
-    hipStream_t graph_stream = nullptr; // where the captured chain was last launched
-    bool graph_stream_set = false;
     bool unverified = false;            // persistent launches have been issued since the last check of the time-out flag
     hipStream_t fused_stream = nullptr; // ... on this stream (the last one): what a check synchronises before it reads the flag
     int opt_blocked = 2;                // option "blocked_accumulation": 2 (default) = every fp32 flavour that has a blocked form, 1 = 128-frame blocks keep one chain per output (-0.5 % per chain, 2-3x the rounding error)
@@ -281,22 +300,12 @@ struct dr_engine {
     int stack_dbg_on = 0;
     int64_t stack_launches = 0;         // fused-kernel launches issued (captured launches count once, at capture)
 
-    // profiling of the dominant kernel
-    double prof_flops = 0.0;            // algorithmic FLOPs of the timed launches
-    std::string prof_name;
-    bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
-    size_t prof_used = 0;
-    int64_t prof_launches = 0;
-    double prof_ms = 0.0;
+    drh::Profile prof;                  // dr_profile_*: timing of the dominant kernel
 
-    // the handles that are not memory; runs before the members' destructors, so the graph goes before the buffers it uses
-    ~dr_engine() {
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        for (auto& p : prof_events) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    }
+    // The captured reverse chain of dr_sample (while it is being captured - chain.capturing() - run_step points the update
+    // at d_dyn).  Declared after every DevBuf member: members are destroyed in reverse order, so the graph goes before the
+    // buffers its nodes point into.
+    drh::Chain chain;
 };
 
 namespace drh {

@@ -109,11 +109,11 @@ static void s3_in(GemmArgs& a, const float* X, int Cp, int T, int prec) {
 // (none left, or not eligible: it runs untimed), then `account` adds its FLOPs and names it.
 template <class Launch, class Account>
 static int profiled(dr_engine* e, hipStream_t st, bool eligible, Launch&& launch, Account&& account) {
-    const bool timed = e->prof && eligible && e->prof_used < e->prof_events.size();
-    if (timed) HIPCHK(e, hipEventRecord(e->prof_events[e->prof_used].first, st));
+    const bool timed = e->prof.on && eligible && e->prof.used < e->prof.events.size();
+    if (timed) HIPCHK(e, hipEventRecord(e->prof.events[e->prof.used].first, st));
     if (int rc = launch()) return rc;
     if (timed) {
-        HIPCHK(e, hipEventRecord(e->prof_events[e->prof_used++].second, st));
+        HIPCHK(e, hipEventRecord(e->prof.events[e->prof.used++].second, st));
         account();
     }
     return DR_OK;
@@ -189,8 +189,8 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
             const double C = e->C, fr = (double)nb * T;
             // executed work only: the last layer's 1x1 computes its skip half alone (the residual half is never read)
             for (int q = p0; q < p1; ++q)
-                e->prof_flops += fr * 2.0 * C * 2.0 * C * ((q & 1) ? (q == 2 * L - 1 ? 0.5 : 1.0) : (double)e->K);
-            e->prof_name = "stack_kernel<" + std::to_string(p.stack_fl) + "> (fused residual stack: dilated conv k=" +
+                e->prof.flops += fr * 2.0 * C * 2.0 * C * ((q & 1) ? (q == 2 * L - 1 ? 0.5 : 1.0) : (double)e->K);
+            e->prof.name = "stack_kernel<" + std::to_string(p.stack_fl) + "> (fused residual stack: dilated conv k=" +
                            std::to_string(e->K) + " + conditioner + gate and 1x1 + residual/skip, phases " +
                            std::to_string(p0) + ".." + std::to_string(p1 - 1) + " of " + std::to_string(2 * L) +
                            (p.stack_chunks > 1 ? ", " + std::to_string(p.stack_chunks) + " sample chunks" : "") +
@@ -242,8 +242,8 @@ static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int 
         HIPCHK(e, launch_tiled(a, EPI_GATE, tile, v.st, prec));
         return DR_OK;
     }, [&] {
-        e->prof_flops += (double)NB * T * 2.0 * e->C * 2.0 * e->C * e->K;
-        e->prof_name = "gemm_kernel<EPI_GATE> (dilated conv k=" + std::to_string(e->K) + " + conditioner + gate)";
+        e->prof.flops += (double)NB * T * 2.0 * e->C * 2.0 * e->C * e->K;
+        e->prof.name = "gemm_kernel<EPI_GATE> (dilated conv k=" + std::to_string(e->K) + " + conditioner + gate)";
     });
 }
 
@@ -327,7 +327,7 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, const PlanKnobs& k,
     ta.ready = e->sync.ready();
     // S - t grows strictly along any chain, a respaced one (option "sampling_steps") included - its visited t decrease
     // strictly - and stays in [1, S], so the words keep growing across chains (dr_sample moves the base on by S per chain).
-    ta.epoch = v.e->use_dyn ? (unsigned)(e->S - v.t) : ++e->win_epoch;
+    ta.epoch = e->chain.capturing() ? (unsigned)(e->S - v.t) : ++e->win_epoch;
     // ticks 112..119 of dr_stack_status: the last tail launch of a chain that has a next step (all its parts run)
     ta.dbg = (e->stack_dbg_on && prime) ? e->stack_dbg + 112 : nullptr;
     HIPCHK(e, launch_tail(ta, v.st));
@@ -413,7 +413,7 @@ int sampler_shape(int sampler, int B, int& NB, int& n_cond) {
 UpdateArgs update_base(const dr_engine* e, int B, int T) {
     UpdateArgs u{};
     u.n = (long)B * T * 88; u.per_sample = (long)T * 88;
-    u.dyn = e->use_dyn ? e->d_dyn : nullptr;
+    u.dyn = e->chain.capturing() ? e->d_dyn : nullptr;
     // (option "window_blend" rides in the word's spare bits - kernels.h: win_H / win_blend; check_options keeps T below them)
     u.win = e->opt.win_O > 0 ? (T - e->opt.win_O) | (e->opt.win_blend << WIN_BLEND_SHIFT) : 0;
     // option "draws": the rows' Philox keys (update_quad.h); windows carry theirs in the table (chain_tables.h: window_table)
@@ -421,7 +421,7 @@ UpdateArgs update_base(const dr_engine* e, int B, int T) {
     // recording boundaries (option "window_break"): the engine's table - always in a captured chain, so that new marks
     // replay the same graph; without marks an eager chain keeps the one-recording definition (null)
     // (the table has STACK_GROUPS words: a larger batch is one recording - check_options refuses marks there)
-    u.win_tab = (u.win > 0 && B <= STACK_GROUPS && (e->use_dyn || !e->win_marks.empty() || e->opt.draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
+    u.win_tab = (u.win > 0 && B <= STACK_GROUPS && (e->chain.capturing() || !e->win_marks.empty() || e->opt.draws > 1)) ? (const unsigned*)e->d_wintab : nullptr;
     return u;
 }
 
@@ -503,9 +503,7 @@ ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u) {
 }
 
 void drop_graph(dr_engine* e) {
-    if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
-    if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; }
-    e->gkey = GraphKey{};
+    e->chain.drop();                // (does not wait: drop_chain / drop_after_device_sync, abi.hip, are the spellings that do)
     e->hist_key.valid = false;      // (option "solver_order": whatever dropped the chain also ends a dr_step history)
 }
 
