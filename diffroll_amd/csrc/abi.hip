@@ -62,19 +62,8 @@ void forget_fused_slot(dr_engine* e) {
     }
     s.cv.notify_all();
 }
-// "The captured chain is stale" has three spellings, by what is waited for first: drop_graph (plan.hip) waits for nothing,
-// drop_chain for the stream the chain was last launched on, drop_after_device_sync for the whole device.
-// the launch mode changed (a FusedMode transition returned true) or a tuning knob did
-int drop_chain(dr_engine* e) {
-    HIPCHK(e, e->chain.wait());
-    drop_graph(e);
-    return DR_OK;
-}
-// an option or the precision changed what the chain's launches read: whatever stream it, or anything else, still runs on
-void drop_after_device_sync(dr_engine* e) {
-    (void)hipDeviceSynchronize();
-    drop_graph(e);
-}
+// "The captured chain is stale" has one spelling, stale(e) (engine_state.h): it moves the generation in the chain's key and
+// destroys nothing.  Only dr_sample, about to capture the replacement, destroys a chain, and the owner waits for it first.
 // Another process on this GPU (tenants.h)?  Asked at creation and in front of a chain, at most every 250 ms (a scan is
 // ~0.1 ms of sysfs reads: 0.4 % of a single-clip chain if it ran every time; force: now - behind a graph capture).
 // Returns 1 = yes, 0 = no, -1 = not looked (rate limit / no sysfs / undecided).  A first look that finds a second queue
@@ -106,17 +95,16 @@ int shared_with_another_process(dr_engine* e, bool force = false, bool may_sync 
 }
 // What a look found goes into the engine's FusedMode: another process computing yields (per-phase launches from the next
 // launch on); while yielded, two looks in a row that find the GPU exclusive again switch the fused launches back on.
-int fused_look(dr_engine* e, int shared) {
+void fused_look(dr_engine* e, int shared) {
     const bool yielded = e->fused.state == FusedMode::YIELDED;
-    if (!e->fused.look(shared)) return DR_OK;
-    if (int rc = drop_chain(e)) return rc;
+    if (!e->fused.look(shared)) return;
+    stale(e);
     if (!yielded && e->fused.yields <= 3)       // per engine (a measurement reads the counter: dr_launch_state); not a log flood
         fprintf(stderr, "[diffroll_amd] engine %p: another process is computing on device %d - one launch per phase from now on (same "
                         "results, no co-residency assumption; yield #%lld of this engine; fused launches come back after two clean looks)\n",
                 (void*)e, e->cfg.device, (long long)e->fused.yields);
     if (yielded && e->fused.rearms <= 3)
         fprintf(stderr, "[diffroll_amd] engine %p: device %d is this process's own again - fused launches back on\n", (void*)e, e->cfg.device);
-    return DR_OK;
 }
 
 // the engine's turn on the slot for the duration of one API call that may issue fused launches
@@ -306,24 +294,31 @@ int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B,
     return DR_OK;
 }
 
+// A setting that captured launches bake in (engine_state.h: dr_engine::baked) takes a new value: a change makes the chain stale
+template <class Field>
+bool put(dr_engine* e, Field& field, int value) {
+    if (field == value) return false;
+    field = value;
+    stale(e);
+    return true;
+}
+
 // dr_set_option (lab = false: the product's options) / dr_debug_set_option (lab = true: the A/B and test knobs too)
 int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (!e || !name) return fail(e, DR_EINVAL, "null argument");
     const std::string n = name;
     DeviceGuard guard(e->cfg.device);
-    if (n == "fused_stack") { if (e->fused.set_option(value)) drop_after_device_sync(e); return DR_OK; }      // (forgets a pending yield or heal)
+    if (n == "fused_stack") { if (e->fused.set_option(value)) stale(e); return DR_OK; }      // (forgets a pending yield or heal)
     if (n == "fused_rearm") { e->fused.rearm_after = value; return DR_OK; }
     if (n == "blocked_accumulation") {
         if (value != 1 && value != 2) return fail(e, DR_EINVAL, "blocked_accumulation is 1 or 2");
-        if (e->opt_blocked != value) drop_after_device_sync(e);
-        e->opt_blocked = value;
+        put(e, e->opt_blocked, value);
         return DR_OK;
     }
-    if (n == "fused_tail") { if (e->opt_tail != value) drop_after_device_sync(e); e->opt_tail = value; return DR_OK; }
+    if (n == "fused_tail") { put(e, e->opt_tail, value); return DR_OK; }
     if (n == "window_overlap") {      // (O <= T / 2 is checked by dr_step / dr_sample, which know T)
         if (value < 0) return fail(e, DR_EINVAL, "window_overlap is >= 0 (0 = off)");
-        if (e->opt.win_O != value) drop_after_device_sync(e);
-        e->opt.win_O = value;
+        put(e, e->opt.win_O, value);
         return DR_OK;
     }
     if (n == "window_blend") {      // (part of the chain's key while "window_overlap" is set: nothing is dropped)
@@ -359,9 +354,8 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (n == "sampling_steps") {
         if (value != 0 && (value < 2 || value > e->S))
             return fail(e, DR_EINVAL, "sampling_steps is 0 (off) or in [2, timesteps = %d], got %d", e->S, value);
-        if (e->opt.steps == value) return DR_OK;
-        drop_after_device_sync(e);
-        e->opt.steps = value;
+        if (!put(e, e->opt.steps, value)) return DR_OK;
+        (void)hipDeviceSynchronize();         // a chain of the previous value may still be reading the two tables rebuilt below
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         if (int rc = build_respaced(e)) { e->opt.steps = 0; return rc; }
         return build_solver(e);               // (its rows belong to the steps this chain visits)
@@ -432,17 +426,17 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         return DR_OK;
     }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
-    if (n == "fused_stack_xcd") { if (e->opt_stack_xcd != value) drop_after_device_sync(e); e->opt_stack_xcd = value; return DR_OK; }
-    if (n == "fused_stack_warm") { if (e->opt_stack_warm != value) drop_after_device_sync(e); e->opt_stack_warm = value; return DR_OK; }
+    if (n == "fused_stack_xcd") { put(e, e->opt_stack_xcd, value); return DR_OK; }
+    if (n == "fused_stack_warm") { put(e, e->opt_stack_warm, value); return DR_OK; }
 #ifdef DR_FAULT_HOOK
-    if (n == "stack_fault_test") { if (e->opt_stack_fault != value) drop_after_device_sync(e); e->opt_stack_fault = value; return DR_OK; }
+    if (n == "stack_fault_test") { put(e, e->opt_stack_fault, value); return DR_OK; }
 #endif
-    if (n == "stack_ticks") { if (e->stack_dbg_on != value) drop_after_device_sync(e); e->stack_dbg_on = value; return DR_OK; }
+    if (n == "stack_ticks") { put(e, e->stack_dbg_on, value); return DR_OK; }
     if (n.compare(0, 5, "tune.") == 0) {      // A/B knobs of planners and launchers: PROCESS-wide (kernels.h: Tuning)
         Tuning& t = tuning();
         const std::string f = n.substr(5);
         if (f == "ksplit_blocks") {
-            if (t.ksplit_blocks.load() != value) { t.ksplit_blocks.store(value); tuning_epoch().fetch_add(1); drop_after_device_sync(e); }
+            if (put(e, t.ksplit_blocks, value)) tuning_epoch().fetch_add(1);
             return DR_OK;
         }
         std::atomic<int>* field = f == "pack_threads" ? &t.pack_threads : f == "tile" ? &t.tile : f == "pw" ? &t.pw : f == "pw_nw" ? &t.pw_nw
@@ -450,11 +444,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
                    : f == "stack_fl" ? &t.stack_fl : f == "tail_t4" ? &t.tail_t4 : f == "xcd_n" ? &t.xcd_n : f == "xcd_model" ? &t.xcd_model
                    : f == "s3_eager" ? &t.s3_eager : f == "debug_chunks" ? &t.debug_chunks : nullptr;
         if (!field) return fail(e, DR_ENAME, "unknown option '%s'", name);
-        if (field->load() != value) {
-            field->store(value);
-            tuning_epoch().fetch_add(1);      // every engine drops its captured chain at its next dr_sample
-            drop_after_device_sync(e);
-        }
+        if (put(e, *field, value)) tuning_epoch().fetch_add(1);      // (part of every engine's chain key: each captures again at its next dr_sample)
         return DR_OK;
     }
     return fail(e, DR_ENAME, "unknown option '%s'", name);
@@ -521,6 +511,7 @@ GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     GraphKey key;
     key.sampler = c.sampler; key.B = c.B; key.T = c.T; key.x = e->xwork; key.noise = c.noise; key.w_zero = (c.w == 0.f);
     key.opt = effective(e->opt, NB == 2 * c.B, e->S, e->steps.at(c.i0));
+    key.baked = e->baked; key.tuning = tuning_epoch().load();
     key.fe_B = e->fe_B;
     key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
     key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
@@ -682,8 +673,8 @@ int dr_frontend(dr_engine* e, const float* d_wav, int B, int L, int T_roll, int 
         HIPCHK(e, hipMemsetAsync(e->mm, 0, e->mm.size() * sizeof(float), st));
     e->mm_scratch_off = mm_vals;
     if (cond_moved || B != e->fe_B || T != e->fe_T) {
-        // a captured chain bakes the conditioner pointers / strides: drop it when they change
-        drop_graph(e);
+        // a captured chain bakes the conditioner pointers / strides: stale when they change
+        stale(e);
     }
 
     // 1. center / reflect padding
@@ -795,12 +786,8 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     int rc = open_chain_call(e, sampler, B, T, nullptr, NB, i0, st);
     if (rc) return rc;
     e->hist_key.valid = false;      // (a whole chain uses the history buffers: a dr_step sequence does not continue across it)
-    if (e->tuning_epoch != tuning_epoch().load()) {      // a tune.* knob changed (any engine, any thread): the cached chain is stale
-        if ((rc = drop_chain(e))) return rc;
-        e->tuning_epoch = tuning_epoch().load();
-    }
     // (a yield is a precaution, not a verdict: the looks in front of later chains, >= 250 ms apart, may re-arm)
-    if (e->fused.may_fuse() && (rc = fused_look(e, shared_with_another_process(e)))) return rc;
+    if (e->fused.may_fuse()) fused_look(e, shared_with_another_process(e));
     FusedTurn turn(e, st);      // (released - event recorded on `st` - when this call returns, behind the chain's launches)
     if (turn.rc) return turn.rc;
     const ChainCall call{sampler, d_noise, B, T, w, seed, first_sample, i0};
@@ -810,19 +797,17 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
         return run_chain(e, call, d_x, st);
     }
 
-    const GraphKey key = chain_key(e, call, NB);
-    for (int attempt = 0; attempt < 2 && !e->chain.holds(key); ++attempt) {
-        drop_graph(e);
+    // (a held chain of another key is stale: the owner waits for its last launch and destroys it, then captures)
+    GraphKey key;
+    for (int attempt = 0; attempt < 2 && !e->chain.holds(key = chain_key(e, call, NB)); ++attempt) {
         Range range("dr_sample: capture + instantiate the chain graph");
         const auto cap = e->chain.capture(key, [&](hipStream_t cs) { return run_chain(e, call, e->xwork, cs); });
         if (cap.failed == Chain::Step::RECORD) return cap.rc;      // (the error text is the failing launch's own)
         if (cap.failed == Chain::Step::END) return fail(e, DR_EHIP, "%s failed: %s", cap.call, hipGetErrorString(cap.hip));
         if (!cap) return fail(e, DR_EHIP, "%s failed: %s (%s:%d)", cap.call, hipGetErrorString(cap.hip), __FILE__, __LINE__);
-        e->tuning_epoch = tuning_epoch().load();
         // capture + instantiation took tens of milliseconds: look again before a chain of persistent launches goes out
-        if (attempt == 0 && e->fused.active() && turn.held) {
-            if ((rc = fused_look(e, shared_with_another_process(e, true)))) return rc;      // (a yield drops the graph: captured again, per phase)
-        }
+        // (a yield makes the chain stale: the key moves, and the second attempt captures per phase)
+        if (attempt == 0 && e->fused.active() && turn.held) fused_look(e, shared_with_another_process(e, true));
     }
     Range range("dr_sample: launch the chain graph");
     const size_t bytes = (size_t)B * T * 88 * sizeof(float);
@@ -854,7 +839,7 @@ int dr_finish(dr_engine* e, void* stream) {
     HIPCHK(e, hipDeviceSynchronize());
     int rc = clear_stack_timeout(e);
     if (rc) return rc;
-    drop_graph(e);
+    stale(e);
     e->unverified = false;
     e->fused.timeout();         // (option "fused_rearm" may fuse again after clean chains; looks no longer do)
     static std::atomic<bool> warned{false};           // (engines of several host threads may get here together)
@@ -892,7 +877,7 @@ int dr_sample_checked(dr_engine* e, int sampler, float* d_x, const float* d_nois
     if (rc) return rc;
     rc = dr_finish(e, st);
     // option "fused_rearm": the tenant that caused a time-out has had that many chains to leave - fuse again
-    if (rc == DR_OK && e->fused.clean_chain() && (rc = drop_chain(e))) return rc;
+    if (rc == DR_OK && e->fused.clean_chain()) stale(e);
     if (rc != DR_ETIMEOUT) return rc;
     if (!may_fuse) return rc;         // (guard: fusing was not possible on entry, so no fused launch was issued)
     HIPCHK(e, hipMemcpyAsync(d_x, e->xsave, per * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -989,10 +974,10 @@ int dr_set_precision(dr_engine* e, int mode) {
     if (!e) return DR_EINVAL;
     if (mode != DR_PRECISION_F32 && mode != DR_PRECISION_BF16X3 && mode != DR_PRECISION_BF16) return fail(e, DR_EINVAL, "unknown precision mode %d", mode);
     if (mode != e->prec) {
-        DeviceGuard guard(e->cfg.device);     // the graph may still be executing on the ENGINE's device
-        drop_after_device_sync(e);
+        DeviceGuard guard(e->cfg.device);
+        stale(e);
         if (mode) {           // the mode changes only once its own packings exist (bf16x3: 520 MB of uploads, bf16: a third - the build can fail)
-            int rc = ensure_packings(e, mode);
+            int rc = ensure_packings(e, mode);      // (adds buffers, frees and rewrites none: nothing to wait for)
             if (rc) return rc;
         }
         e->prec = mode;

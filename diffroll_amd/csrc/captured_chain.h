@@ -3,7 +3,8 @@
 // graph, its executable, the key the sequence was captured under, the non-blocking stream captures happen on (created
 // on first use: the caller's stream may be the null stream), the stream of the last launch and the seconds the last
 // capture + instantiation took.  Move-only; the destructor destroys the executable, then the graph, then the stream.
-// Every graph and capture call of the runtime is in this file.
+// An executable is destroyed only by the capture that replaces it, which waits for its last launch first, and by the
+// destructor and move-assignment, whose callers have waited.  Every graph and capture call of the runtime is in this file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +19,7 @@ class CapturedChain {
 public:
     // What capture() reports: the step that failed and what it failed with - `hip` and `call` (the HIP call as written
     // below) for a step of this file, `rc` for RECORD (the error is the recorder's own, wherever it left its text)
-    enum class Step { OK, STREAM, BEGIN, RECORD, END, INSTANTIATE };
+    enum class Step { OK, WAIT, STREAM, BEGIN, RECORD, END, INSTANTIATE };
     struct Captured {
         Step failed = Step::OK;
         hipError_t hip = hipSuccess;
@@ -43,14 +44,16 @@ public:
     bool capturing() const { return capturing_; }
 
     // Captures what record(stream) launches on the capture stream (thread-local mode: other host threads keep launching) and
-    // instantiates it under `key`.  The capture is ended whatever record returned; a failure of any step leaves nothing held.
-    // What was held before is dropped first (not waited for).
+    // instantiates it under `key`.  What was held before is waited for, then destroyed, first: a failing wait (WAIT) touches
+    // nothing, what was held still is.  The capture is ended whatever record returned; a failure of any later step leaves
+    // nothing held.
     template <class Record>
     Captured capture(const Key& key, Record&& record) {
-        drop();
         Captured c;
         auto failed = [&](Step s, hipError_t st, const char* call) { c.failed = s; c.hip = st; c.call = call; return c; };
         hipError_t st;
+        if ((st = wait()) != hipSuccess) return failed(Step::WAIT, st, "hipStreamSynchronize(last_stream)");
+        drop();
         if (!cap_stream_ && (st = hipStreamCreateWithFlags(&cap_stream_, hipStreamNonBlocking)) != hipSuccess) {
             cap_stream_ = nullptr;
             return failed(Step::STREAM, st, "hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking)");
@@ -81,15 +84,9 @@ public:
         if (st == hipSuccess) { last_stream_ = stream; launched_ = true; }
         return st;
     }
-    // the held chain may still be running, on the stream it was last launched on: wait for it.  (The remembered stream
-    // outlives a drop - a chain captured since and not launched yet waits for its predecessor's stream.)
+    // the held chain may still be running, on the stream it was last launched on: wait for it (never launched: nothing to
+    // wait for).  What capture() does before it destroys, and what a caller does before it frees a buffer the chain reads.
     hipError_t wait() const { return exec_ && launched_ ? hipStreamSynchronize(last_stream_) : hipSuccess; }
-    // Destroys executable and graph and resets the key; waits for nothing; nothing to do on an empty owner
-    void drop() {
-        if (exec_) { (void)hipGraphExecDestroy(exec_); exec_ = nullptr; }
-        if (graph_) { (void)hipGraphDestroy(graph_); graph_ = nullptr; }
-        key_ = Key{};
-    }
 
     double capture_seconds() const { return capture_s_; }      // of the last successful capture + instantiation
     size_t nodes() const {                                     // of the held graph (0: none)
@@ -99,6 +96,13 @@ public:
     }
 
 private:
+    // Destroys executable and graph and resets the key; waits for nothing (see the top); nothing to do on an empty owner
+    void drop() {
+        if (exec_) { (void)hipGraphExecDestroy(exec_); exec_ = nullptr; }
+        if (graph_) { (void)hipGraphDestroy(graph_); graph_ = nullptr; }
+        key_ = Key{};
+        launched_ = false;
+    }
     void release() {
         drop();
         if (cap_stream_) { (void)hipStreamDestroy(cap_stream_); cap_stream_ = nullptr; }

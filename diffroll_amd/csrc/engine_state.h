@@ -105,27 +105,32 @@ inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t) 
 // the samplers whose network output is the x0 prediction (DR_SAMPLER_* 0-5); the others predict epsilon
 inline bool predicts_x0(int sampler) { return !(sampler >= DR_SAMPLER_DDPM_EPS && sampler <= DR_SAMPLER_DDIM2DDPM_EPS); }
 
-// What a captured chain bakes in: sampler, shape, the engine's work buffer and the injected-noise address (test
-// mode).  Seed, batch offset and guidance weight live in the DynParams device block; the caller's roll buffer
-// is copied into / out of the work buffer around the launch.
+// What a captured chain bakes in; the held chain is replayed while the key of the call equals the key it was captured
+// under, and is stale - waited for, destroyed and captured again by dr_sample, nowhere else - once it does not.  By
+// value: sampler, shape, the engine's work buffer and the injected-noise address (test mode).  Seed, batch offset and
+// guidance weight live in the DynParams device block; the caller's roll buffer is copied into / out of the work buffer
+// around the launch.
 struct GraphKey {
     int sampler = -1, B = 0, T = 0;
     float* x = nullptr;
     const float* noise = nullptr;
     bool w_zero = false;        // guidance weight 0 captures a different (conditional-only) chain
     // ... and the effective options: the draw layout of the update's Philox keys, which steps run the unconditional
-    // evaluation, how the prediction is integrated, clamped and thresholded, where the chain begins.  Setting one of them
-    // drops nothing ("sampling_steps" and "window_overlap" apart): a chain captured under another value is simply not
-    // replayed, and a façade that sets them around every call replays one graph.
+    // evaluation, how the prediction is integrated, clamped and thresholded, where the chain begins.  A chain captured
+    // under another value is simply not replayed, and a façade that sets them around every call replays one graph.
     ChainOptions opt;
+    // Everything else, by generation: the engine's own (dr_engine::baked, moved by stale()) and the process-wide one of
+    // the tune.* knobs (kernels.h: tuning_epoch(), moved by any engine on any thread)
+    unsigned baked = 0, tuning = 0;
     // A captured chain also bakes the clip count of the conditioner tensors (GemmArgs::c_n and the per-layer offsets
-    // l * fe_B * 2 Cp T): dr_frontend drops the chain when fe_B changes, the key keeps that from being load-bearing.
+    // l * fe_B * 2 Cp T): dr_frontend calls stale() when fe_B changes, the key keeps that from being load-bearing.
     int fe_B = 0;
     const float* hist = nullptr;              // the history buffer of solver order 2 (null: order < 2; the parity is baked per node)
     const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
-               opt == o.opt && fe_B == o.fe_B && hist == o.hist && thresh_work == o.thresh_work;
+               opt == o.opt && baked == o.baked && tuning == o.tuning && fe_B == o.fe_B && hist == o.hist &&
+               thresh_work == o.thresh_work;
     }
 };
 using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
@@ -289,7 +294,11 @@ struct dr_engine {
     drh::DevBuf<float> xalt;            // the tail kernel writes x_{t-1} here (it must not update x_t in place: other
                                         // blocks still read it); the chain ping-pongs between this and its roll buffer
     int last_mode = 0;                  // DR_MODE_* of the most recently planned evaluation (dr_launch_state)
-    unsigned tuning_epoch = 0;          // tuning_epoch() when the cached chain was captured (dr_sample waits for a chain of another epoch, then drops it)
+    // The generation of everything a captured launch sequence bakes in that is neither an argument of the call nor a
+    // ChainOptions value (both are GraphKey fields of their own): the launch mode (fused.active()), opt_tail, opt_blocked,
+    // opt_stack_xcd, opt_stack_warm, opt_stack_fault, stack_dbg_on and prec; the workspace and conditioner allocations and
+    // fe_B / fe_T; the committed weights; the respaced coefficient table.  Whatever changes one of them calls stale().
+    unsigned baked = 0;
     long kfd_gpu_id = -1;               // the driver's id of this GPU in /sys/class/kfd (tenants.h); -1: unknown, no scans
     double last_tenant_scan_s = -1.0;
     bool unverified = false;            // persistent launches have been issued since the last check of the time-out flag
@@ -369,6 +378,10 @@ struct Range {
     Range& operator=(const Range&) = delete;
 };
 
+// The captured chain is stale and a dr_step history has ended.  Says so and nothing more: the chain stays held - it may
+// still be running - until dr_sample replaces it (CapturedChain::capture waits for it first).
+inline void stale(dr_engine* e) { e->baked += 1; e->hist_key.valid = false; }
+
 // ---- abi.hip
 int clear_stack_timeout(dr_engine* e);
 int set_option(dr_engine* e, const char* name, int value, bool lab);      // lab: the names of dr_debug_set_option too
@@ -394,7 +407,6 @@ const float* zero_vec();
 GemmArgs p4_gemm(const float* Wp, const float* bias, int MT, const float* X, int planes, int NB, int T);
 void p4_out(GemmArgs& a, float* Y, int planes, int T, int rows);
 int build_trainable_cond(dr_engine* e, int T);
-void drop_graph(dr_engine* e);
 int ensure_workspace(dr_engine* e, int NB, int T);
 // What run_step offers run_network so that a whole reverse step becomes TWO launches (the residual stack incl. layer 0's
 // shared contraction + the tail kernel: skip / output projection, update, next input projection) where the fused

@@ -6,8 +6,8 @@
 //   timeout      dr_finish found a group barrier that gave up: per-phase launches until option "fused_rearm" clean
 //                checked chains (0: never) - a time-out outranks a pending yield, looks no longer re-arm
 //   clean_chain  dr_sample_checked finished a chain without a time-out
-// Every transition returns whether active() changed: the caller then drops its captured chain, which bakes the launch
-// mode.  Host code; plain C++ (tests/test_fused_mode_cpu.py compiles it without HIP).
+// Every transition returns whether active() changed: the caller then marks its captured chain, which bakes the launch
+// mode, stale.  Host code; plain C++ (tests/test_fused_mode_cpu.py compiles it without HIP).
 #pragma once
 #include <cstdint>
 

@@ -34,8 +34,8 @@ namespace dr {
 // dr_set_option(e, "tune.<field>", value) by tools/ and tests - the library reads no environment variable.
 // ---------------------------------------------------------------------------------------------
 // Fields are atomics (relaxed loads / stores are all that is needed: independent integers): dr_debug_set_option may run on
-// one host thread while another engine's planner reads them.  Every change bumps tuning_epoch(); an engine compares it in
-// dr_sample and drops a chain it captured under older values.
+// one host thread while another engine's planner reads them.  Every change bumps tuning_epoch(), which is part of the key
+// of every engine's captured chain: dr_sample does not replay a chain captured under older values.
 struct Tuning {
     std::atomic<int> pack_threads{16};   // host threads packing the layers at dr_commit (1 = serial)
     std::atomic<int> tile{0};            // force a conv / LDS-staged 1x1 tile: 3201 / 3202 / 3203 / 3205 (32x32 MFMA, NI) or 1603 / 1605 (16x16, NJ); 0 = cost model

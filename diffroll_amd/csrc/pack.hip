@@ -326,7 +326,8 @@ int commit(dr_engine* e, hipStream_t st) {
     e->consts.clear();
     e->layers.assign(L, LayerW{});
     e->cond_tr_T = 0;       // rebuilt from the new conditioner weights / trainable_parameters at the next use
-    e->ws_T = 0;            // (ensure_workspace is where that happens - and, as no workspace fits T = 0, where drop_graph drops the chain captured over the old weights)
+    e->ws_T = 0;            // (ensure_workspace is where that happens)
+    stale(e);               // a captured chain holds the addresses of the old weights
     int rc;
     auto P = [&](const std::string& n) -> const std::vector<float>& { return *find_param(e, n); };
 

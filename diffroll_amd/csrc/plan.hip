@@ -68,7 +68,7 @@ int build_trainable_cond(dr_engine* e, int T) {
 
 int ensure_workspace(dr_engine* e, int NB, int T) {
     if (NB <= e->ws_NB && T == e->ws_T) return DR_OK;
-    drop_graph(e);       // a captured chain holds the addresses of the buffers that are about to be replaced
+    stale(e);       // a captured chain holds the addresses of the buffers that are about to be replaced
     const int nb = std::max(NB, e->ws_T == T ? e->ws_NB : 0);
     const size_t act = (size_t)nb * e->Cp * T, s3 = act + act / 2, roll = (size_t)nb * T * 88;
     struct { DevBuf<float>& b; size_t n; } ws[] = {{e->h, act}, {e->hd, act}, {e->hd3, s3}, {e->g3, s3}, {e->g, act},
@@ -500,11 +500,6 @@ ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u) {
     a.v = e->opt.x0_thresh;
     a.work = e->thresh_work;
     return a;
-}
-
-void drop_graph(dr_engine* e) {
-    e->chain.drop();                // (does not wait: drop_chain / drop_after_device_sync, abi.hip, are the spellings that do)
-    e->hist_key.valid = false;      // (option "solver_order": whatever dropped the chain also ends a dr_step history)
 }
 
 }  // namespace drh

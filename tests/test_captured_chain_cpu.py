@@ -1,6 +1,6 @@
 """csrc/captured_chain.h without a GPU: the owner of the captured reverse chain compiled against a stub hip/hip_runtime.h
 that logs every graph, stream and capture call, counts live graphs, executables and streams and can fail the next begin,
-end or instantiate.  A small C++ driver is fed commands; after each one it prints the result, the owner's state and what
+end, instantiate or stream synchronisation.  A small C++ driver is fed commands; after each one it prints the result, the owner's state and what
 the stub saw.  The key is an int (0 = no key)."""
 import os
 import shutil
@@ -28,7 +28,7 @@ STUB = r"""
     namespace stub {
     inline int graphs = 0, execs = 0, streams = 0;                  // live
     inline int next_graph = 1, next_exec = 1, next_stream = 1;
-    inline int fail_begin = 0, fail_end = 0, fail_inst = 0;         // fail the next such call with that error
+    inline int fail_begin = 0, fail_end = 0, fail_inst = 0, fail_sync = 0;      // fail the next such call with that error
     inline std::string log;
     inline void note(const std::string& ev) { log += (log.empty() ? "" : " ") + ev; }
     inline std::string n(int id) { return std::to_string(id); }
@@ -46,7 +46,11 @@ STUB = r"""
         delete s;
         return hipSuccess;
     }
-    inline hipError_t hipStreamSynchronize(hipStream_t s) { stub::note("sync#" + stub::n(s->id)); return hipSuccess; }
+    inline hipError_t hipStreamSynchronize(hipStream_t s) {
+        if (int f = stub::take(stub::fail_sync)) { stub::note("sync#" + stub::n(s->id) + ":fail"); return (hipError_t)f; }
+        stub::note("sync#" + stub::n(s->id));
+        return hipSuccess;
+    }
     inline hipError_t hipStreamBeginCapture(hipStream_t s, hipStreamCaptureMode m) {
         if (int f = stub::take(stub::fail_begin)) { stub::note("begin#" + stub::n(s->id) + ":fail"); return (hipError_t)f; }
         stub::note("begin#" + stub::n(s->id) + (m == hipStreamCaptureModeThreadLocal ? ":threadlocal" : ":?"));
@@ -99,6 +103,7 @@ DRIVER = r"""
     static const char* step_name(Chain::Step s) {
         switch (s) {
             case Chain::Step::OK: return "ok";
+            case Chain::Step::WAIT: return "wait";
             case Chain::Step::STREAM: return "stream";
             case Chain::Step::BEGIN: return "begin";
             case Chain::Step::RECORD: return "record";
@@ -127,9 +132,9 @@ DRIVER = r"""
             else if (!strcmp(cmd, "fail_begin")) stub::fail_begin = (int)n;
             else if (!strcmp(cmd, "fail_end")) stub::fail_end = (int)n;
             else if (!strcmp(cmd, "fail_inst")) stub::fail_inst = (int)n;
+            else if (!strcmp(cmd, "fail_sync")) stub::fail_sync = (int)n;
             else if (!strcmp(cmd, "launch")) printf("%d", (int)a.launch(&user[n]));
             else if (!strcmp(cmd, "wait")) printf("%d", (int)a.wait());
-            else if (!strcmp(cmd, "drop")) a.drop();
             else if (!strcmp(cmd, "nodes")) printf("%zu", a.nodes());
             else if (!strcmp(cmd, "timed")) printf("%d", (int)(a.capture_seconds() > 0.0));
             else if (!strcmp(cmd, "move")) b = std::move(a);                 // a -> b (move assignment)
@@ -148,6 +153,7 @@ DRIVER = r"""
 
 BEGIN = "hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal)"
 INST = "hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)"
+SYNC = "hipStreamSynchronize(last_stream)"
 
 
 def build_driver(d, extra=()):
@@ -240,13 +246,11 @@ def test_a_failed_capture_drops_what_was_held(driver):
 def test_recapture_after_drop_reuses_the_stream(driver):
     run(driver, [
         CAPTURE_7,
-        ("drop",         " | 0 | 0 0 1 | exec_destroy#1 graph_destroy#1"),
-        ("holds 7",      "0 | 0 | 0 0 1 | "),
-        # the old pair is gone before the new one exists; no second stream
-        ("capture 8 0",  "ok 0 0 00 '' | 0 | 1 1 1 | begin#1:threadlocal record#1:capturing=1 end#1:graph#2 instantiate#2:exec#2"),
+        # capture drops what it holds first: the old pair is gone before the new one exists; no second stream
+        ("capture 8 0",  "ok 0 0 00 '' | 0 | 1 1 1 | exec_destroy#1 graph_destroy#1 begin#1:threadlocal record#1:capturing=1 "
+                         "end#1:graph#2 instantiate#2:exec#2"),
         ("holds 8",      "1 | 0 | 1 1 1 | "),
         ("holds 7",      "0 | 0 | 1 1 1 | "),
-        # without a drop in between, capture drops first
         ("capture 9 0",  "ok 0 0 00 '' | 0 | 1 1 1 | exec_destroy#2 graph_destroy#2 begin#1:threadlocal record#1:capturing=1 "
                          "end#1:graph#3 instantiate#3:exec#3"),
     ])
@@ -261,17 +265,40 @@ def test_wait_synchronises_the_stream_of_the_last_launch(driver):
         ("wait",      "0 | 0 | 1 1 1 | sync#101"),
         ("launch 1",  "0 | 0 | 1 1 1 | launch#1:on#102"),
         ("wait",      "0 | 0 | 1 1 1 | sync#102"),
-        ("drop",      " | 0 | 0 0 1 | exec_destroy#1 graph_destroy#1"),      # (does not wait)
-        ("wait",      "0 | 0 | 0 0 1 | "),
+        # a capture over a launched chain waits for the stream of its last launch before it destroys it ...
+        ("capture 8 0", "ok 0 0 00 '' | 0 | 1 1 1 | sync#102 exec_destroy#1 graph_destroy#1 begin#1:threadlocal "
+                        "record#1:capturing=1 end#1:graph#2 instantiate#2:exec#2"),
+        ("wait",      "0 | 0 | 1 1 1 | "),                       # ... and the new chain was never launched
+        # a capture over a never-launched chain waits for nothing
+        ("capture 9 0", "ok 0 0 00 '' | 0 | 1 1 1 | exec_destroy#2 graph_destroy#2 begin#1:threadlocal record#1:capturing=1 "
+                        "end#1:graph#3 instantiate#3:exec#3"),
+    ])
+
+
+def test_a_failing_wait_destroys_nothing_and_keeps_the_old_key(driver):
+    run(driver, [
+        CAPTURE_7,
+        ("launch 0",      "0 | 0 | 1 1 1 | launch#1:on#101"),
+        ("fail_sync 903", " | 0 | 1 1 1 | "),
+        ("capture 8 0",   f"wait 903 0 00 '{SYNC}' | 0 | 1 1 1 | sync#101:fail"),      # no begin, record never ran
+        ("holds 7",       "1 | 0 | 1 1 1 | "),
+        ("holds 8",       "0 | 0 | 1 1 1 | "),
+        ("nodes",         "401 | 0 | 1 1 1 | nodes#1"),
+        ("wait",          "0 | 0 | 1 1 1 | sync#101"),           # still launched, still waited for
+        ("capture 8 0",   "ok 0 0 00 '' | 0 | 1 1 1 | sync#101 exec_destroy#1 graph_destroy#1 begin#1:threadlocal "
+                          "record#1:capturing=1 end#1:graph#2 instantiate#2:exec#2"),
+        ("holds 8",       "1 | 0 | 1 1 1 | "),
     ])
 
 
 def test_drop_on_an_empty_owner_does_nothing(driver):
+    # (drop is private: move assignment releases what its target holds, and is the way to an empty owner)
     run(driver, [
-        ("drop",  " | 0 | 0 0 0 | "),
+        ("move",  " | 0 | 0 0 0 | "),                            # empty onto empty
         CAPTURE_7,
-        ("drop",  " | 0 | 0 0 1 | exec_destroy#1 graph_destroy#1"),
-        ("drop",  " | 0 | 0 0 1 | "),
+        ("move",  " | 0 | 1 1 1 | "),                            # onto an empty owner: nothing to destroy
+        ("move",  " | 0 | 0 0 0 | exec_destroy#1 graph_destroy#1 stream_destroy#1"),      # empty onto the holder
+        ("move",  " | 0 | 0 0 0 | "),
     ])
 
 
