@@ -294,6 +294,27 @@ int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B,
     return DR_OK;
 }
 
+// dr_debug_rescale: the statistics launch of a step on the caller's tensors, then the groups' g gathered into d_out
+int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
+    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
+    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
+    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
+    DeviceGuard guard(e->cfg.device);
+    if (e->opt.cfg_rescale == 0) return fail(e, DR_EINVAL, "dr_debug_rescale: cfg_rescale is 0 (off)");
+    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
+    int rc, NB;
+    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
+    if ((rc = grow_chain_buffer(e, e->rescale_work, rescale_work_words(B, T), st))) return rc;
+    if ((rc = write_windows(e, B, false, st))) return rc;
+    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
+    u.x0c = d_x0c; u.x0u = d_x0u;
+    u.w = w; u.onepw = (float)(1.0 + (double)w);
+    const RescaleArgs ra = rescale_args(e, u);
+    HIPCHK(e, launch_rescale(ra, B, st));
+    HIPCHK(e, launch_rescale_gather(ra, B, d_out, st));
+    return DR_OK;
+}
+
 // A setting that captured launches bake in (engine_state.h: dr_engine::baked) takes a new value: a change makes the chain stale
 template <class Field>
 bool put(dr_engine* e, Field& field, int value) {
@@ -415,6 +436,14 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         e->opt.x0_thresh = value;
         return DR_OK;
     }
+    if (n == "cfg_rescale") {      // (stored like "x0_threshold": nothing is dropped; part of the chain's key)
+        if (value < 0 || value > 10000)
+            return fail(e, DR_EINVAL, "cfg_rescale is 0 (off) or phi in units of 1 / 10000, 1 .. 10000 (7000 = 0.7), got %d", value);
+        // (the history of "solver_order" 2 holds the prediction as the previous step rescaled it, as for "x0_clip")
+        if (e->opt.cfg_rescale != value) e->hist_key.valid = false;
+        e->opt.cfg_rescale = value;
+        return DR_OK;
+    }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
         // (no captured chain is dropped: the effective pair is part of the chain's key - GraphKey - as "draws" is; lo > hi is
         // refused by dr_step / dr_sample, once both values are in)
@@ -473,6 +502,8 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
     }
     // option "x0_threshold": the work buffer of the threshold launches (tickets and counts start at zero: armed)
     if (e->opt.x0_thresh != 0 && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
+    // option "cfg_rescale": the work buffer of the statistics launch (the ticket starts at zero: armed), where the sampler guides
+    if (e->opt.cfg_rescale != 0 && NB == 2 * B && (rc = grow_chain_buffer(e, e->rescale_work, rescale_work_words(B, T), st))) return rc;
     return DR_OK;
 }
 
@@ -510,11 +541,12 @@ int run_chain(dr_engine* e, const ChainCall& c, float* xbuf, hipStream_t st) {
 GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     GraphKey key;
     key.sampler = c.sampler; key.B = c.B; key.T = c.T; key.x = e->xwork; key.noise = c.noise; key.w_zero = (c.w == 0.f);
-    key.opt = effective(e->opt, NB == 2 * c.B, e->S, e->steps.at(c.i0));
+    key.opt = effective(e->opt, NB == 2 * c.B, e->S, e->steps.at(c.i0), key.w_zero);
     key.baked = e->baked; key.tuning = tuning_epoch().load();
     key.fe_B = e->fe_B;
     key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
     key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
+    key.rescale_work = key.opt.cfg_rescale != 0 ? (const unsigned*)e->rescale_work : nullptr;
     return key;
 }
 

@@ -84,21 +84,28 @@ struct ChainOptions {
     // "x0_clip" (refused without it: abi.hip: check_options).  A thresholded step offers no tail plan: the stack launch, the
     // head projections, the threshold launches (threshold.hip) and update_thresh_kernel (plan.hip: run_step)
     int x0_thresh = 0;
+    // option "cfg_rescale": 0 = off; 1 .. 10000 = phi (1 / 10000) of the guidance rescale.  A step that guides under it offers
+    // no tail plan either: the statistics launch (rescale.hip) behind the head projections, then the threshold launches'
+    // rescaled forms where "x0_threshold" is set, then update_rescale_kernel (plan.hip: run_step).  A step that does not
+    // guide - another sampler, w = 0, outside the guidance interval - does not read it
+    int cfg_rescale = 0;
     bool operator==(const ChainOptions& o) const {
         return steps == o.steps && win_O == o.win_O && win_blend == o.win_blend && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
                guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
-               start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh;
+               start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && cfg_rescale == o.cfg_rescale;
     }
 };
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
-// step the chain visits first (chain_tables.h: start_position).
-inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t) {
+// step the chain visits first (chain_tables.h: start_position); "cfg_rescale" counts only where a step can guide - a sampler
+// that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
+inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, bool w_zero) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
     if (o.win_O <= 0) o.win_blend = 0;
     o.guid = guiding ? dr::GuidanceInterval{o.guid.lo, o.guid.hi_eff(S)} : dr::GuidanceInterval{};
+    if (!guiding || w_zero) o.cfg_rescale = 0;      // (no step of such a chain reads it)
     o.start = start_t;
     return o;
 }
@@ -127,10 +134,11 @@ struct GraphKey {
     int fe_B = 0;
     const float* hist = nullptr;              // the history buffer of solver order 2 (null: order < 2; the parity is baked per node)
     const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
+    const unsigned* rescale_work = nullptr;   // ... and the one the statistics launch of "cfg_rescale" points into, likewise
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                opt == o.opt && baked == o.baked && tuning == o.tuning && fe_B == o.fe_B && hist == o.hist &&
-               thresh_work == o.thresh_work;
+               thresh_work == o.thresh_work && rescale_work == o.rescale_work;
     }
 };
 using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
@@ -288,6 +296,7 @@ struct dr_engine {
     int hist_par = 0;
     dr::HistoryKey hist_key;            // dr_step under order 2: what the history holds (chain_tables.h)
     drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
+    drh::DevBuf<unsigned> rescale_work; // option "cfg_rescale": its ticket, g records and slots (kernels.h: RescaleArgs), allocated zeroed on first use
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
@@ -389,6 +398,7 @@ void set_kfd_root(const char* root);                                      // dr_
 int build_respaced(dr_engine* e);       // option "sampling_steps": steps and d_coef_rs from opt.steps and h_coef
 int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_solver from the chain's steps and h_coef
 int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);      // dr_debug_threshold
+int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);        // dr_debug_rescale
 
 // ---- pack.hip
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);
@@ -430,6 +440,8 @@ int sampler_shape(int sampler, int B, int& NB, int& n_cond);
 UpdateArgs update_base(const dr_engine* e, int B, int T);
 // option "x0_threshold": the arguments of a step's threshold launches, from the update they precede
 ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u);
+// option "cfg_rescale": the arguments of a step's statistics launch, likewise
+RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u);
 struct ChainState {
     bool inproj_ready = false;
     StepEval ready{};          // the shape inproj_ready holds for (TailPlan::primed of the next step)

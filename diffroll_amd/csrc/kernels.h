@@ -298,6 +298,40 @@ hipError_t launch_update_thresh(const UpdateArgs& a, const ThreshUpd& th, hipStr
 // (dr_debug_threshold) out (G, 2) = {q, s} of the batch's groups in row / recording order
 hipError_t launch_thresh_gather(const ThreshArgs& a, int B, float* out, hipStream_t s);
 
+// Option "cfg_rescale" (include/diffroll_amd.h): the guidance rescale of Lin et al. 2024.  At a step that guides, one factor
+//   g = (float)(1 + phi (sqrt(Vc / Vy) - 1))
+// per GROUP - the group of "x0_threshold" above - scales the guided prediction y towards the spread of the conditional
+// prediction c (both after the shared-frame mean / blend); the update consumes g y.  The statistics launches (rescale.hip)
+// leave g in the record of the group's FIRST row; the update's rescaling form reads it from there.
+// The engine's work buffer: [0] the ticket of the grid form (zero between launches), then one record of RESCALE_ROW_WORDS
+// words per row at RESCALE_HEAD + row * RESCALE_ROW_WORDS ([0] g), then - grid form - one slot of four doubles
+// {S1c, S2c, S1y, S2y} per (row, block of RESCALE_BLOCK frames), row-major, every slot a launch sums written by that launch.
+constexpr int RESCALE_HEAD = 4, RESCALE_ROW_WORDS = 2, RESCALE_BLOCK = 64;
+inline size_t rescale_blocks(int T) { return ((size_t)T + RESCALE_BLOCK - 1) / RESCALE_BLOCK; }
+inline size_t rescale_work_words(int B, int T) { return (size_t)RESCALE_HEAD + (size_t)B * RESCALE_ROW_WORDS + (size_t)B * rescale_blocks(T) * 8; }
+struct RescaleArgs {
+    UpdateArgs u;          // read: what pred_quad reads (ThreshArgs::u); x0u is set - the step guides
+    int phi;               // the option's value, 1 .. 10000
+    unsigned* work;        // the buffer above, rescale_work_words(B, T) words
+};
+// What the update's rescaling form needs beside UpdateArgs (the second kernel argument, as ThreshUpd is): g of row 0's
+// record - row b's is RESCALE_ROW_WORDS floats further per row - and what follows the product: th.qs set = the thresholding
+// of "x0_threshold" with th, else the clamp UpdateArgs names, or nothing.
+struct RescaleUpd {
+    const float* g;
+    ThreshUpd th;
+};
+inline const float* rescale_g(const unsigned* work) { return reinterpret_cast<const float*>(work + RESCALE_HEAD); }
+// a step's statistics: one launch of one workgroup per roll (clips of at most THRESH_ROLL_MAX elements), or one launch of
+// (blocks, rows) workgroups whose last arriver sums the slots (windows, longer clips)
+hipError_t launch_rescale(const RescaleArgs& a, int B, hipStream_t s);
+// a step's threshold launches ranking |g y - m| (threshold.hip: the kernels' rescaled forms); g as in RescaleUpd
+hipError_t launch_threshold_rescaled(ThreshArgs a, const float* g, int B, hipStream_t s);
+// update_kernel's rescaling form (update.hip: update_rescale_kernel)
+hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipStream_t s);
+// (dr_debug_rescale) out (G) = g of the batch's groups in row / recording order
+hipError_t launch_rescale_gather(const RescaleArgs& a, int B, float* out, hipStream_t s);
+
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->
 // classifier-free combine + posterior update -> input projection of the next step.  Same grid / grouping as the
 // stack_kernel launch it follows: NB samples (first `dual` conditional, next `dual` unconditional when dual > 0) x

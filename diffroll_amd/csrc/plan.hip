@@ -472,7 +472,10 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // option "x0_threshold": the selection sits between the network and the update, so the step offers no tail plan - the
     // evaluation keeps its fused stack launch, the head projections write e->x0buf, the rest are ordinary launches
     const bool thresh = e->opt.x0_thresh != 0 && u.clamp_lo < u.clamp_hi;
-    TailPlan* offer = (result && x != xalt && !thresh) ? &plan : nullptr;
+    // option "cfg_rescale": likewise at a step that guides - the statistics sit between the network and everything that reads
+    // the prediction; a step that runs no unconditional evaluation does not read the option and keeps its tail kernel
+    const bool rescale = e->opt.cfg_rescale != 0 && u.x0u != nullptr;
+    TailPlan* offer = (result && x != xalt && !thresh && !rescale) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
@@ -482,6 +485,18 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         return DR_OK;
     }
     if (result) *result = x;
+    if (rescale) {      // statistics, [threshold launches ranking |g y - m|], update on g y
+        const RescaleArgs ra = rescale_args(e, u);
+        RescaleUpd rs{rescale_g(ra.work), ThreshUpd{nullptr, 0.f, 0.f}};
+        HIPCHK(e, launch_rescale(ra, B, st));
+        if (thresh) {
+            const ThreshArgs ta = thresh_args(e, u);
+            HIPCHK(e, launch_threshold_rescaled(ta, rs.g, B, st));
+            rs.th = ThreshUpd{reinterpret_cast<const float*>(ta.work + THRESH_HEAD + THRESH_QS), ta.m, ta.r};
+        }
+        HIPCHK(e, launch_update_rescale(u, rs, st));
+        return DR_OK;
+    }
     if (thresh) {
         const ThreshArgs ta = thresh_args(e, u);
         HIPCHK(e, launch_threshold(ta, B, st));
@@ -499,6 +514,14 @@ ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u) {
     a.m = 0.5f * (u.clamp_lo + u.clamp_hi); a.r = 0.5f * (u.clamp_hi - u.clamp_lo);
     a.v = e->opt.x0_thresh;
     a.work = e->thresh_work;
+    return a;
+}
+
+RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u) {
+    RescaleArgs a{};
+    a.u = u;
+    a.phi = e->opt.cfg_rescale;
+    a.work = e->rescale_work;
     return a;
 }
 

@@ -23,7 +23,17 @@
 //                        to pass is the launch boundary.
 // No workgroup ever waits for another, so neither form assumes anything about what else is resident; the work words are
 // re-armed by the kernels themselves, so a captured chain replays with no host help.
-#include "threshold_quad.h"
+//
+// Option "cfg_rescale": at a guided step under it the launches rank |g y - m|.  Each kernel has a rescaled form that takes
+// the groups' g records as a second argument and puts rescale_quad behind pred_quad.  Both forms are ONE text, the second
+// part of this file, which the first part includes once per form with
+//   TH_ROLL_KERNEL / TH_PASS_KERNEL   the kernels' names
+//   TH_PARAMS                         their parameters (the first is `const ThreshArgs a`)
+//   TH_PRED(i4, y)                    the prediction the selection ranks
+// Text and not a function template: the plain form compiles to what it compiled to before the option existed, register for
+// register (profiles/rescale_kernel_resources.txt) - as a template inlined into two kernels thresh_pass_kernel did not.
+#ifndef TH_ROLL_KERNEL      // ================================================================ part 1: the unit
+#include "rescale_quad.h"
 
 namespace dr {
 
@@ -81,8 +91,87 @@ DR_DEVINL void th_finish(const float m, const float r, const unsigned ak, const 
     qs[1] = q > r ? q : r;      // (a NaN q: s = r)
 }
 
+DR_DEVINL unsigned th_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+DR_DEVINL void th_store(unsigned* p, const unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the plain forms: thresh_roll_kernel, thresh_pass_kernel rank |y - m|
+#define TH_ROLL_KERNEL thresh_roll_kernel
+#define TH_PASS_KERNEL thresh_pass_kernel
+#define TH_PARAMS const ThreshArgs a
+#define TH_PRED(i4, y) pred_quad(a.u, i4, y)
+#include "threshold.hip"
+#undef TH_ROLL_KERNEL
+#undef TH_PASS_KERNEL
+#undef TH_PARAMS
+#undef TH_PRED
+// the rescaled forms (option "cfg_rescale"): thresh_roll_rs_kernel, thresh_pass_rs_kernel rank |g y - m|, g of the quad's group
+// from the records the statistics launch left (rs: RescaleUpd::g)
+#define TH_ROLL_KERNEL thresh_roll_rs_kernel
+#define TH_PASS_KERNEL thresh_pass_rs_kernel
+#define TH_PARAMS const ThreshArgs a, const float* rs
+#define TH_PRED(i4, y) (pred_quad(a.u, i4, y), rescale_quad(a.u, rs, i4, y))
+#include "threshold.hip"
+#undef TH_ROLL_KERNEL
+#undef TH_PASS_KERNEL
+#undef TH_PARAMS
+#undef TH_PRED
+
+// g: null = the plain forms; else the rescaled ones
+static hipError_t launch_threshold_forms(ThreshArgs a, const float* g, int B, hipStream_t s) {
+    const UpdateArgs& u = a.u;
+    if (!u.x0c || !a.work || B < 1 || u.per_sample < 4 || (u.per_sample & 3) || u.n != (long)B * u.per_sample ||
+        u.n >= (1l << 31) || a.v < 5000 || a.v > 10000 || !(a.r > 0.f))
+        return hipErrorInvalidValue;
+    if (win_H(u) == 0 && u.per_sample <= THRESH_ROLL_MAX) {
+        if (g) hipLaunchKernelGGL(thresh_roll_rs_kernel, dim3((unsigned)B), dim3(512), 0, s, a, g);
+        else hipLaunchKernelGGL(thresh_roll_kernel, dim3((unsigned)B), dim3(512), 0, s, a);
+        return hipGetLastError();
+    }
+    if (B > 65535) return hipErrorInvalidValue;
+    const long nq = u.per_sample >> 2;
+    const dim3 grid((unsigned)((nq + TH_CHUNK - 1) / TH_CHUNK), (unsigned)B);
+    for (a.pass = 0; a.pass < 5; ++a.pass) {
+        if (g) hipLaunchKernelGGL(thresh_pass_rs_kernel, grid, dim3(256), 0, s, a, g);
+        else hipLaunchKernelGGL(thresh_pass_kernel, grid, dim3(256), 0, s, a);
+        const hipError_t st = hipGetLastError();
+        if (st != hipSuccess) return st;
+    }
+    return hipSuccess;
+}
+hipError_t launch_threshold(ThreshArgs a, int B, hipStream_t s) { return launch_threshold_forms(a, nullptr, B, s); }
+hipError_t launch_threshold_rescaled(ThreshArgs a, const float* g, int B, hipStream_t s) {
+    return g ? launch_threshold_forms(a, g, B, s) : hipErrorInvalidValue;
+}
+
+// (dr_debug_threshold) the records of the groups' first rows, in row order, as (G, 2)
+__global__ __launch_bounds__(256) void thresh_gather_kernel(const ThreshArgs a, int B, float* out) {
+    for (long b = threadIdx.x; b < B; b += 256) {
+        long first;
+        int f_lo;
+        thresh_place(a.u, b, first, f_lo);
+        if (first != b) continue;
+        long g = b;
+        if (win_H(a.u) > 0) {
+            g = 0;
+            if (a.u.win_tab)
+                for (long j = 0; j < b; ++j) g += window_idx(a.u.win_tab[j]) == 0;
+        }
+        const float* qs = reinterpret_cast<const float*>(a.work + THRESH_HEAD + b * THRESH_ROW_WORDS + THRESH_QS);
+        out[2 * g] = qs[0];
+        out[2 * g + 1] = qs[1];
+    }
+}
+hipError_t launch_thresh_gather(const ThreshArgs& a, int B, float* out, hipStream_t s) {
+    if (!a.work || !out || B < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(thresh_gather_kernel, dim3(1), dim3(256), 0, s, a, B, out);
+    return hipGetLastError();
+}
+
+}  // namespace dr
+
+#else      // ================================================ part 2: the two kernels, as part 1 includes them (inside namespace dr)
 // ---------------------------------------------------------------------------------------------- one workgroup per roll
-__global__ __launch_bounds__(512) void thresh_roll_kernel(const ThreshArgs a) {
+__global__ __launch_bounds__(512) void TH_ROLL_KERNEL(TH_PARAMS) {
     __shared__ unsigned hist[256];
     __shared__ unsigned sel[4];      // the pattern so far, the rank sought within it, the selected bin's count, the successor
     const long row = blockIdx.x;
@@ -96,7 +185,7 @@ __global__ __launch_bounds__(512) void thresh_roll_kernel(const ThreshArgs a) {
         __syncthreads();
         for (long q = threadIdx.x; q < nq; q += 512) {
             float y[4];
-            pred_quad(a.u, q0 + q, y);
+            TH_PRED(q0 + q, y);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned pat = th_pattern(y[e], a.m);
@@ -119,7 +208,7 @@ __global__ __launch_bounds__(512) void thresh_roll_kernel(const ThreshArgs a) {
         unsigned mn = 0xFFFFFFFFu;
         for (long q = threadIdx.x; q < nq; q += 512) {
             float y[4];
-            pred_quad(a.u, q0 + q, y);
+            TH_PRED(q0 + q, y);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned pat = th_pattern(y[e], a.m);
@@ -139,11 +228,8 @@ __global__ __launch_bounds__(512) void thresh_roll_kernel(const ThreshArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- five launches over all rows
-DR_DEVINL unsigned th_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-DR_DEVINL void th_store(unsigned* p, const unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // grid (chunks of TH_CHUNK quads, rows).  Pass 0-3: count; pass 4: the smallest pattern above a[k], then q and s.
-__global__ __launch_bounds__(256) void thresh_pass_kernel(const ThreshArgs a) {
+__global__ __launch_bounds__(256) void TH_PASS_KERNEL(TH_PARAMS) {
     __shared__ unsigned hist[256];
     __shared__ unsigned last_s;
     const int p = a.pass;
@@ -162,7 +248,7 @@ __global__ __launch_bounds__(256) void thresh_pass_kernel(const ThreshArgs a) {
     unsigned mn = 0xFFFFFFFFu;
     for (long q = qa + threadIdx.x; q < qb; q += 256) {
         float y[4];
-        pred_quad(a.u, row * nq + q, y);
+        TH_PRED(row * nq + q, y);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const unsigned pat = th_pattern(y[e], a.m);
@@ -230,48 +316,4 @@ __global__ __launch_bounds__(256) void thresh_pass_kernel(const ThreshArgs a) {
     if (threadIdx.x == 0) th_store(a.work, 0u);
 }
 
-hipError_t launch_threshold(ThreshArgs a, int B, hipStream_t s) {
-    const UpdateArgs& u = a.u;
-    if (!u.x0c || !a.work || B < 1 || u.per_sample < 4 || (u.per_sample & 3) || u.n != (long)B * u.per_sample ||
-        u.n >= (1l << 31) || a.v < 5000 || a.v > 10000 || !(a.r > 0.f))
-        return hipErrorInvalidValue;
-    if (win_H(u) == 0 && u.per_sample <= THRESH_ROLL_MAX) {
-        hipLaunchKernelGGL(thresh_roll_kernel, dim3((unsigned)B), dim3(512), 0, s, a);
-        return hipGetLastError();
-    }
-    if (B > 65535) return hipErrorInvalidValue;
-    const long nq = u.per_sample >> 2;
-    const dim3 grid((unsigned)((nq + TH_CHUNK - 1) / TH_CHUNK), (unsigned)B);
-    for (a.pass = 0; a.pass < 5; ++a.pass) {
-        hipLaunchKernelGGL(thresh_pass_kernel, grid, dim3(256), 0, s, a);
-        const hipError_t st = hipGetLastError();
-        if (st != hipSuccess) return st;
-    }
-    return hipSuccess;
-}
-
-// (dr_debug_threshold) the records of the groups' first rows, in row order, as (G, 2)
-__global__ __launch_bounds__(256) void thresh_gather_kernel(const ThreshArgs a, int B, float* out) {
-    for (long b = threadIdx.x; b < B; b += 256) {
-        long first;
-        int f_lo;
-        thresh_place(a.u, b, first, f_lo);
-        if (first != b) continue;
-        long g = b;
-        if (win_H(a.u) > 0) {
-            g = 0;
-            if (a.u.win_tab)
-                for (long j = 0; j < b; ++j) g += window_idx(a.u.win_tab[j]) == 0;
-        }
-        const float* qs = reinterpret_cast<const float*>(a.work + THRESH_HEAD + b * THRESH_ROW_WORDS + THRESH_QS);
-        out[2 * g] = qs[0];
-        out[2 * g + 1] = qs[1];
-    }
-}
-hipError_t launch_thresh_gather(const ThreshArgs& a, int B, float* out, hipStream_t s) {
-    if (!a.work || !out || B < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(thresh_gather_kernel, dim3(1), dim3(256), 0, s, a, B, out);
-    return hipGetLastError();
-}
-
-}  // namespace dr
+#endif

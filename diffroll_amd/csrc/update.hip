@@ -1,7 +1,7 @@
 // gfx950 (MI355X, CDNA4): the small HBM-bound kernels around the network - posterior update of all nine samplers +
 // classifier-free combine + Philox noise (task/diffusion.py:804-1055), q_sample / extract_x0 (:31-64), frame confusion
 // counts (:381-383), the roll -> note-run scan (:1185-1233).
-#include "threshold_quad.h"
+#include "rescale_quad.h"
 
 namespace dr {
 
@@ -20,6 +20,16 @@ __global__ __launch_bounds__(256) void update_thresh_kernel(const UpdateArgs a, 
     if (i4 * 4 >= a.n) return;
     float4 y;
     reinterpret_cast<float4*>(a.x)[i4] = update_quad<true>(a, i4, &y, &th);
+    if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
+}
+
+// Option "cfg_rescale": the same update on g y, g of the quad's group (rescale_quad.h), then the thresholding or the clamp as
+// rs names them - one form for the rescale alone, with "x0_clip" and with "x0_threshold".
+__global__ __launch_bounds__(256) void update_rescale_kernel(const UpdateArgs a, const RescaleUpd rs) {
+    const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i4 * 4 >= a.n) return;
+    float4 y;
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad<false, true>(a, i4, &y, nullptr, &rs);
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
 }
 
@@ -51,6 +61,13 @@ hipError_t launch_update_thresh(const UpdateArgs& a, const ThreshUpd& th, hipStr
     if (!th.qs) return hipErrorInvalidValue;
     const long n4 = a.n / 4;
     hipLaunchKernelGGL(update_thresh_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a, th);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipStream_t s) {
+    if (!rs.g) return hipErrorInvalidValue;
+    const long n4 = a.n / 4;
+    hipLaunchKernelGGL(update_rescale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a, rs);
     return hipGetLastError();
 }
 

@@ -158,6 +158,9 @@ DR_DEVINL void clamp_quad(const float lo, const float hi, float (&y)[4]) {
 // Option "x0_threshold": what the update's thresholding form does in place of the clamp - defined in threshold_quad.h, which
 // the units that instantiate that form include behind this header.
 DR_DEVINL void thresh_quad(const UpdateArgs& a, const ThreshUpd& th, const long i4, float (&y)[4]);
+// Option "cfg_rescale": what the update's rescaling form does there - y' = g y with g of the quad's group, then the
+// thresholding or the clamp as rs names them - defined in rescale_quad.h, included likewise.
+DR_DEVINL void rescaled_quad(const UpdateArgs& a, const RescaleUpd& rs, const long i4, float (&y)[4]);
 
 // Option "window_blend" (win_blend() of UpdateArgs::win): what a frame shared by windows b and b + 1 takes of the two guided predictions
 // lo (window b's, its frame H + j) and up (window b + 1's, its frame j), j = 0 .. O - 1 the position within the overlap:
@@ -185,9 +188,11 @@ DR_DEVINL void blend_quad(const int mode, const int j, const int O, const float 
 
 // pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean and the clamp of
 // option "x0_clip" (mode 5's history).  TH: update_kernel's thresholding form (option "x0_threshold"; th is set) - the
-// tail kernel instantiates TH = false, the text it always had.
-template <bool TH = false>
-DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr, const ThreshUpd* th = nullptr) {
+// tail kernel instantiates TH = false, the text it always had.  RS: update_kernel's rescaling form (option "cfg_rescale"; rs
+// is set, th is not read): rescaled_quad in that place.
+template <bool TH = false, bool RS = false>
+DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr, const ThreshUpd* th = nullptr,
+                             const RescaleUpd* rs = nullptr) {
 #pragma clang fp contract(off)
     float x0[4];
     // per-call scalars: by value (eager launches) or from the device block (captured chain)
@@ -225,7 +230,8 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         }
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
-    if constexpr (TH) thresh_quad(a, *th, i4, x0);
+    if constexpr (RS) rescaled_quad(a, *rs, i4, x0);
+    else if constexpr (TH) thresh_quad(a, *th, i4, x0);
     else {
         if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, x0);
     }

@@ -137,7 +137,7 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise AttributeError(sampling.type)                               # getattr at task/diffusion.py:255
         # extensions, absent / None in the reference's configs (each key, its validator and the engine option it becomes:
         # schedule.sampling_options): steps, draws, guidance_interval, solver_order, solver_noise, start_step / strength,
-        # x0_clip, x0_threshold
+        # x0_clip, x0_threshold, cfg_rescale
         sampling_options(sampling, timesteps, norm_args)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
@@ -290,6 +290,10 @@ class ClassifierFreeDiffRoll(nn.Module):
     def x0_threshold(self) -> int:
         """hparams.sampling.x0_threshold as the engine's option takes it (0: off, else the percentile in units of 1 / 10000)."""
         return self.sampling_options()["x0_threshold"]
+
+    def cfg_rescale(self) -> int:
+        """hparams.sampling.cfg_rescale as the engine's option takes it (0: off, else phi in units of 1 / 10000)."""
+        return self.sampling_options()["cfg_rescale"]
 
     def guidance_interval(self):
         """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain."""

@@ -236,6 +236,21 @@ def check_guidance_interval(interval, timesteps: int, sampler: str = None):
     return int(interval[0]), int(interval[1])
 
 
+def check_cfg_rescale(value, sampler: str = None) -> int:
+    """Option "cfg_rescale" (include/diffroll_amd.h) as hparams.sampling.cfg_rescale: None / 0 / False = off, a float phi with
+    0 < phi <= 1 = the guidance rescale of Lin et al. 2024 at the steps that guide (0.7 is the paper's value).  Returns the
+    option's value round(phi * 10000) - 1 .. 10000, or 0 for off; any other value (a phi that rounds to 0 included) or a set
+    value with a sampler that does not guide raises ValueError."""
+    if value is None or value is False or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0):
+        return 0
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < value <= 1.0 or int(round(float(value) * 10000)) < 1:
+        raise ValueError(f"cfg_rescale must be 0 / None (off) or a factor phi with 0 < phi <= 1 in steps of 1 / 10000 (0.7 = the "
+                         f"paper's value), got {value!r}")
+    if sampler is not None and sampler not in GUIDING_SAMPLERS:
+        raise ValueError(f"cfg_rescale = {value!r} needs a sampler that guides ({', '.join(GUIDING_SAMPLERS)}), not '{sampler}'")
+    return int(round(float(value) * 10000))
+
+
 def respaced_steps(timesteps: int, n: int) -> List[int]:
     """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
     integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""
@@ -264,6 +279,7 @@ def sampling_options(sampling, timesteps, norm_args=(0, 1)) -> Dict[str, object]
          lambda: check_start(get("start_step"), get("strength"), respaced_steps(timesteps, get("steps") or 0) if started else ())),
         ("x0_clip", "x0_clip", lambda: check_x0_clip(get("x0_clip"), sampler, norm_args)),
         ("x0_threshold", "x0_threshold", lambda: check_x0_threshold(get("x0_threshold"), sampler, get("x0_clip"))),
+        ("cfg_rescale", "cfg_rescale", lambda: check_cfg_rescale(get("cfg_rescale"), sampler)),
     )
     options = {}
     for option, key, check in checks:

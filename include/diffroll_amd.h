@@ -619,6 +619,55 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          is part of a captured chain's key, and the chain replays with no host help (the kernels re-arm
  *                          their own work words).  0 = off: every path is byte-identical to an engine that never set it.
  *                          Nothing is known about quality with real weights.
+ *   "cfg_rescale"      [0] 0, or 1 .. 10000: THE GUIDANCE RESCALE of Lin et al. 2024 ("Common Diffusion Noise Schedules and
+ *                          Sample Steps are Flawed", section 3.4), phi = value / 10000 (7000 = the paper's 0.7).  The guided
+ *                          prediction (1 + w) c - w u is an extrapolation whose spread exceeds the conditional
+ *                          prediction's; the rescale scales the excess back - cell order and zeros preserved - in front
+ *                          of "x0_clip" / "x0_threshold", which cut it off at the range's ends.  WHERE IT ACTS: at a reverse
+ *                          step that guides - the sampler is DR_SAMPLER_CFDG_DDPM_X0, _INPAINTING_DDPM_X0 or
+ *                          _CFDG_DDIM_X0 and the step runs the unconditional evaluation (inside "guidance_t_min" /
+ *                          "guidance_t_max", not a w = 0 chain).  With y the guided prediction after the shared-frame
+ *                          mean / blend of "window_overlap" / "window_blend" and c the conditional prediction put through
+ *                          the same mean / blend alone, per GROUP and in double:
+ *                              N = elements of the group;  S1c = sum c, S2c = sum c c, S1y = sum y, S2y = sum y y
+ *                              Vc = S2c - S1c (S1c / N),  Vy = S2y - S1y (S1y / N)      (each operation rounded once)
+ *                              rho = sqrt(Vc / Vy),  phid = (double)value / 10000.0
+ *                              g = (float)(1.0 + phid (rho - 1.0))
+ *                              g = 1.0f exactly when !(Vy > 0), !(Vc >= 0) or g is not finite (constant rolls, inf / NaN)
+ *                          The step's prediction becomes y' = g y - one fp32 product, the identity where g == 1.0f -
+ *                          and everything behind reads y': the clamp of "x0_clip"; the selection of "x0_threshold", which
+ *                          ranks |g y - m|; both terms of every update; y / c2 of the last step; d and the history p of
+ *                          "solver_order", with or without "solver_noise".  THE GROUP is exactly the group of
+ *                          "x0_threshold": a clip's roll (every draw of "draws" its own); under "window_overlap" the
+ *                          recording's canvas, every canvas frame counted once (a window that is not its recording's first
+ *                          contributes frames [O, T)); "window_break" and draws delimit recordings; a group never spans
+ *                          ranks.  All windows of a recording use the same g on the same blended value: the frames they
+ *                          share stay bit-identical.  THE ORDER OF THE SUMS is part of the definition (a square of an fp32
+ *                          value is exact in double: only the additions round), every level a sequential sum from 0.0:
+ *                              a frame's 88 elements in pitch order;
+ *                              the frames a row counts - all of a clip's, [O, T) of a window that is not its recording's
+ *                              first - in blocks of 64 from its first counted frame, a block's frames in frame order;
+ *                              a group's blocks in row, then block order.
+ *                          g is a function of the inputs alone - no floating-point atomic, the same bits on every grid,
+ *                          replay and launch form.  WHERE IT RUNS: the statistics sit between the network and the update,
+ *                          so a guided step under the option does not use the tail kernel: fused stack, head
+ *                          projections, one statistics launch (csrc/rescale.hip), the threshold launches where
+ *                          "x0_threshold" is set, the update; dr_launch_state reports DR_MODE_FUSED_STACK for it (cost:
+ *                          profiles/rescale_sweep.txt).  A step
+ *                          that does not guide is untouched - no launch is added, it keeps its tail kernel, not a bit
+ *                          changes - and the six samplers that do not guide ignore the option as they ignore the
+ *                          guidance interval.  Any value outside 0 .. 10000 -> DR_EINVAL at the set, naming the value.
+ *                          dr_step follows the rule for its one step; dr_forward, dr_forward_steps, dr_q_sample,
+ *                          dr_extract_x0 and the diffusion of "start_noise" are unaffected; dr_sample_checked's re-run
+ *                          uses the same value.  A change of the value ends a dr_step history of "solver_order" 2, as a
+ *                          change of "x0_clip" does.  Combines with "sampling_steps", "window_overlap" / "window_break" /
+ *                          "window_blend", "draws" / "draw_stride", "guidance_t_min" / "guidance_t_max", "solver_order" /
+ *                          "solver_noise", "start_step" / "start_noise", "x0_clip" / "x0_threshold" (neither is required),
+ *                          all three precisions and sharding.  Stored like "x0_threshold": setting it drops nothing; the
+ *                          value is part of a captured chain's key where a step of the chain can read it - a sampler
+ *                          that guides, at w != 0 - and of no other chain's; the chain replays with no host help.  0 = off:
+ *                          every path is byte-identical to an engine that never set it.  Nothing is known about quality
+ *                          with real weights.
  * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */

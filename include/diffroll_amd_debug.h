@@ -104,6 +104,12 @@ int dr_debug_launch_counts(dr_engine* e, int64_t* out2);
  * the recordings of a window batch (per draw).  Either option at 0 -> DR_EINVAL.  Asynchronous on `stream`. */
 int dr_debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, void* stream);
 
+/* Option "cfg_rescale" on its own: exactly the statistics launch a guided reverse step runs between the network and the
+ * update (csrc/rescale.hip), on the caller's tensors - d_x0c, d_x0u and w as for dr_debug_threshold (d_x0u NULL: y = c) -
+ * under the engine's current "cfg_rescale", "window_overlap", "window_blend", "window_break" and "draws".  d_out receives G
+ * floats: g of each group of the batch, in row / recording order.  The option at 0 -> DR_EINVAL.  Asynchronous on `stream`. */
+int dr_debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
