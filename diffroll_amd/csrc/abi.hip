@@ -161,6 +161,8 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
 // options "solver_order", "x0_clip" and "x0_threshold" act on an x0 prediction (DR_SAMPLER_* 0-5): the epsilon samplers
 // refuse them; "x0_threshold" refines "x0_clip", which names the range, and is refused without it
 // options "guidance_t_min" / "guidance_t_max": the samplers that guide need lo <= hi (the others ignore both)
+// options "cfg_project" / "cfg_norm": refused beside "x0_threshold" (whose selection would have to rank the projected
+// prediction) and beside "cfg_rescale" (an alternative; a combined form would need the spread of the projected prediction)
 int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     const ChainOptions& o = e->opt;
     if (2 * o.win_O > T)
@@ -199,6 +201,12 @@ int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     if (o.x0_clamp != 0 && eps)
         return fail(e, DR_EINVAL, "sampler %d predicts epsilon: x0_clip = %d clamps an x0 prediction (samplers 0-5); set "
                                   "x0_clip 0 for this sampler", sampler, o.x0_clamp);
+    if ((o.cfg_project != 0 || o.cfg_norm != 0) && o.x0_thresh != 0)
+        return fail(e, DR_EINVAL, "cfg_project = %d / cfg_norm = %d do not combine with x0_threshold = %d: the selection would have "
+                                  "to rank the projected prediction; set x0_threshold 0 (x0_clip alone combines)", o.cfg_project, o.cfg_norm, o.x0_thresh);
+    if ((o.cfg_project != 0 || o.cfg_norm != 0) && o.cfg_rescale != 0)
+        return fail(e, DR_EINVAL, "cfg_project = %d / cfg_norm = %d do not combine with cfg_rescale = %d: the two are alternatives; "
+                                  "set one of them 0", o.cfg_project, o.cfg_norm, o.cfg_rescale);
     if (NB == 2 * B && o.guid.empty(e->S))
         return fail(e, DR_EINVAL, "guidance interval is empty: guidance_t_min = %d exceeds guidance_t_max = %d", o.guid.lo,
                     o.guid.hi_eff(e->S));
@@ -312,6 +320,27 @@ int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, i
     const RescaleArgs ra = rescale_args(e, u);
     HIPCHK(e, launch_rescale(ra, B, st));
     HIPCHK(e, launch_rescale_gather(ra, B, d_out, st));
+    return DR_OK;
+}
+
+// dr_debug_project: the statistics launch of a step on the caller's tensors, then the groups' (a, b) gathered into d_out
+int debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
+    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
+    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
+    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
+    DeviceGuard guard(e->cfg.device);
+    if (e->opt.cfg_project == 0 && e->opt.cfg_norm == 0) return fail(e, DR_EINVAL, "dr_debug_project: cfg_project and cfg_norm are both 0 (off)");
+    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
+    int rc, NB;
+    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
+    if ((rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
+    if ((rc = write_windows(e, B, false, st))) return rc;
+    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
+    u.x0c = d_x0c; u.x0u = d_x0u;
+    u.w = w; u.onepw = (float)(1.0 + (double)w);
+    const ProjectArgs pa = project_args(e, u);
+    HIPCHK(e, launch_project(pa, B, st));
+    HIPCHK(e, launch_project_gather(pa, B, d_out, st));
     return DR_OK;
 }
 
@@ -444,6 +473,21 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         e->opt.cfg_rescale = value;
         return DR_OK;
     }
+    if (n == "cfg_project") {      // (stored like "cfg_rescale": nothing is dropped; part of the chain's key)
+        if (value < 0 || value > 10000)
+            return fail(e, DR_EINVAL, "cfg_project is 0 (off) or rho in units of 1 / 10000, 1 .. 10000 (10000 = the whole parallel component), got %d", value);
+        // (the history of "solver_order" 2 holds the prediction as the previous step projected it, as for "x0_clip")
+        if (e->opt.cfg_project != value) e->hist_key.valid = false;
+        e->opt.cfg_project = value;
+        return DR_OK;
+    }
+    if (n == "cfg_norm") {         // (likewise)
+        if (value < 0 || value > 100000)
+            return fail(e, DR_EINVAL, "cfg_norm is 0 (off) or the rms bound r in units of 1 / 10000, 1 .. 100000 (500 = 0.05), got %d", value);
+        if (e->opt.cfg_norm != value) e->hist_key.valid = false;
+        e->opt.cfg_norm = value;
+        return DR_OK;
+    }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
         // (no captured chain is dropped: the effective pair is part of the chain's key - GraphKey - as "draws" is; lo > hi is
         // refused by dr_step / dr_sample, once both values are in)
@@ -504,6 +548,9 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
     if (e->opt.x0_thresh != 0 && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
     // option "cfg_rescale": the work buffer of the statistics launch (the ticket starts at zero: armed), where the sampler guides
     if (e->opt.cfg_rescale != 0 && NB == 2 * B && (rc = grow_chain_buffer(e, e->rescale_work, rescale_work_words(B, T), st))) return rc;
+    // options "cfg_project" / "cfg_norm": likewise
+    if ((e->opt.cfg_project != 0 || e->opt.cfg_norm != 0) && NB == 2 * B &&
+        (rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
     return DR_OK;
 }
 
@@ -547,6 +594,7 @@ GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
     key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
     key.rescale_work = key.opt.cfg_rescale != 0 ? (const unsigned*)e->rescale_work : nullptr;
+    key.project_work = (key.opt.cfg_project != 0 || key.opt.cfg_norm != 0) ? (const unsigned*)e->project_work : nullptr;
     return key;
 }
 

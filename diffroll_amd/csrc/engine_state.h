@@ -89,23 +89,30 @@ struct ChainOptions {
     // rescaled forms where "x0_threshold" is set, then update_rescale_kernel (plan.hip: run_step).  A step that does not
     // guide - another sampler, w = 0, outside the guidance interval - does not read it
     int cfg_rescale = 0;
+    // options "cfg_project" / "cfg_norm": 0 = off; rho = cfg_project / 10000 of the update's component parallel to the
+    // conditional prediction is removed, r = cfg_norm / 10000 bounds the rms of c - u (adaptive projected guidance without
+    // momentum).  A step that guides under either offers no tail plan: the statistics launch (project.hip) behind the head
+    // projections, then update_project_kernel (plan.hip: run_step).  Refused beside "x0_threshold" and "cfg_rescale"
+    // (abi.hip: check_options); a step that does not guide reads neither
+    int cfg_project = 0, cfg_norm = 0;
     bool operator==(const ChainOptions& o) const {
         return steps == o.steps && win_O == o.win_O && win_blend == o.win_blend && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
                guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
-               start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && cfg_rescale == o.cfg_rescale;
+               start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && cfg_rescale == o.cfg_rescale &&
+               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm;
     }
 };
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
-// step the chain visits first (chain_tables.h: start_position); "cfg_rescale" counts only where a step can guide - a sampler
+// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project" and "cfg_norm" count only where a step can guide - a sampler
 // that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, bool w_zero) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
     if (o.win_O <= 0) o.win_blend = 0;
     o.guid = guiding ? dr::GuidanceInterval{o.guid.lo, o.guid.hi_eff(S)} : dr::GuidanceInterval{};
-    if (!guiding || w_zero) o.cfg_rescale = 0;      // (no step of such a chain reads it)
+    if (!guiding || w_zero) o.cfg_rescale = o.cfg_project = o.cfg_norm = 0;      // (no step of such a chain reads them)
     o.start = start_t;
     return o;
 }
@@ -135,10 +142,11 @@ struct GraphKey {
     const float* hist = nullptr;              // the history buffer of solver order 2 (null: order < 2; the parity is baked per node)
     const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
     const unsigned* rescale_work = nullptr;   // ... and the one the statistics launch of "cfg_rescale" points into, likewise
+    const unsigned* project_work = nullptr;   // ... and that of "cfg_project" / "cfg_norm"
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                opt == o.opt && baked == o.baked && tuning == o.tuning && fe_B == o.fe_B && hist == o.hist &&
-               thresh_work == o.thresh_work && rescale_work == o.rescale_work;
+               thresh_work == o.thresh_work && rescale_work == o.rescale_work && project_work == o.project_work;
     }
 };
 using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
@@ -297,6 +305,7 @@ struct dr_engine {
     dr::HistoryKey hist_key;            // dr_step under order 2: what the history holds (chain_tables.h)
     drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
     drh::DevBuf<unsigned> rescale_work; // option "cfg_rescale": its ticket, g records and slots (kernels.h: RescaleArgs), allocated zeroed on first use
+    drh::DevBuf<unsigned> project_work; // options "cfg_project" / "cfg_norm": ticket, (a, b) records and slots (kernels.h: ProjectArgs), allocated zeroed on first use
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
@@ -399,6 +408,7 @@ int build_respaced(dr_engine* e);       // option "sampling_steps": steps and d_
 int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_solver from the chain's steps and h_coef
 int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);      // dr_debug_threshold
 int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);        // dr_debug_rescale
+int debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);        // dr_debug_project
 
 // ---- pack.hip
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);
@@ -442,6 +452,8 @@ UpdateArgs update_base(const dr_engine* e, int B, int T);
 ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u);
 // option "cfg_rescale": the arguments of a step's statistics launch, likewise
 RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u);
+// options "cfg_project" / "cfg_norm": likewise
+ProjectArgs project_args(const dr_engine* e, const UpdateArgs& u);
 struct ChainState {
     bool inproj_ready = false;
     StepEval ready{};          // the shape inproj_ready holds for (TailPlan::primed of the next step)

@@ -332,6 +332,41 @@ hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipS
 // (dr_debug_rescale) out (G) = g of the batch's groups in row / recording order
 hipError_t launch_rescale_gather(const RescaleArgs& a, int B, float* out, hipStream_t s);
 
+// Options "cfg_project" / "cfg_norm" (include/diffroll_amd.h): adaptive projected guidance (Sadat et al. 2024) without its
+// momentum - that part needs a roll-sized state with validity rules like the solver history's and is left to a later change;
+// the combined form with "cfg_rescale" (which would need the spread of y') and with "x0_threshold" (a third text form of
+// threshold.hip) are refused (abi.hip: check_options).  At a step that guides, one pair
+//   a = (float)((1 - s) - s (rho k)),   b = (float)s
+// per GROUP - the group of "x0_threshold" above - turns the guided prediction y into y' = (a c) + (b y), c the conditional
+// prediction (both after the shared-frame mean / blend): the update c - u bounded in rms, its component parallel to c reduced
+// by rho.  The statistics launches (project.hip) leave (a, b) in the record of the group's FIRST row; the update's projecting
+// form reads them from there.
+// The engine's work buffer: [0] the ticket of the grid form (zero between launches), then one record of PROJECT_ROW_WORDS
+// words per row at PROJECT_HEAD + row * PROJECT_ROW_WORDS ([0] a, [1] b), then - grid form - one slot of three doubles
+// {Scc, Scd, Sdd} per (row, block of PROJECT_BLOCK frames), row-major, every slot a launch sums written by that launch.
+constexpr int PROJECT_HEAD = 4, PROJECT_ROW_WORDS = 2, PROJECT_BLOCK = 64;
+inline size_t project_blocks(int T) { return ((size_t)T + PROJECT_BLOCK - 1) / PROJECT_BLOCK; }
+inline size_t project_work_words(int B, int T) { return (size_t)PROJECT_HEAD + (size_t)B * PROJECT_ROW_WORDS + (size_t)B * project_blocks(T) * 6; }
+struct ProjectArgs {
+    UpdateArgs u;          // read: what pred_quad reads (ThreshArgs::u); x0u is set - the step guides
+    int rho;               // "cfg_project", 0 .. 10000
+    int norm;              // "cfg_norm", 0 .. 100000 (0: no bound); one of the two is not 0
+    unsigned* work;        // the buffer above, project_work_words(B, T) words
+};
+// What the update's projecting form needs beside UpdateArgs (the second kernel argument, as ThreshUpd is): (a, b) of row 0's
+// record - row b's is PROJECT_ROW_WORDS floats further per row.  What follows is the clamp UpdateArgs names, or nothing.
+struct ProjectUpd {
+    const float* ab;
+};
+inline const float* project_ab(const unsigned* work) { return reinterpret_cast<const float*>(work + PROJECT_HEAD); }
+// a step's statistics: one launch of one workgroup per roll (clips of at most THRESH_ROLL_MAX elements), or one launch of
+// (blocks, rows) workgroups whose last arriver sums the slots (windows, longer clips)
+hipError_t launch_project(const ProjectArgs& a, int B, hipStream_t s);
+// update_kernel's projecting form (update.hip: update_project_kernel)
+hipError_t launch_update_project(const UpdateArgs& a, const ProjectUpd& pj, hipStream_t s);
+// (dr_debug_project) out (G, 2) = (a, b) of the batch's groups in row / recording order
+hipError_t launch_project_gather(const ProjectArgs& a, int B, float* out, hipStream_t s);
+
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->
 // classifier-free combine + posterior update -> input projection of the next step.  Same grid / grouping as the
 // stack_kernel launch it follows: NB samples (first `dual` conditional, next `dual` unconditional when dual > 0) x

@@ -475,7 +475,9 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // option "cfg_rescale": likewise at a step that guides - the statistics sit between the network and everything that reads
     // the prediction; a step that runs no unconditional evaluation does not read the option and keeps its tail kernel
     const bool rescale = e->opt.cfg_rescale != 0 && u.x0u != nullptr;
-    TailPlan* offer = (result && x != xalt && !thresh && !rescale) ? &plan : nullptr;
+    // options "cfg_project" / "cfg_norm": likewise (check_options has refused them beside "x0_threshold" and "cfg_rescale")
+    const bool project = (e->opt.cfg_project != 0 || e->opt.cfg_norm != 0) && u.x0u != nullptr;
+    TailPlan* offer = (result && x != xalt && !thresh && !rescale && !project) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
@@ -485,6 +487,12 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         return DR_OK;
     }
     if (result) *result = x;
+    if (project) {      // statistics, update on (a c) + (b y)
+        const ProjectArgs pa = project_args(e, u);
+        HIPCHK(e, launch_project(pa, B, st));
+        HIPCHK(e, launch_update_project(u, ProjectUpd{project_ab(pa.work)}, st));
+        return DR_OK;
+    }
     if (rescale) {      // statistics, [threshold launches ranking |g y - m|], update on g y
         const RescaleArgs ra = rescale_args(e, u);
         RescaleUpd rs{rescale_g(ra.work), ThreshUpd{nullptr, 0.f, 0.f}};
@@ -522,6 +530,15 @@ RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u) {
     a.u = u;
     a.phi = e->opt.cfg_rescale;
     a.work = e->rescale_work;
+    return a;
+}
+
+ProjectArgs project_args(const dr_engine* e, const UpdateArgs& u) {
+    ProjectArgs a{};
+    a.u = u;
+    a.rho = e->opt.cfg_project;
+    a.norm = e->opt.cfg_norm;
+    a.work = e->project_work;
     return a;
 }
 

@@ -2,6 +2,7 @@
 // classifier-free combine + Philox noise (task/diffusion.py:804-1055), q_sample / extract_x0 (:31-64), frame confusion
 // counts (:381-383), the roll -> note-run scan (:1185-1233).
 #include "rescale_quad.h"
+#include "project_quad.h"
 
 namespace dr {
 
@@ -30,6 +31,16 @@ __global__ __launch_bounds__(256) void update_rescale_kernel(const UpdateArgs a,
     if (i4 * 4 >= a.n) return;
     float4 y;
     reinterpret_cast<float4*>(a.x)[i4] = update_quad<false, true>(a, i4, &y, nullptr, &rs);
+    if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
+}
+
+// Options "cfg_project" / "cfg_norm": the same update on y' = (a c) + (b y), (a, b) of the quad's group and c the conditional
+// prediction recomputed (project_quad.h), then the clamp of "x0_clip" where UpdateArgs names one.
+__global__ __launch_bounds__(256) void update_project_kernel(const UpdateArgs a, const ProjectUpd pj) {
+    const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i4 * 4 >= a.n) return;
+    float4 y;
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad<false, false, true>(a, i4, &y, nullptr, nullptr, &pj);
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
 }
 
@@ -68,6 +79,13 @@ hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipS
     if (!rs.g) return hipErrorInvalidValue;
     const long n4 = a.n / 4;
     hipLaunchKernelGGL(update_rescale_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a, rs);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_project(const UpdateArgs& a, const ProjectUpd& pj, hipStream_t s) {
+    if (!pj.ab || !a.x0u) return hipErrorInvalidValue;
+    const long n4 = a.n / 4;
+    hipLaunchKernelGGL(update_project_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a, pj);
     return hipGetLastError();
 }
 

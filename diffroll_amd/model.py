@@ -137,7 +137,7 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise AttributeError(sampling.type)                               # getattr at task/diffusion.py:255
         # extensions, absent / None in the reference's configs (each key, its validator and the engine option it becomes:
         # schedule.sampling_options): steps, draws, guidance_interval, solver_order, solver_noise, start_step / strength,
-        # x0_clip, x0_threshold, cfg_rescale
+        # x0_clip, x0_threshold, cfg_rescale, cfg_project, cfg_norm
         sampling_options(sampling, timesteps, norm_args)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
@@ -294,6 +294,14 @@ class ClassifierFreeDiffRoll(nn.Module):
     def cfg_rescale(self) -> int:
         """hparams.sampling.cfg_rescale as the engine's option takes it (0: off, else phi in units of 1 / 10000)."""
         return self.sampling_options()["cfg_rescale"]
+
+    def cfg_project(self) -> int:
+        """hparams.sampling.cfg_project as the engine's option takes it (0: off, else rho in units of 1 / 10000)."""
+        return self.sampling_options()["cfg_project"]
+
+    def cfg_norm(self) -> int:
+        """hparams.sampling.cfg_norm as the engine's option takes it (0: off, else the rms bound r in units of 1 / 10000)."""
+        return self.sampling_options()["cfg_norm"]
 
     def guidance_interval(self):
         """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain."""
@@ -538,6 +546,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         like x_T and diffused to t_s by the chain's first node (z: row 0 of noise, or Philox keyed as the steps' draws with
         step word timesteps + t_s); without a start configured it is diffused to the chain's first step.  Without init and
         with a start configured, x_T is x AT step t_s (resume: a row of sample_trajectory).
+        With hparams.sampling.cfg_project = rho and / or .cfg_norm = r (options "cfg_project" / "cfg_norm": adaptive projected
+        guidance) every step that guides removes the share rho of the guidance update's component parallel to the conditional
+        prediction and bounds the update's rms by r, per roll; not beside x0_threshold or cfg_rescale.
         check=True (default): the call returns with the FINISHED, verified roll, as task/diffusion.py:528-538 does
         (synchronous; a fused-kernel time-out caused by another tenant of the device is healed by re-running the chain
         on the per-phase kernels - Engine.sample).  check=False: asynchronous; call engine.finish() before use."""

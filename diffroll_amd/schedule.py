@@ -251,6 +251,35 @@ def check_cfg_rescale(value, sampler: str = None) -> int:
     return int(round(float(value) * 10000))
 
 
+def _check_projected(name: str, what: str, value, hi: float, sampler, x0_threshold, cfg_rescale) -> int:
+    if value is None or value is False or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0):
+        return 0
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < value <= hi or int(round(float(value) * 10000)) < 1:
+        raise ValueError(f"{name} must be 0 / None (off) or {what} in (0, {hi:g}] in steps of 1 / 10000, got {value!r}")
+    if sampler is not None and sampler not in GUIDING_SAMPLERS:
+        raise ValueError(f"{name} = {value!r} needs a sampler that guides ({', '.join(GUIDING_SAMPLERS)}), not '{sampler}'")
+    for other, theirs in (("x0_threshold", x0_threshold), ("cfg_rescale", cfg_rescale)):
+        if theirs is not None and theirs is not False and theirs != 0:
+            raise ValueError(f"{name} = {value!r} does not combine with {other} = {theirs!r}: set one of them None")
+    return int(round(float(value) * 10000))
+
+
+def check_cfg_project(value, sampler: str = None, x0_threshold=None, cfg_rescale=None) -> int:
+    """Option "cfg_project" (include/diffroll_amd.h) as hparams.sampling.cfg_project: None / 0 / False = off, a float rho with
+    0 < rho <= 1 = the share of the guidance update's component parallel to the conditional prediction that a guided step
+    removes (adaptive projected guidance, Sadat et al. 2024; 1.0 is the paper's eta = 0).  Returns the option's value
+    round(rho * 10000) - 1 .. 10000, or 0 for off; any other value, a set value with a sampler that does not guide, or one
+    beside a set x0_threshold or cfg_rescale raises ValueError."""
+    return _check_projected("cfg_project", "a share rho", value, 1.0, sampler, x0_threshold, cfg_rescale)
+
+
+def check_cfg_norm(value, sampler: str = None, x0_threshold=None, cfg_rescale=None) -> int:
+    """Option "cfg_norm" (include/diffroll_amd.h) as hparams.sampling.cfg_norm: None / 0 / False = off, a float r with
+    0 < r <= 10 = the bound on the per-element rms of the guidance update c - u over the roll at a guided step.  Returns the
+    option's value round(r * 10000) - 1 .. 100000, or 0 for off; refusals as check_cfg_project's."""
+    return _check_projected("cfg_norm", "an rms bound r", value, 10.0, sampler, x0_threshold, cfg_rescale)
+
+
 def respaced_steps(timesteps: int, n: int) -> List[int]:
     """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
     integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""
@@ -280,6 +309,8 @@ def sampling_options(sampling, timesteps, norm_args=(0, 1)) -> Dict[str, object]
         ("x0_clip", "x0_clip", lambda: check_x0_clip(get("x0_clip"), sampler, norm_args)),
         ("x0_threshold", "x0_threshold", lambda: check_x0_threshold(get("x0_threshold"), sampler, get("x0_clip"))),
         ("cfg_rescale", "cfg_rescale", lambda: check_cfg_rescale(get("cfg_rescale"), sampler)),
+        ("cfg_project", "cfg_project", lambda: check_cfg_project(get("cfg_project"), sampler, get("x0_threshold"), get("cfg_rescale"))),
+        ("cfg_norm", "cfg_norm", lambda: check_cfg_norm(get("cfg_norm"), sampler, get("x0_threshold"), get("cfg_rescale"))),
     )
     options = {}
     for option, key, check in checks:

@@ -668,7 +668,71 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          that guides, at w != 0 - and of no other chain's; the chain replays with no host help.  0 = off:
  *                          every path is byte-identical to an engine that never set it.  Nothing is known about quality
  *                          with real weights.
- * Unknown names -> DR_ENAME.  (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
+ *   "cfg_project"      [0] 0, or 1 .. 10000, and
+ *   "cfg_norm"         [0] 0, or 1 .. 100000: ADAPTIVE PROJECTED GUIDANCE of Sadat et al. 2024 ("Eliminating Oversaturation
+ *                          and Artifacts of High Guidance Scales in Diffusion Models"), without its momentum (that part needs
+ *                          a roll-sized state with validity rules like the solver history's; it is not built).  The guided
+ *                          prediction y = (1 + w) c - w u moves the conditional prediction c by w (c - u).  The part of that
+ *                          update parallel to c only scales c up - the saturation "x0_clip", "x0_threshold" and
+ *                          "cfg_rescale" fight afterwards; the orthogonal part carries the conditioning.  rho = cfg_project /
+ *                          10000 is the share of the parallel component that is removed (10000 = APG's eta = 0); r =
+ *                          cfg_norm / 10000 is the bound on the per-element rms of c - u over the group (the rms, not
+ *                          APG's absolute norm: one value means the same for a 125-frame clip and a long canvas).  The
+ *                          projected form runs at a step that guides when either value is not 0.  WHERE IT ACTS: at a
+ *                          reverse step that guides, as "cfg_rescale" defines it - the sampler is
+ *                          DR_SAMPLER_CFDG_DDPM_X0, _INPAINTING_DDPM_X0 or _CFDG_DDIM_X0 and the step runs the
+ *                          unconditional evaluation (inside "guidance_t_min" / "guidance_t_max", w != 0).  With y the
+ *                          guided prediction after the shared-frame mean / blend of "window_overlap" / "window_blend", c
+ *                          the conditional prediction put through the same mean / blend alone and w the step's weight,
+ *                          per GROUP and in double:
+ *                              d_i = (double)y_i - (double)c_i
+ *                              Scc = sum c_i c_i,  Scd = sum c_i d_i,  Sdd = sum d_i d_i,  N = elements of the group
+ *                                  (every product and every addition rounded once, no contraction)
+ *                              k = Scd / Scc,  k = 0.0 when !(Scc > 0)
+ *                              rho = (double)cfg_project / 10000.0
+ *                              s = 1.0;  if cfg_norm != 0: r = (double)cfg_norm / 10000.0,
+ *                                  q = sqrt(Sdd / N) / fabs((double)w),  if (q > r) s = r / q
+ *                              a = (float)((1.0 - s) - s (rho k)),  b = (float)s
+ *                              a = 0.0f, b = 1.0f exactly when a or b is not finite
+ *                              y' = y where a == 0.0f and b == 1.0f (bit for bit)
+ *                              y' = (a c) + (b y) otherwise, fp32, each operation rounded once
+ *                          which is y' = c + s (d - rho k c): the update is bounded and its parallel component reduced
+ *                          by rho.  Everything behind reads y': the clamp of "x0_clip"; both terms of every update; y /
+ *                          c2 of the last step; d and the history p of "solver_order", with or without "solver_noise".
+ *                          THE GROUP is exactly the group of "x0_threshold" / "cfg_rescale": a clip's roll (every draw
+ *                          of "draws" its own); under "window_overlap" the recording's canvas, every canvas frame counted
+ *                          once (a window that is not its recording's first contributes frames [O, T)); "window_break"
+ *                          and draws delimit recordings; a group never spans ranks.  All windows of a recording use the
+ *                          same (a, b) on the same blended values: the frames they share stay bit-identical.  THE ORDER
+ *                          OF THE SUMS is part of the definition and is "cfg_rescale"'s, every level a sequential sum
+ *                          from 0.0:
+ *                              a frame's 88 elements in pitch order;
+ *                              the frames a row counts - all of a clip's, [O, T) of a window that is not its recording's
+ *                              first - in blocks of 64 from its first counted frame, a block's frames in frame order;
+ *                              a group's blocks in row, then block order.
+ *                          a and b are functions of the inputs alone - no floating-point atomic, the same bits on every
+ *                          grid, replay and launch form.  WHERE IT RUNS: the statistics sit between the network and the
+ *                          update, so a guided step under the options does not use the tail kernel: fused stack, head
+ *                          projections, one statistics launch (csrc/project.hip), the update's projecting form;
+ *                          dr_launch_state reports DR_MODE_FUSED_STACK for it (cost: profiles/project_sweep.txt).  A step
+ *                          that does not guide is untouched - no launch is added, it keeps its tail kernel, not a bit
+ *                          changes - and the six samplers that do not guide ignore both options as they ignore the
+ *                          guidance interval.  REFUSED: beside "x0_threshold" (its selection would have to rank the
+ *                          projected prediction) and beside "cfg_rescale" (the two are alternatives; a combined form
+ *                          would need the spread of y') - DR_EINVAL naming both options from dr_sample / dr_step, for every
+ *                          sampler.  A value outside its range -> DR_EINVAL at the set, naming the value.  dr_step follows
+ *                          the rule for its one step; dr_forward, dr_forward_steps, dr_q_sample, dr_extract_x0 and the
+ *                          diffusion of "start_noise" are unaffected; dr_sample_checked's re-run uses the same values.  A
+ *                          change of either value ends a dr_step history of "solver_order" 2, as a change of "x0_clip"
+ *                          does.  Combines with "sampling_steps", "window_overlap" / "window_break" / "window_blend",
+ *                          "draws" / "draw_stride", "guidance_t_min" / "guidance_t_max", "solver_order" / "solver_noise",
+ *                          "start_step" / "start_noise", "x0_clip", all three precisions and sharding.  Stored like
+ *                          "cfg_rescale": setting them drops nothing; the values are part of a captured chain's key
+ *                          where a step of the chain can read them - a sampler that guides, at w != 0 - and of no other
+ *                          chain's; the chain replays with no host help.  Both 0 = off: every path is byte-identical to
+ *                          an engine that never set them.  Nothing is known about quality with real weights
+ *                          (INTEGRATION.md 3c).
+ * Unknown names -> DR_ENAME. (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
 int dr_set_option(dr_engine* e, const char* name, int value);

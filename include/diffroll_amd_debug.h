@@ -110,6 +110,13 @@ int dr_debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int
  * floats: g of each group of the batch, in row / recording order.  The option at 0 -> DR_EINVAL.  Asynchronous on `stream`. */
 int dr_debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, void* stream);
 
+/* Options "cfg_project" / "cfg_norm" on their own: exactly the statistics launch a guided reverse step runs between the
+ * network and the update (csrc/project.hip), on the caller's tensors - d_x0c, d_x0u and w as for dr_debug_threshold (d_x0u
+ * NULL: y = c) - under the engine's current "cfg_project", "cfg_norm", "window_overlap", "window_blend", "window_break" and
+ * "draws".  d_out receives G x 2 floats: (a, b) of each group of the batch, in row / recording order.  Both options at 0 ->
+ * DR_EINVAL, as beside "x0_threshold" or "cfg_rescale".  Asynchronous on `stream`. */
+int dr_debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
