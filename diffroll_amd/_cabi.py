@@ -43,11 +43,12 @@ DEBUG_EXPORTS = [
     "dr_debug_stft_power", "dr_debug_bounds", "dr_debug_tenants", "dr_debug_kfd_root", "dr_debug_set_option", "dr_debug_ticks",
     "dr_stack_status", "dr_cold_times", "dr_profile_enable", "dr_profile_read", "dr_profile_read_ex",
     "dr_bench_layer", "dr_bench_pointwise", "dr_debug_launch_counts", "dr_debug_threshold", "dr_debug_rescale", "dr_debug_project",
+    "dr_debug_momentum",
 ]
 # the options dr_set_option knows; every other name goes to dr_debug_set_option (Engine.set_option)
 PUBLIC_OPTIONS = ("blocked_accumulation", "fused_rearm", "fused_stack", "fused_tail", "window_overlap", "window_break", "window_blend", "sampling_steps", "draws", "draw_stride",
                   "guidance_t_min", "guidance_t_max", "solver_order", "start_step", "start_noise", "solver_noise", "x0_clip", "x0_threshold", "cfg_rescale",
-                  "cfg_project", "cfg_norm")
+                  "cfg_project", "cfg_norm", "cfg_momentum")
 MODES = {0: "none", 1: "per_phase", 2: "fused_stack", 3: "fused_stack+tail"}
 
 
@@ -174,6 +175,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.dr_debug_rescale.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.dr_debug_project.restype = C.c_int
     lib.dr_debug_project.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]
+    lib.dr_debug_momentum.restype = C.c_int
+    lib.dr_debug_momentum.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]
     lib.dr_comm_unique_id.restype = C.c_int
     lib.dr_comm_unique_id.argtypes = [C.c_char_p]
     lib.dr_comm_create.restype = C.c_int

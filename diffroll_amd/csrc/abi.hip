@@ -163,6 +163,7 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
 // options "guidance_t_min" / "guidance_t_max": the samplers that guide need lo <= hi (the others ignore both)
 // options "cfg_project" / "cfg_norm": refused beside "x0_threshold" (whose selection would have to rank the projected
 // prediction) and beside "cfg_rescale" (an alternative; a combined form would need the spread of the projected prediction)
+// option "cfg_momentum": refused while "cfg_project" and "cfg_norm" are both 0 (beside either, the two refusals above cover it)
 int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     const ChainOptions& o = e->opt;
     if (2 * o.win_O > T)
@@ -207,6 +208,9 @@ int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     if ((o.cfg_project != 0 || o.cfg_norm != 0) && o.cfg_rescale != 0)
         return fail(e, DR_EINVAL, "cfg_project = %d / cfg_norm = %d do not combine with cfg_rescale = %d: the two are alternatives; "
                                   "set one of them 0", o.cfg_project, o.cfg_norm, o.cfg_rescale);
+    if (o.cfg_momentum != 0 && o.cfg_project == 0 && o.cfg_norm == 0)
+        return fail(e, DR_EINVAL, "cfg_momentum = %d acts on the update that cfg_project / cfg_norm shape, and cfg_project = %d and "
+                                  "cfg_norm = %d are both off; set one of them, or cfg_momentum 0", o.cfg_momentum, o.cfg_project, o.cfg_norm);
     if (NB == 2 * B && o.guid.empty(e->S))
         return fail(e, DR_EINVAL, "guidance interval is empty: guidance_t_min = %d exceeds guidance_t_max = %d", o.guid.lo,
                     o.guid.hi_eff(e->S));
@@ -344,6 +348,30 @@ int debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, i
     return DR_OK;
 }
 
+// dr_debug_momentum: the statistics launch of a step under "cfg_momentum" on the caller's tensors and state, the groups' (a, b)
+// gathered into d_out, and - where wanted - the state the step would leave
+int debug_momentum(dr_engine* e, const float* d_x0c, const float* d_x0u, const float* d_m_prev, float* d_m_next, int B, int T, float w,
+                   float* d_out, hipStream_t st) {
+    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
+    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
+    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
+    DeviceGuard guard(e->cfg.device);
+    if (e->opt.cfg_momentum == 0) return fail(e, DR_EINVAL, "dr_debug_momentum: cfg_momentum is 0 (off)");
+    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
+    int rc, NB;
+    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
+    if ((rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
+    if ((rc = write_windows(e, B, false, st))) return rc;
+    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
+    u.x0c = d_x0c; u.x0u = d_x0u;
+    u.w = w; u.onepw = (float)(1.0 + (double)w);
+    const MomentumArgs ma{project_args(e, u), d_m_prev, momentum_bf(e)};
+    HIPCHK(e, launch_momentum(ma, B, st));
+    HIPCHK(e, launch_project_gather(ma.p, B, d_out, st));
+    if (d_m_next) HIPCHK(e, launch_momentum_state(u, d_m_prev, ma.bf, d_m_next, st));
+    return DR_OK;
+}
+
 // A setting that captured launches bake in (engine_state.h: dr_engine::baked) takes a new value: a change makes the chain stale
 template <class Field>
 bool put(dr_engine* e, Field& field, int value) {
@@ -376,7 +404,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
             return fail(e, DR_EINVAL, "window_blend is 0 (the mean of the two windows' predictions), 1 (linear cross-fade) or 2 (hand-over "
                                       "at the middle of the overlap), got %d", value);
         // (under "solver_order" 2 the history holds the prediction as the previous step blended it, as for "x0_clip")
-        if (e->opt.win_blend != value) e->hist_key.valid = false;
+        if (e->opt.win_blend != value) end_step_states(e);
         e->opt.win_blend = value;
         return DR_OK;
     }
@@ -392,7 +420,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         // (no captured chain is dropped: the value is part of the chain's key - GraphKey - so a chain captured under
         // another value is simply not replayed, and one captured under this value still is)
         if (value < 1) return fail(e, DR_EINVAL, "draws is >= 1 (1 = every roll its own clip), got %d", value);
-        if (e->opt.draws != value) e->hist_key.valid = false;
+        if (e->opt.draws != value) end_step_states(e);
         e->opt.draws = value;
         return DR_OK;
     }
@@ -418,7 +446,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (e->opt.solver == value) return DR_OK;
         (void)hipDeviceSynchronize();         // a chain of the previous order may still be reading the table
         e->opt.solver = value;
-        e->hist_key.valid = false;
+        end_step_states(e);
         if (!e->committed) return DR_OK;      // (dr_commit builds it)
         return build_solver(e);
     }
@@ -430,7 +458,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (e->opt.solver_noise == value) return DR_OK;
         if (e->opt.solver != 0) (void)hipDeviceSynchronize();      // a chain of the previous value may still be reading the table
         e->opt.solver_noise = value;
-        e->hist_key.valid = false;
+        end_step_states(e);
         if (!e->committed || e->opt.solver == 0) return DR_OK;      // (dr_commit / "solver_order" builds it)
         return build_solver(e);
     }
@@ -453,7 +481,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
             return fail(e, DR_EINVAL, "x0_clip is 0 (off), 1 (clamp the x0 prediction to [0, 1]) or 2 (to [-1, 1]), got %d", value);
         // (under "solver_order" 2 the history holds the prediction as the previous step clamped it: a dr_step sequence does
         // not continue across a change - the next step that is not a chain's first is refused, as for "solver_noise")
-        if (e->opt.x0_clamp != value) e->hist_key.valid = false;
+        if (e->opt.x0_clamp != value) end_step_states(e);
         e->opt.x0_clamp = value;
         return DR_OK;
     }
@@ -461,7 +489,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value != 0 && (value < 5000 || value > 10000))
             return fail(e, DR_EINVAL, "x0_threshold is 0 (off) or the percentile in units of 1 / 10000, 5000 .. 10000 (9950 = 99.5 %%), got %d", value);
         // (the history of "solver_order" 2 holds the prediction as the previous step thresholded it, as for "x0_clip")
-        if (e->opt.x0_thresh != value) e->hist_key.valid = false;
+        if (e->opt.x0_thresh != value) end_step_states(e);
         e->opt.x0_thresh = value;
         return DR_OK;
     }
@@ -469,7 +497,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value < 0 || value > 10000)
             return fail(e, DR_EINVAL, "cfg_rescale is 0 (off) or phi in units of 1 / 10000, 1 .. 10000 (7000 = 0.7), got %d", value);
         // (the history of "solver_order" 2 holds the prediction as the previous step rescaled it, as for "x0_clip")
-        if (e->opt.cfg_rescale != value) e->hist_key.valid = false;
+        if (e->opt.cfg_rescale != value) end_step_states(e);
         e->opt.cfg_rescale = value;
         return DR_OK;
     }
@@ -477,15 +505,22 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value < 0 || value > 10000)
             return fail(e, DR_EINVAL, "cfg_project is 0 (off) or rho in units of 1 / 10000, 1 .. 10000 (10000 = the whole parallel component), got %d", value);
         // (the history of "solver_order" 2 holds the prediction as the previous step projected it, as for "x0_clip")
-        if (e->opt.cfg_project != value) e->hist_key.valid = false;
+        if (e->opt.cfg_project != value) end_step_states(e);
         e->opt.cfg_project = value;
         return DR_OK;
     }
     if (n == "cfg_norm") {         // (likewise)
         if (value < 0 || value > 100000)
             return fail(e, DR_EINVAL, "cfg_norm is 0 (off) or the rms bound r in units of 1 / 10000, 1 .. 100000 (500 = 0.05), got %d", value);
-        if (e->opt.cfg_norm != value) e->hist_key.valid = false;
+        if (e->opt.cfg_norm != value) end_step_states(e);
         e->opt.cfg_norm = value;
+        return DR_OK;
+    }
+    if (n == "cfg_momentum") {     // (likewise; the state dr_step left holds sums under the previous value)
+        if (value < -9999 || value > 9999)
+            return fail(e, DR_EINVAL, "cfg_momentum is 0 (off) or beta in units of 1 / 10000, -9999 .. 9999 (-5000 = -0.5), got %d", value);
+        if (e->opt.cfg_momentum != value) end_step_states(e);
+        e->opt.cfg_momentum = value;
         return DR_OK;
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
@@ -551,6 +586,12 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
     // options "cfg_project" / "cfg_norm": likewise
     if ((e->opt.cfg_project != 0 || e->opt.cfg_norm != 0) && NB == 2 * B &&
         (rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
+    // option "cfg_momentum": the state, one float per roll element (a buffer that grew holds nothing)
+    if (e->opt.cfg_momentum != 0 && NB == 2 * B) {
+        const size_t need = (size_t)B * T * 88;
+        if (!e->momentum.fits(need)) e->mom_key.valid = false;
+        if ((rc = grow_chain_buffer(e, e->momentum, need, st))) return rc;
+    }
     return DR_OK;
 }
 
@@ -595,6 +636,7 @@ GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
     key.rescale_work = key.opt.cfg_rescale != 0 ? (const unsigned*)e->rescale_work : nullptr;
     key.project_work = (key.opt.cfg_project != 0 || key.opt.cfg_norm != 0) ? (const unsigned*)e->project_work : nullptr;
+    key.momentum = key.opt.cfg_momentum != 0 ? (const float*)e->momentum : nullptr;
     return key;
 }
 
@@ -837,6 +879,17 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     int NB, i0;
     int rc = open_chain_call(e, sampler, B, T, &t, NB, i0, (hipStream_t)stream);
     if (rc) return rc;
+    // Both pieces of engine state a step can continue are asked about before either is touched: a refusal changes nothing.
+    // option "cfg_momentum": the state, over the steps that guide (chain_tables.h: momentum_step)
+    const bool momentum = e->opt.cfg_momentum != 0 && NB == 2 * B && step_guided(e->opt.guid, e->S, w == 0.f, t);
+    MomentumVerdict mv{MomentumStep::STARTS, t};
+    if (momentum) {
+        mv = momentum_step(e->mom_key, sampler, B, T, t, e->steps, e->opt.start, e->opt.guid, e->S, w == 0.f);
+        if (mv.what == MomentumStep::REFUSED)
+            return fail(e, DR_ESTATE, "cfg_momentum = %d: dr_step at step %d continues no momentum state - the step expected next is %d "
+                                      "(the chain's first guided step starts a new state; every other guided step follows the guided "
+                                      "step before it)", e->opt.cfg_momentum, t, mv.expect);
+    }
     if (e->opt.solver == 2) {
         // the history is engine state: t starts one or continues the one the previous dr_step left (chain_tables.h: history_step)
         const HistoryVerdict v = history_step(e->hist_key, sampler, B, T, t, e->steps, e->opt.start);
@@ -846,6 +899,10 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
         if (v.what == HistoryStep::STARTS) e->hist_par = 0;
         e->hist_key.valid = false;      // (until the step has been issued)
     }
+    if (momentum) {
+        e->mom_start = mv.what == MomentumStep::STARTS;
+        e->mom_key.valid = false;       // (until the step has been issued)
+    }
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
     if ((rc = write_windows(e, B, false, (hipStream_t)stream))) return rc;
@@ -854,6 +911,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if (res != d_x)      // the fused step wrote x_{t-1} into the engine's buffer: hand it back in place
         HIPCHK(e, hipMemcpyAsync(d_x, res, (size_t)B * T * 88 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (e->opt.solver == 2 && t > 0) { auto& k = e->hist_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
+    if (momentum) { auto& k = e->mom_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
     return DR_OK;
 }
 
@@ -866,6 +924,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     int rc = open_chain_call(e, sampler, B, T, nullptr, NB, i0, st);
     if (rc) return rc;
     e->hist_key.valid = false;      // (a whole chain uses the history buffers: a dr_step sequence does not continue across it)
+    e->mom_key.valid = false;       // (... and the momentum state)
     // (a yield is a precaution, not a verdict: the looks in front of later chains, >= 250 ms apart, may re-arm)
     if (e->fused.may_fuse()) fused_look(e, shared_with_another_process(e));
     FusedTurn turn(e, st);      // (released - event recorded on `st` - when this call returns, behind the chain's launches)

@@ -1,6 +1,6 @@
 // The tables of a reverse chain: the steps it visits (option "sampling_steps"), the coefficient rows derived for them
 // (respaced rows; options "solver_order" / "solver_noise"), the position option "start_step" names, the rule by which a
-// dr_step continues the history of solver order 2, and the per-window words of options "window_break" / "draws".  Every
+// dr_step continues the history of solver order 2 or the state of option "cfg_momentum", and the per-window words of options "window_break" / "draws".  Every
 // one is a pure function of host values; abi.hip uploads what they return and words the refusals.  Host code; plain C++
 // (tests/test_chain_tables_cpu.py compiles it without HIP).
 #pragma once
@@ -154,6 +154,34 @@ inline HistoryVerdict history_step(const HistoryKey& k, int sampler, int B, int 
     const int next = same ? steps.successor(k.t) : -1;
     const int expect = next >= 0 ? next : first;
     return {same && expect == t ? HistoryStep::CONTINUES : HistoryStep::REFUSED, expect};
+}
+
+// dr_step under option "cfg_momentum": what the engine's momentum state holds - m of the guided step t of a (sampler, B, T) chain
+struct MomentumKey { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; };
+// The first step at or below `from` (from < 0: from the chain's first step) that the chain visits and that guides; -1: none.
+// Guiding is launch_plan.h's step_guided: w != 0, inside the guidance interval (the caller has a sampler that guides).
+inline int guided_from(const ChainSteps& steps, int from, const GuidanceInterval& g, int S, bool w_zero) {
+    for (int i = 0, n = steps.count(); i < n; ++i) {
+        const int t = steps.at(i);
+        if ((from < 0 || t <= from) && step_guided(g, S, w_zero, t)) return t;
+    }
+    return -1;
+}
+// The state is engine state with the history's discipline, over the steps that guide alone (a step that does not guide
+// neither reads nor writes it, and is never asked about here): the first guided step of a chain from its start position
+// (option "start_step") starts it; every other guided step continues the one the previous guided dr_step left - it must be
+// the guided visited step behind that one, in a chain of the same (sampler, B, T) - or is refused, with the step expected
+// next (the first guided step where nothing continues).
+enum class MomentumStep { STARTS, CONTINUES, REFUSED };
+struct MomentumVerdict { MomentumStep what; int expect; };
+inline MomentumVerdict momentum_step(const MomentumKey& k, int sampler, int B, int T, int t, const ChainSteps& steps, int start_step,
+                                     const GuidanceInterval& g, int S, bool w_zero) {
+    const int first = guided_from(steps, start_step, g, S, w_zero);
+    if (t == first) return {MomentumStep::STARTS, t};
+    const bool same = k.valid && k.sampler == sampler && k.B == B && k.T == T;
+    const int next = same && k.t > 0 ? guided_from(steps, k.t - 1, g, S, w_zero) : -1;
+    const int expect = next >= 0 ? next : first;
+    return {same && expect == t ? MomentumStep::CONTINUES : MomentumStep::REFUSED, expect};
 }
 
 // one word per window: Philox key offset of its recording (the ordinal in the batch; + draw x stride under option "draws":

@@ -22,6 +22,11 @@ int dr_debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B
     return drh::debug_project(e, d_x0c, d_x0u, B, T, w, d_out, (hipStream_t)stream);
 }
 
+int dr_debug_momentum(dr_engine* e, const float* d_x0c, const float* d_x0u, const float* d_m_prev, float* d_m_next, int B, int T, float w,
+                      float* d_out, void* stream) {
+    return drh::debug_momentum(e, d_x0c, d_x0u, d_m_prev, d_m_next, B, T, w, d_out, (hipStream_t)stream);
+}
+
 int dr_debug_kfd_root(const char* kfd_root) {
     drh::set_kfd_root(kfd_root);
     return DR_OK;

@@ -95,24 +95,28 @@ struct ChainOptions {
     // projections, then update_project_kernel (plan.hip: run_step).  Refused beside "x0_threshold" and "cfg_rescale"
     // (abi.hip: check_options); a step that does not guide reads neither
     int cfg_project = 0, cfg_norm = 0;
+    // option "cfg_momentum": 0 = off; beta = cfg_momentum / 10000, -9999 .. 9999, the momentum of adaptive projected guidance:
+    // a guided step under "cfg_project" / "cfg_norm" runs the statistics in their momentum form and update_momentum_kernel
+    // (momentum.hip) over the engine's state (dr_engine::momentum).  Refused while both partners are 0 (abi.hip: check_options)
+    int cfg_momentum = 0;
     bool operator==(const ChainOptions& o) const {
         return steps == o.steps && win_O == o.win_O && win_blend == o.win_blend && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
                guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
                start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && cfg_rescale == o.cfg_rescale &&
-               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm;
+               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm && cfg_momentum == o.cfg_momentum;
     }
 };
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
-// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project" and "cfg_norm" count only where a step can guide - a sampler
+// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum" count only where a step can guide - a sampler
 // that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, bool w_zero) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
     if (o.win_O <= 0) o.win_blend = 0;
     o.guid = guiding ? dr::GuidanceInterval{o.guid.lo, o.guid.hi_eff(S)} : dr::GuidanceInterval{};
-    if (!guiding || w_zero) o.cfg_rescale = o.cfg_project = o.cfg_norm = 0;      // (no step of such a chain reads them)
+    if (!guiding || w_zero) o.cfg_rescale = o.cfg_project = o.cfg_norm = o.cfg_momentum = 0;      // (no step of such a chain reads them)
     o.start = start_t;
     return o;
 }
@@ -143,10 +147,11 @@ struct GraphKey {
     const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
     const unsigned* rescale_work = nullptr;   // ... and the one the statistics launch of "cfg_rescale" points into, likewise
     const unsigned* project_work = nullptr;   // ... and that of "cfg_project" / "cfg_norm"
+    const float* momentum = nullptr;          // the state of "cfg_momentum" (null: off; "starts" is baked per node)
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                opt == o.opt && baked == o.baked && tuning == o.tuning && fe_B == o.fe_B && hist == o.hist &&
-               thresh_work == o.thresh_work && rescale_work == o.rescale_work && project_work == o.project_work;
+               thresh_work == o.thresh_work && rescale_work == o.rescale_work && project_work == o.project_work && momentum == o.momentum;
     }
 };
 using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
@@ -306,6 +311,12 @@ struct dr_engine {
     drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
     drh::DevBuf<unsigned> rescale_work; // option "cfg_rescale": its ticket, g records and slots (kernels.h: RescaleArgs), allocated zeroed on first use
     drh::DevBuf<unsigned> project_work; // options "cfg_project" / "cfg_norm": ticket, (a, b) records and slots (kernels.h: ProjectArgs), allocated zeroed on first use
+    // option "cfg_momentum": the state m, one float per roll element (B x T x 88), updated in place by update_momentum_kernel.
+    // mom_key: what it holds between dr_steps (chain_tables.h: momentum_step); mom_start: the verdict for the dr_step under
+    // way - its guided step starts the state (run_step reads it where no chain says)
+    drh::DevBuf<float> momentum;
+    dr::MomentumKey mom_key;
+    bool mom_start = true;
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
@@ -398,7 +409,9 @@ struct Range {
 
 // The captured chain is stale and a dr_step history has ended.  Says so and nothing more: the chain stays held - it may
 // still be running - until dr_sample replaces it (CapturedChain::capture waits for it first).
-inline void stale(dr_engine* e) { e->baked += 1; e->hist_key.valid = false; }
+inline void stale(dr_engine* e) { e->baked += 1; e->hist_key.valid = false; e->mom_key.valid = false; }
+// an option that shapes the prediction takes a new value: what dr_step left - the solver history, the momentum state - ends
+inline void end_step_states(dr_engine* e) { e->hist_key.valid = false; e->mom_key.valid = false; }
 
 // ---- abi.hip
 int clear_stack_timeout(dr_engine* e);
@@ -409,6 +422,8 @@ int build_solver(dr_engine* e);         // option "solver_order": h_solver / d_s
 int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);      // dr_debug_threshold
 int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);        // dr_debug_rescale
 int debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st);        // dr_debug_project
+int debug_momentum(dr_engine* e, const float* d_x0c, const float* d_x0u, const float* d_m_prev, float* d_m_next, int B, int T, float w,
+                   float* d_out, hipStream_t st);                                                                                    // dr_debug_momentum
 
 // ---- pack.hip
 const std::vector<float>* find_param(dr_engine* e, const std::string& name);
@@ -454,11 +469,14 @@ ThreshArgs thresh_args(const dr_engine* e, const UpdateArgs& u);
 RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u);
 // options "cfg_project" / "cfg_norm": likewise
 ProjectArgs project_args(const dr_engine* e, const UpdateArgs& u);
+// option "cfg_momentum": bf, the factor the kernels multiply m_prev by
+inline float momentum_bf(const dr_engine* e) { return (float)((double)e->opt.cfg_momentum / 10000.0); }
 struct ChainState {
     bool inproj_ready = false;
     StepEval ready{};          // the shape inproj_ready holds for (TailPlan::primed of the next step)
     int next_t = -1;
     float* x_out = nullptr;    // where a fused step writes x_{t-1} (null: e->xalt)
+    bool guided = false;       // option "cfg_momentum": a guided step has run in this chain (the next one continues the state)
 };
 int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int T, int t, float w, uint64_t seed,
              int first_sample, hipStream_t st, float** result = nullptr, ChainState* chain = nullptr);

@@ -333,7 +333,7 @@ hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipS
 hipError_t launch_rescale_gather(const RescaleArgs& a, int B, float* out, hipStream_t s);
 
 // Options "cfg_project" / "cfg_norm" (include/diffroll_amd.h): adaptive projected guidance (Sadat et al. 2024) without its
-// momentum - that part needs a roll-sized state with validity rules like the solver history's and is left to a later change;
+// momentum - that part needs a roll-sized state with validity rules like the solver history's and is option "cfg_momentum" below;
 // the combined form with "cfg_rescale" (which would need the spread of y') and with "x0_threshold" (a third text form of
 // threshold.hip) are refused (abi.hip: check_options).  At a step that guides, one pair
 //   a = (float)((1 - s) - s (rho k)),   b = (float)s
@@ -366,6 +366,34 @@ hipError_t launch_project(const ProjectArgs& a, int B, hipStream_t s);
 hipError_t launch_update_project(const UpdateArgs& a, const ProjectUpd& pj, hipStream_t s);
 // (dr_debug_project) out (G, 2) = (a, b) of the batch's groups in row / recording order
 hipError_t launch_project_gather(const ProjectArgs& a, int B, float* out, hipStream_t s);
+
+// Option "cfg_momentum" (include/diffroll_amd.h): the momentum of adaptive projected guidance - the third part of the method,
+// beside "cfg_project" / "cfg_norm".  At a step that guides, per element and in fp32 (each operation rounded once),
+//   d = y - c,   m = d at the step that STARTS the state, else m = d + (bf * m_prev),   yb = c + m
+// and everything the two options above define happens with yb in place of y.  m is the engine's state: one float per roll
+// element (the layout of the roll, B x T x 88), updated IN PLACE by the update - an element's thread is its word's only
+// reader and writer; neighbouring windows read each other's predictions, never each other's state (a frame two windows
+// share holds the same m in both rows: d is bit-identical there).  The statistics launch reads m_prev and forms m and yb on
+// the fly (momentum.hip: the two launch forms, slots and ticket of project.hip, on the same work buffer - a step runs one of
+// the two); "starts" is a fact of the step, baked per node in a captured chain (chain_tables.h: momentum_step for dr_step).
+struct MomentumArgs {
+    ProjectArgs p;         // what the statistics of "cfg_project" / "cfg_norm" read and write
+    const float* m_prev;   // the state the step reads; null: the step STARTS the state (nothing is read)
+    float bf;              // (float)((double)cfg_momentum / 10000.0)
+};
+// What the update's momentum form needs beside UpdateArgs (its second kernel argument, in ProjectUpd's place)
+struct MomentumUpd {
+    const float* ab;       // ProjectUpd::ab
+    float* m;              // the state: read unless `start`, then written, by the element's own thread
+    float bf;
+    int start;             // 1: the step starts the state
+};
+// a step's statistics in their momentum form: launch_project's two forms over yb
+hipError_t launch_momentum(const MomentumArgs& a, int B, hipStream_t s);
+// update_kernel's momentum form (momentum.hip: update_momentum_kernel)
+hipError_t launch_update_momentum(const UpdateArgs& a, const MomentumUpd& mo, hipStream_t s);
+// (dr_debug_momentum) m_next = m of every element, by the device function the update uses; m_prev null: starts
+hipError_t launch_momentum_state(const UpdateArgs& a, const float* m_prev, float bf, float* m_next, hipStream_t s);
 
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->
 // classifier-free combine + posterior update -> input projection of the next step.  Same grid / grouping as the

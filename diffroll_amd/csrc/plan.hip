@@ -489,6 +489,17 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     if (result) *result = x;
     if (project) {      // statistics, update on (a c) + (b y)
         const ProjectArgs pa = project_args(e, u);
+        if (e->opt.cfg_momentum != 0) {
+            // option "cfg_momentum": the same two launches in their momentum form, over the engine's state.  Whether this
+            // step starts the state is a fact of the chain - its first guided step - or dr_step's verdict; a captured chain
+            // bakes it into the node
+            const bool start = chain ? !chain->guided : e->mom_start;
+            if (chain) chain->guided = true;
+            float* const m = e->momentum;
+            HIPCHK(e, launch_momentum(MomentumArgs{pa, start ? nullptr : m, momentum_bf(e)}, B, st));
+            HIPCHK(e, launch_update_momentum(u, MomentumUpd{project_ab(pa.work), m, momentum_bf(e), start ? 1 : 0}, st));
+            return DR_OK;
+        }
         HIPCHK(e, launch_project(pa, B, st));
         HIPCHK(e, launch_update_project(u, ProjectUpd{project_ab(pa.work)}, st));
         return DR_OK;

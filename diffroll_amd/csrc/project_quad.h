@@ -1,8 +1,9 @@
 // Options "cfg_project" / "cfg_norm" (include/diffroll_amd.h), the per-quad pieces of adaptive projected guidance (Sadat et al.
 // 2024): a frame's three sums, a group's coefficients (a, b) from its sums, and what the update applies - shared by
 // project.hip and update_project_kernel (update.hip).
-// Not here: APG's momentum - it needs a roll-sized state with validity rules like the solver history's - and the combined
-// forms with "cfg_rescale" (which would need the spread of y') and "x0_threshold"; both combinations are refused.
+// Not here: APG's momentum - it needs a roll-sized state with validity rules like the solver history's and is option
+// "cfg_momentum", momentum_quad.h - and the combined forms with "cfg_rescale" (which would need the spread of y') and
+// "x0_threshold"; both combinations are refused.
 #pragma once
 #include "threshold_quad.h"
 

@@ -165,6 +165,9 @@ DR_DEVINL void rescaled_quad(const UpdateArgs& a, const RescaleUpd& rs, const lo
 // quad's group and c the conditional prediction, then the clamp where UpdateArgs names one - defined in project_quad.h,
 // included likewise.
 DR_DEVINL void projected_quad(const UpdateArgs& a, const ProjectUpd& pj, const long i4, float (&y)[4]);
+// Option "cfg_momentum": what the update's momentum form does there - m = d + (bf * m_prev) of d = y - c, stored in place,
+// then the projecting form's y' over yb = c + m and the clamp - defined in momentum_quad.h, included likewise.
+DR_DEVINL void momentum_update_quad(const UpdateArgs& a, const MomentumUpd& mo, const long i4, float (&y)[4]);
 
 // Option "window_blend" (win_blend() of UpdateArgs::win): what a frame shared by windows b and b + 1 takes of the two guided predictions
 // lo (window b's, its frame H + j) and up (window b + 1's, its frame j), j = 0 .. O - 1 the position within the overlap:
@@ -194,10 +197,11 @@ DR_DEVINL void blend_quad(const int mode, const int j, const int O, const float 
 // option "x0_clip" (mode 5's history).  TH: update_kernel's thresholding form (option "x0_threshold"; th is set) - the
 // tail kernel instantiates TH = false, the text it always had.  RS: update_kernel's rescaling form (option "cfg_rescale"; rs
 // is set, th is not read): rescaled_quad in that place.  PJ: update_kernel's projecting form (options "cfg_project" /
-// "cfg_norm"; pj is set, th and rs are not read): projected_quad in that place.
-template <bool TH = false, bool RS = false, bool PJ = false>
+// "cfg_norm"; pj is set, th and rs are not read): projected_quad in that place.  MO: its momentum form (option "cfg_momentum";
+// mo is set, nothing else is read): momentum_update_quad in that place.
+template <bool TH = false, bool RS = false, bool PJ = false, bool MO = false>
 DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr, const ThreshUpd* th = nullptr,
-                             const RescaleUpd* rs = nullptr, const ProjectUpd* pj = nullptr) {
+                             const RescaleUpd* rs = nullptr, const ProjectUpd* pj = nullptr, const MomentumUpd* mo = nullptr) {
 #pragma clang fp contract(off)
     float x0[4];
     // per-call scalars: by value (eager launches) or from the device block (captured chain)
@@ -235,7 +239,8 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         }
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
-    if constexpr (PJ) projected_quad(a, *pj, i4, x0);
+    if constexpr (MO) momentum_update_quad(a, *mo, i4, x0);
+    else if constexpr (PJ) projected_quad(a, *pj, i4, x0);
     else if constexpr (RS) rescaled_quad(a, *rs, i4, x0);
     else if constexpr (TH) thresh_quad(a, *th, i4, x0);
     else {

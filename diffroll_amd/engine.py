@@ -55,6 +55,7 @@ _MIRRORED = {
     "cfg_rescale": 0,            # 1 .. 10000 = phi (1 / 10000) of the guidance rescale at the steps that guide
     "cfg_project": 0,            # 1 .. 10000 = rho (1 / 10000): the share of the guidance update parallel to c that is removed
     "cfg_norm": 0,               # 1 .. 100000 = r (1 / 10000): the bound on the rms of the guidance update c - u
+    "cfg_momentum": 0,           # -9999 .. 9999 = beta (1 / 10000): the momentum of the guidance update, beside the two above
     "blocked_accumulation": 2,   # 2 = every fp32 flavour that has a blocked form, 1 = single chain on 128-frame blocks
 }
 
@@ -362,7 +363,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'window_blend', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'window_blend', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'cfg_momentum' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -379,7 +380,7 @@ class Engine:
     def holding(self, **options):
         """Options held for one call and put back afterwards, also when the call raises: mirrored option names, and
         window_breaks = the marks.  An option that already has the value is not set at all - 'sampling_steps' would drop the
-        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'window_blend' and the marks never do (they are part of its key or plain data), so a loop of
+        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'cfg_momentum', 'window_blend' and the marks never do (they are part of its key or plain data), so a loop of
         such calls replays one graph, and putting them back behind an asynchronous call touches nothing in flight."""
         def put(name, value):
             if name == "window_breaks":
@@ -454,6 +455,24 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.dr_debug_project(self.h, c.data_ptr(), _ptr(u), B, T, float(w), out.data_ptr(), self._stream()))
         return out if groups is None else out[:int(groups)]
+
+    def momentum_stats(self, x0c: torch.Tensor, x0u: Optional[torch.Tensor] = None, m_prev: Optional[torch.Tensor] = None, w: float = 0.0,
+                       groups: Optional[int] = None, want_state: bool = True):
+        """Diagnostic (dr_debug_momentum): the statistics launch of a guided step under option 'cfg_momentum' on the predictions
+        x0c / x0u (B, T, 88) combined with weight w and the state m_prev (B, T, 88; None: the step starts the state) ->
+        ((groups, 2) the coefficients (a, b) per group over yb = c + m, in row / recording order, and m (B, T, 88), the state the
+        step leaves - None unless want_state)."""
+        c = self._dev(x0c)
+        u = None if x0u is None else self._dev(x0u)
+        mp = None if m_prev is None else self._dev(m_prev)
+        B, T, K = c.shape
+        assert K == 88 and (u is None or u.shape == c.shape) and (mp is None or mp.shape == c.shape)
+        out = torch.zeros(B, 2, device=self.device, dtype=torch.float32)      # (never more groups than rows)
+        m = torch.empty_like(c) if want_state else None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.dr_debug_momentum(self.h, c.data_ptr(), _ptr(u), _ptr(mp), _ptr(m), B, T, float(w), out.data_ptr(),
+                                                   self._stream()))
+        return (out if groups is None else out[:int(groups)]), m
 
     def set_window_breaks(self, marks):
         """Replace the marks of option 'window_break' (the windows of the next batch that start a new recording)."""

@@ -280,6 +280,26 @@ def check_cfg_norm(value, sampler: str = None, x0_threshold=None, cfg_rescale=No
     return _check_projected("cfg_norm", "an rms bound r", value, 10.0, sampler, x0_threshold, cfg_rescale)
 
 
+def check_cfg_momentum(value, sampler: str = None, cfg_project=None, cfg_norm=None) -> int:
+    """Option "cfg_momentum" (include/diffroll_amd.h) as hparams.sampling.cfg_momentum: None / 0 / False = off, a float beta with
+    0 < |beta| < 1 = the momentum of adaptive projected guidance (Sadat et al. 2024; the paper's values are -0.5 .. -0.75): a
+    guided step's update becomes d + beta m_prev.  Returns the option's value round(beta * 10000) - -9999 .. 9999, or 0 for
+    off; any other value (a beta that rounds to 0 or to +-1 included), a set value with a sampler that does not guide, or one
+    beside neither cfg_project nor cfg_norm raises ValueError.  (Beside x0_threshold or cfg_rescale those two are refused.)"""
+    if value is None or value is False or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0):
+        return 0
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < abs(value) < 1.0 or \
+            not 1 <= abs(int(round(float(value) * 10000))) <= 9999:
+        raise ValueError(f"cfg_momentum must be 0 / None (off) or a momentum beta with 0 < |beta| < 1 in steps of 1 / 10000 (-0.5 = the "
+                         f"paper's value), got {value!r}")
+    if sampler is not None and sampler not in GUIDING_SAMPLERS:
+        raise ValueError(f"cfg_momentum = {value!r} needs a sampler that guides ({', '.join(GUIDING_SAMPLERS)}), not '{sampler}'")
+    if all(v is None or v is False or v == 0 for v in (cfg_project, cfg_norm)):
+        raise ValueError(f"cfg_momentum = {value!r} needs cfg_project or cfg_norm: it acts on the update those two shape, and "
+                         f"cfg_project = {cfg_project!r} and cfg_norm = {cfg_norm!r} are both off")
+    return int(round(float(value) * 10000))
+
+
 def respaced_steps(timesteps: int, n: int) -> List[int]:
     """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
     integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""
@@ -311,6 +331,7 @@ def sampling_options(sampling, timesteps, norm_args=(0, 1)) -> Dict[str, object]
         ("cfg_rescale", "cfg_rescale", lambda: check_cfg_rescale(get("cfg_rescale"), sampler)),
         ("cfg_project", "cfg_project", lambda: check_cfg_project(get("cfg_project"), sampler, get("x0_threshold"), get("cfg_rescale"))),
         ("cfg_norm", "cfg_norm", lambda: check_cfg_norm(get("cfg_norm"), sampler, get("x0_threshold"), get("cfg_rescale"))),
+        ("cfg_momentum", "cfg_momentum", lambda: check_cfg_momentum(get("cfg_momentum"), sampler, get("cfg_project"), get("cfg_norm"))),
     )
     options = {}
     for option, key, check in checks:

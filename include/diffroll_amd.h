@@ -670,8 +670,9 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          with real weights.
  *   "cfg_project"      [0] 0, or 1 .. 10000, and
  *   "cfg_norm"         [0] 0, or 1 .. 100000: ADAPTIVE PROJECTED GUIDANCE of Sadat et al. 2024 ("Eliminating Oversaturation
- *                          and Artifacts of High Guidance Scales in Diffusion Models"), without its momentum (that part needs
- *                          a roll-sized state with validity rules like the solver history's; it is not built).  The guided
+ *                          and Artifacts of High Guidance Scales in Diffusion Models"), without its momentum, which is option
+ *                          "cfg_momentum" below (that part needs a roll-sized state with validity rules like the solver
+ *                          history's).  The guided
  *                          prediction y = (1 + w) c - w u moves the conditional prediction c by w (c - u).  The part of that
  *                          update parallel to c only scales c up - the saturation "x0_clip", "x0_threshold" and
  *                          "cfg_rescale" fight afterwards; the orthogonal part carries the conditioning.  rho = cfg_project /
@@ -732,6 +733,45 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          chain's; the chain replays with no host help.  Both 0 = off: every path is byte-identical to
  *                          an engine that never set them.  Nothing is known about quality with real weights
  *                          (INTEGRATION.md 3c).
+ *   "cfg_momentum"     [0] 0, or -9999 .. 9999 except 0: THE MOMENTUM of adaptive projected guidance (Sadat et al. 2024), the
+ *                          third part of the method beside "cfg_project" / "cfg_norm": beta = cfg_momentum / 10000 (the paper's values are -0.5
+ *                          .. -0.75, i.e. -5000 .. -7500).  A reverse momentum (beta < 0) keeps the guidance update from
+ *                          accumulating in one direction from step to step; the projection and the norm bound treat one
+ *                          step at a time.  WHERE IT ACTS: at a step that guides, as "cfg_project" defines it, and only
+ *                          beside "cfg_project" and / or "cfg_norm".  With y the guided prediction and c the conditional
+ *                          one, both after the shared-frame mean / blend, per element, in fp32, no contraction, each
+ *                          operation rounded once:
+ *                              bf = (float)((double)cfg_momentum / 10000.0)
+ *                              d  = y - c
+ *                              m  = d                  at the step that STARTS the state (nothing is read)
+ *                              m  = d + (bf * m_prev)  at every other guided step
+ *                              yb = c + m
+ *                          and everything "cfg_project" / "cfg_norm" define happens with yb in place of y: the three sums
+ *                          use d_i = (double)yb_i - (double)c_i in the same fixed order, (a, b) and its |w| are unchanged, y'
+ *                          = (a c) + (b yb), y' = yb where a == 0.0f and b == 1.0f, then the clamp of "x0_clip".  m is what
+ *                          the next guided step reads as m_prev.  A non-finite m stays non-finite for that element for the
+ *                          rest of the chain; its group then gets a = 0.0f, b = 1.0f, as under "cfg_project".  THE STATE is
+ *                          one float per roll element, engine memory, updated in place; a frame two windows share holds
+ *                          the same m in both rows (d is bit-identical there), and each rank holds the state of its rows.
+ *                          WHICH STEP STARTS IT: the first guided step a chain runs - from the chain's start position
+ *                          ("start_step"), the highest visited step that guides (a sampler that guides, w != 0, inside
+ *                          "guidance_t_min" / "guidance_t_max").  Steps that do not guide neither read nor write the state;
+ *                          a guided step after a gap continues from the last guided one.  A captured chain bakes "starts"
+ *                          into the step's nodes: no memset, no host help, every replay restarts by itself.  WHERE IT RUNS:
+ *                          the launches of a guided step under "cfg_project" in their momentum form (csrc/momentum.hip) -
+ *                          fused stack, head projections, one statistics launch that reads the state, the update that
+ *                          advances it; dr_launch_state reports DR_MODE_FUSED_STACK.  dr_step: the state is engine state
+ *                          with the discipline of the history of "solver_order" 2 - a guided dr_step starts it (the first
+ *                          guided step) or continues the previous guided dr_step of the same (sampler, B, T), which must be
+ *                          the guided visited step before it; otherwise DR_ESTATE naming the step expected next.  The state
+ *                          ends on dr_sample, dr_frontend with another shape, growth of the state, every option change that
+ *                          ends a solver history, and a change of "cfg_momentum" itself.  REFUSED: a value that is not 0
+ *                          while "cfg_project" and "cfg_norm" are both 0 - DR_EINVAL naming the three options from dr_sample /
+ *                          dr_step; beside "x0_threshold" / "cfg_rescale" the refusals of "cfg_project" hold.  A value out of
+ *                          range -> DR_EINVAL at the set, stating the range.  Combines with everything "cfg_project"
+ *                          combines with.  Stored like "cfg_project": the value is part of a captured chain's key where a
+ *                          step can read it.  0 = off: every path is byte-identical to an engine that never set it.
+ *                          Nothing is known about quality with real weights.
  * Unknown names -> DR_ENAME. (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */

@@ -117,6 +117,15 @@ int dr_debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B
  * DR_EINVAL, as beside "x0_threshold" or "cfg_rescale".  Asynchronous on `stream`. */
 int dr_debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, void* stream);
 
+/* Option "cfg_momentum" on its own: exactly the statistics launch a guided reverse step runs under the option
+ * (csrc/momentum.hip), on the caller's tensors - d_x0c, d_x0u and w as for dr_debug_project - and the caller's state: d_m_prev
+ * (B, T, 88) is the state the step reads, NULL = the step starts the state.  d_out receives G x 2 floats, (a, b) of each group
+ * over yb = c + m.  d_m_next, unless NULL, receives m (B, T, 88) - what the step leaves as state - through the device function
+ * the update uses; it may not alias d_m_prev.  Under the engine's current "cfg_momentum", "cfg_project", "cfg_norm" and window
+ * options; "cfg_momentum" at 0 -> DR_EINVAL, as beside two partners at 0.  Asynchronous on `stream`. */
+int dr_debug_momentum(dr_engine* e, const float* d_x0c, const float* d_x0u, const float* d_m_prev, float* d_m_next, int B, int T, float w,
+                      float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
