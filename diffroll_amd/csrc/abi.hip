@@ -316,14 +316,14 @@ int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, i
     if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
     int rc, NB;
     if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->rescale_work, rescale_work_words(B, T), st))) return rc;
+    if ((rc = grow_chain_buffer(e, e->rescale_work, gs_work_words(B, T, RESCALE_SUMS), st))) return rc;
     if ((rc = write_windows(e, B, false, st))) return rc;
     UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
     u.x0c = d_x0c; u.x0u = d_x0u;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     const RescaleArgs ra = rescale_args(e, u);
     HIPCHK(e, launch_rescale(ra, B, st));
-    HIPCHK(e, launch_rescale_gather(ra, B, d_out, st));
+    HIPCHK(e, launch_group_gather(ra.u, ra.work, 1, B, d_out, st));
     return DR_OK;
 }
 
@@ -337,14 +337,14 @@ int debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, i
     if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
     int rc, NB;
     if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
+    if ((rc = grow_chain_buffer(e, e->project_work, gs_work_words(B, T, PROJECT_SUMS), st))) return rc;
     if ((rc = write_windows(e, B, false, st))) return rc;
     UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
     u.x0c = d_x0c; u.x0u = d_x0u;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     const ProjectArgs pa = project_args(e, u);
     HIPCHK(e, launch_project(pa, B, st));
-    HIPCHK(e, launch_project_gather(pa, B, d_out, st));
+    HIPCHK(e, launch_group_gather(pa.u, pa.work, 2, B, d_out, st));
     return DR_OK;
 }
 
@@ -360,14 +360,14 @@ int debug_momentum(dr_engine* e, const float* d_x0c, const float* d_x0u, const f
     if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
     int rc, NB;
     if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
+    if ((rc = grow_chain_buffer(e, e->project_work, gs_work_words(B, T, PROJECT_SUMS), st))) return rc;
     if ((rc = write_windows(e, B, false, st))) return rc;
     UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
     u.x0c = d_x0c; u.x0u = d_x0u;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
     const MomentumArgs ma{project_args(e, u), d_m_prev, momentum_bf(e)};
     HIPCHK(e, launch_momentum(ma, B, st));
-    HIPCHK(e, launch_project_gather(ma.p, B, d_out, st));
+    HIPCHK(e, launch_group_gather(ma.p.u, ma.p.work, 2, B, d_out, st));
     if (d_m_next) HIPCHK(e, launch_momentum_state(u, d_m_prev, ma.bf, d_m_next, st));
     return DR_OK;
 }
@@ -582,10 +582,10 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
     // option "x0_threshold": the work buffer of the threshold launches (tickets and counts start at zero: armed)
     if (e->opt.x0_thresh != 0 && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
     // option "cfg_rescale": the work buffer of the statistics launch (the ticket starts at zero: armed), where the sampler guides
-    if (e->opt.cfg_rescale != 0 && NB == 2 * B && (rc = grow_chain_buffer(e, e->rescale_work, rescale_work_words(B, T), st))) return rc;
+    if (e->opt.cfg_rescale != 0 && NB == 2 * B && (rc = grow_chain_buffer(e, e->rescale_work, gs_work_words(B, T, RESCALE_SUMS), st))) return rc;
     // options "cfg_project" / "cfg_norm": likewise
     if ((e->opt.cfg_project != 0 || e->opt.cfg_norm != 0) && NB == 2 * B &&
-        (rc = grow_chain_buffer(e, e->project_work, project_work_words(B, T), st))) return rc;
+        (rc = grow_chain_buffer(e, e->project_work, gs_work_words(B, T, PROJECT_SUMS), st))) return rc;
     // option "cfg_momentum": the state, one float per roll element (a buffer that grew holds nothing)
     if (e->opt.cfg_momentum != 0 && NB == 2 * B) {
         const size_t need = (size_t)B * T * 88;

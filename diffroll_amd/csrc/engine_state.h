@@ -309,8 +309,8 @@ struct dr_engine {
     int hist_par = 0;
     dr::HistoryKey hist_key;            // dr_step under order 2: what the history holds (chain_tables.h)
     drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
-    drh::DevBuf<unsigned> rescale_work; // option "cfg_rescale": its ticket, g records and slots (kernels.h: RescaleArgs), allocated zeroed on first use
-    drh::DevBuf<unsigned> project_work; // options "cfg_project" / "cfg_norm": ticket, (a, b) records and slots (kernels.h: ProjectArgs), allocated zeroed on first use
+    drh::DevBuf<unsigned> rescale_work; // option "cfg_rescale": the work buffer of its statistics launch (kernels.h: GS_HEAD has the layout), allocated zeroed on first use
+    drh::DevBuf<unsigned> project_work; // options "cfg_project" / "cfg_norm" / "cfg_momentum": theirs, likewise
     // option "cfg_momentum": the state m, one float per roll element (B x T x 88), updated in place by update_momentum_kernel.
     // mom_key: what it holds between dr_steps (chain_tables.h: momentum_step); mom_start: the verdict for the dr_step under
     // way - its guided step starts the state (run_step reads it where no chain says)

@@ -298,30 +298,40 @@ hipError_t launch_update_thresh(const UpdateArgs& a, const ThreshUpd& th, hipStr
 // (dr_debug_threshold) out (G, 2) = {q, s} of the batch's groups in row / recording order
 hipError_t launch_thresh_gather(const ThreshArgs& a, int B, float* out, hipStream_t s);
 
+// The work buffer of a statistics launch over the GROUPS above ("cfg_rescale", "cfg_project" / "cfg_norm", "cfg_momentum";
+// group_sums.h has the launch) - one layout, stated here alone:
+//   [0] the ticket of the grid form (zero between launches);
+//   then one record of GS_ROW_WORDS words per row of the batch at GS_HEAD + row * GS_ROW_WORDS - a group's result, in the
+//   record of its FIRST row;
+//   then - grid form - one slot of K doubles per (row, block of GS_BLOCK frames), row-major: the block's K sums.  Every slot
+//   a launch adds up was written by that launch: the slots need no re-arming, and one buffer serves every batch that fits.
+constexpr int GS_HEAD = 4, GS_ROW_WORDS = 2, GS_BLOCK = 64;
+inline size_t gs_blocks(int T) { return ((size_t)T + GS_BLOCK - 1) / GS_BLOCK; }
+inline size_t gs_work_words(int B, int T, int K) { return (size_t)GS_HEAD + (size_t)B * GS_ROW_WORDS + (size_t)B * gs_blocks(T) * K * 2; }
+inline const float* gs_records(const unsigned* work) { return reinterpret_cast<const float*>(work + GS_HEAD); }
+// (dr_debug_rescale / dr_debug_project / dr_debug_momentum) out (G, words) = the first `words` words of the records of the
+// batch's groups, in row / recording order; u = the Args' UpdateArgs, work = their buffer
+hipError_t launch_group_gather(const UpdateArgs& u, const unsigned* work, int words, int B, float* out, hipStream_t s);
+
 // Option "cfg_rescale" (include/diffroll_amd.h): the guidance rescale of Lin et al. 2024.  At a step that guides, one factor
 //   g = (float)(1 + phi (sqrt(Vc / Vy) - 1))
 // per GROUP - the group of "x0_threshold" above - scales the guided prediction y towards the spread of the conditional
 // prediction c (both after the shared-frame mean / blend); the update consumes g y.  The statistics launches (rescale.hip)
 // leave g in the record of the group's FIRST row; the update's rescaling form reads it from there.
-// The engine's work buffer: [0] the ticket of the grid form (zero between launches), then one record of RESCALE_ROW_WORDS
-// words per row at RESCALE_HEAD + row * RESCALE_ROW_WORDS ([0] g), then - grid form - one slot of four doubles
-// {S1c, S2c, S1y, S2y} per (row, block of RESCALE_BLOCK frames), row-major, every slot a launch sums written by that launch.
-constexpr int RESCALE_HEAD = 4, RESCALE_ROW_WORDS = 2, RESCALE_BLOCK = 64;
-inline size_t rescale_blocks(int T) { return ((size_t)T + RESCALE_BLOCK - 1) / RESCALE_BLOCK; }
-inline size_t rescale_work_words(int B, int T) { return (size_t)RESCALE_HEAD + (size_t)B * RESCALE_ROW_WORDS + (size_t)B * rescale_blocks(T) * 8; }
+// The engine's work buffer is the one above: a record is [0] g, a slot the four doubles {S1c, S2c, S1y, S2y}.
+constexpr int RESCALE_SUMS = 4;
 struct RescaleArgs {
     UpdateArgs u;          // read: what pred_quad reads (ThreshArgs::u); x0u is set - the step guides
     int phi;               // the option's value, 1 .. 10000
-    unsigned* work;        // the buffer above, rescale_work_words(B, T) words
+    unsigned* work;        // the buffer above, gs_work_words(B, T, RESCALE_SUMS) words
 };
 // What the update's rescaling form needs beside UpdateArgs (the second kernel argument, as ThreshUpd is): g of row 0's
-// record - row b's is RESCALE_ROW_WORDS floats further per row - and what follows the product: th.qs set = the thresholding
-// of "x0_threshold" with th, else the clamp UpdateArgs names, or nothing.
+// record (gs_records) - row b's is GS_ROW_WORDS floats further per row - and what follows the product: th.qs set = the
+// thresholding of "x0_threshold" with th, else the clamp UpdateArgs names, or nothing.
 struct RescaleUpd {
     const float* g;
     ThreshUpd th;
 };
-inline const float* rescale_g(const unsigned* work) { return reinterpret_cast<const float*>(work + RESCALE_HEAD); }
 // a step's statistics: one launch of one workgroup per roll (clips of at most THRESH_ROLL_MAX elements), or one launch of
 // (blocks, rows) workgroups whose last arriver sums the slots (windows, longer clips)
 hipError_t launch_rescale(const RescaleArgs& a, int B, hipStream_t s);
@@ -329,8 +339,6 @@ hipError_t launch_rescale(const RescaleArgs& a, int B, hipStream_t s);
 hipError_t launch_threshold_rescaled(ThreshArgs a, const float* g, int B, hipStream_t s);
 // update_kernel's rescaling form (update.hip: update_rescale_kernel)
 hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipStream_t s);
-// (dr_debug_rescale) out (G) = g of the batch's groups in row / recording order
-hipError_t launch_rescale_gather(const RescaleArgs& a, int B, float* out, hipStream_t s);
 
 // Options "cfg_project" / "cfg_norm" (include/diffroll_amd.h): adaptive projected guidance (Sadat et al. 2024) without its
 // momentum - that part needs a roll-sized state with validity rules like the solver history's and is option "cfg_momentum" below;
@@ -341,31 +349,24 @@ hipError_t launch_rescale_gather(const RescaleArgs& a, int B, float* out, hipStr
 // prediction (both after the shared-frame mean / blend): the update c - u bounded in rms, its component parallel to c reduced
 // by rho.  The statistics launches (project.hip) leave (a, b) in the record of the group's FIRST row; the update's projecting
 // form reads them from there.
-// The engine's work buffer: [0] the ticket of the grid form (zero between launches), then one record of PROJECT_ROW_WORDS
-// words per row at PROJECT_HEAD + row * PROJECT_ROW_WORDS ([0] a, [1] b), then - grid form - one slot of three doubles
-// {Scc, Scd, Sdd} per (row, block of PROJECT_BLOCK frames), row-major, every slot a launch sums written by that launch.
-constexpr int PROJECT_HEAD = 4, PROJECT_ROW_WORDS = 2, PROJECT_BLOCK = 64;
-inline size_t project_blocks(int T) { return ((size_t)T + PROJECT_BLOCK - 1) / PROJECT_BLOCK; }
-inline size_t project_work_words(int B, int T) { return (size_t)PROJECT_HEAD + (size_t)B * PROJECT_ROW_WORDS + (size_t)B * project_blocks(T) * 6; }
+// The engine's work buffer is the one above (a second one): a record is [0] a, [1] b, a slot the three doubles {Scc, Scd, Sdd}.
+constexpr int PROJECT_SUMS = 3;
 struct ProjectArgs {
     UpdateArgs u;          // read: what pred_quad reads (ThreshArgs::u); x0u is set - the step guides
     int rho;               // "cfg_project", 0 .. 10000
     int norm;              // "cfg_norm", 0 .. 100000 (0: no bound); one of the two is not 0
-    unsigned* work;        // the buffer above, project_work_words(B, T) words
+    unsigned* work;        // the buffer above, gs_work_words(B, T, PROJECT_SUMS) words
 };
 // What the update's projecting form needs beside UpdateArgs (the second kernel argument, as ThreshUpd is): (a, b) of row 0's
-// record - row b's is PROJECT_ROW_WORDS floats further per row.  What follows is the clamp UpdateArgs names, or nothing.
+// record (gs_records) - row b's is GS_ROW_WORDS floats further per row.  What follows is the clamp UpdateArgs names, or nothing.
 struct ProjectUpd {
     const float* ab;
 };
-inline const float* project_ab(const unsigned* work) { return reinterpret_cast<const float*>(work + PROJECT_HEAD); }
 // a step's statistics: one launch of one workgroup per roll (clips of at most THRESH_ROLL_MAX elements), or one launch of
 // (blocks, rows) workgroups whose last arriver sums the slots (windows, longer clips)
 hipError_t launch_project(const ProjectArgs& a, int B, hipStream_t s);
 // update_kernel's projecting form (update.hip: update_project_kernel)
 hipError_t launch_update_project(const UpdateArgs& a, const ProjectUpd& pj, hipStream_t s);
-// (dr_debug_project) out (G, 2) = (a, b) of the batch's groups in row / recording order
-hipError_t launch_project_gather(const ProjectArgs& a, int B, float* out, hipStream_t s);
 
 // Option "cfg_momentum" (include/diffroll_amd.h): the momentum of adaptive projected guidance - the third part of the method,
 // beside "cfg_project" / "cfg_norm".  At a step that guides, per element and in fp32 (each operation rounded once),

@@ -28,30 +28,24 @@ DR_DEVINL void momentum_quad(const float (&y)[4], const float (&c)[4], const flo
     for (int e = 0; e < 4; ++e) yb[e] = c[e] + m[e];
 }
 
-// project_frame over yb: s = {Scc, Scd, Sdd} of one frame, d = (double)yb - (double)c, the same order and roundings.
-DR_DEVINL void momentum_frame(const UpdateArgs& u, const UpdateArgs& uc, const float* m_prev, const float bf, const long row,
-                              const int f, double (&s)[3]) {
+// project_frame over yb (project_quad.h: its in_y): s = {Scc, Scd, Sdd} of one frame with d = (double)yb - (double)c, the same
+// order and roundings.
+struct MomentumY {
+    const float* m_prev;
+    float bf;
+    DR_DEVINL void operator()(const long i4, const float (&c)[4], float (&y)[4]) const {
 #pragma clang fp contract(off)
-    s[0] = s[1] = s[2] = 0.0;
-    const long q0 = row * (u.per_sample >> 2) + (long)f * 22;
-    for (int q = 0; q < 22; ++q) {
-        float y[4], c[4], m[4], yb[4];
-        pred_quad(u, q0 + q, y);
-        pred_quad(uc, q0 + q, c);
-        momentum_quad(y, c, m_prev, bf, q0 + q, m, yb);
+        float m[4], yb[4];
+        momentum_quad(y, c, m_prev, bf, i4, m, yb);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double cd = (double)c[e], dd = (double)yb[e] - cd;
-            const double cc = cd * cd, cx = cd * dd, xx = dd * dd;
-            s[0] = s[0] + cc; s[1] = s[1] + cx; s[2] = s[2] + xx;
-        }
+        for (int e = 0; e < 4; ++e) y[e] = yb[e];
     }
-}
+};
 
 // What update_kernel's momentum form does between the shared-frame blend and the update (update_quad.h): m recomputed from
 // the y it is handed and c, stored over m_prev by the element's own thread; y' = (a c) + (b yb) with (a, b) of the quad's
 // group - yb itself, bit for bit, where a == 0.0f and b == 1.0f - then the clamp of "x0_clip" where UpdateArgs names one.
-DR_DEVINL void momentum_update_quad(const UpdateArgs& a, const MomentumUpd& mo, const long i4, float (&y)[4]) {
+DR_DEVINL void form_quad(const UpdateArgs& a, const MomentumUpd& mo, const long i4, float (&y)[4]) {
 #pragma clang fp contract(off)
     UpdateArgs uc = a;
     uc.x0u = nullptr;
@@ -62,7 +56,7 @@ DR_DEVINL void momentum_update_quad(const UpdateArgs& a, const MomentumUpd& mo, 
     long first;
     int f_lo;
     thresh_place(a, i4 * 4 / a.per_sample, first, f_lo);
-    const float av = mo.ab[first * PROJECT_ROW_WORDS], bv = mo.ab[first * PROJECT_ROW_WORDS + 1];
+    const float av = mo.ab[first * GS_ROW_WORDS], bv = mo.ab[first * GS_ROW_WORDS + 1];
 #pragma unroll
     for (int e = 0; e < 4; ++e) y[e] = yb[e];
     if (!(av == 0.0f && bv == 1.0f)) {

@@ -497,16 +497,16 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
             if (chain) chain->guided = true;
             float* const m = e->momentum;
             HIPCHK(e, launch_momentum(MomentumArgs{pa, start ? nullptr : m, momentum_bf(e)}, B, st));
-            HIPCHK(e, launch_update_momentum(u, MomentumUpd{project_ab(pa.work), m, momentum_bf(e), start ? 1 : 0}, st));
+            HIPCHK(e, launch_update_momentum(u, MomentumUpd{gs_records(pa.work), m, momentum_bf(e), start ? 1 : 0}, st));
             return DR_OK;
         }
         HIPCHK(e, launch_project(pa, B, st));
-        HIPCHK(e, launch_update_project(u, ProjectUpd{project_ab(pa.work)}, st));
+        HIPCHK(e, launch_update_project(u, ProjectUpd{gs_records(pa.work)}, st));
         return DR_OK;
     }
     if (rescale) {      // statistics, [threshold launches ranking |g y - m|], update on g y
         const RescaleArgs ra = rescale_args(e, u);
-        RescaleUpd rs{rescale_g(ra.work), ThreshUpd{nullptr, 0.f, 0.f}};
+        RescaleUpd rs{gs_records(ra.work), ThreshUpd{nullptr, 0.f, 0.f}};
         HIPCHK(e, launch_rescale(ra, B, st));
         if (thresh) {
             const ThreshArgs ta = thresh_args(e, u);

@@ -1,176 +1,55 @@
 // gfx950 (MI355X, CDNA4): option "cfg_rescale" - the statistics behind the guidance rescale (Lin et al. 2024, section 3.4).
 // Per GROUP (kernels.h: RescaleArgs - a clip's roll, or a recording's canvas) the launch here leaves
 //   g = (float)(1 + phi (sqrt(Vc / Vy) - 1)),   V = S2 - S1 (S1 / N)
-// in the group's record, the sums over the conditional prediction c and the guided prediction y, both after the
-// shared-frame mean / blend, in double and in ONE fixed order (include/diffroll_amd.h states it):
-//   a frame's 88 elements in pitch order;
-//   the frames a row counts in blocks of RESCALE_BLOCK from its first counted frame, a block's frames in frame order;
-//   a group's blocks in row, then block order;
-// every level a sequential sum from 0.  A lane owns a frame, a wave a block: the block's frame sums meet in LDS and lane 0
-// adds them up in frame order.  A function of the inputs alone - no floating-point atomic, no dependence on the grid or on
-// timing.  y and c are recomputed by pred_quad from the head projections' L2-resident output; nothing but sums is stored.
-//
-// Two forms, chosen by the launcher:
-//   rescale_roll_kernel   clips of at most THRESH_ROLL_MAX elements: one workgroup per roll, the blocks' sums in LDS, no
-//                         work word touched but the result;
-//   rescale_grid_kernel   windows and longer clips: (blocks, rows) workgroups of one wave.  A workgroup parks its block's
-//                         sums in its slot and draws a ticket; the workgroup that draws the last one adds up every group's
-//                         slots and leaves the ticket zero (frame_counts_kernel's pattern; every slot that is read was
-//                         written by this launch, so the slots need no re-arming).
-// No workgroup ever waits for another, so neither form assumes anything about what else is resident; a captured chain
-// replays with no host help.
+// in the group's record: the sums over the conditional prediction c and the guided prediction y, in the fixed order and by the
+// two launch forms of group_sums.h.  Here: the statistic, its two kernels and launcher, and the debug entries' gather.
 #include "rescale_quad.h"
+#include "group_sums.h"
 
 namespace dr {
-
-constexpr int RS_ROLL_BLOCKS = (int)((THRESH_ROLL_MAX / 88 + RESCALE_BLOCK - 1) / RESCALE_BLOCK);      // blocks of the longest roll of the one-workgroup form
-
-// One wave, two steps with a workgroup barrier between them: lane l leaves the sums of frame f0 + l of `row` in fs (the
-// wave's RESCALE_BLOCK x 4 doubles of LDS); then lane 0 adds up the block's frames [f0, f1) in frame order.
-DR_DEVINL void rs_frames(const UpdateArgs& u, const UpdateArgs& uc, const long row, const int f0, const int f1, double* fs) {
-    const int lane = (int)(threadIdx.x & 63);
-    if (f0 + lane < f1) {
-        double s[4];
-        rescale_frame(u, uc, row, f0 + lane, s);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) fs[lane * 4 + k] = s[k];
-    }
-}
-DR_DEVINL void rs_block(const int frames, const double* fs, double (&b)[4]) {
 #pragma clang fp contract(off)
-    b[0] = b[1] = b[2] = b[3] = 0.0;
-    for (int j = 0; j < frames; ++j)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) b[k] = b[k] + fs[j * 4 + k];
-}
 
-// ---------------------------------------------------------------------------------------------- one workgroup per roll
-__global__ __launch_bounds__(256) void rescale_roll_kernel(const RescaleArgs a) {
-#pragma clang fp contract(off)
-    __shared__ double fs[4][RESCALE_BLOCK * 4];
-    __shared__ double bs[RS_ROLL_BLOCKS][4];
-    const long row = blockIdx.x;
-    const int T = (int)(a.u.per_sample / 88), nb = (T + RESCALE_BLOCK - 1) / RESCALE_BLOCK;      // (nb <= RS_ROLL_BLOCKS: launcher)
-    const int wave = (int)(threadIdx.x >> 6);
-    UpdateArgs uc = a.u;
-    uc.x0u = nullptr;
-    for (int j0 = 0; j0 < nb; j0 += 4) {      // (uniform over the workgroup: four blocks per round, one per wave)
-        const int j = j0 + wave;
-        const int f0 = j * RESCALE_BLOCK, f1 = f0 + RESCALE_BLOCK < T ? f0 + RESCALE_BLOCK : T;
-        rs_frames(a.u, uc, row, f0, f1, fs[wave]);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0 && j < nb) {
-            double b[4];
-            rs_block(f1 - f0, fs[wave], b);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) bs[j][k] = b[k];
-        }
-        __syncthreads();
+struct RescaleStat {
+    static constexpr int K = RESCALE_SUMS;
+    using Args = RescaleArgs;
+    __host__ __device__ static inline const UpdateArgs& u(const Args& a) { return a.u; }
+    __host__ __device__ static inline unsigned* work(const Args& a) { return a.work; }
+    static DR_DEVINL void frame(const Args& a, const UpdateArgs& uc, const long row, const int f, double (&s)[K]) {
+        rescale_frame(a.u, uc, row, f, s);
     }
-    if (threadIdx.x == 0) {
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int j = 0; j < nb; ++j)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s[k] = s[k] + bs[j][k];
-        reinterpret_cast<float*>(a.work + RESCALE_HEAD)[row * RESCALE_ROW_WORDS] = rescale_factor(a.phi, (double)a.u.per_sample, s);
+    static DR_DEVINL void record(const Args& a, const long row, const double N, const double (&s)[K]) {
+        reinterpret_cast<float*>(a.work + GS_HEAD)[row * GS_ROW_WORDS] = rescale_factor(a.phi, N, s);
     }
-}
+};
 
-// ---------------------------------------------------------------------------------------------- one launch over all rows
-DR_DEVINL double rs_load(const double* p) {
-    return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-DR_DEVINL void rs_store(double* p, const double v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// grid (blocks of RESCALE_BLOCK frames, rows), one wave each.  Block j of a row covers its counted frames
-// [f_lo + j RESCALE_BLOCK, ..): a row that counts fewer frames than it has leaves its last slots unwritten and unread.
-__global__ __launch_bounds__(64) void rescale_grid_kernel(const RescaleArgs a) {
-#pragma clang fp contract(off)
-    __shared__ double fs[RESCALE_BLOCK * 4];
-    __shared__ unsigned last_s;
-    const long row = blockIdx.y, B = gridDim.y, nbmax = gridDim.x;
-    const int T = (int)(a.u.per_sample / 88);
-    double* const slots = reinterpret_cast<double*>(a.work + RESCALE_HEAD + B * RESCALE_ROW_WORDS);
-    long first;
-    int f_lo;
-    thresh_place(a.u, row, first, f_lo);
-    const int f0 = f_lo + (int)blockIdx.x * RESCALE_BLOCK, f1 = f0 + RESCALE_BLOCK < T ? f0 + RESCALE_BLOCK : T;
-    UpdateArgs uc = a.u;
-    uc.x0u = nullptr;
-    rs_frames(a.u, uc, row, f0, f1, fs);
-    __syncthreads();
-    if (threadIdx.x == 0 && f0 < T) {
-        double b[4];
-        rs_block(f1 - f0, fs, b);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) rs_store(slots + (row * nbmax + blockIdx.x) * 4 + k, b[k]);
-    }
-    // this workgroup's slot is written -> ticket; the last arriver sees every workgroup's
-    __threadfence();
-    if (threadIdx.x == 0) {
-        const unsigned ticket = __hip_atomic_fetch_add(a.work, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        last_s = ticket == gridDim.x * gridDim.y - 1u;
-    }
-    __syncthreads();
-    if (!last_s) return;
-    __threadfence();
-    for (long g = threadIdx.x; g < B; g += 64) {      // one lane per group
-        long gf;
-        int gl;
-        thresh_place(a.u, g, gf, gl);
-        if (gf != g) continue;
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        long frames = 0;
-        for (long r = g; r < B; ++r) {
-            thresh_place(a.u, r, gf, gl);
-            if (gf != g) break;
-            const int nb = (T - gl + RESCALE_BLOCK - 1) / RESCALE_BLOCK;
-            for (int j = 0; j < nb; ++j)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) s[k] = s[k] + rs_load(slots + (r * nbmax + j) * 4 + k);
-            frames += T - gl;
-        }
-        reinterpret_cast<float*>(a.work + RESCALE_HEAD)[g * RESCALE_ROW_WORDS] = rescale_factor(a.phi, (double)(frames * 88), s);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(a.work, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__global__ __launch_bounds__(256) void rescale_roll_kernel(const RescaleArgs a) { gs_roll<RescaleStat>(a); }
+__global__ __launch_bounds__(64) void rescale_grid_kernel(const RescaleArgs a) { gs_grid<RescaleStat>(a); }
 
 hipError_t launch_rescale(const RescaleArgs& a, int B, hipStream_t s) {
-    const UpdateArgs& u = a.u;
-    if (!u.x0c || !a.work || B < 1 || u.per_sample < 88 || u.per_sample % 88 || u.n != (long)B * u.per_sample ||
-        u.n >= (1l << 31) || a.phi < 1 || a.phi > 10000)
-        return hipErrorInvalidValue;
-    if (win_H(u) == 0 && u.per_sample <= THRESH_ROLL_MAX) {
-        hipLaunchKernelGGL(rescale_roll_kernel, dim3((unsigned)B), dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-    if (B > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rescale_grid_kernel, dim3((unsigned)rescale_blocks((int)(u.per_sample / 88)), (unsigned)B), dim3(64), 0, s, a);
-    return hipGetLastError();
+    if (a.phi < 1 || a.phi > 10000) return hipErrorInvalidValue;
+    return gs_launch<RescaleStat>(rescale_roll_kernel, rescale_grid_kernel, a, B, s);
 }
 
-// (dr_debug_rescale) g of the groups' first rows, in row order
-__global__ __launch_bounds__(256) void rescale_gather_kernel(const RescaleArgs a, int B, float* out) {
+// (dr_debug_rescale / dr_debug_project / dr_debug_momentum) the first `words` words of the records of the groups' first rows,
+// in row order
+__global__ __launch_bounds__(256) void group_gather_kernel(const UpdateArgs u, const float* rec, int words, int B, float* out) {
     for (long b = threadIdx.x; b < B; b += 256) {
         long first;
         int f_lo;
-        thresh_place(a.u, b, first, f_lo);
+        thresh_place(u, b, first, f_lo);
         if (first != b) continue;
         long g = b;
-        if (win_H(a.u) > 0) {
+        if (win_H(u) > 0) {
             g = 0;
-            if (a.u.win_tab)
-                for (long j = 0; j < b; ++j) g += window_idx(a.u.win_tab[j]) == 0;
+            if (u.win_tab)
+                for (long j = 0; j < b; ++j) g += window_idx(u.win_tab[j]) == 0;
         }
-        out[g] = reinterpret_cast<const float*>(a.work + RESCALE_HEAD)[b * RESCALE_ROW_WORDS];
+        for (int k = 0; k < words; ++k) out[g * words + k] = rec[b * GS_ROW_WORDS + k];
     }
 }
-hipError_t launch_rescale_gather(const RescaleArgs& a, int B, float* out, hipStream_t s) {
-    if (!a.work || !out || B < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rescale_gather_kernel, dim3(1), dim3(256), 0, s, a, B, out);
+hipError_t launch_group_gather(const UpdateArgs& u, const unsigned* work, int words, int B, float* out, hipStream_t s) {
+    if (!work || !out || B < 1 || words < 1 || words > GS_ROW_WORDS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(group_gather_kernel, dim3(1), dim3(256), 0, s, u, gs_records(work), words, B, out);
     return hipGetLastError();
 }
 

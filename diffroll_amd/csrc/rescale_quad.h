@@ -12,16 +12,16 @@ DR_DEVINL void rescale_quad(const UpdateArgs& a, const float* g, const long i4, 
     long first;
     int f_lo;
     thresh_place(a, i4 * 4 / a.per_sample, first, f_lo);
-    const float gv = g[first * RESCALE_ROW_WORDS];
+    const float gv = g[first * GS_ROW_WORDS];
 #pragma unroll
     for (int e = 0; e < 4; ++e) y[e] = gv * y[e];
 }
 
 // ... and what update_kernel's rescaling form does between the shared-frame blend and the update (update_quad.h): the
 // product, then the thresholding of "x0_threshold" where rs.th is set, else the clamp of "x0_clip" where UpdateArgs names one
-DR_DEVINL void rescaled_quad(const UpdateArgs& a, const RescaleUpd& rs, const long i4, float (&y)[4]) {
+DR_DEVINL void form_quad(const UpdateArgs& a, const RescaleUpd& rs, const long i4, float (&y)[4]) {
     rescale_quad(a, rs.g, i4, y);
-    if (rs.th.qs) thresh_quad(a, rs.th, i4, y);
+    if (rs.th.qs) form_quad(a, rs.th, i4, y);
     else if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, y);
 }
 

@@ -49,7 +49,7 @@ DR_DEVINL void thresh_place(const UpdateArgs& a, const long smp, long& first, in
 // ... and what the update does with s of its quad's group: with u = y - m, y' = m + (clamp(u, -s, s) r) / s where s > r, else
 // the static clamp itself - a step whose quantile does not exceed r is bit-identical to the "x0_clip" step.  One rounding
 // per operation; compare-and-select as in clamp_quad (a NaN stays a NaN).
-DR_DEVINL void thresh_quad(const UpdateArgs& a, const ThreshUpd& th, const long i4, float (&y)[4]) {
+DR_DEVINL void form_quad(const UpdateArgs& a, const ThreshUpd& th, const long i4, float (&y)[4]) {
 #pragma clang fp contract(off)
     long first;
     int f_lo;

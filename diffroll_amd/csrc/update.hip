@@ -14,13 +14,13 @@ __global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;      // (option "solver_order")
 }
 
-// Option "x0_threshold": the same update with thresh_quad in place of the clamp (threshold_quad.h).  The selection's result
+// Option "x0_threshold": the same update with the thresholding in place of the clamp (threshold_quad.h).  The selection's result
 // travels as a second argument; UpdateArgs is the block every other launch passes.
 __global__ __launch_bounds__(256) void update_thresh_kernel(const UpdateArgs a, const ThreshUpd th) {
     const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
     if (i4 * 4 >= a.n) return;
     float4 y;
-    reinterpret_cast<float4*>(a.x)[i4] = update_quad<true>(a, i4, &y, &th);
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4, &y, th);
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
 }
 
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void update_rescale_kernel(const UpdateArgs a,
     const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
     if (i4 * 4 >= a.n) return;
     float4 y;
-    reinterpret_cast<float4*>(a.x)[i4] = update_quad<false, true>(a, i4, &y, nullptr, &rs);
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4, &y, rs);
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
 }
 
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void update_project_kernel(const UpdateArgs a,
     const long i4 = (long)blockIdx.x * 256 + threadIdx.x;
     if (i4 * 4 >= a.n) return;
     float4 y;
-    reinterpret_cast<float4*>(a.x)[i4] = update_quad<false, false, true>(a, i4, &y, nullptr, nullptr, &pj);
+    reinterpret_cast<float4*>(a.x)[i4] = update_quad(a, i4, &y, pj);
     if (a.mode == 5 && hist_next(a)) reinterpret_cast<float4*>(hist_next(a))[i4] = y;
 }
 

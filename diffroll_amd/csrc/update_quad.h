@@ -155,19 +155,13 @@ DR_DEVINL void clamp_quad(const float lo, const float hi, float (&y)[4]) {
     for (int e = 0; e < 4; ++e) y[e] = y[e] < lo ? lo : (y[e] > hi ? hi : y[e]);
 }
 
-// Option "x0_threshold": what the update's thresholding form does in place of the clamp - defined in threshold_quad.h, which
-// the units that instantiate that form include behind this header.
-DR_DEVINL void thresh_quad(const UpdateArgs& a, const ThreshUpd& th, const long i4, float (&y)[4]);
-// Option "cfg_rescale": what the update's rescaling form does there - y' = g y with g of the quad's group, then the
-// thresholding or the clamp as rs names them - defined in rescale_quad.h, included likewise.
-DR_DEVINL void rescaled_quad(const UpdateArgs& a, const RescaleUpd& rs, const long i4, float (&y)[4]);
-// Options "cfg_project" / "cfg_norm": what the update's projecting form does there - y' = (a c) + (b y) with (a, b) of the
-// quad's group and c the conditional prediction, then the clamp where UpdateArgs names one - defined in project_quad.h,
-// included likewise.
-DR_DEVINL void projected_quad(const UpdateArgs& a, const ProjectUpd& pj, const long i4, float (&y)[4]);
-// Option "cfg_momentum": what the update's momentum form does there - m = d + (bf * m_prev) of d = y - c, stored in place,
-// then the projecting form's y' over yb = c + m and the clamp - defined in momentum_quad.h, included likewise.
-DR_DEVINL void momentum_update_quad(const UpdateArgs& a, const MomentumUpd& mo, const long i4, float (&y)[4]);
+// The update's plain form: the clamp where UpdateArgs names one.  What stands in this place in the other forms is the
+// overload of form_quad on the form's second kernel argument - ThreshUpd (threshold_quad.h), RescaleUpd (rescale_quad.h),
+// ProjectUpd (project_quad.h), MomentumUpd (momentum_quad.h) - which the units that instantiate a form include behind this header.
+struct PlainUpd {};
+DR_DEVINL void form_quad(const UpdateArgs& a, const PlainUpd&, const long, float (&y)[4]) {
+    if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, y);
+}
 
 // Option "window_blend" (win_blend() of UpdateArgs::win): what a frame shared by windows b and b + 1 takes of the two guided predictions
 // lo (window b's, its frame H + j) and up (window b + 1's, its frame j), j = 0 .. O - 1 the position within the overlap:
@@ -194,14 +188,10 @@ DR_DEVINL void blend_quad(const int mode, const int j, const int O, const float 
 }
 
 // pred (optional): receives the prediction the update consumed - guided, after the shared-frame mean and the clamp of
-// option "x0_clip" (mode 5's history).  TH: update_kernel's thresholding form (option "x0_threshold"; th is set) - the
-// tail kernel instantiates TH = false, the text it always had.  RS: update_kernel's rescaling form (option "cfg_rescale"; rs
-// is set, th is not read): rescaled_quad in that place.  PJ: update_kernel's projecting form (options "cfg_project" /
-// "cfg_norm"; pj is set, th and rs are not read): projected_quad in that place.  MO: its momentum form (option "cfg_momentum";
-// mo is set, nothing else is read): momentum_update_quad in that place.
-template <bool TH = false, bool RS = false, bool PJ = false, bool MO = false>
-DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr, const ThreshUpd* th = nullptr,
-                             const RescaleUpd* rs = nullptr, const ProjectUpd* pj = nullptr, const MomentumUpd* mo = nullptr) {
+// option "x0_clip" (mode 5's history).  form: what the step does between the shared-frame blend and the update - form_quad
+// of its type; the tail kernel instantiates the plain form, the text it always had.
+template <class Form = PlainUpd>
+DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = nullptr, const Form& form = Form{}) {
 #pragma clang fp contract(off)
     float x0[4];
     // per-call scalars: by value (eager launches) or from the device block (captured chain)
@@ -239,13 +229,7 @@ DR_DEVINL float4 update_quad(const UpdateArgs& a, const long i4, float4* pred = 
         }
         window_key(a, rec, idx, within, first_sample, key_q, key_smp);
     }
-    if constexpr (MO) momentum_update_quad(a, *mo, i4, x0);
-    else if constexpr (PJ) projected_quad(a, *pj, i4, x0);
-    else if constexpr (RS) rescaled_quad(a, *rs, i4, x0);
-    else if constexpr (TH) thresh_quad(a, *th, i4, x0);
-    else {
-        if (a.clamp_lo < a.clamp_hi) clamp_quad(a.clamp_lo, a.clamp_hi, x0);
-    }
+    form_quad(a, form, i4, x0);
     if (pred) *pred = make_float4(x0[0], x0[1], x0[2], x0[3]);
     const float c0 = a.coef[0], c1 = a.coef[1], c2 = a.coef[2], c3 = a.coef[3], c4 = a.coef[4];
     float o[4];

@@ -380,13 +380,23 @@ def test_the_new_kernels_text_and_the_parents():
     quad = open(os.path.join(csrc, "momentum_quad.h")).read()
     hip = open(os.path.join(csrc, "momentum.hip")).read()
     assert quad.count("clamp_quad(") == 1 and "clamp_quad" not in hip and "clamp_quad" not in open(os.path.join(csrc, "update.hip")).read()
-    assert "project_coef(" in hip and "thresh_place(" in hip and "thresh_place(" in quad      # the parent's pieces, reused
+    # the parent's pieces, reused: its frame sums and its record writer (project_coef inside) from project_quad.h, the groups'
+    # places in the skeleton the three statistics share and in the update's form
+    skel = open(os.path.join(csrc, "group_sums.h")).read()
+    pquad = open(os.path.join(csrc, "project_quad.h")).read()
+    record = pquad[pquad.index("DR_DEVINL void project_record("):]
+    assert "project_frame(" in hip and "project_record(" in hip and "project_coef(" in record[:record.index("\n}\n")]
+    assert "thresh_place(" in skel and "thresh_place(" in quad and '#include "group_sums.h"' in hip
     pragma = "#pragma clang fp contract(off)"
     assert hip.index(pragma) < hip.index("DR_DEVINL") and quad.count(pragma) == quad.count("DR_DEVINL void") == 3
-    code = "\n".join(line.split("//")[0] for line in (hip + quad).splitlines())
+    assert skel.index(pragma) < skel.index("DR_DEVINL") and skel.count(pragma) == skel.count("DR_DEVINL") + 1
+    code = "\n".join(line.split("//")[0] for line in (hip + quad + skel).splitlines())
     for banned in ("unsafeAtomicAdd", "atomicAdd(", "atomicMax(", "atomicMin(", "while (", "__builtin_amdgcn_s_sleep"):
         assert banned not in code, banned
-    for kernel in ("momentum_roll_kernel", "momentum_grid_kernel", "update_momentum_kernel", "update_quad<false, false, false, true>"):
+    for kernel in ("momentum_roll_kernel", "momentum_grid_kernel", "update_momentum_kernel"):
         assert kernel in code, kernel
+    # the momentum kernel hands its MomentumUpd to update_quad, whose form it selects
+    assert re.search(r"void update_momentum_kernel\(const UpdateArgs a, const MomentumUpd mo\) \{[^}]*update_quad\(a, i4, &y, mo\)", code)
+    assert "DR_DEVINL void form_quad(const UpdateArgs& a, const MomentumUpd& mo," in quad
     from diffroll_amd import build
     assert "momentum.hip" in build.SOURCES and any(h.endswith("momentum_quad.h") for h in build.HEADERS)

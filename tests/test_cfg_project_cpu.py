@@ -323,10 +323,14 @@ def test_the_parents_kernels_keep_their_text():
     for word in ("clamp_quad", "clamp_lo", "blend_quad"):
         assert word not in update, word
     hip = open(os.path.join(csrc, "project.hip")).read()
-    src = hip + quad
-    # contraction off throughout: for the whole of project.hip in front of its first function, and in every function of the header
+    skel = open(os.path.join(csrc, "group_sums.h")).read()      # the loops of the statistics launch, which project.hip instantiates
+    src = hip + quad + skel
+    # contraction off throughout: for the whole of project.hip and of the skeleton in front of their first function, and in every
+    # function of the two headers (project_quad.h: the frame's sums and their in_y, the coefficients, the record, the update's form)
     pragma = "#pragma clang fp contract(off)"
-    assert hip.index(pragma) < hip.index("DR_DEVINL") and quad.count(pragma) == quad.count("DR_DEVINL void") == 3
+    assert hip.index(pragma) < hip.index("DR_DEVINL") and quad.count(pragma) == quad.count("DR_DEVINL void") == 5
+    assert skel.index(pragma) < skel.index("DR_DEVINL") and skel.count(pragma) == skel.count("DR_DEVINL") + 1
+    assert '#include "group_sums.h"' in hip and "gs_roll<ProjectStat>(a)" in hip and "gs_grid<ProjectStat>(a)" in hip
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     for banned in ("unsafeAtomicAdd", "atomicAdd(", "atomicMax(", "atomicMin(", "while (", "__builtin_amdgcn_s_sleep"):
         assert banned not in code, banned

@@ -220,10 +220,18 @@ def test_the_parents_kernels_keep_their_text():
     kern = open(os.path.join(csrc, "kernels.h")).read()
     upd = kern[kern.index("struct UpdateArgs {"):kern.index("// (mode 5) the half the step reads")]
     assert "rescale" not in upd.lower() and upd.rstrip().endswith("float clamp_lo, clamp_hi;\n};".rstrip())
-    src = open(os.path.join(csrc, "rescale.hip")).read() + open(os.path.join(csrc, "rescale_quad.h")).read()
+    # (the loops of the statistics launch live in group_sums.h, which rescale.hip instantiates)
+    skel = open(os.path.join(csrc, "group_sums.h")).read()
+    hip = open(os.path.join(csrc, "rescale.hip")).read()
+    src = hip + open(os.path.join(csrc, "rescale_quad.h")).read() + skel
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     for banned in ("unsafeAtomicAdd", "atomicAdd(", "atomicMax(", "atomicMin(", "while (", "__builtin_amdgcn_s_sleep"):
         assert banned not in code, banned
+    assert '#include "group_sums.h"' in hip and "gs_roll<RescaleStat>(a)" in code and "gs_grid<RescaleStat>(a)" in code
+    # contraction off in the skeleton: in front of its first function, and in every function
+    pragma = "#pragma clang fp contract(off)"
+    assert skel.index(pragma) < skel.index("DR_DEVINL") and skel.count(pragma) == skel.count("DR_DEVINL") + 1
+    assert code.count("__hip_atomic_fetch_add") == 1      # the ticket, once
     # the rescaled forms of the selection kernels are the text of threshold.hip itself, which test_x0_threshold_cpu.py scans:
     # the unit includes no file of kernel text but itself
     sel = open(os.path.join(csrc, "threshold.hip")).read()
