@@ -284,92 +284,85 @@ int grow_chain_buffer(dr_engine* e, DevBuf<V>& buf, size_t n, hipStream_t st) {
     return DR_OK;
 }
 
-// dr_debug_threshold: the threshold launches of a step on the caller's tensors, then the groups' {q, s} gathered into d_out
-int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
+// The engine's one work buffer of the statistics launches ("cfg_rescale", "cfg_project" / "cfg_norm" / "cfg_momentum"): sized for the
+// widest of them whichever is set, so a switch between the options at one shape neither grows it nor costs a captured chain its key
+int grow_stats_work(dr_engine* e, int B, int T, hipStream_t st) {
+    return grow_chain_buffer(e, e->stats_work, gs_work_words(B, T, GS_SUMS_MAX), st);
+}
+
+// The opening the four dr_debug_* probes of the stages share: the engine is committed, the probed option - a or b - is on (else
+// refused with `off`), the options are ones a step of B rolls of T frames can run under, the window table is written, and the
+// update a step would hand its stage stands on the caller's tensors (clamp: with the range "x0_clip" names).  Then `body`, the
+// probe's own buffer growth, launch and gather, on the engine's device.
+struct ProbeOf { int ChainOptions::*a, ChainOptions::*b; const char* off; bool clamp; };
+template <class Body>
+int probe(dr_engine* e, const ProbeOf& of, const float* d_x0c, const float* d_x0u, int B, int T, float w, const float* d_out,
+          hipStream_t st, Body&& body) {
     if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
     if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
     if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
     DeviceGuard guard(e->cfg.device);
-    if (e->opt.x0_thresh == 0) return fail(e, DR_EINVAL, "dr_debug_threshold: x0_threshold is 0 (off)");
+    if (e->opt.*of.a == 0 && e->opt.*of.b == 0) return fail(e, DR_EINVAL, "%s", of.off);
     if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
     int rc, NB;
     if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
     if ((rc = write_windows(e, B, false, st))) return rc;
     UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
     u.x0c = d_x0c; u.x0u = d_x0u;
     u.w = w; u.onepw = (float)(1.0 + (double)w);
-    u.clamp_lo = e->opt.x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f;
-    const ThreshArgs ta = thresh_args(e, u);
-    HIPCHK(e, launch_threshold(ta, B, st));
-    HIPCHK(e, launch_thresh_gather(ta, B, d_out, st));
-    return DR_OK;
+    if (of.clamp) { u.clamp_lo = e->opt.x0_clamp == 2 ? -1.f : 0.f; u.clamp_hi = 1.f; }
+    return body(u);
+}
+
+// dr_debug_threshold: the threshold launches of a step on the caller's tensors, then the groups' {q, s} gathered into d_out
+int debug_threshold(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
+    const ProbeOf of{&ChainOptions::x0_thresh, &ChainOptions::x0_thresh, "dr_debug_threshold: x0_threshold is 0 (off)", true};
+    return probe(e, of, d_x0c, d_x0u, B, T, w, d_out, st, [&](const UpdateArgs& u) -> int {
+        if (int rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st)) return rc;
+        const ThreshArgs ta = thresh_args(e, u);
+        HIPCHK(e, launch_threshold(ta, B, st));
+        HIPCHK(e, launch_thresh_gather(ta, B, d_out, st));
+        return DR_OK;
+    });
 }
 
 // dr_debug_rescale: the statistics launch of a step on the caller's tensors, then the groups' g gathered into d_out
 int debug_rescale(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
-    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
-    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
-    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
-    DeviceGuard guard(e->cfg.device);
-    if (e->opt.cfg_rescale == 0) return fail(e, DR_EINVAL, "dr_debug_rescale: cfg_rescale is 0 (off)");
-    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
-    int rc, NB;
-    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->rescale_work, gs_work_words(B, T, RESCALE_SUMS), st))) return rc;
-    if ((rc = write_windows(e, B, false, st))) return rc;
-    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
-    u.x0c = d_x0c; u.x0u = d_x0u;
-    u.w = w; u.onepw = (float)(1.0 + (double)w);
-    const RescaleArgs ra = rescale_args(e, u);
-    HIPCHK(e, launch_rescale(ra, B, st));
-    HIPCHK(e, launch_group_gather(ra.u, ra.work, 1, B, d_out, st));
-    return DR_OK;
+    const ProbeOf of{&ChainOptions::cfg_rescale, &ChainOptions::cfg_rescale, "dr_debug_rescale: cfg_rescale is 0 (off)", false};
+    return probe(e, of, d_x0c, d_x0u, B, T, w, d_out, st, [&](const UpdateArgs& u) -> int {
+        if (int rc = grow_stats_work(e, B, T, st)) return rc;
+        const RescaleArgs ra = rescale_args(e, u);
+        HIPCHK(e, launch_rescale(ra, B, st));
+        HIPCHK(e, launch_group_gather(ra.u, ra.work, 1, B, d_out, st));
+        return DR_OK;
+    });
 }
 
 // dr_debug_project: the statistics launch of a step on the caller's tensors, then the groups' (a, b) gathered into d_out
 int debug_project(dr_engine* e, const float* d_x0c, const float* d_x0u, int B, int T, float w, float* d_out, hipStream_t st) {
-    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
-    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
-    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
-    DeviceGuard guard(e->cfg.device);
-    if (e->opt.cfg_project == 0 && e->opt.cfg_norm == 0) return fail(e, DR_EINVAL, "dr_debug_project: cfg_project and cfg_norm are both 0 (off)");
-    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
-    int rc, NB;
-    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->project_work, gs_work_words(B, T, PROJECT_SUMS), st))) return rc;
-    if ((rc = write_windows(e, B, false, st))) return rc;
-    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
-    u.x0c = d_x0c; u.x0u = d_x0u;
-    u.w = w; u.onepw = (float)(1.0 + (double)w);
-    const ProjectArgs pa = project_args(e, u);
-    HIPCHK(e, launch_project(pa, B, st));
-    HIPCHK(e, launch_group_gather(pa.u, pa.work, 2, B, d_out, st));
-    return DR_OK;
+    const ProbeOf of{&ChainOptions::cfg_project, &ChainOptions::cfg_norm, "dr_debug_project: cfg_project and cfg_norm are both 0 (off)", false};
+    return probe(e, of, d_x0c, d_x0u, B, T, w, d_out, st, [&](const UpdateArgs& u) -> int {
+        if (int rc = grow_stats_work(e, B, T, st)) return rc;
+        const ProjectArgs pa = project_args(e, u);
+        HIPCHK(e, launch_project(pa, B, st));
+        HIPCHK(e, launch_group_gather(pa.u, pa.work, 2, B, d_out, st));
+        return DR_OK;
+    });
 }
 
 // dr_debug_momentum: the statistics launch of a step under "cfg_momentum" on the caller's tensors and state, the groups' (a, b)
 // gathered into d_out, and - where wanted - the state the step would leave
 int debug_momentum(dr_engine* e, const float* d_x0c, const float* d_x0u, const float* d_m_prev, float* d_m_next, int B, int T, float w,
                    float* d_out, hipStream_t st) {
-    if (!e || !d_x0c || !d_out) return fail(e, DR_EINVAL, "null argument");
-    if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
-    if (!e->committed) return fail(e, DR_ESTATE, "dr_commit has not been called");
-    DeviceGuard guard(e->cfg.device);
-    if (e->opt.cfg_momentum == 0) return fail(e, DR_EINVAL, "dr_debug_momentum: cfg_momentum is 0 (off)");
-    if (B % e->opt.draws) return fail(e, DR_EINVAL, "draws = %d does not divide B = %d", e->opt.draws, B);
-    int rc, NB;
-    if ((rc = check_options(e, DR_SAMPLER_DDPM_X0, B, NB, T))) return rc;
-    if ((rc = grow_chain_buffer(e, e->project_work, gs_work_words(B, T, PROJECT_SUMS), st))) return rc;
-    if ((rc = write_windows(e, B, false, st))) return rc;
-    UpdateArgs u = update_base(e, B, T);      // (never captured: no d_dyn, the table only where marks or draws need it)
-    u.x0c = d_x0c; u.x0u = d_x0u;
-    u.w = w; u.onepw = (float)(1.0 + (double)w);
-    const MomentumArgs ma{project_args(e, u), d_m_prev, momentum_bf(e)};
-    HIPCHK(e, launch_momentum(ma, B, st));
-    HIPCHK(e, launch_group_gather(ma.p.u, ma.p.work, 2, B, d_out, st));
-    if (d_m_next) HIPCHK(e, launch_momentum_state(u, d_m_prev, ma.bf, d_m_next, st));
-    return DR_OK;
+    const ProbeOf of{&ChainOptions::cfg_momentum, &ChainOptions::cfg_momentum, "dr_debug_momentum: cfg_momentum is 0 (off)", false};
+    return probe(e, of, d_x0c, d_x0u, B, T, w, d_out, st, [&](const UpdateArgs& u) -> int {
+        if (int rc = grow_stats_work(e, B, T, st)) return rc;
+        const MomentumArgs ma{project_args(e, u), d_m_prev, momentum_bf(e)};
+        HIPCHK(e, launch_momentum(ma, B, st));
+        HIPCHK(e, launch_group_gather(ma.p.u, ma.p.work, 2, B, d_out, st));
+        if (d_m_next) HIPCHK(e, launch_momentum_state(u, d_m_prev, ma.bf, d_m_next, st));
+        return DR_OK;
+    });
 }
 
 // A setting that captured launches bake in (engine_state.h: dr_engine::baked) takes a new value: a change makes the chain stale
@@ -380,6 +373,41 @@ bool put(dr_engine* e, Field& field, int value) {
     stale(e);
     return true;
 }
+
+// The options that are a value of ChainOptions and nothing else: refused outside [lo, hi] (or_zero: 0 is accepted beside it)
+// with the option's own text, which takes the value; stored.  None drops a captured chain - each is part of the chain's key
+// (GraphKey), so a chain captured under another value is simply not replayed and one captured under this value still is.
+// ends_step_states: the option shapes the prediction - under "solver_order" 2 the history holds the prediction as the previous
+// step blended / clamped / thresholded / rescaled / projected it, and the momentum state holds sums under the previous value - so
+// a dr_step sequence does not continue across a change: the next step that is not a chain's first is refused, as for "solver_noise".
+// What a value needs of a call - "draws" B % D and the front-end's batch, "x0_threshold" its "x0_clip", ... - check_options asks.
+struct ValueOption {
+    const char* name;
+    int ChainOptions::*field;
+    int lo, hi;
+    bool or_zero, ends_step_states;
+    const char* refusal;
+};
+constexpr int NO_BOUND = 0x7fffffff;
+const ValueOption VALUE_OPTIONS[] = {
+    {"window_blend", &ChainOptions::win_blend, 0, 2, false, true,
+     "window_blend is 0 (the mean of the two windows' predictions), 1 (linear cross-fade) or 2 (hand-over at the middle of the overlap), got %d"},
+    {"draws", &ChainOptions::draws, 1, NO_BOUND, false, true, "draws is >= 1 (1 = every roll its own clip), got %d"},
+    {"draw_stride", &ChainOptions::draw_G, 0, NO_BOUND, false, false, "draw_stride is >= 0 (0 = the clips of the batch), got %d"},
+    {"start_noise", &ChainOptions::start_noise, 0, 1, false, false,
+     "start_noise is 0 (x on entry is x at the start step) or 1 (a clean roll, diffused to it), got %d"},
+    {"x0_clip", &ChainOptions::x0_clamp, 0, 2, false, true, "x0_clip is 0 (off), 1 (clamp the x0 prediction to [0, 1]) or 2 (to [-1, 1]), got %d"},
+    {"x0_threshold", &ChainOptions::x0_thresh, 5000, 10000, true, true,
+     "x0_threshold is 0 (off) or the percentile in units of 1 / 10000, 5000 .. 10000 (9950 = 99.5 %%), got %d"},
+    {"cfg_rescale", &ChainOptions::cfg_rescale, 0, 10000, false, true,
+     "cfg_rescale is 0 (off) or phi in units of 1 / 10000, 1 .. 10000 (7000 = 0.7), got %d"},
+    {"cfg_project", &ChainOptions::cfg_project, 0, 10000, false, true,
+     "cfg_project is 0 (off) or rho in units of 1 / 10000, 1 .. 10000 (10000 = the whole parallel component), got %d"},
+    {"cfg_norm", &ChainOptions::cfg_norm, 0, 100000, false, true,
+     "cfg_norm is 0 (off) or the rms bound r in units of 1 / 10000, 1 .. 100000 (500 = 0.05), got %d"},
+    {"cfg_momentum", &ChainOptions::cfg_momentum, -9999, 9999, false, true,
+     "cfg_momentum is 0 (off) or beta in units of 1 / 10000, -9999 .. 9999 (-5000 = -0.5), got %d"},
+};
 
 // dr_set_option (lab = false: the product's options) / dr_debug_set_option (lab = true: the A/B and test knobs too)
 int set_option(dr_engine* e, const char* name, int value, bool lab) {
@@ -399,13 +427,11 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         put(e, e->opt.win_O, value);
         return DR_OK;
     }
-    if (n == "window_blend") {      // (part of the chain's key while "window_overlap" is set: nothing is dropped)
-        if (value < 0 || value > 2)
-            return fail(e, DR_EINVAL, "window_blend is 0 (the mean of the two windows' predictions), 1 (linear cross-fade) or 2 (hand-over "
-                                      "at the middle of the overlap), got %d", value);
-        // (under "solver_order" 2 the history holds the prediction as the previous step blended it, as for "x0_clip")
-        if (e->opt.win_blend != value) end_step_states(e);
-        e->opt.win_blend = value;
+    for (const ValueOption& o : VALUE_OPTIONS) {
+        if (n != o.name) continue;
+        if ((value < o.lo || value > o.hi) && !(o.or_zero && value == 0)) return fail(e, DR_EINVAL, o.refusal, value);
+        if (o.ends_step_states && e->opt.*o.field != value) end_step_states(e);
+        e->opt.*o.field = value;
         return DR_OK;
     }
     // (a mark >= B is refused by dr_step / dr_sample, which know B; no captured chain is dropped: the table is data)
@@ -414,19 +440,6 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value == 0) { e->win_marks.clear(); return DR_OK; }
         auto at = std::lower_bound(e->win_marks.begin(), e->win_marks.end(), value);
         if (at == e->win_marks.end() || *at != value) e->win_marks.insert(at, value);
-        return DR_OK;
-    }
-    if (n == "draws") {      // (B % D and the front-end's batch are checked by the calls, which know B)
-        // (no captured chain is dropped: the value is part of the chain's key - GraphKey - so a chain captured under
-        // another value is simply not replayed, and one captured under this value still is)
-        if (value < 1) return fail(e, DR_EINVAL, "draws is >= 1 (1 = every roll its own clip), got %d", value);
-        if (e->opt.draws != value) end_step_states(e);
-        e->opt.draws = value;
-        return DR_OK;
-    }
-    if (n == "draw_stride") {
-        if (value < 0) return fail(e, DR_EINVAL, "draw_stride is >= 0 (0 = the clips of the batch), got %d", value);
-        e->opt.draw_G = value;
         return DR_OK;
     }
     if (n == "sampling_steps") {
@@ -468,59 +481,6 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         if (value < -1 || value >= e->S)
             return fail(e, DR_EINVAL, "start_step is -1 (the chain's first step) or in [0, timesteps = %d), got %d", e->S, value);
         e->opt.start = value;
-        return DR_OK;
-    }
-    if (n == "start_noise") {      // (part of the chain's key too)
-        if (value != 0 && value != 1)
-            return fail(e, DR_EINVAL, "start_noise is 0 (x on entry is x at the start step) or 1 (a clean roll, diffused to it), got %d", value);
-        e->opt.start_noise = value;
-        return DR_OK;
-    }
-    if (n == "x0_clip") {      // (part of the chain's key too: nothing is dropped, a chain captured under another value is not replayed)
-        if (value < 0 || value > 2)
-            return fail(e, DR_EINVAL, "x0_clip is 0 (off), 1 (clamp the x0 prediction to [0, 1]) or 2 (to [-1, 1]), got %d", value);
-        // (under "solver_order" 2 the history holds the prediction as the previous step clamped it: a dr_step sequence does
-        // not continue across a change - the next step that is not a chain's first is refused, as for "solver_noise")
-        if (e->opt.x0_clamp != value) end_step_states(e);
-        e->opt.x0_clamp = value;
-        return DR_OK;
-    }
-    if (n == "x0_threshold") {      // (stored like "solver_noise": nothing is dropped; part of the chain's key)
-        if (value != 0 && (value < 5000 || value > 10000))
-            return fail(e, DR_EINVAL, "x0_threshold is 0 (off) or the percentile in units of 1 / 10000, 5000 .. 10000 (9950 = 99.5 %%), got %d", value);
-        // (the history of "solver_order" 2 holds the prediction as the previous step thresholded it, as for "x0_clip")
-        if (e->opt.x0_thresh != value) end_step_states(e);
-        e->opt.x0_thresh = value;
-        return DR_OK;
-    }
-    if (n == "cfg_rescale") {      // (stored like "x0_threshold": nothing is dropped; part of the chain's key)
-        if (value < 0 || value > 10000)
-            return fail(e, DR_EINVAL, "cfg_rescale is 0 (off) or phi in units of 1 / 10000, 1 .. 10000 (7000 = 0.7), got %d", value);
-        // (the history of "solver_order" 2 holds the prediction as the previous step rescaled it, as for "x0_clip")
-        if (e->opt.cfg_rescale != value) end_step_states(e);
-        e->opt.cfg_rescale = value;
-        return DR_OK;
-    }
-    if (n == "cfg_project") {      // (stored like "cfg_rescale": nothing is dropped; part of the chain's key)
-        if (value < 0 || value > 10000)
-            return fail(e, DR_EINVAL, "cfg_project is 0 (off) or rho in units of 1 / 10000, 1 .. 10000 (10000 = the whole parallel component), got %d", value);
-        // (the history of "solver_order" 2 holds the prediction as the previous step projected it, as for "x0_clip")
-        if (e->opt.cfg_project != value) end_step_states(e);
-        e->opt.cfg_project = value;
-        return DR_OK;
-    }
-    if (n == "cfg_norm") {         // (likewise)
-        if (value < 0 || value > 100000)
-            return fail(e, DR_EINVAL, "cfg_norm is 0 (off) or the rms bound r in units of 1 / 10000, 1 .. 100000 (500 = 0.05), got %d", value);
-        if (e->opt.cfg_norm != value) end_step_states(e);
-        e->opt.cfg_norm = value;
-        return DR_OK;
-    }
-    if (n == "cfg_momentum") {     // (likewise; the state dr_step left holds sums under the previous value)
-        if (value < -9999 || value > 9999)
-            return fail(e, DR_EINVAL, "cfg_momentum is 0 (off) or beta in units of 1 / 10000, -9999 .. 9999 (-5000 = -0.5), got %d", value);
-        if (e->opt.cfg_momentum != value) end_step_states(e);
-        e->opt.cfg_momentum = value;
         return DR_OK;
     }
     if (n == "guidance_t_min" || n == "guidance_t_max") {
@@ -579,15 +539,13 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
         if (!e->hist.fits(need)) e->hist_key.valid = false;
         if ((rc = grow_chain_buffer(e, e->hist, need, st))) return rc;
     }
+    const Stages stage = stages_of(e->opt, predicts_x0(sampler), NB == 2 * B);      // (what a step of this sampler can run, at some w)
     // option "x0_threshold": the work buffer of the threshold launches (tickets and counts start at zero: armed)
-    if (e->opt.x0_thresh != 0 && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
-    // option "cfg_rescale": the work buffer of the statistics launch (the ticket starts at zero: armed), where the sampler guides
-    if (e->opt.cfg_rescale != 0 && NB == 2 * B && (rc = grow_chain_buffer(e, e->rescale_work, gs_work_words(B, T, RESCALE_SUMS), st))) return rc;
-    // options "cfg_project" / "cfg_norm": likewise
-    if ((e->opt.cfg_project != 0 || e->opt.cfg_norm != 0) && NB == 2 * B &&
-        (rc = grow_chain_buffer(e, e->project_work, gs_work_words(B, T, PROJECT_SUMS), st))) return rc;
+    if (stage.thresh && (rc = grow_chain_buffer(e, e->thresh_work, thresh_work_words(B), st))) return rc;
+    // options "cfg_rescale" and "cfg_project" / "cfg_norm": the work buffer of the statistics launch (the ticket starts at zero: armed)
+    if ((stage.rescale || stage.project) && (rc = grow_stats_work(e, B, T, st))) return rc;
     // option "cfg_momentum": the state, one float per roll element (a buffer that grew holds nothing)
-    if (e->opt.cfg_momentum != 0 && NB == 2 * B) {
+    if (stage.momentum) {
         const size_t need = (size_t)B * T * 88;
         if (!e->momentum.fits(need)) e->mom_key.valid = false;
         if ((rc = grow_chain_buffer(e, e->momentum, need, st))) return rc;
@@ -633,10 +591,11 @@ GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     key.baked = e->baked; key.tuning = tuning_epoch().load();
     key.fe_B = e->fe_B;
     key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
-    key.thresh_work = e->opt.x0_thresh != 0 ? (const unsigned*)e->thresh_work : nullptr;
-    key.rescale_work = key.opt.cfg_rescale != 0 ? (const unsigned*)e->rescale_work : nullptr;
-    key.project_work = (key.opt.cfg_project != 0 || key.opt.cfg_norm != 0) ? (const unsigned*)e->project_work : nullptr;
-    key.momentum = key.opt.cfg_momentum != 0 ? (const float*)e->momentum : nullptr;
+    // the buffers of the stages a step of this chain can run (the same question effective() asked for key.opt)
+    const Stages stage = stages_of(e->opt, predicts_x0(c.sampler), NB == 2 * c.B && !key.w_zero);
+    key.thresh_work = stage.thresh ? (const unsigned*)e->thresh_work : nullptr;
+    key.stats_work = (stage.rescale || stage.project) ? (const unsigned*)e->stats_work : nullptr;
+    key.momentum = stage.momentum ? (const float*)e->momentum : nullptr;
     return key;
 }
 
@@ -881,7 +840,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
     if (rc) return rc;
     // Both pieces of engine state a step can continue are asked about before either is touched: a refusal changes nothing.
     // option "cfg_momentum": the state, over the steps that guide (chain_tables.h: momentum_step)
-    const bool momentum = e->opt.cfg_momentum != 0 && NB == 2 * B && step_guided(e->opt.guid, e->S, w == 0.f, t);
+    const bool momentum = stages_of(e->opt, predicts_x0(sampler), NB == 2 * B && step_guided(e->opt.guid, e->S, w == 0.f, t)).momentum;
     MomentumVerdict mv{MomentumStep::STARTS, t};
     if (momentum) {
         mv = momentum_step(e->mom_key, sampler, B, T, t, e->steps, e->opt.start, e->opt.guid, e->S, w == 0.f);

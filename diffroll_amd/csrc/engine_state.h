@@ -106,17 +106,33 @@ struct ChainOptions {
                cfg_project == o.cfg_project && cfg_norm == o.cfg_norm && cfg_momentum == o.cfg_momentum;
     }
 };
+// Which stages between the network and the update run - the one statement of it, for a step and for a chain: the threshold
+// launches of "x0_threshold" (the x0-prediction samplers, under the range "x0_clip" names), the statistics launch of
+// "cfg_rescale", that of "cfg_project" / "cfg_norm", and its momentum form under "cfg_momentum".  guides: asked about a step,
+// the step runs the unconditional evaluation; asked about a chain, a step of it can - a guiding sampler, w != 0.
+struct Stages { bool thresh, rescale, project, momentum; };
+inline Stages stages_of(const ChainOptions& o, bool x0_sampler, bool guides) {
+    Stages s{};
+    s.thresh = o.x0_thresh != 0 && o.x0_clamp != 0 && x0_sampler;
+    s.rescale = o.cfg_rescale != 0 && guides;
+    s.project = (o.cfg_project != 0 || o.cfg_norm != 0) && guides;
+    s.momentum = s.project && o.cfg_momentum != 0;
+    return s;
+}
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
-// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum" count only where a step can guide - a sampler
-// that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
+// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum" count only for the stages a step of the
+// chain can run (stages_of) - a sampler that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, bool w_zero) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
     if (o.win_O <= 0) o.win_blend = 0;
     o.guid = guiding ? dr::GuidanceInterval{o.guid.lo, o.guid.hi_eff(S)} : dr::GuidanceInterval{};
-    if (!guiding || w_zero) o.cfg_rescale = o.cfg_project = o.cfg_norm = o.cfg_momentum = 0;      // (no step of such a chain reads them)
+    const Stages s = stages_of(o, true, guiding && !w_zero);      // (no step of the chain reads the values of a stage none of them runs)
+    if (!s.rescale) o.cfg_rescale = 0;
+    if (!s.project) o.cfg_project = o.cfg_norm = 0;
+    if (!s.momentum) o.cfg_momentum = 0;
     o.start = start_t;
     return o;
 }
@@ -145,13 +161,12 @@ struct GraphKey {
     int fe_B = 0;
     const float* hist = nullptr;              // the history buffer of solver order 2 (null: order < 2; the parity is baked per node)
     const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
-    const unsigned* rescale_work = nullptr;   // ... and the one the statistics launch of "cfg_rescale" points into, likewise
-    const unsigned* project_work = nullptr;   // ... and that of "cfg_project" / "cfg_norm"
+    const unsigned* stats_work = nullptr;     // ... and the one the statistics launch of "cfg_rescale" or "cfg_project" / "cfg_norm" points into, likewise
     const float* momentum = nullptr;          // the state of "cfg_momentum" (null: off; "starts" is baked per node)
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                opt == o.opt && baked == o.baked && tuning == o.tuning && fe_B == o.fe_B && hist == o.hist &&
-               thresh_work == o.thresh_work && rescale_work == o.rescale_work && project_work == o.project_work && momentum == o.momentum;
+               thresh_work == o.thresh_work && stats_work == o.stats_work && momentum == o.momentum;
     }
 };
 using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
@@ -309,8 +324,9 @@ struct dr_engine {
     int hist_par = 0;
     dr::HistoryKey hist_key;            // dr_step under order 2: what the history holds (chain_tables.h)
     drh::DevBuf<unsigned> thresh_work;  // option "x0_threshold": its work words and results (kernels.h: ThreshArgs), allocated zeroed on first use
-    drh::DevBuf<unsigned> rescale_work; // option "cfg_rescale": the work buffer of its statistics launch (kernels.h: GS_HEAD has the layout), allocated zeroed on first use
-    drh::DevBuf<unsigned> project_work; // options "cfg_project" / "cfg_norm" / "cfg_momentum": theirs, likewise
+    // options "cfg_rescale" and "cfg_project" / "cfg_norm" / "cfg_momentum": the one work buffer of their statistics launches (kernels.h:
+    // GS_HEAD has the layout; a step runs one of them), gs_work_words(B, T, GS_SUMS_MAX) words whichever is set, allocated zeroed on first use
+    drh::DevBuf<unsigned> stats_work;
     // option "cfg_momentum": the state m, one float per roll element (B x T x 88), updated in place by update_momentum_kernel.
     // mom_key: what it holds between dr_steps (chain_tables.h: momentum_step); mom_start: the verdict for the dr_step under
     // way - its guided step starts the state (run_step reads it where no chain says)

@@ -304,7 +304,8 @@ hipError_t launch_thresh_gather(const ThreshArgs& a, int B, float* out, hipStrea
 //   then one record of GS_ROW_WORDS words per row of the batch at GS_HEAD + row * GS_ROW_WORDS - a group's result, in the
 //   record of its FIRST row;
 //   then - grid form - one slot of K doubles per (row, block of GS_BLOCK frames), row-major: the block's K sums.  Every slot
-//   a launch adds up was written by that launch: the slots need no re-arming, and one buffer serves every batch that fits.
+//   a launch adds up was written by that launch: the slots need no re-arming, and one buffer serves every batch that fits -
+//   and every one of the options: the engine holds ONE, of gs_work_words(B, T, GS_SUMS_MAX) words (below), a step runs one launch.
 constexpr int GS_HEAD = 4, GS_ROW_WORDS = 2, GS_BLOCK = 64;
 inline size_t gs_blocks(int T) { return ((size_t)T + GS_BLOCK - 1) / GS_BLOCK; }
 inline size_t gs_work_words(int B, int T, int K) { return (size_t)GS_HEAD + (size_t)B * GS_ROW_WORDS + (size_t)B * gs_blocks(T) * K * 2; }
@@ -323,7 +324,7 @@ constexpr int RESCALE_SUMS = 4;
 struct RescaleArgs {
     UpdateArgs u;          // read: what pred_quad reads (ThreshArgs::u); x0u is set - the step guides
     int phi;               // the option's value, 1 .. 10000
-    unsigned* work;        // the buffer above, gs_work_words(B, T, RESCALE_SUMS) words
+    unsigned* work;        // the buffer above, at least gs_work_words(B, T, RESCALE_SUMS) words
 };
 // What the update's rescaling form needs beside UpdateArgs (the second kernel argument, as ThreshUpd is): g of row 0's
 // record (gs_records) - row b's is GS_ROW_WORDS floats further per row - and what follows the product: th.qs set = the
@@ -349,13 +350,14 @@ hipError_t launch_update_rescale(const UpdateArgs& a, const RescaleUpd& rs, hipS
 // prediction (both after the shared-frame mean / blend): the update c - u bounded in rms, its component parallel to c reduced
 // by rho.  The statistics launches (project.hip) leave (a, b) in the record of the group's FIRST row; the update's projecting
 // form reads them from there.
-// The engine's work buffer is the one above (a second one): a record is [0] a, [1] b, a slot the three doubles {Scc, Scd, Sdd}.
+// The engine's work buffer is the one above (the same one): a record is [0] a, [1] b, a slot the three doubles {Scc, Scd, Sdd}.
 constexpr int PROJECT_SUMS = 3;
+constexpr int GS_SUMS_MAX = RESCALE_SUMS > PROJECT_SUMS ? RESCALE_SUMS : PROJECT_SUMS;      // the K the engine's one buffer is sized for
 struct ProjectArgs {
     UpdateArgs u;          // read: what pred_quad reads (ThreshArgs::u); x0u is set - the step guides
     int rho;               // "cfg_project", 0 .. 10000
     int norm;              // "cfg_norm", 0 .. 100000 (0: no bound); one of the two is not 0
-    unsigned* work;        // the buffer above, gs_work_words(B, T, PROJECT_SUMS) words
+    unsigned* work;        // the buffer above, at least gs_work_words(B, T, PROJECT_SUMS) words
 };
 // What the update's projecting form needs beside UpdateArgs (the second kernel argument, as ThreshUpd is): (a, b) of row 0's
 // record (gs_records) - row b's is GS_ROW_WORDS floats further per row.  What follows is the clamp UpdateArgs names, or nothing.

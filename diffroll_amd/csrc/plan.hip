@@ -471,13 +471,11 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // (x and the tail kernel's output buffer must differ: a caller that hands us xalt itself gets the unfused tail)
     // option "x0_threshold": the selection sits between the network and the update, so the step offers no tail plan - the
     // evaluation keeps its fused stack launch, the head projections write e->x0buf, the rest are ordinary launches
-    const bool thresh = e->opt.x0_thresh != 0 && u.clamp_lo < u.clamp_hi;
     // option "cfg_rescale": likewise at a step that guides - the statistics sit between the network and everything that reads
     // the prediction; a step that runs no unconditional evaluation does not read the option and keeps its tail kernel
-    const bool rescale = e->opt.cfg_rescale != 0 && u.x0u != nullptr;
     // options "cfg_project" / "cfg_norm": likewise (check_options has refused them beside "x0_threshold" and "cfg_rescale")
-    const bool project = (e->opt.cfg_project != 0 || e->opt.cfg_norm != 0) && u.x0u != nullptr;
-    TailPlan* offer = (result && x != xalt && !thresh && !rescale && !project) ? &plan : nullptr;
+    const Stages stage = stages_of(e->opt, predicts_x0(sampler), u.x0u != nullptr);
+    TailPlan* offer = (result && x != xalt && !stage.thresh && !stage.rescale && !stage.project) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
@@ -487,9 +485,9 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         return DR_OK;
     }
     if (result) *result = x;
-    if (project) {      // statistics, update on (a c) + (b y)
+    if (stage.project) {      // statistics, update on (a c) + (b y)
         const ProjectArgs pa = project_args(e, u);
-        if (e->opt.cfg_momentum != 0) {
+        if (stage.momentum) {
             // option "cfg_momentum": the same two launches in their momentum form, over the engine's state.  Whether this
             // step starts the state is a fact of the chain - its first guided step - or dr_step's verdict; a captured chain
             // bakes it into the node
@@ -504,11 +502,11 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         HIPCHK(e, launch_update_project(u, ProjectUpd{gs_records(pa.work)}, st));
         return DR_OK;
     }
-    if (rescale) {      // statistics, [threshold launches ranking |g y - m|], update on g y
+    if (stage.rescale) {      // statistics, [threshold launches ranking |g y - m|], update on g y
         const RescaleArgs ra = rescale_args(e, u);
         RescaleUpd rs{gs_records(ra.work), ThreshUpd{nullptr, 0.f, 0.f}};
         HIPCHK(e, launch_rescale(ra, B, st));
-        if (thresh) {
+        if (stage.thresh) {
             const ThreshArgs ta = thresh_args(e, u);
             HIPCHK(e, launch_threshold_rescaled(ta, rs.g, B, st));
             rs.th = ThreshUpd{reinterpret_cast<const float*>(ta.work + THRESH_HEAD + THRESH_QS), ta.m, ta.r};
@@ -516,7 +514,7 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         HIPCHK(e, launch_update_rescale(u, rs, st));
         return DR_OK;
     }
-    if (thresh) {
+    if (stage.thresh) {
         const ThreshArgs ta = thresh_args(e, u);
         HIPCHK(e, launch_threshold(ta, B, st));
         HIPCHK(e, launch_update_thresh(u, ThreshUpd{reinterpret_cast<const float*>(ta.work + THRESH_HEAD + THRESH_QS), ta.m, ta.r}, st));
@@ -540,7 +538,7 @@ RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u) {
     RescaleArgs a{};
     a.u = u;
     a.phi = e->opt.cfg_rescale;
-    a.work = e->rescale_work;
+    a.work = e->stats_work;
     return a;
 }
 
@@ -549,7 +547,7 @@ ProjectArgs project_args(const dr_engine* e, const UpdateArgs& u) {
     a.u = u;
     a.rho = e->opt.cfg_project;
     a.norm = e->opt.cfg_norm;
-    a.work = e->project_work;
+    a.work = e->stats_work;
     return a;
 }
 

@@ -417,44 +417,42 @@ class Engine:
         self._check(self.lib.dr_debug_launch_counts(self.h, out))
         return int(out[0]), int(out[1])
 
-    def threshold_stats(self, x0c: torch.Tensor, x0u: Optional[torch.Tensor] = None, w: float = 0.0, groups: Optional[int] = None) -> torch.Tensor:
-        """Diagnostic (dr_debug_threshold): the threshold launches of a step under option 'x0_threshold' on the predictions
-        x0c / x0u (B, T, 88), combined with weight w -> (groups, 2) {q, s} per group of the batch, in row / recording order.
-        groups: B clips by default; a window batch passes its number of recordings (times the draws)."""
+    def _stage_stats(self, probe, per_group, x0c, x0u, w, groups, state=None):
+        """What the four dr_debug_* probes of a step's stages share: the predictions (B, T, 88) on the device, the probe's call,
+        -> ((groups, *per_group) its result per group, the state it leaves).  state = (m_prev, want_state): the probe takes the
+        momentum state between the predictions and the shape (None where it takes none)."""
         c = self._dev(x0c)
         u = None if x0u is None else self._dev(x0u)
         B, T, K = c.shape
         assert K == 88 and (u is None or u.shape == c.shape)
-        out = torch.zeros(B, 2, device=self.device, dtype=torch.float32)      # (never more groups than rows)
+        out = torch.zeros(B, *per_group, device=self.device, dtype=torch.float32)      # (never more groups than rows)
+        extra, m = (), None
+        if state is not None:
+            mp = None if state[0] is None else self._dev(state[0])
+            assert mp is None or mp.shape == c.shape
+            m = torch.empty_like(c) if state[1] else None
+            extra = (_ptr(mp), _ptr(m))
         with torch.cuda.device(self.device):
-            self._check(self.lib.dr_debug_threshold(self.h, c.data_ptr(), _ptr(u), B, T, float(w), out.data_ptr(), self._stream()))
-        return out if groups is None else out[:int(groups)]
+            self._check(probe(self.h, c.data_ptr(), _ptr(u), *extra, B, T, float(w), out.data_ptr(), self._stream()))
+        return (out if groups is None else out[:int(groups)]), m
+
+    def threshold_stats(self, x0c: torch.Tensor, x0u: Optional[torch.Tensor] = None, w: float = 0.0, groups: Optional[int] = None) -> torch.Tensor:
+        """Diagnostic (dr_debug_threshold): the threshold launches of a step under option 'x0_threshold' on the predictions
+        x0c / x0u (B, T, 88), combined with weight w -> (groups, 2) {q, s} per group of the batch, in row / recording order.
+        groups: B clips by default; a window batch passes its number of recordings (times the draws)."""
+        return self._stage_stats(self.lib.dr_debug_threshold, (2,), x0c, x0u, w, groups)[0]
 
     def rescale_stats(self, x0c: torch.Tensor, x0u: Optional[torch.Tensor] = None, w: float = 0.0, groups: Optional[int] = None) -> torch.Tensor:
         """Diagnostic (dr_debug_rescale): the statistics launch of a guided step under option 'cfg_rescale' on the predictions
         x0c / x0u (B, T, 88), combined with weight w -> (groups,) the factor g per group of the batch, in row / recording order.
         groups: B clips by default; a window batch passes its number of recordings (times the draws)."""
-        c = self._dev(x0c)
-        u = None if x0u is None else self._dev(x0u)
-        B, T, K = c.shape
-        assert K == 88 and (u is None or u.shape == c.shape)
-        out = torch.zeros(B, device=self.device, dtype=torch.float32)      # (never more groups than rows)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.dr_debug_rescale(self.h, c.data_ptr(), _ptr(u), B, T, float(w), out.data_ptr(), self._stream()))
-        return out if groups is None else out[:int(groups)]
+        return self._stage_stats(self.lib.dr_debug_rescale, (), x0c, x0u, w, groups)[0]
 
     def project_stats(self, x0c: torch.Tensor, x0u: Optional[torch.Tensor] = None, w: float = 0.0, groups: Optional[int] = None) -> torch.Tensor:
         """Diagnostic (dr_debug_project): the statistics launch of a guided step under options 'cfg_project' / 'cfg_norm' on the
         predictions x0c / x0u (B, T, 88), combined with weight w -> (groups, 2) the coefficients (a, b) per group of the batch,
         in row / recording order.  groups: B clips by default; a window batch passes its number of recordings (times the draws)."""
-        c = self._dev(x0c)
-        u = None if x0u is None else self._dev(x0u)
-        B, T, K = c.shape
-        assert K == 88 and (u is None or u.shape == c.shape)
-        out = torch.zeros(B, 2, device=self.device, dtype=torch.float32)      # (never more groups than rows)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.dr_debug_project(self.h, c.data_ptr(), _ptr(u), B, T, float(w), out.data_ptr(), self._stream()))
-        return out if groups is None else out[:int(groups)]
+        return self._stage_stats(self.lib.dr_debug_project, (2,), x0c, x0u, w, groups)[0]
 
     def momentum_stats(self, x0c: torch.Tensor, x0u: Optional[torch.Tensor] = None, m_prev: Optional[torch.Tensor] = None, w: float = 0.0,
                        groups: Optional[int] = None, want_state: bool = True):
@@ -462,17 +460,7 @@ class Engine:
         x0c / x0u (B, T, 88) combined with weight w and the state m_prev (B, T, 88; None: the step starts the state) ->
         ((groups, 2) the coefficients (a, b) per group over yb = c + m, in row / recording order, and m (B, T, 88), the state the
         step leaves - None unless want_state)."""
-        c = self._dev(x0c)
-        u = None if x0u is None else self._dev(x0u)
-        mp = None if m_prev is None else self._dev(m_prev)
-        B, T, K = c.shape
-        assert K == 88 and (u is None or u.shape == c.shape) and (mp is None or mp.shape == c.shape)
-        out = torch.zeros(B, 2, device=self.device, dtype=torch.float32)      # (never more groups than rows)
-        m = torch.empty_like(c) if want_state else None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.dr_debug_momentum(self.h, c.data_ptr(), _ptr(u), _ptr(mp), _ptr(m), B, T, float(w), out.data_ptr(),
-                                                   self._stream()))
-        return (out if groups is None else out[:int(groups)]), m
+        return self._stage_stats(self.lib.dr_debug_momentum, (2,), x0c, x0u, w, groups, state=(m_prev, want_state))
 
     def set_window_breaks(self, marks):
         """Replace the marks of option 'window_break' (the windows of the next batch that start a new recording)."""

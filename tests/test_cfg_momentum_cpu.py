@@ -347,7 +347,7 @@ def test_option_is_public_and_documented():
         for word in words:
             assert word in body, (doc_name, word)
     abi = open(os.path.join(ROOT, "diffroll_amd", "csrc", "abi.hip")).read()
-    assert 'n == "cfg_momentum"' in abi and "momentum_step(" in abi
+    assert '{"cfg_momentum", &ChainOptions::cfg_momentum,' in abi and "momentum_step(" in abi      # (its row of the option table)
 
 
 def test_the_built_library_knows_the_option():

@@ -284,7 +284,7 @@ def test_options_are_public_and_documented():
         for word in words:
             assert word in body, (doc_name, word)
     abi = open(os.path.join(ROOT, "diffroll_amd", "csrc", "abi.hip")).read()
-    assert 'n == "cfg_project"' in abi and 'n == "cfg_norm"' in abi
+    assert '{"cfg_project", &ChainOptions::cfg_project,' in abi and '{"cfg_norm", &ChainOptions::cfg_norm,' in abi      # (their rows of the option table)
     quad = open(os.path.join(ROOT, "diffroll_amd", "csrc", "project_quad.h")).read()
     assert "momentum" in quad and '"cfg_rescale"' in quad      # what is left out, said where the code is
 

@@ -194,7 +194,7 @@ def test_option_is_public_and_documented():
         for word in words:
             assert word in body, (doc_name, word)
     abi = open(os.path.join(ROOT, "diffroll_amd", "csrc", "abi.hip")).read()
-    assert 'n == "cfg_rescale"' in abi
+    assert '{"cfg_rescale", &ChainOptions::cfg_rescale,' in abi      # (its row of the option table)
     assert set(re.findall(r'n == "(guidance\w*)"', abi)) == {"guidance_t_min", "guidance_t_max"}
 
 
