@@ -29,6 +29,7 @@ PlanKnobs plan_knobs() {
     PlanKnobs k;
     k.tile = t.tile; k.pw = t.pw; k.pw_nw = t.pw_nw; k.pwk = t.pwk; k.ksplit_max = t.ksplit_max;
     k.ksplit_blocks = t.ksplit_blocks; k.stack3 = t.stack3; k.stack_fl = t.stack_fl;
+    k.xcd_n = t.xcd_n; k.xcd_model = t.xcd_model; k.tail_t4 = t.tail_t4; k.one_ks = t.one_ks;
     return k;
 }
 
@@ -233,27 +234,9 @@ hipError_t launch_pointwise_ksplit(const GemmArgs& a, int NW, hipStream_t s) {
     return NW == 1 ? launch_pwk_t<1>(a, s) : NW == 2 ? launch_pwk_t<2>(a, s) : hipErrorInvalidValue;
 }
 
-// Block -> XCD mapping of a per-phase GEMM launch (see gemm_kernel): 0 = one weight panel (M tile) per XCD, 1 = the M
-// tiles of a frame tile share an XCD.  Chosen by the bytes each choice pulls through the XCDs' L2s (what the FETCH
-// counters see): with mapping 0 every XCD streams ITS panel once (L2-resident if it fits) and all of X; with mapping 1
-// every XCD streams its share of X once and ALL panels - once if the whole weight matrix fits its L2, else once per
-// round of concurrently resident frame tiles.  (Until round 3 the rule was "xbytes > wbytes", which picked mapping 1
-// for 5-round launches of big convs - 640-frame generation batches - and paid 13.9x the algorithmic traffic.)
+// Block -> XCD mapping of this launch: launch_plan.h: pick_xcd_mapping, under the knobs as they are now
 static int pick_xcd_mapping(const GemmArgs& a, int NT, int BN) {
-    // weights: MT*128 rows x 32*kchunks*taps floats; activations: NT frame tiles of BN frames x 32*kchunks floats
-    const int MT = a.MT;
-    const double wbytes = 4.0 * 128.0 * a.MT * 32.0 * a.kchunks * a.taps, xbytes = 4.0 * (double)NT * BN * 32.0 * a.kchunks;
-    if (MT <= 1 || NT % 8 != 0) return 0;
-    if (tuning().xcd_n >= 0) return tuning().xcd_n;      // A/B experiments
-    if (!tuning().xcd_model) return xbytes > wbytes ? 1 : 0;
-    const double l2 = 4.0 * 1024 * 1024, cus_per_xcd = 32.0;
-    const double conc = cus_per_xcd / MT < 1.0 ? 1.0 : cus_per_xcd / MT;               // frame tiles resident per XCD (mapping 1)
-    const double rounds1 = wbytes <= l2 ? 1.0 : ((NT / 8.0) / conc < 1.0 ? 1.0 : (NT / 8.0) / conc);
-    const double cost1 = 8.0 * rounds1 * wbytes + xbytes;
-    const double panel = wbytes / MT;
-    const double rounds0 = panel <= l2 ? 1.0 : (double)((long)MT * NT + 255) / 256;    // a panel that does not fit is re-streamed per round
-    const double cost0 = rounds0 * wbytes + 8.0 * xbytes;
-    return cost1 < cost0 ? 1 : 0;
+    return pick_xcd_mapping(plan_knobs(), a.MT, NT, BN, a.kchunks, a.taps);
 }
 
 template <int NW>
@@ -444,12 +427,7 @@ hipError_t launch_gemm(const GemmArgs& a, int epi, int NI, hipStream_t s, int pr
             return a.kchunks % 4 == 0 ? launch_gemm_t<1, 4, EPI_RES_SKIP, 1>(a, s) : launch_gemm_t<1, 1, EPI_RES_SKIP, 1>(a, s);
         return hipErrorInvalidValue;
     }
-    // 1x1 GEMMs restage X every step: take up to 128 channels per chunk there (fewer hand-overs);
-    // EPI_RES_SKIP also keeps its read-modify-write tile in LDS, which leaves room for 64 channels at NI = 2
-    int KS = a.taps != 1 ? 1 : (a.kchunks % 4 == 0 ? 4 : (a.kchunks % 2 == 0 ? 2 : 1));
-    if (epi == EPI_RES_SKIP && NI == 2 && KS == 4) KS = 2;
-    const int ks_force = tuning().one_ks;
-    if (ks_force && a.taps == 1 && a.kchunks % ks_force == 0) KS = ks_force;
+    const int KS = pick_one_ks(a.taps, a.kchunks, NI, epi, tuning().one_ks);      // channels per hand-over (launch_plan.h)
     if (NI == 1) {
         if (KS == 4) return launch_gemm_ni<1, 4>(a, epi, s);
         return KS == 2 ? launch_gemm_ni<1, 2>(a, epi, s) : launch_gemm_ni<1, 1>(a, epi, s);

@@ -40,15 +40,18 @@ struct Tuning {
     std::atomic<int> pack_threads{16};   // host threads packing the layers at dr_commit (1 = serial)
     std::atomic<int> tile{0};            // force a conv / LDS-staged 1x1 tile: 3201 / 3202 / 3203 / 3205 (32x32 MFMA, NI) or 1603 / 1605 (16x16, NJ); 0 = cost model
     std::atomic<int> pw{1};              // 1x1 residual/skip GEMM: 1 = operands direct from L2 (pw_kernel), 0 = the LDS-staged kernels
-    std::atomic<int> pw_nw{0};           // force 32 * pw_nw frames per pw_kernel block (2..5); 0 = cost model
-    std::atomic<int> pwk{1};             // under-filled 1x1 launches: K split over the block's waves (pwk_kernel)
+    std::atomic<int> pw_nw{0};           // force 32 * pw_nw frames per pw_kernel block (2..5); 0 = cost model; under pwk = 2: 1 / 2 = pwk_kernel's width
+    std::atomic<int> pwk{1};             // under-filled 1x1 launches: K split over the block's waves (pwk_kernel); 0 = never; 2 = at every fill,
+                                         // wherever the kernel exists (fp32, K slabs a multiple of 4): tests
     std::atomic<int> ksplit_max{16};     // largest split-K factor of gemm_kernel launches (1 = never split)
     std::atomic<long> ksplit_blocks{0};  // cap on tiles x ksplit (0 = 2048 fp32 / 256 split-bf16)
-    std::atomic<int> one_ks{0};          // force the 1x1 GEMMs' channels-per-hand-over (KS = 1 / 2 / 4); 0 = by divisibility
+    std::atomic<int> one_ks{0};          // force the 1x1 GEMMs' channels-per-hand-over (KS = 1 / 2 / 4) where it divides the K slabs and fits the LDS;
+                                         // 0 = by divisibility (launch_plan.h: pick_one_ks)
     std::atomic<int> stack3{1};          // the split-bf16 flavour of the fused residual stack
     std::atomic<int> stack_fl{0};        // force the fused stack's block flavour (1 / 2 / 5 = 64 / 128 / 160-frame blocks); -5 = never the 160-frame one; 0 = cost model
     std::atomic<int> tail_t4{0};         // force the item width of the tail kernel's first-layer conv (1 = 64, 3 = 96 frames); 0 = by rounds x width
-    std::atomic<int> xcd_n{-1};          // force the block -> XCD mapping of per-phase GEMM launches (0 / 1); -1 = traffic model
+    std::atomic<int> xcd_n{-1};          // force the block -> XCD mapping of per-phase GEMM launches (0 / 1) where mapping 1 exists (more than one
+                                         // M tile, frame tiles a multiple of 8); -1 = traffic model (launch_plan.h: pick_xcd_mapping)
     std::atomic<int> xcd_model{1};       // 0 = the rounds 1-2 rule (activation bytes > weight bytes)
     std::atomic<int> s3_eager{0};        // build the split-bf16 packings at every dr_commit (rounds 1-3 behaviour)
     std::atomic<int> debug_chunks{0};    // dr_debug_ticks prints the chunk-start tick marks

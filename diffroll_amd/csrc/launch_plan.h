@@ -32,6 +32,7 @@ struct PlanKnobs {
     int tile = 0, pw = 1, pw_nw = 0, pwk = 1, ksplit_max = 16;
     long ksplit_blocks = 0;
     int stack3 = 1, stack_fl = 0;
+    int xcd_n = -1, xcd_model = 1, tail_t4 = 0, one_ks = 0;
 };
 
 // frames per block of gemm_kernel<NI, ...>: 64 / 128 (NI = 1 / 2), 96 / 160 (NI = 3 / 5: that many 32-frame MFMA tiles per
@@ -42,6 +43,53 @@ inline size_t gemm_lds_bytes(int NI, int KS, int taps, int dil, int prec, int ep
     const int BN = gemm_block_frames(NI);
     const int FW = BN + 2 * halo;
     return (size_t)2 * (prec == 2 ? 4 : prec ? 12 : 8) * KS * FW * 16 + (epi == EPI_RES_SKIP ? (size_t)32 * BN * 16 : 0);
+}
+
+// Block -> XCD mapping of a per-phase GEMM launch (gemm.hip: block_tile) of MT row tiles x NT frame tiles of BN frames:
+// 0 = one weight panel (M tile) per XCD, 1 = the M tiles of a frame tile share an XCD (needs NT % 8 == 0 and more than one
+// M tile; a forced tune.xcd_n is ignored elsewhere).  Chosen by the bytes each choice pulls through the XCDs' L2s (what the
+// FETCH counters see): with mapping 0 every XCD streams ITS panel once (L2-resident if it fits) and all of X; with mapping 1
+// every XCD streams its share of X once and ALL panels - once if the whole weight matrix fits its L2, else once per
+// round of concurrently resident frame tiles.  (Until round 3 the rule was "xbytes > wbytes" - tune.xcd_model = 0 - which
+// picked mapping 1 for 5-round launches of big convs - 640-frame generation batches - and paid 13.9x the algorithmic traffic.)
+inline int pick_xcd_mapping(const PlanKnobs& k, int MT, int NT, int BN, int kchunks, int taps) {
+    // weights: MT*128 rows x 32*kchunks*taps floats; activations: NT frame tiles of BN frames x 32*kchunks floats
+    const double wbytes = 4.0 * 128.0 * MT * 32.0 * kchunks * taps, xbytes = 4.0 * (double)NT * BN * 32.0 * kchunks;
+    if (MT <= 1 || NT % 8 != 0) return 0;
+    if (k.xcd_n >= 0) return k.xcd_n;      // A/B experiments
+    if (!k.xcd_model) return xbytes > wbytes ? 1 : 0;
+    const double l2 = 4.0 * 1024 * 1024, cus_per_xcd = 32.0;
+    const double conc = cus_per_xcd / MT < 1.0 ? 1.0 : cus_per_xcd / MT;               // frame tiles resident per XCD (mapping 1)
+    const double rounds1 = wbytes <= l2 ? 1.0 : ((NT / 8.0) / conc < 1.0 ? 1.0 : (NT / 8.0) / conc);
+    const double cost1 = 8.0 * rounds1 * wbytes + xbytes;
+    const double panel = wbytes / MT;
+    const double rounds0 = panel <= l2 ? 1.0 : (double)((long)MT * NT + 255) / 256;    // a panel that does not fit is re-streamed per round
+    const double cost0 = rounds0 * wbytes + 8.0 * xbytes;
+    return cost1 < cost0 ? 1 : 0;
+}
+
+// Channels per hand-over of an fp32 gemm_kernel launch, in 32-channel slabs (KS = 1 / 2 / 4).  1x1 GEMMs restage X every
+// step: take up to 128 channels per chunk there (fewer hand-overs); EPI_RES_SKIP also keeps its read-modify-write tile in
+// LDS, which leaves room for 64 channels at NI = 2.  A forced value (tune.one_ks) is taken where it divides the slabs and
+// its X tiles fit the 160 KiB of LDS; elsewhere the unforced choice stands.
+inline int pick_one_ks(int taps, int kchunks, int NI, int epi, int forced) {
+    int KS = taps != 1 ? 1 : (kchunks % 4 == 0 ? 4 : (kchunks % 2 == 0 ? 2 : 1));
+    if (epi == EPI_RES_SKIP && NI == 2 && KS == 4) KS = 2;
+    if ((forced == 1 || forced == 2 || forced == 4) && taps == 1 && kchunks % forced == 0 &&
+        gemm_lds_bytes(NI, forced, 1, 1, 0, epi) <= 160 * 1024)
+        KS = forced;
+    return KS;
+}
+
+// Item width of the tail kernel's copy of the next step's first-layer conv (its part T4), as gemm_kernel's NI: 1 = 64-frame
+// items, 3 = 96.  Rounds over the pair's 2 * gsize blocks (gsize where this step is not guided: dual = 0; gsize = MT x the
+// BN-frame tiles of a clip) x frames per item: 64 unless 96 is strictly cheaper or forced (tune.tail_t4 = 3; 1 forces 64).
+// The 96-frame body exists with blocked accumulation only (fold).
+inline int tail_t4_width(bool fold, int forced, bool dual, int MT, int T, int BN) {
+    const long pair_blocks = (dual ? 2L : 1L) * MT * ((T + BN - 1) / BN);
+    const long n64 = (long)MT * ((T + 63) / 64), n96 = (long)MT * ((T + 95) / 96);
+    const long c64 = (n64 + pair_blocks - 1) / pair_blocks * 64, c96 = (n96 + pair_blocks - 1) / pair_blocks * 96;
+    return (fold && forced != 1 && (c96 < c64 || forced == 3)) ? 3 : 1;
 }
 
 // THE split-K decision of gemm_kernel launches (the launcher takes it; the engine's tile choice prices a launch with it,
@@ -150,11 +198,16 @@ inline int pick_ni(const PlanKnobs& k, int MT, int NB, int T, int taps, int dil,
     return pick_tile(k, MT, NB, T, taps, dil, prec, EPI_GATE, false).n;
 }
 // tile of the 1x1 residual/skip GEMM: flavor 2 = operands direct from L2 (pw_kernel), fp32 only
-// (kchunks: 32-channel slabs of K; 0 = MT tiles cover all rows)
+// (kchunks: 32-channel slabs of K; 0 = MT tiles cover all rows); flavor 3 = pwk_kernel, the K loop split over the block's waves
 inline Tile pick_pointwise_tile(const PlanKnobs& k, int MT, int NB, int T, int prec, int kchunks = 0) {
     if (prec) return Tile{0, 1};
     const int pw = k.pw, pw_ni = k.pw_nw;      // A/B experiments: 0 = LDS-staged kernels / force 32*NW-frame blocks
     if (!pw) return pick_tile(k, MT, NB, T, 1, 1, 0, EPI_RES_SKIP, true);
+    // tune.pwk = 2 (tests): pwk_kernel wherever it exists (K slabs a multiple of 4), whatever the fill; tune.pw_nw = 1 / 2
+    // then names ITS width
+    const bool pwk_ok = (kchunks ? kchunks : 2 * MT) % 4 == 0;
+    const int pwk_nw = (long)4 * MT * NB * ((T + 31) / 32) <= 512 ? 1 : 2;
+    if (k.pwk == 2 && pwk_ok && pw_ni <= 2) return Tile{3, pw_ni ? pw_ni : pwk_nw};
     if (pw_ni) return Tile{2, pw_ni};
     // launches that cannot fill half the chip even with 64-frame blocks (single clips): 32-row x 32-frame tiles whose
     // four waves split K in-block (flavor 3, pwk_kernel: 256 blocks at config 1, 13.9 -> 8 us per launch); without it
@@ -162,8 +215,7 @@ inline Tile pick_pointwise_tile(const PlanKnobs& k, int MT, int NB, int T, int p
     // split-K through the workspace.  (Measured and rejected in round 3: 32-frame blocks of the direct kernel instead -
     // 64 blocks at config 1 - 35.2 vs 34.0 ms per chain.)
     if ((long)MT * NB * ((T + 63) / 64) <= 128) {
-        if (k.pwk && k.ksplit_max > 1 && (kchunks ? kchunks : 2 * MT) % 4 == 0)
-            return Tile{3, (long)4 * MT * NB * ((T + 31) / 32) <= 512 ? 1 : 2};
+        if (k.pwk && k.ksplit_max > 1 && pwk_ok) return Tile{3, pwk_nw};
         return pick_tile(k, MT, NB, T, 1, 1, 0, EPI_RES_SKIP, true);
     }
     // cost = block rounds over the 256 CUs x frames per block; 64-frame blocks carry a measured 7 % penalty

@@ -316,7 +316,7 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, const PlanKnobs& k,
             ta.c_bs = (long)2 * Cp * T; ta.c_n = e->fe_B;
             ta.taps = e->K; ta.dil = w0.dil;
             ta.fold = np.fold;
-            ta.t4_ni = tuning().tail_t4;
+            ta.t4_ni = k.tail_t4;
             ta.g = e->g;
         }
     }

@@ -256,12 +256,7 @@ hipError_t launch_tail(const TailArgs& s, hipStream_t st) {
     size_t lds = 24 * 32 * 16;
     if (s.conv_w) {
         if (s.dual_next <= 0 || !s.in_w || (s.taps & 1) == 0) return hipErrorInvalidValue;
-        // T4's item width: rounds over the pair's 2 * gsize blocks (gsize where this step is not guided) x frames per item,
-        // 64 unless 96 is strictly cheaper (the 96-frame body exists with blocked accumulation only)
-        const long pair_blocks = (s.dual > 0 ? 2L : 1L) * MT * tps;
-        const long n64 = (long)MT * ((s.T + 63) / 64), n96 = (long)MT * ((s.T + 95) / 96);
-        const long c64 = (n64 + pair_blocks - 1) / pair_blocks * 64, c96 = (n96 + pair_blocks - 1) / pair_blocks * 96;
-        b.t4_ni = (s.fold && s.t4_ni != 1 && (c96 < c64 || s.t4_ni == 3)) ? 3 : 1;
+        b.t4_ni = tail_t4_width(s.fold, s.t4_ni, s.dual > 0, MT, s.T, s.BN);      // T4's item width (launch_plan.h); s.t4_ni: forced
         lds = std::max(lds, gemm_lds_bytes(b.t4_ni, 1, s.taps, s.dil, 0, EPI_GATE));
         if (lds > 160 * 1024) return hipErrorInvalidValue;
     }

@@ -40,6 +40,10 @@ DRIVER = r"""
                 else if (f == "ksplit_blocks") k.ksplit_blocks = value;
                 else if (f == "stack3") k.stack3 = (int)value;
                 else if (f == "stack_fl") k.stack_fl = (int)value;
+                else if (f == "xcd_n") k.xcd_n = (int)value;
+                else if (f == "xcd_model") k.xcd_model = (int)value;
+                else if (f == "tail_t4") k.tail_t4 = (int)value;
+                else if (f == "one_ks") k.one_ks = (int)value;
                 else { printf("unknown knob %s\n", name); return 1; }
             }
             const dr::NetPlan p = dr::plan_network(s, k);
