@@ -15,7 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
 from oracle import diffroll_ref as R  # noqa: E402
-from test_gpu_parity import make_model  # noqa: E402
+from testlib import make_model  # noqa: E402
 from tools import tuning_env  # noqa: E402
 
 tuning_env.install()        # the parent pins the kernel flavours of this process (DR_TEST_TUNE)

@@ -2,7 +2,7 @@
 reference is computed once per process and shared: tests/test_x0_clip_cpu.py checks on the references alone that every
 case exercises the bounds it claims, the GPU tests hold the engine to the same tensors.
 
-Shapes: B = 2, T = 40, hp_of(layers=3, k=3) of test_gpu_respaced.py (64 channels, 200 steps).  The seeds below were picked
+Shapes: B = 2, T = 40, testlib.hp_of(layers=3, k=3) (64 channels, 200 steps).  The seeds below were picked
 on the CPU, before any GPU run, until the conditions of test_x0_clip_cpu.py::test_gpu_cases_exercise_the_clamp held: with
 this synthetic network an unguided or weakly guided (w = 0.5) prediction lies in about [-0.6, 0.6] - it crosses 0 on half
 of its elements and never reaches 1 or -1 - while at w = 3 a few per cent leave [-1, 1] on either side.  So the lower
@@ -13,7 +13,7 @@ import functools
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_respaced import S, hp_of, inputs
+from testlib import ATOL, HOP, S, hp_of, inputs
 
 import chain_ref as CR
 import clip_ref as CL
@@ -109,7 +109,6 @@ def fused_reference(code=1, seed=5):
 def long_case():
     """Long-form windows as test_gpu_solver_noise.py sizes them: three 640-frame windows sharing 160 frames, C = 128."""
     from diffroll_amd import longform
-    from test_gpu_respaced import HOP
     hp = hp_of(channels=128, layers=3)
     p = R.synthetic_params(hp, seed=81)
     g = torch.Generator().manual_seed(81)
@@ -129,7 +128,6 @@ def long_inputs(n=20):
     """(x_T gathered into its windows, their spectrograms, {t: the canvas draw of step t gathered into the windows})."""
     from diffroll_amd import longform
     from oracle import philox
-    from test_gpu_respaced import HOP
     hp, p, plan, wav, x_T = long_case()
     z = {t: longform.gather_windows(torch.from_numpy(philox.step_noise(LONG_SEED, LONG_REC, 1, plan.T_c * 88, t)).reshape(plan.T_c, 88),
                                     plan).unsqueeze(1)
@@ -151,7 +149,6 @@ def exercised(moved, claims, roll, unclipped):
     """The conditions a case's reference must meet for the case to test the clamp: each bound it claims moves at least 1 % of
     the elements at some visited step, no step has more than 90 % moved, and the clipped roll is at least 100 ATOL away from
     the unclipped one.  A case that claims nothing is the inert one: nothing moves and the two rolls are equal."""
-    from test_gpu_respaced import ATOL
     lo = max(v[0] for v in moved.values())
     hi = max(v[1] for v in moved.values())
     worst = max(v[0] + v[1] for v in moved.values())

@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model, maxdiff
+from testlib import make_model, maxdiff
 
 import chain_ref as CR
 

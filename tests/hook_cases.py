@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import ATOL_STEP, make_model, maxdiff
+from testlib import ATOL_STEP, make_model, maxdiff
 
 pytestmark = pytest.mark.gpu
 

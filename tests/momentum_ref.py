@@ -53,12 +53,12 @@ def explicit_sum(ds, beta: int) -> torch.Tensor:
     return out
 
 
-def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, momentum: int = 0,
-                 project: int = 0, norm: int = 0, w: float = 0.0, code: int = 0, O: int = 0, mode: int = 0, marks=(), draws: int = 1,
+def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, cfg_momentum: int = 0,
+                 cfg_project: int = 0, cfg_norm: int = 0, w: float = 0.0, code: int = 0, O: int = 0, mode: int = 0, marks=(), draws: int = 1,
                  interval=None, order: int = 0, solver_noise: int = 0, start: Optional[int] = None):
     """project_ref.sample_chain with the momentum: at a step that guides, y and c after the blend -> m, yb by the recurrence
     (the first guided step the chain runs starts the state; a step that does not guide neither reads nor writes it) -> (a, b)
-    per group over yb -> y' = (a c) + (b yb) -> the clamp of code -> update.  momentum = 0: project_ref's chain, bit for bit.
+    per group over yb -> y' = (a c) + (b yb) -> the clamp of code -> update.  cfg_momentum = 0: project_ref's chain, bit for bit.
     Returns (the final roll, {t: [(k, rho, s, a, b) float64 per group]}, {t: (rms |m|, rms |d|)}) over the guided steps."""
     S = int(hp["timesteps"])
     family, branch = CR.SAMPLERS[sampler]
@@ -72,13 +72,13 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
         for t, row in CR.chain_rows(hp, sampler, n, order, solver_noise, start).items():
             guides = branch is not None and w != 0.0 and lo <= t <= hi
             y = CR.prediction(params, hp, sampler, x, spec_c, t, w if guides else 0.0, table)
-            c = CR.prediction(params, hp, sampler, x, spec_c, t, 0.0, table) if guides and (project or norm) else None
+            c = CR.prediction(params, hp, sampler, x, spec_c, t, 0.0, table) if guides and (cfg_project or cfg_norm) else None
             if O:
                 y = BR.blend_groups(y, groups, T - O, O, mode)
                 c = BR.blend_groups(c, groups, T - O, O, mode) if c is not None else None
             if c is not None:
-                if momentum:
-                    state, yb = recurrence(y, c, state, momentum)
+                if cfg_momentum:
+                    state, yb = recurrence(y, c, state, cfg_momentum)
                     d = (y - c).double()
                     rms[t] = (float(state.double().pow(2).mean().sqrt()), float(d.pow(2).mean().sqrt()))
                     y = yb
@@ -86,8 +86,8 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
                 seen[t] = []
                 for i, rows in enumerate(groups):
                     sums = PR.group_sums(c, y, rows)
-                    ab[i] = PR.coefficients(project, norm, w, *sums)
-                    seen[t].append(PR.parts(project, norm, w, *sums))
+                    ab[i] = PR.coefficients(cfg_project, cfg_norm, w, *sums)
+                    seen[t].append(PR.parts(cfg_project, cfg_norm, w, *sums))
                 y = PR.apply(c, y, ab, groups)
             if code:
                 y = y.clamp(*CL.BOUNDS[code])

@@ -10,7 +10,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import diffroll_ref as R                      # noqa: E402  (checker only)
-from tests.test_gpu_parity import make_model             # noqa: E402
+from tests.testlib import make_model                  # noqa: E402
 
 
 def main():

@@ -1,13 +1,13 @@
 """The inputs of the "cfg_project" / "cfg_norm" GPU tests (tests/test_gpu_cfg_project.py) and their CPU references - test
 infrastructure.  Each reference is computed once per process and shared; it is never modified.
 
-The inputs are those of tests/rescale_cases.py: B = 2, T = 40, hp_of() of test_gpu_respaced.py (64 channels, 4 layers, k = 9,
+The inputs are those of tests/rescale_cases.py: B = 2, T = 40, testlib.hp_of() (64 channels, 4 layers, k = 9,
 200 steps), 20 visited steps, w = 3; the inpainting sampler's time mask covers spectrogram frames [10, 20)."""
-import functools
-
 import project_ref as PR
 import rescale_cases as RC
+import stage_scenarios as SS
 from rescale_cases import B, GUIDING, MASK, N_STEPS, PHILOX_SEED, TN, W, mask_of, philox_z, setup, spec_of, start_step  # noqa: F401
+from testlib import ATOL
 
 # (cfg_project, cfg_norm): rho = 0.5 and 1, alone and with r = 0.05; the last bound never binds
 VALUES = ((5000, 0), (10000, 0), (5000, 500), (10000, 500), (10000, 100000))
@@ -18,26 +18,15 @@ MAIN = (10000, 500)
 OPTION_CASES = [(name, kw, facade) for name, kw, facade in RC.OPTION_CASES if name != "clip-threshold"]
 
 
-@functools.lru_cache(maxsize=None)
-def _reference(sampler, project, norm, philox, opts):
-    hp, p, _, x, noise = setup()
-    kw = dict(opts)
-    if kw.get("start") == "strength":
-        kw["start"] = start_step()
-    return PR.sample_chain(p, hp, sampler, x, spec_of(sampler), philox_z() if philox else noise, N_STEPS, project=project, norm=norm,
-                           w=W, **kw)
-
-
 def reference(sampler, project, norm, philox=False, **opts):
     """(final roll, {t: [(k, rho, s, a, b) per roll]}) of the restatement; project = norm = 0: the options off."""
-    return _reference(sampler, project, norm, philox, tuple(sorted(opts.items())))
+    return SS.reference(PR.sample_chain, sampler, {"cfg_project": project, "cfg_norm": norm}, philox, **opts)
 
 
 def assert_active(sampler, project, norm, philox=False, **opts):
     """The case projects: rho k >= 0.2 at every guided step and roll of the restated chain, s <= 0.9 there where r = 0.05, and
     the roll is at least 100 ATOL (10 ATOL under the guidance interval, as in rescale_cases) from the chain with the options
     off.  Returns the reference roll."""
-    from test_gpu_respaced import ATOL
     roll, seen = reference(sampler, project, norm, philox, **opts)
     off, _ = reference(sampler, 0, 0, philox, **opts)
     rows = [row for step in seen.values() for row in step]

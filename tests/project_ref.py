@@ -104,12 +104,12 @@ def apply(c: torch.Tensor, y: torch.Tensor, ab: np.ndarray, groups) -> torch.Ten
     return y
 
 
-def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, project: int = 0,
-                 norm: int = 0, w: float = 0.0, code: int = 0, O: int = 0, mode: int = 0, marks=(), draws: int = 1, interval=None,
+def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, cfg_project: int = 0,
+                 cfg_norm: int = 0, w: float = 0.0, code: int = 0, O: int = 0, mode: int = 0, marks=(), draws: int = 1, interval=None,
                  order: int = 0, solver_noise: int = 0, start: Optional[int] = None):
     """The chain of chain_ref.sample_chain with the projected step: predict y (weight w) and c (weight 0) -> blend both over
     the shared frames (O > 0: a window batch with recording marks / draws as thresh_ref.window_groups reads them) -> at a step
-    that guides y = (a c) + (b y) per group -> the clamp of code -> update.  project = norm = 0: the options off.
+    that guides y = (a c) + (b y) per group -> the clamp of code -> update.  cfg_project = cfg_norm = 0: the options off.
     Returns (the final roll, {t: [(k, rho, s, a, b) float64 per group]} over the guided steps)."""
     S = int(hp["timesteps"])
     family, branch = CR.SAMPLERS[sampler]
@@ -123,7 +123,7 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
         for t, row in CR.chain_rows(hp, sampler, n, order, solver_noise, start).items():
             guides = branch is not None and w != 0.0 and lo <= t <= hi
             y = CR.prediction(params, hp, sampler, x, spec_c, t, w if guides else 0.0, table)
-            c = CR.prediction(params, hp, sampler, x, spec_c, t, 0.0, table) if guides and (project or norm) else None
+            c = CR.prediction(params, hp, sampler, x, spec_c, t, 0.0, table) if guides and (cfg_project or cfg_norm) else None
             if O:
                 y = BR.blend_groups(y, groups, T - O, O, mode)
                 c = BR.blend_groups(c, groups, T - O, O, mode) if c is not None else None
@@ -132,8 +132,8 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
                 seen[t] = []
                 for i, rows in enumerate(groups):
                     sums = group_sums(c, y, rows)
-                    ab[i] = coefficients(project, norm, w, *sums)
-                    seen[t].append(parts(project, norm, w, *sums))
+                    ab[i] = coefficients(cfg_project, cfg_norm, w, *sums)
+                    seen[t].append(parts(cfg_project, cfg_norm, w, *sums))
                 y = apply(c, y, ab, groups)
             if code:
                 y = y.clamp(*CL.BOUNDS[code])

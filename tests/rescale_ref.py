@@ -80,12 +80,12 @@ def group_g(c: torch.Tensor, u: Optional[torch.Tensor], w: float, value: int, gr
     return out
 
 
-def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, value: int, w: float = 0.0,
+def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[torch.Tensor], noise, n: int, *, cfg_rescale: int, w: float = 0.0,
                  code: int = 0, v: int = 0, O: int = 0, mode: int = 0, marks=(), draws: int = 1, interval=None, order: int = 0,
                  solver_noise: int = 0, start: Optional[int] = None):
     """The chain of chain_ref.sample_chain with the rescale: predict y (weight w) and c (weight 0) -> blend both over the
     shared frames (O > 0: a window batch with recording marks / draws as thresh_ref.window_groups reads them) -> at a step
-    that guides y = g y per group -> the clamp of code / the thresholding at v -> update.  value = 0: the option off.
+    that guides y = g y per group -> the clamp of code / the thresholding at v -> update.  cfg_rescale = 0: the option off.
     Returns (the final roll, {t: (G,) fp32 g} over the guided steps)."""
     S = int(hp["timesteps"])
     family, branch = CR.SAMPLERS[sampler]
@@ -99,7 +99,7 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
         for t, row in CR.chain_rows(hp, sampler, n, order, solver_noise, start).items():
             guides = branch is not None and w != 0.0 and lo <= t <= hi
             y = CR.prediction(params, hp, sampler, x, spec_c, t, w if guides else 0.0, table)
-            c = CR.prediction(params, hp, sampler, x, spec_c, t, 0.0, table) if guides and value else None
+            c = CR.prediction(params, hp, sampler, x, spec_c, t, 0.0, table) if guides and cfg_rescale else None
             if O:
                 y = BR.blend_groups(y, groups, T - O, O, mode)
                 c = BR.blend_groups(c, groups, T - O, O, mode) if c is not None else None
@@ -109,7 +109,7 @@ def sample_chain(params, hp, sampler: str, x: torch.Tensor, spec_c: Optional[tor
                 for i, rows in enumerate(groups):
                     N, S1c, S2c = group_sums(c, rows)
                     _, S1y, S2y = group_sums(y, rows)
-                    g[i] = factor(value, N, S1c, S2c, S1y, S2y)
+                    g[i] = factor(cfg_rescale, N, S1c, S2c, S1y, S2y)
                 for i, rows in enumerate(groups):
                     for b, _ in rows:
                         y[b] = torch.tensor(g[i]) * y[b]

@@ -21,6 +21,7 @@ import bf16_ref as Q
 import chain_ref
 from diffroll_amd import _cabi
 from oracle import diffroll_ref as R
+from facade_fakes import clip, facade
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -131,7 +132,6 @@ def chain_inputs():
 
 def test_the_facade_sets_the_mode_once_and_no_option():
     assert "bf16" in _cabi.PRECISIONS
-    from test_facade_cpu import clip, facade
     m, eng = facade("cfdg_ddpm_x0", precision="bf16")
     assert eng.precision == "bf16"                  # the constructor's keyword reached the engine at its first use
     m, eng = facade("cfdg_ddpm_x0")

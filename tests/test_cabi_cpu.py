@@ -7,6 +7,8 @@ import re
 import pytest
 import torch
 
+from testlib import header_functions
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -16,12 +18,6 @@ def lib():
     from diffroll_amd import _cabi
     build(verbose=False)
     return _cabi.load_library()
-
-
-def header_functions(name="diffroll_amd.h"):
-    text = open(os.path.join(ROOT, "include", name)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(dr_[a-z_0-9]+)\s*\(", text)))
 
 
 def test_header_and_binding_agree(lib):

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_respaced import ATOL, S
+from testlib import ATOL, S
 
 import chain_ref as CR
 import momentum_cases as MC

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from testlib import ATOL
+
 import clip_cases as CC
 import project_cases as PC
 import project_ref as PR
@@ -118,7 +120,6 @@ def test_gpu_chain_cases_are_active(sampler):
 
 @pytest.mark.parametrize("name,kw,_", PC.OPTION_CASES, ids=[c[0] for c in PC.OPTION_CASES])
 def test_gpu_option_cases_are_active(name, kw, _):
-    from test_gpu_respaced import ATOL
     assert name != "clip-threshold" and "v" not in kw
     roll = PC.assert_active("cfdg_ddpm_x0", *PC.MAIN, **kw)
     # the option beside the projection matters on these inputs: its chain is not the plain projected one

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from testlib import ATOL
+
 import clip_cases as CC
 import rescale_cases as RC
 import rescale_ref as RR
@@ -77,11 +79,10 @@ def test_window_groups_share_one_factor_and_count_every_frame_once():
 def test_the_issues_figures():
     """clip_cases.setup() with the guided case of thresh_cases (cfdg_ddpm_x0, w = 3), 20 steps, phi = 0.7: |g - 1| >= 0.4 at
     every visited step and roll, and the rescaled roll is more than 100 ATOL from the unrescaled one's."""
-    from test_gpu_respaced import ATOL
     hp, p, _, x, noise, spec = CC.setup()
     sampler, w, _, _ = TC.GUIDED
-    roll, gs = RR.sample_chain(p, hp, sampler, x, spec, noise, 20, value=7000, w=w)
-    off, none = RR.sample_chain(p, hp, sampler, x, spec, noise, 20, value=0, w=w)
+    roll, gs = RR.sample_chain(p, hp, sampler, x, spec, noise, 20, cfg_rescale=7000, w=w)
+    off, none = RR.sample_chain(p, hp, sampler, x, spec, noise, 20, cfg_rescale=0, w=w)
     g = np.concatenate(list(gs.values()))
     print(f"\ng in {g.min():.3f} .. {g.max():.3f}; max |rescaled - unrescaled| {float((roll - off).abs().max()):.3e}")
     assert g.shape == (40,) and (np.abs(g - 1.0) >= 0.4).all() and not none
@@ -98,7 +99,6 @@ def test_gpu_chain_cases_are_active(sampler):
 
 @pytest.mark.parametrize("name,kw,_", RC.OPTION_CASES, ids=[c[0] for c in RC.OPTION_CASES])
 def test_gpu_option_cases_are_active(name, kw, _):
-    from test_gpu_respaced import ATOL
     roll = RC.assert_active("cfdg_ddpm_x0", 7000, **kw)
     # the option beside the rescale matters on these inputs: its chain is not the plain rescaled one
     assert float((roll - RC.reference("cfdg_ddpm_x0", 7000)[0]).abs().max()) >= 100 * ATOL

@@ -3,11 +3,12 @@ diffroll_amd.distributed is exercised with a stand-in model whose ``sample`` is 
 per-sample function (the real engine needs a GPU); the result must equal the single-process one and
 must not depend on the world size."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.multiprocessing as mp
+
+from testlib import free_port
 
 
 class FakeEngine:
@@ -34,14 +35,6 @@ class FakeModel:
                 g = torch.Generator().manual_seed(seed * 1000003 + first_sample + b)
                 out[b] += torch.randn(out[b].shape, generator=g)
         return out, None
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, B, use_noise, ret):
@@ -75,7 +68,7 @@ def test_sharded_sampling_equals_single_process(B, use_noise):
     single = sample_sharded(FakeModel(), x, wav, noise, seed=5)      # no process group: world = 1
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, B, use_noise, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -50,6 +50,19 @@ def test_cited_paths_exist():
     assert not missing, missing
 
 
+def test_no_test_module_is_imported_by_another_file():
+    """What tests share lives in plain modules (tests/testlib.py, facade_fakes.py, stage_scenarios.py).  A test_*.py imported
+    by name is loaded a second time beside the copy pytest collected as tests.test_*, with its own module state - at any
+    indent, and in the scripts the tests hand to child processes."""
+    lending = re.compile(r"\b(?:from|import)\s+(?:tests\.)?test_\w+")
+    found = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "tests", "*.py"))):
+        for i, line in enumerate(open(path), 1):
+            if lending.search(line.split("#")[0]):
+                found.append((os.path.basename(path), i, line.strip()))
+    assert not found, found
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Numbers in prose come from the records (VERDICT r5 item 6).
 #

@@ -18,7 +18,7 @@ import torch
 import bf16_ref as Q
 import chain_ref
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model
+from testlib import make_model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

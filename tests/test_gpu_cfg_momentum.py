@@ -4,21 +4,21 @@ forms, with and without a state, zero / inf / NaN inputs and states, window canv
 restated chain - the three guiding samplers, every row of project_cases.OPTION_CASES, eager = captured and the captured chain
 launched twice (the baked start) - the identities of the option at 0 and of steps that do not guide, dr_step's state rule,
 windows and draws, the fused geometry and the two bf16 precisions.  Inputs and references: tests/momentum_cases.py, which
-tests/test_cfg_momentum_cpu.py shows to carry momentum.  Tolerance: agree / ATOL of tests/test_gpu_respaced.py; the observed
-margins are recorded in profiles/momentum_margins.txt."""
+tests/test_cfg_momentum_cpu.py shows to carry momentum.  Tolerance: agree / ATOL of tests/testlib.py; the observed
+margins are recorded in profiles/momentum_margins.txt.  The scenarios every guidance stage is held to are those of
+tests/stage_scenarios.py."""
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_cfg_project import one, project_model, run_windows, unconditional
-from test_gpu_parity import make_model, maxdiff
-from test_gpu_respaced import ATOL, S, agree
-from test_gpu_x0_threshold import kernel_inputs, same_bits
+from testlib import ATOL, agree, kernel_inputs, maxdiff, same_bits
 
 import blend_cases as BC
 import momentum_cases as MC
 import momentum_ref as MR
+import stage_scenarios as SS
 import thresh_ref as TR
+from stage_scenarios import one, run_batch_windows, unconditional
 
 from diffroll_amd import longform
 
@@ -28,23 +28,19 @@ pytestmark = pytest.mark.gpu
 TRIPLES = ((-5000, 10000, 500), (5000, 10000, 500), (-5000, 10000, 0), (5000, 10000, 0))
 
 
-def momentum_model(hp, p, sampler, momentum, project, norm, **kw):
-    """test_gpu_cfg_project.project_model with hparams.sampling.cfg_momentum = the value / 10000."""
-    m = project_model(hp, p, sampler, project, norm, **kw)
-    m.hparams.sampling.cfg_momentum = momentum / 10000.0 if momentum else None
-    return m
+def mpn(momentum, project, norm):
+    """The stage's values by option name."""
+    return {"cfg_momentum": momentum, "cfg_project": project, "cfg_norm": norm}
+
+
+MAIN = mpn(*MC.MAIN)
+NOTE = f" (bound {ATOL:.0e})"
 
 
 # ---------------------------------------------------------------------------------------------- 1. the kernel alone
 @pytest.fixture(scope="module")
 def lab():
-    """A committed engine whose options the kernel tests set; handed back with every one of them off."""
-    hp, p, _, _, _ = MC.setup()
-    eng = make_model(hp, p, sampler="cfdg_ddpm_x0").engine
-    yield eng
-    for name, value in (("window_overlap", 0), ("window_blend", 0), ("window_break", 0), ("draws", 1), ("cfg_momentum", 0), ("cfg_project", 0),
-                        ("cfg_norm", 0)):
-        eng.set_option(name, value)
+    yield from SS.lab_engine(("cfg_momentum", "cfg_project", "cfg_norm"))
 
 
 def check_kernel(lab, c, u, states, groups, plan=None, note=()):
@@ -139,35 +135,26 @@ def test_window_canvases(lab, O, marks, draws):
     prev = 3.0 * torch.randn(B, T, 88, generator=g)
     for lo, up in shared:
         prev[up, :O] = prev[lo, T - O:]
-    try:
-        lab.set_option("window_overlap", O)
-        lab.set_window_breaks(marks)
-        lab.set_option("draws", draws)
-        for mode in (0, 1, 2):
-            lab.set_option("window_blend", mode)
+    with SS.window_canvases(lab, O, marks, draws) as modes:
+        for mode in modes:
             want = check_kernel(lab, c, u, (None, prev), groups, plan=(O, mode), note=("windows", mode))
             for ab, m in want.values():
                 assert ab.shape == (len(groups), 2) and (np.abs(ab[:, 0]) > 0.05).all()
                 for lo, up in shared:
                     assert torch.equal(m[up, :O], m[lo, T - O:])
-    finally:
-        lab.set_option("draws", 1)
-        lab.set_window_breaks(())
-        lab.set_option("window_blend", 0)
-        lab.set_option("window_overlap", 0)
 
 
 # ---------------------------------------------------------------------------------------------- 2. the chains
 def record(name, d):
     """(the lines profiles/momentum_margins.txt is made of)"""
-    print(f"\ncfg_momentum {name}: max |d| {d:.3e} (bound {ATOL:.0e})")
+    SS.margin(f"cfg_momentum {name}", d, NOTE)
 
 
 @pytest.mark.parametrize("values", MC.VALUES, ids=[str(v[0]) for v in MC.VALUES])
 @pytest.mark.parametrize("sampler", MC.GUIDING)
 def test_chain_vs_restatement(sampler, values):
     hp, p, wav, x, noise = MC.setup()
-    m = momentum_model(hp, p, sampler, *values)
+    m = SS.stage_model(hp, p, sampler, mpn(*values))
     ref = MC.assert_active(sampler, *values)          # (the inputs carry momentum, before the engine's roll is looked at)
     roll, _ = m.sample(x, wav, noise=noise)
     eager, _ = m.sample(x, wav, use_graph=False, noise=noise)
@@ -184,7 +171,7 @@ def test_chain_vs_restatement(sampler, values):
 @pytest.mark.parametrize("name,kw,facade", MC.OPTION_CASES, ids=[c[0] for c in MC.OPTION_CASES])
 def test_other_options_vs_restatement(name, kw, facade, values):
     hp, p, wav, x, noise = MC.setup()
-    m = momentum_model(hp, p, "cfdg_ddpm_x0", *values, **facade)
+    m = SS.stage_model(hp, p, "cfdg_ddpm_x0", mpn(*values), **facade)
     ref = MC.assert_active("cfdg_ddpm_x0", *values, **kw)
     roll, _ = m.sample(x, wav, noise=noise)
     eager, _ = m.sample(x, wav, noise=noise, use_graph=False)
@@ -195,17 +182,8 @@ def test_other_options_vs_restatement(name, kw, facade, values):
 
 
 # ---------------------------------------------------------------------------------------------- 3. the captured chain
-def _engine(steps=4, sampler="cfdg_ddpm_x0", w=MC.W):
-    hp, p, wav, x, _ = MC.setup()
-    m = make_model(hp, p, sampler=sampler, w=w)
-    m.hparams.sampling.steps = steps
-    eng = m.engine
-    eng.frontend(wav, MC.TN)
-    return eng, x.squeeze(1).to(eng.device).contiguous()
-
-
 def test_a_captured_chain_restarts_its_state_at_every_launch_and_the_value_is_in_its_key():
-    eng, x_T = _engine()
+    eng, x_T = SS.chain_engine()
 
     def run(**kw):
         return eng.sample("cfdg_ddpm_x0", x_T.clone(), None, w=MC.W, seed=MC.PHILOX_SEED, **kw)
@@ -236,7 +214,7 @@ def test_a_captured_chain_restarts_its_state_at_every_launch_and_the_value_is_in
 
 # ---------------------------------------------------------------------------------------------- 4. the parent's chain
 def test_value_0_is_the_parents_projected_chain_bitwise_and_replays_it():
-    eng, x_T = _engine()
+    eng, x_T = SS.chain_engine()
 
     def run():
         return eng.sample("cfdg_ddpm_x0", x_T.clone(), None, w=MC.W, seed=MC.PHILOX_SEED)
@@ -257,7 +235,7 @@ def test_value_0_is_the_parents_projected_chain_bitwise_and_replays_it():
         for name in ("cfg_momentum", "cfg_project", "cfg_norm"):
             eng.set_option(name, 0)
     hp, p, wav, x, noise = MC.setup()
-    m = momentum_model(hp, p, "cfdg_ddpm_x0", 0, 10000, 500)
+    m = SS.stage_model(hp, p, "cfdg_ddpm_x0", mpn(0, 10000, 500))
     roll, _ = m.sample(x, wav, noise=noise)
     ok, d = agree(roll, MC.PC.reference("cfdg_ddpm_x0", 10000, 500)[0])
     assert ok, d
@@ -265,43 +243,14 @@ def test_value_0_is_the_parents_projected_chain_bitwise_and_replays_it():
 
 @pytest.mark.parametrize("sampler,w", [("ddpm_x0", 0.0), ("ddim", 0.0), ("cfdg_ddpm_x0", 0.0)])
 def test_a_chain_that_does_not_guide_is_untouched(sampler, w):
-    eng, x_T = _engine(sampler=sampler, w=w)
-
-    def run(**kw):
-        t0 = eng.tail_launches
-        return eng.sample(sampler, x_T.clone(), None, w=w, seed=MC.PHILOX_SEED, **kw), eng.tail_launches - t0
-
-    (first, tails), c0 = run(), eng.launch_counts()
-    eng.set_option("cfg_project", 10000)
-    eng.set_option("cfg_momentum", -5000)
-    try:
-        (again, tails_on), c1 = run(), eng.launch_counts()
-        eager, _ = run(use_graph=False)
-    finally:
-        eng.set_option("cfg_momentum", 0)
-        eng.set_option("cfg_project", 0)
-    assert torch.equal(again, first) and torch.equal(eager, first)
-    assert tails_on == tails and c1 == c0, (c0, c1)
+    SS.unguided_chain_is_untouched(sampler, w, {"cfg_project": 10000, "cfg_momentum": -5000}, off=("cfg_momentum", "cfg_project"))
 
 
 def test_steps_outside_the_interval_keep_every_bit_and_the_state_starts_inside():
     """dr_step over the visited steps under the interval [60, 140]: the rolls behind the steps above 140 hold the same bits with
     the option on and off; the first step <= 140 starts the state (there m = d: the roll equals the projected chain's), the
     second one parts the two; the whole matches the restatement."""
-    hp, p, wav, x, _ = MC.setup()
-    m = momentum_model(hp, p, "cfdg_ddpm_x0", *MC.MAIN, guidance_interval=[60, 140])
-    kw = dict(seed=MC.PHILOX_SEED)
-    on, _ = m.sample_trajectory(x, wav, **kw)
-    whole, _ = m.sample(x, wav, **kw)
-    assert torch.equal(whole, on[-1])                 # the dr_step sequence equals dr_sample
-    m.hparams.sampling.cfg_momentum = None
-    off, _ = m.sample_trajectory(x, wav, **kw)
-    visited = m.visited_steps()
-    above = [i for i, t in enumerate(visited) if t > 140]
-    first = above[-1] + 1
-    assert 60 <= visited[first] <= 140
-    for i in above:
-        assert torch.equal(on[i], off[i]), visited[i]
+    _, whole, on, off, first = SS.steps_outside_the_interval(MAIN, ("cfg_momentum",))
     assert not torch.equal(on[first + 1], off[first + 1])
     ref = MC.reference("cfdg_ddpm_x0", *MC.MAIN, philox=True, interval=(60, 140))[0]
     ok, d = agree(whole, ref)
@@ -312,7 +261,7 @@ def test_steps_outside_the_interval_keep_every_bit_and_the_state_starts_inside()
 # ---------------------------------------------------------------------------------------------- 5. dr_step
 def test_dr_step_state_rule():
     from diffroll_amd.engine import EngineError
-    eng, xb = _engine(steps=20)
+    eng, xb = SS.chain_engine(steps=20)
     v = eng.visited_steps()
 
     def step(t, x=None):
@@ -365,19 +314,8 @@ def test_dr_step_state_rule():
 
 
 # ---------------------------------------------------------------------------------------------- 6. windows and draws
-def window_reference(recs, marks=(), draws=1, values=MC.MAIN, x_T=None, noise=None):
-    """test_gpu_cfg_project.window_reference with the momentum."""
-    hp, p = recs[0][0], recs[0][1]
-    if x_T is None:
-        x = torch.cat([BC.windows_of(r[4].reshape(r[2].T_c, 88), r[2]) for r in recs], 0)
-        z = torch.cat([BC.windows_of(r[5].reshape(-1, r[2].T_c, 88), r[2]) for r in recs], 1)
-    else:
-        plan = recs[0][2]
-        x = torch.cat([BC.windows_of(x_T[d, 0], plan) for d in range(draws)], 0)
-        z = torch.cat([BC.windows_of(noise[:, d, 0], plan) for d in range(draws)], 1)
-    spec = torch.cat([r[6] for r in recs], 0).repeat(draws, 1, 1)
-    return MR.sample_chain(p, hp, BC.SAMPLER, x, spec, z, 0, momentum=values[0], project=values[1], norm=values[2], w=MC.W, O=BC.OPT_O,
-                           marks=marks, draws=draws)
+def window_reference(recs, values=MC.MAIN, **kw):
+    return SS.window_reference(MR.sample_chain, mpn(*values), recs, **kw)
 
 
 def test_windows_match_and_shared_frames_are_bit_identical():
@@ -385,32 +323,32 @@ def test_windows_match_and_shared_frames_are_bit_identical():
     hp, p, plan, wav, x_T, noise, _ = rec
     ref, seen, rms = window_reference([rec])
     assert len(seen) == len(rms) == 4
-    m = momentum_model(hp, p, BC.SAMPLER, *MC.MAIN, n=0)
-    got = run_windows(m, one(plan), [wav], [x_T], [noise])
+    m = SS.stage_model(hp, p, BC.SAMPLER, MAIN, n=0)
+    got = run_batch_windows(m, one(plan), [wav], [x_T], [noise])
     for b in range(plan.n - 1):                       # the stitched roll is a plain gather
         assert torch.equal(got[b, plan.stride:], got[b + 1, :plan.overlap]), b
     d = maxdiff(got, ref[:, 0])
     record(f"windows w 3 values {MC.MAIN}", d)
     assert d <= ATOL, d
-    assert torch.equal(run_windows(m, one(plan), [wav], [x_T], [noise], use_graph=False), got)
+    assert torch.equal(run_batch_windows(m, one(plan), [wav], [x_T], [noise], use_graph=False), got)
     assert maxdiff(got, window_reference([rec], values=(0,) + MC.MAIN[1:])[0][:, 0]) > 100 * ATOL
 
 
 def test_window_break_and_draws_match():
     a, b = BC.break_case()
     batch = longform.BatchPlan(plans=[a[2], b[2]], first=[0, 2], marks=[2], n=3)
-    m = momentum_model(a[0], a[1], BC.SAMPLER, *MC.MAIN, n=0)
-    got = run_windows(m, batch, [a[3], b[3]], [a[4], b[4]], [a[5], b[5]])
+    m = SS.stage_model(a[0], a[1], BC.SAMPLER, MAIN, n=0)
+    got = run_batch_windows(m, batch, [a[3], b[3]], [a[4], b[4]], [a[5], b[5]])
     d = maxdiff(got, window_reference([a, b], marks=(2,))[0][:, 0])
     record(f"window_break w 3 values {MC.MAIN}", d)
     assert d <= ATOL, d
-    alone_a = run_windows(m, one(a[2]), [a[3]], [a[4]], [a[5]])
+    alone_a = run_batch_windows(m, one(a[2]), [a[3]], [a[4]], [a[5]])
     assert torch.equal(got[:2], alone_a)              # each recording equals its own chain
     rec = BC.recording(BC.OPT_O, 3300)
     hp, p, plan, wav, _, _, _ = rec
     x_T, noise = BC.option_canvases("draws")
-    m = momentum_model(hp, p, BC.SAMPLER, *MC.MAIN, n=0)
-    got = run_windows(m, one(plan), [wav], [x_T], [noise], D=2)
+    m = SS.stage_model(hp, p, BC.SAMPLER, MAIN, n=0)
+    got = run_batch_windows(m, one(plan), [wav], [x_T], [noise], D=2)
     d = maxdiff(got, window_reference([rec], draws=2, x_T=x_T, noise=noise)[0][:, 0])
     record(f"draws w 3 values {MC.MAIN}", d)
     assert d <= ATOL, d
@@ -421,87 +359,18 @@ def test_window_break_and_draws_match():
 
 # ---------------------------------------------------------------------------------------------- 7. the fused geometry
 def test_fused_geometry_guided_steps_report_fused_stack_and_unguided_ones_come_back():
-    """3 guided clips x 40 frames at C = 64, 3 layers, k = 9 - the smallest case of tests/fused_cases.py."""
-    from oracle import diffroll_ref as R
-    from test_gpu_respaced import hp_of, inputs
-    from tools import tuning_env
-    if any(tuning_env.is_forced(k) for k in ("fused_stack", "fused_tail", "blocked_accumulation")):
-        pytest.skip("DR_TEST_TUNE pins the options this test switches")
-    hp = hp_of(channels=64, layers=3, k=9)
-    p = R.synthetic_params(hp, seed=73)
-    wav, x, _ = inputs(3, 40, 73)
-    m = momentum_model(hp, p, "cfdg_ddpm_x0", *MC.MAIN)
-    eng = m.engine
-    pins = {"tune.ksplit_max": (1, 16), "tune.tile": (3201, 0), "tune.pw_nw": (2, 0), "tune.stack_fl": (1, 0)}
-    for k, (val, _) in pins.items():
-        eng.set_option(k, val)
-    eng.set_option("fused_stack", 2)
-    try:
-        t0 = eng.tail_launches
-        g, _ = m.sample(x, wav, seed=5)
-        st = eng.launch_state()
-        assert st["mode"] == "fused_stack" and eng.tail_launches == t0 and st["fallbacks"] == 0 and st["yields"] == 0, st
-        e, _ = m.sample(x, wav, seed=5, use_graph=False)
-        m.hparams.sampling.guidance_interval = [60, 140]
-        gi, _ = m.sample(x, wav, seed=5, use_graph=False)
-        st = eng.launch_state()
-        assert st["mode"] == "fused_stack+tail" and 0 < eng.tail_launches - t0 <= 12 and st["fallbacks"] == 0 and st["yields"] == 0, st
-        gig, _ = m.sample(x, wav, seed=5)
-        eng.set_option("fused_stack", 0)              # per-phase launches: the same bits
-        ppi, _ = m.sample(x, wav, seed=5)
-        m.hparams.sampling.guidance_interval = None
-        pp, _ = m.sample(x, wav, seed=5)
-        assert eng.launch_state()["mode"] == "per_phase"
-    finally:
-        eng.set_option("fused_stack", 1)
-        for k, (_, val) in pins.items():
-            eng.set_option(k, val)
-    assert torch.equal(g, e) and torch.equal(g, pp)
-    assert torch.equal(gi, gig) and torch.equal(gi, ppi) and not torch.equal(gi, g)
-    ref, seen, _ = MR.sample_chain(p, hp, "cfdg_ddpm_x0", x, R.frontend(wav, hp, 40), MR.CR.philox_noise(5, 0, S, 3, 40), 20,
-                                   momentum=MC.MAIN[0], project=MC.MAIN[1], norm=MC.MAIN[2], w=MC.W)
+    with SS.fused_geometry(MAIN) as (hp, p, m, wav, x):
+        g = SS.fused_guided_steps_leave_the_tail_kernel(m, wav, x)
+    _, seen, _ = SS.fused_roll_vs_restatement(MR.sample_chain, MAIN, hp, p, wav, x, g, f"cfg_momentum fused geometry w 3 values {MC.MAIN} n 20", NOTE)
     assert len(seen) == 20
-    ok, d = agree(g, ref)
-    record(f"fused geometry w 3 values {MC.MAIN} n 20", d)
-    assert ok, d
 
 
 # ---------------------------------------------------------------------------------------------- 8. bf16x3 and bf16
 def test_split_bf16_vs_restatement():
-    hp, p, wav, x, noise = MC.setup()
-    m = momentum_model(hp, p, "cfdg_ddpm_x0", *MC.MAIN, n=8, precision="bf16x3")
-    ref, seen, rms = MR.sample_chain(p, hp, "cfdg_ddpm_x0", x, MC.spec_of("cfdg_ddpm_x0"), noise, 8, momentum=MC.MAIN[0], project=MC.MAIN[1],
-                                     norm=MC.MAIN[2], w=MC.W)
-    assert len(seen) == len(rms) == 8
-    roll, _ = m.sample(x, wav, noise=noise)
-    ok, d = agree(roll, ref)
-    record(f"bf16x3 w 3 values {MC.MAIN} n 8", d)
-    assert ok, d
+    _, _, rms = SS.split_bf16_vs_restatement(MR.sample_chain, MAIN, f"cfg_momentum bf16x3 w 3 values {MC.MAIN} n 8", NOTE)
+    assert len(rms) == 8
 
 
 def test_bf16_chain_lies_in_the_restatements_band():
-    """tests/test_gpu_bf16.py's chain (8 steps, C = 128, w = 0.5) under MAIN: the rms distance of the bf16 roll from the restated
-    fp32 chain lies within 0.5 .. 1.5 x that of the restated bf16 chain, as in test_gpu_cfg_project.py."""
-    import bf16_ref as Q
-    from oracle import diffroll_ref as R
-    hp, p, x, wav, _ = Q.case_inputs(Q.CHAIN_GEOMETRY, timesteps=Q.CHAIN_STEPS)
-    B, T = Q.CHAIN_GEOMETRY[3:]
-    nz = torch.randn(Q.CHAIN_STEPS, B, 1, T, 88, generator=torch.Generator().manual_seed(5))
-    with torch.no_grad():
-        spec = R.frontend(wav, hp, T)
-    kw = dict(momentum=MC.MAIN[0], project=MC.MAIN[1], norm=MC.MAIN[2], w=0.5)
-    ref, seen, _ = MR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, nz, 0, **kw)
-    assert len(seen) == Q.CHAIN_STEPS
-    with Q.patched(Q.rne, None):
-        d_ref = Q.rms(MR.sample_chain(p, hp, "cfdg_ddpm_x0", x, spec, nz, 0, **kw)[0] - ref)
-    m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5, precision="bf16")
-    m.hparams.sampling.cfg_project = 1.0
-    m.hparams.sampling.cfg_norm = 0.05
-    m.hparams.sampling.cfg_momentum = -0.5
-    got = m.sample(x, wav, noise=nz)[0]
-    d = Q.rms(got.cpu() - ref)
-    print(f"\ncfg_momentum bf16 chain: rms distance from the fp32 chain {d:.3e} restated {d_ref:.3e} ratio {d / d_ref:.3f}")
-    assert 0.5 * d_ref <= d <= 1.5 * d_ref, (d, d_ref)
-    assert torch.equal(m.sample(x, wav, noise=nz)[0], got)
-    assert torch.equal(m.sample(x, wav, noise=nz, use_graph=False)[0], got)
-    assert m.engine.cfg_momentum == -5000
+    """stage_scenarios.bf16_chain_lies_in_the_restatements_band under MAIN, as in test_gpu_cfg_project.py."""
+    SS.bf16_chain_lies_in_the_restatements_band(MR.sample_chain, MAIN, "cfg_momentum")

@@ -7,8 +7,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model, maxdiff
-from test_gpu_respaced import HOP, S, agree, hp_of, inputs
+from testlib import HOP, S, agree, assert_shared_frames_agree, hp_of, inputs, make_model, maxdiff, run_plan_windows
 
 import chain_ref as CR
 
@@ -189,7 +188,6 @@ def test_dr_step_over_the_visited_steps_and_out_of_sequence():
 
 def test_sample_long_vs_restatement():
     from diffroll_amd import longform
-    from test_gpu_longform import assert_shared_frames_agree, run_windows
     hp = hp_of(channels=128, layers=3)
     p = R.synthetic_params(hp, seed=81)
     m = solver_model(hp, p, "cfdg_ddpm_x0", 20, 2)
@@ -202,7 +200,7 @@ def test_sample_long_vs_restatement():
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
     ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, None, 20, order=2, w=0.5, plan=plan)
-    win = run_windows(m, plan, wav, x_T, None, seed=4, recording=1)
+    win = run_plan_windows(m, plan, wav, x_T, None, seed=4, recording=1)
     assert_shared_frames_agree(win, plan)
     ok, d = agree(win, ref[:, 0])
     print(f"\nlong-form order 2 n 20: max |d| {d:.3e}")

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model
+from testlib import make_model
 from tuning_pins import pinned
 
 from diffroll_amd import longform

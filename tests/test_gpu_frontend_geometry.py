@@ -5,7 +5,7 @@ n_mels % 4, the multi-workgroup min-max and the conditioner GEMM at every K - ag
 reference front-end.  Needs a real MI355X: ``pytest -m gpu``.
 
 Tolerances:
-  * normalised log-mel:  ATOL_SPEC = 4e-5 of tests/test_gpu_parity.py, against float64 (the fp32 reference itself is
+  * normalised log-mel:  ATOL_SPEC = 4e-5 of tests/testlib.py, against float64 (the fp32 reference itself is
                          <= 1.2e-5 away at every compared clip: tests/test_frontend_geometry_cpu.py).
   * a windowed-DFT case: the same, except the one case of RESTATED (2400 / 600 at 48 kHz), which exceeded it: there the
                          bound is twice the distance to float64 of a CPU fp32 restatement of the same n_fft-term sum
@@ -25,7 +25,7 @@ import torch
 
 import frontend_cases as FC
 from oracle import diffroll_ref as R
-from test_gpu_parity import ATOL_FWD, ATOL_SPEC, make_model
+from testlib import ATOL_FWD, ATOL_SPEC, make_model
 
 pytestmark = pytest.mark.gpu
 

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model
+from testlib import make_model
 
 pytestmark = pytest.mark.gpu
 

@@ -16,15 +16,13 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model, maxdiff
+from testlib import HOP, agree, assert_shared_frames_agree, make_model, maxdiff, run_plan_windows
 from tuning_pins import pinned
 
 import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
 
-ATOL = 1e-5
-HOP = 512
 S, B, T, W = 12, 2, 125, 0.5
 GUIDING = ["cfdg_ddpm_x0", "inpainting_ddpm_x0", "cfdg_ddim_x0"]
 MASK = [30, 60]                      # the inpainting sampler's time mask (spectrogram frames)
@@ -44,16 +42,6 @@ def inputs(n, Tn, seed):
     x = torch.randn(n, 1, Tn, 88, generator=g)
     noise = torch.randn(S, n, 1, Tn, 88, generator=g)
     return wav, x, noise
-
-
-def agree(roll, ref):
-    """The comparison rule of tests/test_gpu_respaced.py: |d| <= ATOL max(1, |ref|) and the same thresholded roll except
-    within ATOL of the threshold.  Returns (ok, max |d|)."""
-    roll = roll.cpu()
-    d = maxdiff(roll, ref)
-    within = ((roll - ref).abs() <= ATOL * ref.abs().clamp(min=1.0)).all()
-    near = (ref - 0.5).abs() < ATOL
-    return bool(within) and bool((((roll > 0.5) == (ref > 0.5)) | near).all()), d
 
 
 def model_of(sampler, hp=None, seed=70, **kw):
@@ -260,7 +248,6 @@ def test_with_window_overlap_vs_restatement():
     """Three windows of T = 64 frames sharing O = 16: a step is guided or not for all windows alike, and the shared-frame
     mean is taken of whichever prediction the step uses."""
     from diffroll_amd import longform
-    from test_gpu_longform import assert_shared_frames_agree, run_windows
     hp, p, m, _ = model_of("cfdg_ddpm_x0")
     m.hparams.sampling.guidance_interval = [4, 8]
     g = torch.Generator().manual_seed(77)
@@ -275,7 +262,7 @@ def test_with_window_overlap_vs_restatement():
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
     ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, zw, 0, w=W, interval=(4, 8), plan=plan)
     for use_graph in (True, False):
-        win = run_windows(m, plan, wav, x_T, noise, use_graph=use_graph)
+        win = run_plan_windows(m, plan, wav, x_T, noise, use_graph=use_graph)
         assert_shared_frames_agree(win, plan)
         ok, d = agree(win, ref[:, 0])
         assert ok, (use_graph, d)

@@ -3,11 +3,11 @@ tests/test_launch_variants_cpu.py proves reaches what it claims) and held to a t
 oracle: the block -> XCD mapping of the per-phase GEMM launches (A), the one-chain 1x1 GEMMs across kernels and channels per
 hand-over (B), pwk_kernel<1> against <2> (C), the tail kernel's 64- / 96-frame items (D), every split-K factor (E).  The
 twins differ only in which block computes which tile, or in how one fp32 chain is cut into hand-overs - never in the order of
-a sum - so every comparison between them is torch.equal; the tolerances against the oracle are test_gpu_parity's."""
+a sum - so every comparison between them is torch.equal; the tolerances against the oracle are those of tests/testlib.py."""
 import pytest
 import torch
 
-from test_gpu_parity import ATOL_FWD, ATOL_STEP, make_model, maxdiff
+from testlib import ATOL_FWD, ATOL_STEP, make_model, maxdiff
 from tuning_pins import pinned
 
 import variant_cases as V

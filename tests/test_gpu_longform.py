@@ -10,53 +10,15 @@ import torch
 
 from oracle import diffroll_ref as R
 from oracle import philox
-from test_gpu_parity import make_model, maxdiff
-
-import chain_ref as CR
+from testlib import ATOL, HOP, assert_shared_frames_agree, long_hp_of, make_model, maxdiff, oracle_long, run_plan_windows
 
 from diffroll_amd import longform
 
 pytestmark = pytest.mark.gpu
 
-ATOL = 1e-5
-HOP = 512
-
-
-def hp_of(layers=15, k=9, steps=4, channels=None):
-    hp = dict(R.DEFAULT_HP)
-    hp.update(residual_layers=layers, kernel_size=k, timesteps=steps)
-    if channels:
-        hp["residual_channels"] = channels
-    return hp
-
-
-def oracle_long(p, hp, sampler, plan, wav, x_T, noise, w):
-    """The joint chain on the CPU: windows of the canvas x_T / noise, one front-end per window crop, and the chain loop of
-    tests/chain_ref.py over every step - the guided prediction of each window, the mean on shared frames, the posterior
-    update.  Returns windows (n, 1, T, 88)."""
-    S = int(hp["timesteps"])
-    x = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
-    zs = longform.gather_windows(noise.reshape(S, plan.T_c, 88), plan).unsqueeze(2)
-    spec = None
-    if sampler != "generation_ddpm_x0":
-        spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
-    return CR.sample_chain(p, hp, sampler, x, spec, zs, 0, w=w, plan=plan)
-
-
-def run_windows(m, plan, wav, x_T, noise, seed=0, recording=0, use_graph=True):
-    """sample_long's chain, keeping the windows: (n, T, 88) on the host."""
-    batch = longform.BatchPlan(plans=[plan], first=[0], marks=[], n=plan.n)
-    return m._sample_windows(batch, None if wav is None else [wav], [x_T], None if noise is None else [noise], 1, seed,
-                             recording, use_graph, True).cpu()
-
-
-def assert_shared_frames_agree(win, plan):
-    for b in range(plan.n - 1):
-        assert torch.equal(win[b, plan.stride:], win[b + 1, :plan.overlap]), b
-
 
 def test_joint_windows_against_the_oracle_per_phase_fused_graph_eager():
-    hp = hp_of()
+    hp = long_hp_of()
     p = R.synthetic_params(hp, seed=1400)
     g = torch.Generator().manual_seed(1400)
     L = 1400 * HOP - 100                              # ~2.2 windows: n = 3 at O = 160
@@ -84,7 +46,7 @@ def test_joint_windows_against_the_oracle_per_phase_fused_graph_eager():
     # split-bf16, per-phase
     mb = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5, precision="bf16x3")
     mb.engine.set_option("fused_stack", 0)
-    bb = run_windows(mb, plan, wav, x_T, noise)
+    bb = run_plan_windows(mb, plan, wav, x_T, noise)
     d = maxdiff(bb, ref[:, 0])
     assert d <= ATOL, ("bf16x3", d)
     assert_shared_frames_agree(bb, plan)
@@ -93,7 +55,7 @@ def test_joint_windows_against_the_oracle_per_phase_fused_graph_eager():
 def _joint_windows_cases(m, eng, hp, p, plan, wav, x_T, noise, ref, ref_roll, L):
     # per-phase
     eng.set_option("fused_stack", 0)
-    pp = run_windows(m, plan, wav, x_T, noise)
+    pp = run_plan_windows(m, plan, wav, x_T, noise)
     d = maxdiff(pp, ref[:, 0])
     assert d <= ATOL, ("per-phase", d)
     assert torch.equal(pp > 0.5, ref[:, 0] > 0.5)
@@ -105,13 +67,13 @@ def _joint_windows_cases(m, eng, hp, p, plan, wav, x_T, noise, ref, ref_roll, L)
     # forced fused: the 160-frame stack flavour, the tail kernel with the neighbour wait
     eng.set_option("fused_stack", 2)
     eng.profile_enable(True)                           # (a profiled chain runs eager)
-    fe = run_windows(m, plan, wav, x_T, noise)
+    fe = run_plan_windows(m, plan, wav, x_T, noise)
     _, _, _, kname = eng.profile_read_ex()
     eng.profile_enable(False)
     st = eng.launch_state()
     assert st["mode"] == "fused_stack+tail", st
     assert kname.startswith("stack_kernel<5>"), kname
-    fg = run_windows(m, plan, wav, x_T, noise, use_graph=True)
+    fg = run_plan_windows(m, plan, wav, x_T, noise, use_graph=True)
     st = eng.launch_state()
     assert st["fallbacks"] == 0 and st["yields"] == 0, st
     assert maxdiff(fe, ref[:, 0]) <= ATOL
@@ -119,12 +81,12 @@ def _joint_windows_cases(m, eng, hp, p, plan, wav, x_T, noise, ref, ref_roll, L)
     assert torch.equal(fg, fe), maxdiff(fg, fe)       # graph == eager
     assert_shared_frames_agree(fg, plan)
     eng.set_option("fused_stack", 0)
-    pe = run_windows(m, plan, wav, x_T, noise, use_graph=False)
+    pe = run_plan_windows(m, plan, wav, x_T, noise, use_graph=False)
     assert torch.equal(pe, pp)
 
 
 def test_philox_keys_by_canvas_element_and_anchor_to_sample():
-    hp = hp_of(layers=3, steps=4, channels=128)
+    hp = long_hp_of(layers=3, steps=4, channels=128)
     p = R.synthetic_params(hp, seed=33)
     m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5)
     g = torch.Generator().manual_seed(33)
@@ -173,7 +135,7 @@ def test_philox_keys_by_canvas_element_and_anchor_to_sample():
 
 def test_engine_rejects_overlap_beyond_half_the_window():
     from diffroll_amd.engine import EngineError
-    hp = hp_of(layers=2, steps=4, channels=64)
+    hp = long_hp_of(layers=2, steps=4, channels=64)
     p = R.synthetic_params(hp, seed=5)
     m = make_model(hp, p, sampler="generation_ddpm_x0")
     eng = m.engine
@@ -188,12 +150,12 @@ def test_engine_rejects_overlap_beyond_half_the_window():
 
 
 def test_long_generation_keeps_shared_frames_equal():
-    hp = hp_of(layers=4, steps=4)
+    hp = long_hp_of(layers=4, steps=4)
     p = R.synthetic_params(hp, seed=1500)
     m = make_model(hp, p, sampler="generation_ddpm_x0")
     plan = longform.plan_windows(1500, None, overlap=160)
     x_T = torch.randn(1, 1, plan.T_c, 88, generator=torch.Generator().manual_seed(15))
-    win = run_windows(m, plan, None, x_T, None, seed=3, recording=1)
+    win = run_plan_windows(m, plan, None, x_T, None, seed=3, recording=1)
     assert_shared_frames_agree(win, plan)
     roll = m.sample_long(frames=1500, overlap=160, seed=3, recording=1, x_T=x_T).cpu()
     assert roll.shape == (1, 1, 1500, 88) and torch.isfinite(roll).all()
@@ -219,7 +181,7 @@ def test_cli_transcribes_whole_files(tmp_path):
         assert roll.shape == (1, 1, math.ceil(L / HOP), 88) and np.isfinite(roll).all()
         assert (out / f"clean_midi_{stem}.mid").exists()
         if m is None:
-            hp = hp_of(layers=2, steps=4, channels=64)
+            hp = long_hp_of(layers=2, steps=4, channels=64)
             m = make_model(hp, R.synthetic_params(hp, seed=0))
         pitches, iv = midi.extract_notes_wo_velocity(m.engine, torch.from_numpy(roll))[0]
         ons = sorted((int(p) + midi.MIN_MIDI, int(float(a) * (HOP / 16000.0) * midi.TICKS_PER_SECOND))

@@ -8,8 +8,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_longform import assert_shared_frames_agree, hp_of, oracle_long
-from test_gpu_parity import make_model, maxdiff
+from testlib import assert_shared_frames_agree, long_hp_of, make_model, maxdiff, oracle_long
 from tuning_pins import pinned
 
 from diffroll_amd import longform
@@ -41,7 +40,7 @@ def full_size_case():
     windows and the oracle's windows of each, computed once for the two tests that use them."""
     if _FULL:
         return _FULL
-    hp = hp_of()
+    hp = long_hp_of()
     p = R.synthetic_params(hp, seed=1400)
     # The rolls of the synthetic network as drawn are spread evenly across the 0.5 threshold (mean 0.03, std 0.35: about
     # 11 of the 225 280 elements within 1e-4 of it whatever the input seed - 28 seeds gave margins of 2.4e-7 .. 3.2e-5), so
@@ -161,7 +160,7 @@ def test_the_boundary_is_real():
 
 
 def small_case(seed=33):
-    hp = hp_of(layers=3, steps=4, channels=128)
+    hp = long_hp_of(layers=3, steps=4, channels=128)
     p = R.synthetic_params(hp, seed=seed)
     g = torch.Generator().manual_seed(seed)
     lengths = [W + 100 * HOP + 3, 300 * HOP + 17, 1400 * HOP - 100]     # 2, 1 (in the middle) and 3 windows

@@ -1,16 +1,7 @@
 """Parity of the HIP engine (through the C-ABI) against the golden vectors produced by the
 reference and against the CPU oracle.  Needs a real MI355X: ``pytest -m gpu``.
 
-Tolerances (fp32 everywhere; the kernels use the exact-fp32 MFMA, so differences come only from
-summation order, the FFT implementation and the hardware exp/rcp of the gate):
-  * one network evaluation:      atol 1e-5  (outputs are O(1); observed <= 2.9e-6 over the whole suite)
-  * one reverse step / chain:    atol 1e-5  (observed <= 2.9e-6; SURVEY.md 8c proposes 2e-5 per kernel)
-  * normalised log-mel:          atol 4e-5  (values in [0,1]; observed <= 8.5e-6: own FFT vs torch's, amplified by
-                                             the log at near-silent bins)
-  * same clips, other shard / batch geometry (other tile flavour or split-K order): atol 1e-5 (observed <= 2.9e-6)
-i.e. 3.4-5x the observed margins (DR_PARITY_LOG=<file> records every comparison): a 5x regression fails.
-(Until the front-end tables were built with the reference's fp32 filterbank arithmetic the log-mel differed by
-2e-5 and every conditional evaluation by up to 3e-5 - diffroll_amd/frontend_tables.py.)
+Tolerances: ATOL_FWD / ATOL_STEP / ATOL_SPEC / ATOL_SHARD of tests/testlib.py, where their reasons are given.
 """
 import json
 import os
@@ -20,13 +11,9 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
+from testlib import ATOL_FWD, ATOL_SHARD, ATOL_SPEC, ATOL_STEP, cfg2_inputs, make_model, maxdiff
 
 pytestmark = pytest.mark.gpu
-
-ATOL_FWD = 1e-5
-ATOL_STEP = 1e-5
-ATOL_SPEC = 4e-5
-ATOL_SHARD = 1e-5
 
 
 def load(golden_dir, name):
@@ -38,38 +25,10 @@ def T(a):
     return torch.from_numpy(np.asarray(a))
 
 
-def make_model(hp, params, sampler="cfdg_ddpm_x0", w=0.5, inpainting_t=None, inpainting_f=None, precision="f32", **extra):
-    from diffroll_amd import ClassifierFreeDiffRoll
-    m = ClassifierFreeDiffRoll(
-        residual_channels=hp["residual_channels"], unconditional=False, condition="fixed",
-        n_mels=hp["n_mels"], norm_args=[0, 1, "imagewise"], residual_layers=hp["residual_layers"],
-        kernel_size=hp["kernel_size"], dilation_base=hp["dilation_base"],
-        dilation_bound=hp["dilation_bound"],
-        spec_args=dict(sample_rate=hp["sample_rate"], n_fft=hp["n_fft"], hop_length=hp["hop_length"],
-                       n_mels=hp["n_mels"], f_min=hp["f_min"], f_max=hp["f_max"], center=True,
-                       normalized=True, pad_mode="reflect"),
-        spec_dropout=0.1, inpainting_t=inpainting_t, inpainting_f=inpainting_f,
-        timesteps=hp["timesteps"], beta_start=hp["beta_start"], beta_end=hp["beta_end"],
-        training={"mode": "x_0"}, sampling={"type": sampler, "w": w}, precision=precision, **extra)
-    m.load_state_dict(params)
-    return m
-
-
 def fixture_model(g, **kw):
     hp = json.loads(str(g["hp"]))
     p = R.synthetic_params(hp, seed=int(g["seed"]))
     return hp, p, make_model(hp, p, **kw)
-
-
-def maxdiff(a, b):
-    d = float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
-    log = os.environ.get("DR_PARITY_LOG")          # observed margins, one line per comparison (tools/gpu_*.sh)
-    if log:
-        import inspect
-        fr = inspect.stack()[1]
-        with open(log, "a") as f:
-            f.write(f"{fr.function}:{fr.lineno} {d:.3e}\n")
-    return d
 
 
 # --------------------------------------------------------------------------------------------
@@ -342,19 +301,9 @@ def test_full_200_step_guided_chain_vs_oracle(full_model):
 # --------------------------------------------------------------------------------------------
 # size-independent properties at BASELINE config 2 shape (B=16, T=125, k=9, 200 steps)
 # --------------------------------------------------------------------------------------------
-def _cfg2_inputs(B=16, steps=200):
-    torch.manual_seed(0)
-    L = 64000
-    Tn = L // 512
-    wav = 0.1 * torch.randn(B, L)
-    x = torch.randn(B, 1, Tn, 88)
-    noise = torch.randn(steps, B, 1, Tn, 88)
-    return wav, x, noise
-
-
 def test_full_chain_graph_equals_eager_and_is_deterministic(full_model):
     hp, p, m = full_model
-    wav, x, noise = _cfg2_inputs()
+    wav, x, noise = cfg2_inputs()
     a, _ = m.sample(x, wav, noise=noise, use_graph=True)
     b, _ = m.sample(x, wav, noise=noise, use_graph=False)
     c, _ = m.sample(x, wav, noise=noise, use_graph=True)
@@ -370,7 +319,7 @@ def test_batch_shard_invariance_injected_and_philox(full_model):
     geometry), so across DIFFERENT local batch sizes the agreement is fp32 round-off, not bitwise; the
     bitwise statement for a fixed contraction order is test_batch_shard_bitwise_without_splitk."""
     hp, p, m = full_model
-    wav, x, noise = _cfg2_inputs(B=8)
+    wav, x, noise = cfg2_inputs(B=8)
     full, _ = m.sample(x, wav, noise=noise)
     lo, _ = m.sample(x[:4], wav[:4], noise=noise[:, :4])
     hi, _ = m.sample(x[4:], wav[4:], noise=noise[:, 4:])
@@ -395,10 +344,10 @@ def test_batch_shard_bitwise_without_splitk():
         sys.path.insert(0, %r)
         from tools import tuning_env; tuning_env.install()
         from oracle import diffroll_ref as R
-        from tests.test_gpu_parity import make_model, _cfg2_inputs
+        from tests.testlib import make_model, cfg2_inputs
         hp = dict(R.DEFAULT_HP); hp.update(kernel_size=9, timesteps=20)
         m = make_model(hp, R.synthetic_params(hp, seed=3), sampler="cfdg_ddpm_x0", w=0.5)
-        wav, x, noise = _cfg2_inputs(B=8, steps=20)
+        wav, x, noise = cfg2_inputs(B=8, steps=20)
         full, _ = m.sample(x, wav, noise=noise)
         lo, _ = m.sample(x[:4], wav[:4], noise=noise[:, :4]); hi, _ = m.sample(x[4:], wav[4:], noise=noise[:, 4:])
         ok = torch.equal(full, torch.cat([lo, hi], 0))
@@ -624,7 +573,7 @@ def test_cfg_weight_zero_equals_conditional_sampler(full_model):
     """(1+w) c - w u with w = 0 is c: cfdg_ddpm_x0(w=0) == ddpm_x0 (task/diffusion.py:953).  The two run with
     different batch geometry (2B vs B evaluations), i.e. possibly different contraction orders: round-off."""
     hp, p, _ = full_model
-    wav, x, noise = _cfg2_inputs(B=2, steps=200)
+    wav, x, noise = cfg2_inputs(B=2, steps=200)
     m0 = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.0)
     m1 = make_model(hp, p, sampler="ddpm_x0")
     a, _ = m0.sample(x, wav, noise=noise)
@@ -1145,7 +1094,7 @@ def test_flexible_width_tiles_vs_oracle(monkeypatch):
         sys.path.insert(0, %r)
         from tools import tuning_env; tuning_env.install()
         from oracle import diffroll_ref as R
-        from tests.test_gpu_parity import make_model
+        from tests.testlib import make_model
         hp = dict(R.DEFAULT_HP); hp.update(residual_channels=128, residual_layers=4, kernel_size=9, timesteps=6)
         p = R.synthetic_params(hp, seed=77)
         m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5)

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import ATOL_FWD, ATOL_SPEC, ATOL_STEP, make_model, maxdiff
+from testlib import ATOL_FWD, ATOL_SPEC, ATOL_STEP, make_model, maxdiff
 
 pytestmark = pytest.mark.gpu
 

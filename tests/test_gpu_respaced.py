@@ -9,40 +9,11 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model, maxdiff
+from testlib import ATOL, HOP, S, agree, assert_shared_frames_agree, ckpt_path, hp_of, inputs, load_trained, make_model, maxdiff, run_plan_windows, trained_noise, trained_params
 
 import chain_ref as CR
 
 pytestmark = pytest.mark.gpu
-
-ATOL = 1e-5
-HOP = 512
-S = 200
-
-
-def hp_of(channels=64, layers=4, k=9):
-    hp = dict(R.DEFAULT_HP)
-    hp.update(residual_channels=channels, residual_layers=layers, kernel_size=k, timesteps=S)
-    return hp
-
-
-def inputs(B, Tn, seed):
-    g = torch.Generator().manual_seed(seed)
-    wav = 0.1 * torch.randn(B, Tn * HOP, generator=g)
-    x = torch.randn(B, 1, Tn, 88, generator=g)
-    noise = torch.randn(S, B, 1, Tn, 88, generator=g)
-    return wav, x, noise
-
-
-def agree(roll, ref):
-    """|d| <= ATOL where |ref| <= 1 (the x0 families' rolls), ATOL |ref| beyond - the epsilon samplers' rolls reach
-    |x| ~ 17 under a random network (x_T / sqrt_acp and worse), where fp32 itself spacing is 2e-6 - and the same
-    thresholded roll except within ATOL of the threshold.  Returns (ok, max |d|)."""
-    roll = roll.cpu()
-    d = maxdiff(roll, ref)
-    within = ((roll - ref).abs() <= ATOL * ref.abs().clamp(min=1.0)).all()
-    near = (ref - 0.5).abs() < ATOL
-    return bool(within) and bool((((roll > 0.5) == (ref > 0.5)) | near).all()), d
 
 
 def test_option_is_public_and_validated():
@@ -181,7 +152,6 @@ def test_dr_step_over_the_visited_steps_equals_dr_sample():
 def test_sample_long_at_50_steps_vs_restatement():
     from diffroll_amd import longform
     from oracle import philox
-    from test_gpu_longform import assert_shared_frames_agree, run_windows
     hp = hp_of(channels=128, layers=3)
     p = R.synthetic_params(hp, seed=68)
     m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5)
@@ -199,7 +169,7 @@ def test_sample_long_at_50_steps_vs_restatement():
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
     ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, z, 50, w=0.5, plan=plan)
-    win = run_windows(m, plan, wav, x_T, None, seed=seed, recording=rec)
+    win = run_plan_windows(m, plan, wav, x_T, None, seed=seed, recording=rec)
     assert_shared_frames_agree(win, plan)
     ok, d = agree(win, ref[:, 0])
     assert ok, d
@@ -213,14 +183,13 @@ def test_trained_proxy_thresholded_roll(golden_dir, n):
     """tests/golden/trained_small.ckpt at n steps: the HIP thresholded roll equals the restatement's.  The F1 is
     reported, not asserted: this proxy task is too easy to show a quality cost of fewer steps."""
     from diffroll_amd import ClassifierFreeDiffRoll
-    from test_trained_golden import _ckpt_path, _load, _noise, _params
-    gd = _load(golden_dir)
+    gd = load_trained(golden_dir)
     hp = json.loads(str(gd["hp"]))
-    _, p = _params(golden_dir, gd)
-    x_T, noise = _noise(gd)
+    _, p = trained_params(golden_dir, gd)
+    x_T, noise = trained_noise(gd)
     wav, label = torch.from_numpy(gd["wav"]), torch.from_numpy(gd["label"])
     w = float(gd["w"])
-    m = ClassifierFreeDiffRoll.load_from_checkpoint(_ckpt_path(golden_dir), sampling={"type": "cfdg_ddpm_x0", "w": w, "steps": n})
+    m = ClassifierFreeDiffRoll.load_from_checkpoint(ckpt_path(golden_dir), sampling={"type": "cfdg_ddpm_x0", "w": w, "steps": n})
     ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", x_T, R.frontend(wav, hp, x_T.shape[2]), noise, n, w=w)
     roll, _ = m.sample(x_T, wav, noise=noise)
     thr = float(gd["frame_threshold"])

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
+from testlib import shard_model
 
 pytestmark = pytest.mark.gpu
 
@@ -24,20 +25,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ATOL_SHARD = 1e-5      # other local batch size -> other tile flavour / split-K order: fp32 round-off (observed ~1e-6)
 
 
-def _model(sampler="cfdg_ddpm_x0", layers=4, steps=12, k=9, C=128):
-    from test_gpu_parity import make_model
-    hp = dict(R.DEFAULT_HP)
-    hp.update(residual_channels=C, residual_layers=layers, kernel_size=k, timesteps=steps)
-    p = R.synthetic_params(hp, seed=11)
-    return hp, p, make_model(hp, p, sampler=sampler, w=0.5)
-
-
 @pytest.mark.parametrize("G", [2, 3, 8])
 @pytest.mark.parametrize("mode", ["philox", "injected"])
 def test_fake_ranks_equal_unsharded(G, mode):
     """B = 5 clips over G ranks: shards of 3+2, 2+2+1 and 1+1+1+1+1+0+0+0 (three empty ranks)."""
     from diffroll_amd.distributed import sample_sharded, sample_sharded_sequential, shard_bounds
-    hp, p, m = _model()
+    hp, p, m = shard_model()
     torch.manual_seed(5)
     B, Tn = 5, 40
     wav = 0.1 * torch.randn(B, Tn * 512)
@@ -59,7 +52,7 @@ def test_fake_ranks_equal_unsharded(G, mode):
 
 def test_fake_ranks_generation_without_waveform():
     from diffroll_amd.distributed import sample_sharded, sample_sharded_sequential
-    hp, p, m = _model(sampler="generation_ddpm_x0")
+    hp, p, m = shard_model(sampler="generation_ddpm_x0")
     torch.manual_seed(6)
     x = torch.randn(6, 1, 48, 88)
     whole = sample_sharded(m, x, None, seed=1)
@@ -78,10 +71,10 @@ dev = torch.device("cuda", 0)
 dist = launch.init_process_group(dev, force_single=True)         # 1-rank RCCL group
 info = launch.dist_info(dist)
 assert info["ranks_seen"] == 1 and info["backend"] == "nccl", info
-from test_gpu_sharding import _model
+from testlib import shard_model
 from diffroll_amd.distributed import sample_sharded, gather_rolls, world
 assert world() == (0, 1)
-hp, p, m = _model()
+hp, p, m = shard_model()
 torch.manual_seed(5)
 B, Tn = 3, 40
 wav = 0.1 * torch.randn(B, Tn * 512)
@@ -174,10 +167,10 @@ os.environ["MASTER_ADDR"] = "127.0.0.1"
 os.environ["MASTER_PORT"] = sys.argv[3]
 torch.cuda.set_device(0)                     # both ranks on the one leased GPU
 dist.init_process_group("gloo", rank=rank, world_size=world)
-from test_gpu_sharding import _model
+from testlib import shard_model
 from diffroll_amd.distributed import sample_sharded, world as wfn
 assert wfn() == (rank, world)
-hp, p, m = _model(layers=3, steps=8, C=512)       # full width, 14 evaluations per rank: the fused residual-stack kernel is the one that runs
+hp, p, m = shard_model(layers=3, steps=8, C=512)       # full width, 14 evaluations per rank: the fused residual-stack kernel is the one that runs
 torch.manual_seed(5)
 B, Tn = 14, 125
 wav = 0.1 * torch.randn(B, Tn * 512)
@@ -217,7 +210,7 @@ def test_two_processes_share_the_gpu_and_gather(tmp_path):
         #                                                 that sees the other one computing (csrc/tenants.h) yields to per-phase
         #                                                 launches instead of running into the ~1 s spin bound
     got = torch.load(res)
-    hp, p, m = _model(layers=3, steps=8, C=512)
+    hp, p, m = shard_model(layers=3, steps=8, C=512)
     torch.manual_seed(5)
     B, Tn = 14, 125
     wav = 0.1 * torch.randn(B, Tn * 512)
@@ -317,7 +310,7 @@ def test_engine_yields_to_a_busy_co_tenant_and_comes_back(tmp_path):
     gc.collect()                                          # engines of earlier tests
     lib.dr_debug_kfd_root(busy.encode())
     try:
-        hp, p, m = _model(layers=3, steps=8, C=512)
+        hp, p, m = shard_model(layers=3, steps=8, C=512)
         torch.manual_seed(11)
         B, Tn = 16, 125                                   # 32 evaluations x 8 M tiles: the fused kernels' own geometry
         wav = 0.1 * torch.randn(B, Tn * 512)

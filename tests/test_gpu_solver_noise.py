@@ -8,8 +8,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model, maxdiff
-from test_gpu_respaced import HOP, S, agree, hp_of, inputs
+from testlib import HOP, S, agree, assert_shared_frames_agree, hp_of, inputs, make_model, maxdiff, run_plan_windows
 
 import chain_ref as CR
 
@@ -201,7 +200,6 @@ def test_option_at_0_is_the_engine_that_never_set_it():
 def test_sample_long_vs_restatement():
     from diffroll_amd import longform
     from oracle import philox
-    from test_gpu_longform import assert_shared_frames_agree, run_windows
     hp = hp_of(channels=128, layers=3)
     p = R.synthetic_params(hp, seed=81)
     m = noisy_model(hp, p, "cfdg_ddpm_x0", 20, 2)
@@ -218,7 +216,7 @@ def test_sample_long_vs_restatement():
     xw = longform.gather_windows(x_T.reshape(plan.T_c, 88), plan).unsqueeze(1)
     spec = R.frontend(longform.window_audio(wav, plan, HOP), hp, plan.T)
     ref = CR.sample_chain(p, hp, "cfdg_ddpm_x0", xw, spec, z, 20, order=2, solver_noise=1, w=0.5, plan=plan)
-    win = run_windows(m, plan, wav, x_T, None, seed=seed, recording=rec)
+    win = run_plan_windows(m, plan, wav, x_T, None, seed=seed, recording=rec)
     assert_shared_frames_agree(win, plan)
     ok, d = agree(win, ref[:, 0])
     print(f"\nlong-form stochastic order 2 n 20: max |d| {d:.3e}")

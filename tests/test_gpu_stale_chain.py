@@ -6,7 +6,7 @@ Geometry and four-step chain of test_gpu_x0_clip.py::test_inert_option_values_re
 import pytest
 import torch
 
-from test_gpu_parity import make_model
+from testlib import make_model
 
 import clip_cases as CC
 

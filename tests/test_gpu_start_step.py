@@ -9,8 +9,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
-from test_gpu_parity import make_model, maxdiff
-from test_gpu_respaced import ATOL, HOP, S, agree, hp_of, inputs
+from testlib import ATOL, HOP, S, agree, assert_shared_frames_agree, hp_of, inputs, make_model, maxdiff
 
 import chain_ref as CR
 
@@ -214,7 +213,6 @@ def test_fused_path_graph_eager_per_phase_and_nothing_across_replays():
 # ---------------------------------------------------------------------------------------------- 6. long form
 def test_long_form_refinement():
     from diffroll_amd import longform
-    from test_gpu_longform import assert_shared_frames_agree
     hp = hp_of(channels=128, layers=3)
     p = R.synthetic_params(hp, seed=81)
     m = make_model(hp, p, sampler="cfdg_ddpm_x0", w=0.5)

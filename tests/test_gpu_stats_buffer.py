@@ -7,8 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import make_model
-from test_gpu_x0_threshold import same_bits
+from testlib import make_model, same_bits
 
 import project_ref as PR
 import rescale_cases as RC

@@ -6,8 +6,7 @@ shows to move with the mode.  Tolerance: ATOL = 1e-5 of the long-form tests."""
 import pytest
 import torch
 
-from test_gpu_longform import ATOL, assert_shared_frames_agree
-from test_gpu_parity import make_model, maxdiff
+from testlib import ATOL, assert_shared_frames_agree, make_model, maxdiff
 
 import blend_cases as BC
 import blend_ref as BR

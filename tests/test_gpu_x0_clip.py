@@ -9,8 +9,7 @@ parity tests - a clamp is 1-Lipschitz, so the established margin carries over.""
 import pytest
 import torch
 
-from test_gpu_parity import make_model, maxdiff
-from test_gpu_respaced import S, agree
+from testlib import S, agree, assert_shared_frames_agree, make_model, maxdiff, run_plan_windows
 
 import chain_ref as CR
 import clip_cases as CC
@@ -164,12 +163,11 @@ def test_strength_with_init_vs_restatement():
 # ---------------------------------------------------------------------------------------------- 5. windows, draws, shards
 def test_sample_long_vs_restatement():
     from diffroll_amd import longform
-    from test_gpu_longform import assert_shared_frames_agree, run_windows
     hp, p, plan, wav, x_T = CC.long_case()
     ref, moved = CC.long_reference()
     CC.exercised(moved, ("lo", "hi"), ref, CC.long_reference(0)[0])
     m = clipped_model(hp, p, "cfdg_ddpm_x0", 3.0, 1, 20)
-    win = run_windows(m, plan, wav, x_T, None, seed=CC.LONG_SEED, recording=CC.LONG_REC)
+    win = run_plan_windows(m, plan, wav, x_T, None, seed=CC.LONG_SEED, recording=CC.LONG_REC)
     assert_shared_frames_agree(win, plan)             # two windows clamp the same mean: torch.equal on the frames they share
     ok, d = agree(win, ref[:, 0])
     print(f"\nlong-form w 3 code 1 n 20: max |d| {d:.3e}")

@@ -8,8 +8,7 @@ tests/test_x0_threshold_cpu.py shows to be active or inert as claimed.  Toleranc
 import pytest
 import torch
 
-from test_gpu_parity import make_model, maxdiff
-from test_gpu_respaced import ATOL, S, agree
+from testlib import ATOL, S, agree, assert_shared_frames_agree, kernel_inputs, make_model, maxdiff, run_plan_windows, same_bits
 
 import chain_ref as CR
 import clip_cases as CC
@@ -42,13 +41,6 @@ def guided(n=20, **kw):
     return thresh_model(hp, p, s, w, code, v, n, **kw), wav, x, noise
 
 
-def same_bits(got, want):
-    """Bit equality of two fp32 tensors, a NaN equal to a NaN (its payload is the adder's, not the option's)."""
-    got, want = got.cpu(), want.cpu()
-    both_nan = torch.isnan(got) & torch.isnan(want)
-    return bool(((got.view(torch.int32) == want.view(torch.int32)) | both_nan).all())
-
-
 # ---------------------------------------------------------------------------------------------- 1. the kernel alone
 @pytest.fixture(scope="module")
 def lab():
@@ -58,23 +50,6 @@ def lab():
     yield eng
     for name, value in (("window_overlap", 0), ("window_break", 0), ("draws", 1), ("x0_threshold", 0), ("x0_clip", 0)):
         eng.set_option(name, value)
-
-
-def kernel_inputs(B, T, seed):
-    """name -> the conditional prediction (B, T, 88): normal noise, all equal, two values with the tie straddling k and k + 1
-    at v = 5000, a roll with +-0 and +-inf, a roll with one NaN, a roll of only NaN."""
-    g = torch.Generator().manual_seed(seed)
-    n = T * 88
-    noise = 1.2 * torch.randn(B, T, 88, generator=g)
-    two = torch.cat([torch.full((n // 2,), -1.5), torch.full((n - n // 2,), 2.5)])
-    two = two[torch.randperm(n, generator=g)].reshape(1, T, 88).repeat(B, 1, 1)
-    specials = noise.clone()
-    specials[0].view(-1)[:4] = torch.tensor([0.0, -0.0, float("inf"), float("-inf")])[: min(4, n)]
-    one_nan = noise.clone()
-    one_nan[B - 1].view(-1)[n // 2] = float("nan")
-    only_nan = noise.clone()
-    only_nan[0] = float("nan")
-    return {"noise": noise, "equal": torch.full((B, T, 88), 0.75), "two": two, "specials": specials, "one_nan": one_nan, "only_nan": only_nan}
 
 
 def guided_y(c, u, w):
@@ -306,17 +281,16 @@ def test_fused_geometry_leaves_the_tail_kernel_and_comes_back():
 # ---------------------------------------------------------------------------------------------- 6. long form
 def test_sample_long_vs_the_per_canvas_restatement():
     from diffroll_amd import longform
-    from test_gpu_longform import assert_shared_frames_agree, run_windows
     hp, p, plan, wav, x_T = CC.long_case()
     ref, stats, r = TC.long_reference()
     assert all(TR.active(stats, r))
     m = thresh_model(hp, p, "cfdg_ddpm_x0", 3.0, 2, 9950, 20)
-    win = run_windows(m, plan, wav, x_T, None, seed=CC.LONG_SEED, recording=CC.LONG_REC)
+    win = run_plan_windows(m, plan, wav, x_T, None, seed=CC.LONG_SEED, recording=CC.LONG_REC)
     assert_shared_frames_agree(win, plan)             # all windows of the recording use the same s on the same mean
     ok, d = agree(win, ref[:, 0])
     print(f"\nlong-form w 3 code 2 v 9950 n 20: max |d| {d:.3e}")
     assert ok, d
-    eager = run_windows(m, plan, wav, x_T, None, seed=CC.LONG_SEED, recording=CC.LONG_REC, use_graph=False)
+    eager = run_plan_windows(m, plan, wav, x_T, None, seed=CC.LONG_SEED, recording=CC.LONG_REC, use_graph=False)
     assert torch.equal(win, eager)
     roll = m.sample_long(wav, overlap=160, seed=CC.LONG_SEED, recording=CC.LONG_REC, x_T=x_T).cpu()
     assert torch.equal(roll[0, 0], longform.stitch(win, plan))

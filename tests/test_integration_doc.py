@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from oracle import diffroll_ref as R
+from testlib import make_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -106,7 +107,6 @@ def test_the_documented_block_is_valid_python_and_names_the_header_symbols():
 @pytest.mark.gpu
 def test_the_documented_binding_runs_and_matches_the_facade_bit_for_bit(tmp_path):
     import json
-    from test_gpu_parity import make_model
     hp = dict(R.DEFAULT_HP)
     hp.update(residual_channels=64, residual_layers=4, kernel_size=9, timesteps=12)
     out = str(tmp_path / "roll.pt")

@@ -12,8 +12,10 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from testlib import free_port
+
 import chain_ref as CR
-from test_facade_cpu import MELS, RecordingEngine, clip, eq, facade, sample_call
+from facade_fakes import HOP, L1, L2, MELS, RecordingEngine, clip, eq, facade, sample_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -180,7 +182,6 @@ def test_facade_trajectory_and_drivers():
 
 def test_facade_long_form_init():
     from diffroll_amd import longform
-    from test_facade_cpu import HOP, L1, L2
     m, eng = start_facade(timesteps=4, sampling={"strength": 0.5})
     g = torch.Generator().manual_seed(5)
     wav = torch.randn(L2, generator=g)
@@ -334,7 +335,6 @@ def _shard_worker(rank, world, port, B, draws, ret):
 
 @pytest.mark.parametrize("B,draws", [(5, 1), (3, 2)])
 def test_init_is_sharded_like_x_T(B, draws):
-    from test_distributed_cpu import _free_port
     from diffroll_amd.distributed import sample_shard, sample_sharded
     torch.manual_seed(0)
     init, wav = torch.rand(draws * B, 1, 6, 88), torch.randn(B, 64)
@@ -345,7 +345,7 @@ def test_init_is_sharded_like_x_T(B, draws):
         sample_shard(ShardModel(), init, wav, None, 5, 0, 1, draws, init)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_shard_worker, args=(r, 2, port, B, draws, q)) for r in range(2)]
     for p in procs:
         p.start()

@@ -7,6 +7,8 @@ import re
 import pytest
 import torch
 
+from testlib import header_functions
+
 import blend_cases as BC
 import blend_ref as BR
 import chain_ref as CR
@@ -189,7 +191,6 @@ def test_option_is_public_and_documented():
 
 def test_abi_stays_at_11_and_30_functions():
     from diffroll_amd import _cabi
-    from test_cabi_cpu import header_functions
     assert _cabi.DR_ABI_VERSION == 11
     text = open(os.path.join(ROOT, "include", "diffroll_amd.h")).read()
     assert int(re.search(r"#define DR_ABI_VERSION (\d+)", text).group(1)) == 11

@@ -8,6 +8,8 @@ import re
 import pytest
 import torch
 
+from testlib import ATOL
+
 import clip_cases as CC
 import clip_ref as CL
 import thresh_cases as TC
@@ -107,7 +109,6 @@ def test_the_issues_figures():
 
 
 def test_gpu_fused_and_long_cases_are_active():
-    from test_gpu_respaced import ATOL
     for (roll, stats, r), clipped in ((TC.fused_reference(), CC.fused_reference(2)[0]), (TC.long_reference(), CC.long_reference(2)[0])):
         flags = TR.active(stats, r)
         assert flags and all(flags)

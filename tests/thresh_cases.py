@@ -10,6 +10,7 @@ import functools
 
 import clip_cases as CC
 import thresh_ref as TR
+from testlib import ATOL
 
 # (sampler, w, code, v)
 ACTIVE = [
@@ -55,7 +56,6 @@ def reference(sampler, w, code, v, n, philox=False, **opts):
 def assert_active(sampler, w, code, v, n, philox=False, **opts):
     """An active case: s > r at every visited step and roll - under a guidance interval at every guided step and at no other -
     and the roll at least 100 ATOL from the clipped chain's.  Returns the reference roll."""
-    from test_gpu_respaced import ATOL
     roll, stats, r = reference(sampler, w, code, v, n, philox, **opts)
     flags = TR.active(stats, r)
     if "interval" in opts:      # an unguided step thresholds the conditional prediction alone: under code 2 that is inert
