@@ -27,7 +27,7 @@ SAMPLERS = {
     "ddim2ddpm": 8,     # epsilon prediction (:894-911)
 }
 COND_SPEC, COND_UNCOND = 0, 1
-PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2}
+PRECISIONS = {"f32": 0, "bf16x3": 1, "bf16": 2, "f16": 4}      # (3 is reserved: dr_set_precision refuses it)
 NORM_MODES = {"imagewise": 0, "framewise": 1}
 
 # every symbol include/diffroll_amd.h declares (the boundary) ...

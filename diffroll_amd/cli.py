@@ -115,7 +115,7 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
         for part in parts[:-1]:
             node = node.setdefault(part, {})
         node[parts[-1]] = _parse_value(v)
-    # precision=f32 | bf16x3 | bf16: the arithmetic of the two hot contractions (Engine.set_precision)
+    # precision=f32 | bf16x3 | bf16 | f16: the arithmetic of the two hot contractions (Engine.set_precision)
     from ._cabi import PRECISIONS
     if cfg.get("precision", "f32") not in PRECISIONS:
         raise SystemExit(f"precision must be one of {sorted(PRECISIONS)}, got {cfg.get('precision')!r}")

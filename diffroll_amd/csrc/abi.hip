@@ -138,7 +138,7 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
                                     "same time? call dr_finish (or dr_stack_status) to clear the condition and recompute - "
                                     "dr_finish also switches this engine to per-phase launches; dr_sample_checked does all of that");
     if (B <= 0 || T <= 0) return fail(e, DR_EINVAL, "bad shape B=%d T=%d", B, T);
-    if (e->prec && !(e->prec == 2 ? e->bf16_ready : e->s3_ready)) {       // (a commit after dr_set_precision, or a packing build that failed: never launch without them)
+    if (!packings_ready(e, e->prec)) {       // (a commit after dr_set_precision, or a packing build that failed: never launch without them)
         int rc = ensure_packings(e, e->prec);
         if (rc) return rc;
     }
@@ -1070,11 +1070,13 @@ int dr_set_spec_norm(dr_engine* e, int mode) {
 
 int dr_set_precision(dr_engine* e, int mode) {
     if (!e) return DR_EINVAL;
-    if (mode != DR_PRECISION_F32 && mode != DR_PRECISION_BF16X3 && mode != DR_PRECISION_BF16) return fail(e, DR_EINVAL, "unknown precision mode %d", mode);
+    // (3 is reserved: refused like every other unknown value, the engine stays where it was)
+    if (mode != DR_PRECISION_F32 && mode != DR_PRECISION_BF16X3 && mode != DR_PRECISION_BF16 && mode != DR_PRECISION_F16)
+        return fail(e, DR_EINVAL, "unknown precision mode %d", mode);
     if (mode != e->prec) {
         DeviceGuard guard(e->cfg.device);
         stale(e);
-        if (mode) {           // the mode changes only once its own packings exist (bf16x3: 520 MB of uploads, bf16: a third - the build can fail)
+        if (mode) {           // the mode changes only once its own packings exist (bf16x3: 520 MB of uploads, bf16 and f16: a third each - the build can fail)
             int rc = ensure_packings(e, mode);      // (adds buffers, frees and rewrites none: nothing to wait for)
             if (rc) return rc;
         }

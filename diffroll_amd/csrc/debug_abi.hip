@@ -116,7 +116,7 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     const int Cp = e->Cp, P = Cp / 4;
     const LayerW& w = e->layers[layer];
     GemmArgs a = p4_gemm(w.conv_w_of(e->prec), w.conv_b, Cp / 64, e->hd, P, NB, T);
-    const long act_bs = (long)Cp * T, s3_bs = e->prec == 2 ? act_bs / 2 : act_bs + act_bs / 2;
+    const long act_bs = (long)Cp * T, s3_bs = one_plane16(e->prec) ? act_bs / 2 : act_bs + act_bs / 2;
     if (e->prec) {
         a.X = e->hd3; a.x_bs = s3_bs; a.x_piece = (long)(Cp / 8) * T * 4; a.x_ps = (long)T * 4; a.x_fs = 4;
         a.x_planes = Cp / 8; a.kchunks = Cp / 32;
@@ -149,7 +149,7 @@ int dr_bench_pointwise(dr_engine* e, int layer, int NB, int T, void* stream) {
     GemmArgs a = p4_gemm(w.out_w_of(e->prec), w.out_b, Cp / 64, e->g, P, NB, T);
     if (e->prec) {
         const long act_bs = (long)Cp * T;
-        a.X = e->g3; a.x_bs = e->prec == 2 ? act_bs / 2 : act_bs + act_bs / 2; a.x_piece = (long)(Cp / 8) * T * 4; a.x_ps = (long)T * 4; a.x_fs = 4;
+        a.X = e->g3; a.x_bs = one_plane16(e->prec) ? act_bs / 2 : act_bs + act_bs / 2; a.x_piece = (long)(Cp / 8) * T * 4; a.x_ps = (long)T * 4; a.x_fs = 4;
         a.x_planes = Cp / 8; a.kchunks = Cp / 32;
     }
     p4_out(a, e->h, P, T, Cp);
@@ -157,7 +157,7 @@ int dr_bench_pointwise(dr_engine* e, int layer, int NB, int T, void* stream) {
     {   // second output as in the chain: hd = h + d_{l+1} (fp32 P4 or split-bf16)
         const long act_bs = (long)Cp * T;
         a.d2 = e->d_dtab + (size_t)((layer + 1) % e->L) * Cp;
-        if (e->prec) { a.Y2 = e->hd3; a.y2_bs = e->prec == 2 ? act_bs / 2 : act_bs + act_bs / 2; a.out_s3 = 2; }
+        if (e->prec) { a.Y2 = e->hd3; a.y2_bs = one_plane16(e->prec) ? act_bs / 2 : act_bs + act_bs / 2; a.out_s3 = 2; }
         else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     }
     HIPCHK(e, e->dbg_ticks.ensure(16, true));

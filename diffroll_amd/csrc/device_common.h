@@ -55,7 +55,7 @@ static void host_extent(const void* p, size_t bytes, const char* what, const cha
     }
 }
 static void check_gemm_extents(const GemmArgs& a, int epi, int prec, const char* kernel) {
-    const size_t slab = prec == 2 ? 8192 : prec ? 24576 : 16384;
+    const size_t slab = weight_slab_bytes(prec);
     const int mts = a.mt0 + a.MT;
     host_extent(a.Wp, (size_t)mts * a.kchunks * a.taps * slab, "packed weights", kernel);
     host_extent(a.bias, (size_t)mts * 128 * 4, "bias", kernel);
@@ -107,8 +107,10 @@ hipError_t init_frontend_kernels();
 
 struct AF4 { float4 v[4]; };                         // fp32 A fragments of one K step (32 channels): one per 8-channel group
 struct AF6 { uint4 v[6]; };                          // split-bf16 A fragments of one K step: [g16 * 3 + piece]
-struct AF2 { uint4 v[2]; };                          // one-pass bf16 A fragments of one K step: [g16]
+struct AF2 { uint4 v[2]; };                          // one-pass bf16 / f16 A fragments of one K step: [g16]
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 // allow the whole 160 KiB of dynamic LDS for every kernel given; stops at the first error
 template <class... K>
@@ -175,14 +177,11 @@ DR_DEVINL void store_s3_quad(float* dst, const float (&v)[4], int row0, int t, i
         *reinterpret_cast<uint2*>(q) = w;
     }
 }
-// One-pass bf16 (precision "bf16"): piece 0 of the split alone - the round-to-nearest-even bf16 of the value - in a tensor
-// of ONE plane set, [batch][plane8 = channel/8][frame][8 bf16].  The quad is the low (half = 0) or high 8 bytes of its
-// plane8 unit; COH / write_through as store_s3_quad.
+// The one-plane 16-bit modes (launch_plan.h: one_plane16) keep a tensor as ONE plane set, [batch][plane8 = channel/8][frame]
+// [8 x 16 bit].  A quad of 4 consecutive channels, packed two per word (the lower channel in the low half), is the low
+// (half = 0) or high 8 bytes of its plane8 unit; COH / write_through as store_s3_quad.
 template <int COH = 0>
-DR_DEVINL void store_bf16_quad(float* dst, const float (&v)[4], int row0, int t, int T, const int write_through = 0) {
-    uint2 w;
-    w.x = (bf16_rne_bits(v[0]) >> 16) | bf16_rne_bits(v[1]);
-    w.y = (bf16_rne_bits(v[2]) >> 16) | bf16_rne_bits(v[3]);
+DR_DEVINL void store_quad16(float* dst, const uint2 w, int row0, int t, int T, const int write_through) {
     char* q = reinterpret_cast<char*>(dst) + ((long)(row0 >> 3) * T + t) * 16 + ((row0 >> 2) & 1) * 8;
     if constexpr (COH && DR_FAULT != 2) {
         if (write_through) {       // wave-uniform
@@ -194,8 +193,47 @@ DR_DEVINL void store_bf16_quad(float* dst, const float (&v)[4], int row0, int t,
     }
     *reinterpret_cast<uint2*>(q) = w;
 }
+// One-pass bf16 (precision "bf16"): piece 0 of the split alone - the round-to-nearest-even bf16 of the value.
+template <int COH = 0>
+DR_DEVINL void store_bf16_quad(float* dst, const float (&v)[4], int row0, int t, int T, const int write_through = 0) {
+    uint2 w;
+    w.x = (bf16_rne_bits(v[0]) >> 16) | bf16_rne_bits(v[1]);
+    w.y = (bf16_rne_bits(v[2]) >> 16) | bf16_rne_bits(v[3]);
+    store_quad16<COH>(dst, w, row0, t, T, write_through);
+}
+// One-pass fp16 (precision "f16"): the IEEE binary16 of the value.  (_Float16)float is v_cvt_f16_f32 / v_cvt_pk_f16_f32:
+// round to nearest even under the kernels' default mode, subnormal results kept (float_denorm_mode_16_64 = 3), 65520 and
+// above to infinity, NaN to NaN.  (NOT the cvt_pkrtz builtin, which rounds toward zero.)
+DR_DEVINL uint32_t f16_rne_pair(float lo, float hi) {         // binary16(lo) in the low half, binary16(hi) in the high half
+    const f16x2 h = {(_Float16)lo, (_Float16)hi};
+    return __builtin_bit_cast(uint32_t, h);
+}
+template <int COH = 0>
+DR_DEVINL void store_f16_quad(float* dst, const float (&v)[4], int row0, int t, int T, const int write_through = 0) {
+    uint2 w;
+    w.x = f16_rne_pair(v[0], v[1]);
+    w.y = f16_rne_pair(v[2], v[3]);
+    store_quad16<COH>(dst, w, row0, t, T, write_through);
+}
 DR_DEVINL f32x16 mma_bf16(const uint4 a, const uint4 b, const f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// v_mfma_f32_32x32x16_f16: the bf16 instruction's shape, lane maps, rate and operand bytes on binary16 operands
+DR_DEVINL f32x16 mma_f16(const uint4 a, const uint4 b, const f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// What distinguishes the one-plane 16-bit modes - the conversion and the MFMA - selected by the precision code
+template <int PREC, int COH = 0>
+DR_DEVINL void store_quad_of(float* dst, const float (&v)[4], int row0, int t, int T, const int write_through = 0) {
+    static_assert(one_plane16(PREC), "a one-plane 16-bit mode");
+    if constexpr (PREC == DR_PRECISION_F16) store_f16_quad<COH>(dst, v, row0, t, T, write_through);
+    else store_bf16_quad<COH>(dst, v, row0, t, T, write_through);
+}
+template <int PREC>
+DR_DEVINL f32x16 mma_of(const uint4 a, const uint4 b, const f32x16 c) {
+    static_assert(one_plane16(PREC), "a one-plane 16-bit mode");
+    if constexpr (PREC == DR_PRECISION_F16) return mma_f16(a, b, c);
+    else return mma_bf16(a, b, c);
 }
 
 // sched_group_barrier helper (masks: 0x8 MFMA, 0x100 DS read): the next N instructions of that class
@@ -215,7 +253,7 @@ DR_DEVINL void sgb_mix() {
         sgb_mix<N - 1, (V > 0 ? V - 1 : 0)>();
     }
 }
-// N x (1 MFMA, 1 LDS read [, 1 vector-memory read for the first V]): the one-pass bf16 K step, one fragment read per MFMA
+// N x (1 MFMA, 1 LDS read [, 1 vector-memory read for the first V]): the one-pass bf16 / f16 K step, one fragment read per MFMA
 template <int N, int V>
 DR_DEVINL void sgb_mix1() {
     if constexpr (N > 0) {

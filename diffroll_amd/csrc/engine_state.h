@@ -46,9 +46,11 @@ struct LayerW {
     float* out_w3 = nullptr;     // split-bf16 packing of out_w
     float* conv_wb = nullptr;    // one-pass bf16 packing of conv_w  [MTc][kch][k] slabs of 8 KiB
     float* out_wb = nullptr;     // one-pass bf16 packing of out_w
-    // the packing of the two hot GEMMs that precision `prec` contracts
-    const float* conv_w_of(int prec) const { return prec == 2 ? conv_wb : prec ? conv_w3 : conv_w; }
-    const float* out_w_of(int prec) const { return prec == 2 ? out_wb : prec ? out_w3 : out_w; }
+    float* conv_wh = nullptr;    // one-pass f16 packing of conv_w: bf16's slabs and index order, IEEE binary16 values
+    float* out_wh = nullptr;     // one-pass f16 packing of out_w
+    // the packing of the two hot GEMMs that precision `prec` (DR_PRECISION_*) contracts
+    const float* conv_w_of(int prec) const { return prec == DR_PRECISION_F16 ? conv_wh : prec == DR_PRECISION_BF16 ? conv_wb : prec ? conv_w3 : conv_w; }
+    const float* out_w_of(int prec) const { return prec == DR_PRECISION_F16 ? out_wh : prec == DR_PRECISION_BF16 ? out_wb : prec ? out_w3 : out_w; }
     float* out_w = nullptr;      // packed (natural halves) 1x1
     float* out_b = nullptr;
     float* cond_w = nullptr;     // packed (paired rows) conditioner 1x1
@@ -268,10 +270,12 @@ struct dr_engine {
     drh::DevBuf<unsigned> sk_cnt;
     drh::DevBuf<float> h, hd, g, skip, tmp, x0buf;
     drh::DevBuf<float> xwork;              // the captured chain runs in place on this roll buffer (not the caller's)
-    drh::DevBuf<float> hd3, g3;            // split-bf16 (S3) versions of hd and g: 1.5x the fp32 size
-    int prec = 0;                          // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3, 6 products), 2: one-pass bf16 (1 product)
+    drh::DevBuf<float> hd3, g3;            // split-bf16 (S3) versions of hd and g: 1.5x the fp32 size; the one-plane 16-bit modes
+                                           // (bf16, f16) use the first third - only one mode is active at a time
+    int prec = 0;                          // 0: exact fp32 MFMA, 1: split-bf16 (bf16x3, 6 products), 2: one-pass bf16 (1 product), 4: one-pass f16 (1 product)
     bool s3_ready = false;                 // the split-bf16 packings exist (built on first use: ensure_s3)
     bool bf16_ready = false;               // the one-pass bf16 packings exist (built on first use: ensure_bf16)
+    bool f16_ready = false;                // the one-pass f16 packings exist (built on first use: ensure_f16)
     double t_pack_s = 0.0, t_upload_s = 0.0, t_tables_s = 0.0;      // dr_cold_times (the capture's seconds: chain)
     int norm_framewise = 0;                // spectrogram normalisation: 0 imagewise, 1 framewise (norm_args[2])
     // conditioner tensors of the last dr_frontend: [L][fe_B][2Cp/4][fe_T][4]
@@ -446,6 +450,8 @@ const std::vector<float>* find_param(dr_engine* e, const std::string& name);
 size_t expected_numel(const dr_engine* e, const std::string& name);
 int ensure_s3(dr_engine* e);            // the split-bf16 packings, built on first use
 int ensure_bf16(dr_engine* e);          // the one-pass bf16 packings, built on first use (independent of ensure_s3)
+int ensure_f16(dr_engine* e);           // the one-pass f16 packings, built on first use (independent of the other two)
+bool packings_ready(const dr_engine* e, int prec);      // the packings precision `prec` contracts exist
 int ensure_packings(dr_engine* e, int prec);      // what precision `prec` needs beyond the fp32 packings (nothing for 0)
 int commit(dr_engine* e, hipStream_t st);
 

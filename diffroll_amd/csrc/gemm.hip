@@ -5,6 +5,7 @@
 //   gemm_kernel<.., PREC=0>  exact fp32 on v_mfma_f32_32x32x2_f32      (default; 64/128-frame blocks)
 //   gemm_kernel<.., PREC=1>  split-bf16 on v_mfma_f32_32x32x16_bf16    (opt-in "bf16x3", hot kernels)
 //   gemm_kernel<.., PREC=2>  one-pass bf16 on the same MFMA            (opt-in "bf16", hot kernels)
+//   gemm_kernel<.., PREC=4>  one-pass fp16 on v_mfma_f32_32x32x16_f16   (opt-in "f16", hot kernels)
 //   gemm16_kernel            exact fp32 on v_mfma_f32_16x16x4_f32      (96/160-frame blocks, hot kernels)
 // used for
 //   * dilated Conv1d (k taps) + conditioner add + sigmoid*tanh gate   (model/diffwave.py:139-147)
@@ -362,6 +363,9 @@ hipError_t init_kernels() {
     // one-pass bf16 instantiations: the same four, and the 128-frame conv with blocked accumulation
     if ((e = allow_max_lds(&gemm_kernel<1, 1, EPI_GATE, 2>, &gemm_kernel<2, 1, EPI_GATE, 2>, &gemm_kernel<1, 4, EPI_RES_SKIP, 2>,
                            &gemm_kernel<1, 1, EPI_RES_SKIP, 2>, &gemm_kernel<2, 1, EPI_GATE, 2, 1>)) != hipSuccess) return e;
+    // one-pass f16 instantiations: the same five
+    if ((e = allow_max_lds(&gemm_kernel<1, 1, EPI_GATE, 4>, &gemm_kernel<2, 1, EPI_GATE, 4>, &gemm_kernel<1, 4, EPI_RES_SKIP, 4>,
+                           &gemm_kernel<1, 1, EPI_RES_SKIP, 4>, &gemm_kernel<2, 1, EPI_GATE, 4, 1>)) != hipSuccess) return e;
     // the explicit FOLDP flavours of the gated conv, and the 96 / 160-frame blocks
     if ((e = allow_max_lds(&gemm_kernel<2, 1, EPI_GATE, 0, 1>, &gemm_kernel<1, 1, EPI_GATE, 0, 0>, &gemm_kernel<2, 1, EPI_GATE, 1, 1>,
                            &gemm_kernel<5, 1, EPI_GATE, 0, 1>, &gemm_kernel<3, 1, EPI_GATE, 0, 1>)) != hipSuccess) return e;
@@ -372,10 +376,10 @@ hipError_t init_kernels() {
     return init_gemm16();
 }
 
-// precision "bf16": the P4 fp32 tensor as one bf16 plane set.  One thread per (sample, plane8, frame): two float4 in
-// (the planes 2 p and 2 p + 1 of that frame), one 16-byte unit out.
-__global__ __launch_bounds__(256) void round_bf16_kernel(const float* __restrict__ src, float* __restrict__ dst, const int P8, const int T,
-                                                         const long n) {
+// precisions "bf16" / "f16": the P4 fp32 tensor as one 16-bit plane set.  One thread per (sample, plane8, frame): two float4
+// in (the planes 2 p and 2 p + 1 of that frame), one 16-byte unit out; pack2(lo, hi) = the mode's rounding of two values.
+template <class Pack2>
+DR_DEVINL void round16_unit(const float* __restrict__ src, float* __restrict__ dst, const int P8, const int T, const long n, Pack2 pack2) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;       // = (b * P8 + p) * T + t
     if (i >= n) return;
     const long bp = i / T;
@@ -386,17 +390,32 @@ __global__ __launch_bounds__(256) void round_bf16_kernel(const float* __restrict
     const float4 lo = *reinterpret_cast<const float4*>(s0);
     const float4 hi = *reinterpret_cast<const float4*>(s0 + (long)T * 4);
     uint4 o;
-    o.x = (bf16_rne_bits(lo.x) >> 16) | bf16_rne_bits(lo.y);
-    o.y = (bf16_rne_bits(lo.z) >> 16) | bf16_rne_bits(lo.w);
-    o.z = (bf16_rne_bits(hi.x) >> 16) | bf16_rne_bits(hi.y);
-    o.w = (bf16_rne_bits(hi.z) >> 16) | bf16_rne_bits(hi.w);
+    o.x = pack2(lo.x, lo.y);
+    o.y = pack2(lo.z, lo.w);
+    o.z = pack2(hi.x, hi.y);
+    o.w = pack2(hi.z, hi.w);
     *reinterpret_cast<uint4*>(dst + i * 4) = o;
 }
-hipError_t launch_round_bf16(const float* src, float* dst, int NB, int Cp, int T, hipStream_t s) {
+__global__ __launch_bounds__(256) void round_bf16_kernel(const float* __restrict__ src, float* __restrict__ dst, const int P8, const int T,
+                                                         const long n) {
+    round16_unit(src, dst, P8, T, n, [](float lo, float hi) { return (bf16_rne_bits(lo) >> 16) | bf16_rne_bits(hi); });
+}
+__global__ __launch_bounds__(256) void round_f16_kernel(const float* __restrict__ src, float* __restrict__ dst, const int P8, const int T,
+                                                        const long n) {
+    round16_unit(src, dst, P8, T, n, [](float lo, float hi) { return f16_rne_pair(lo, hi); });
+}
+template <class K>
+static hipError_t launch_round16(K kernel, const float* src, float* dst, int NB, int Cp, int T, hipStream_t s) {
     if (NB < 1 || T < 1 || Cp < 8 || (Cp & 7)) return hipErrorInvalidValue;
     const long n = (long)NB * (Cp >> 3) * T;
-    hipLaunchKernelGGL(round_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, Cp >> 3, T, n);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, Cp >> 3, T, n);
     return hipGetLastError();
+}
+hipError_t launch_round_bf16(const float* src, float* dst, int NB, int Cp, int T, hipStream_t s) {
+    return launch_round16(round_bf16_kernel, src, dst, NB, Cp, T, s);
+}
+hipError_t launch_round_f16(const float* src, float* dst, int NB, int Cp, int T, hipStream_t s) {
+    return launch_round16(round_f16_kernel, src, dst, NB, Cp, T, s);
 }
 
 template <int NI, int KS>
@@ -413,20 +432,21 @@ static hipError_t launch_gemm_ni(const GemmArgs& a, int epi, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
+// split-bf16, one-pass bf16 or one-pass f16 input: only the two hot kernels exist in these precisions
+template <int PREC>
+static hipError_t launch_gemm_lowp(const GemmArgs& a, int epi, int NI, hipStream_t s) {
+    if (epi == EPI_GATE) return NI == 1 ? launch_gemm_t<1, 1, EPI_GATE, PREC>(a, s) : launch_gemm_t<2, 1, EPI_GATE, PREC>(a, s);
+    if (epi == EPI_RES_SKIP && a.taps == 1)
+        return a.kchunks % 4 == 0 ? launch_gemm_t<1, 4, EPI_RES_SKIP, PREC>(a, s) : launch_gemm_t<1, 1, EPI_RES_SKIP, PREC>(a, s);
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_gemm(const GemmArgs& a, int epi, int NI, hipStream_t s, int prec) {
     if (a.kchunks < 1) return hipErrorInvalidValue;   // the X tile width is only bounded by LDS (checked per launch)
-    if (prec == 2) {   // one-pass bf16 input: the same two hot kernels
-        if (epi == EPI_GATE) return NI == 1 ? launch_gemm_t<1, 1, EPI_GATE, 2>(a, s) : launch_gemm_t<2, 1, EPI_GATE, 2>(a, s);
-        if (epi == EPI_RES_SKIP && a.taps == 1)
-            return a.kchunks % 4 == 0 ? launch_gemm_t<1, 4, EPI_RES_SKIP, 2>(a, s) : launch_gemm_t<1, 1, EPI_RES_SKIP, 2>(a, s);
-        return hipErrorInvalidValue;
-    }
-    if (prec == 1) {   // split-bf16 input: only the two hot kernels exist in this precision
-        if (epi == EPI_GATE) return NI == 1 ? launch_gemm_t<1, 1, EPI_GATE, 1>(a, s) : launch_gemm_t<2, 1, EPI_GATE, 1>(a, s);
-        if (epi == EPI_RES_SKIP && a.taps == 1)
-            return a.kchunks % 4 == 0 ? launch_gemm_t<1, 4, EPI_RES_SKIP, 1>(a, s) : launch_gemm_t<1, 1, EPI_RES_SKIP, 1>(a, s);
-        return hipErrorInvalidValue;
-    }
+    if (prec == DR_PRECISION_F16) return launch_gemm_lowp<DR_PRECISION_F16>(a, epi, NI, s);
+    if (prec == DR_PRECISION_BF16) return launch_gemm_lowp<DR_PRECISION_BF16>(a, epi, NI, s);
+    if (prec == DR_PRECISION_BF16X3) return launch_gemm_lowp<DR_PRECISION_BF16X3>(a, epi, NI, s);
+    if (prec != DR_PRECISION_F32) return hipErrorInvalidValue;
     const int KS = pick_one_ks(a.taps, a.kchunks, NI, epi, tuning().one_ks);      // channels per hand-over (launch_plan.h)
     if (NI == 1) {
         if (KS == 4) return launch_gemm_ni<1, 4>(a, epi, s);

@@ -1,5 +1,5 @@
 // The three GEMM bodies every contraction of the path is made of (device code, templates): gemm_body (LDS-staged X,
-// 32x32x2 fp32 / 32x32x16 split-bf16 or one-pass bf16 MFMA), pw_body (1x1, both operands straight from L2) and gemm16_body (16x16x4 MFMA,
+// 32x32x2 fp32 / 32x32x16 split-bf16 or one-pass bf16 / f16 MFMA), pw_body (1x1, both operands straight from L2) and gemm16_body (16x16x4 MFMA,
 // 96 / 160-frame blocks).  Included by gemm.hip (one launch per phase), stack.hip and tail.hip (persistent kernels): the
 // same device code everywhere, which is what makes the fused kernels bit-identical to the per-phase launches.
 // What the bodies have in common is written once, in front of them: the epilogue arithmetic on register quads
@@ -59,13 +59,14 @@ DR_DEVINL void hd_quad(const float (&h)[4], const float4 d, float (&o)[4]) {
 }
 // ... and its store for rows p0..p0+3, frame t of sample b: split-bf16 (a.out_s3 & 2) or fp32 P4.  COH3 / COH4: that
 // flavour's store is write-through when a.wt_store says so (tensors handed to other workgroups of a fused launch), else plain.
-// BF: the one-pass bf16 tensor (precision "bf16": the bodies with PREC = 2 write nothing else)
+// BF: the precision code of a one-plane 16-bit tensor (precisions "bf16" / "f16": the bodies with PREC = 2 / 4 write nothing
+// else), 0 otherwise
 template <int COH3, int COH4, int BF = 0>
 DR_DEVINL void store_y2(const GemmArgs& a, const int b, const float (&o)[4], const float4 d, const int p0, const int t) {
     float o2[4];
     hd_quad(o, d, o2);
     if constexpr (BF) {
-        store_bf16_quad<COH3>(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.wt_store);
+        store_quad_of<BF, COH3>(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.wt_store);
     } else if (a.out_s3 & 2) {
         store_s3_quad<COH3>(a.Y2 + (long)b * a.y2_bs, o2, p0, t, a.T, a.y_rows >> 3, a.wt_store);
     } else {
@@ -118,13 +119,14 @@ DR_DEVINL void dma_tile(float4* Rs, PlaneOf plane_of, const int T, const int t0,
 //   staging.  Producers therefore issue a handful of instructions per chunk and no longer steal
 //   issue slots from the consumers' MFMA stream (measured: 70.7 -> 66 ticks per MFMA when idle).
 //   PREC = 1: the X tile rows are the split-bf16 planes [(sub*2 + g)*6 + piece*2 + kq] (see gemm_body).
-//   PREC = 2: the one-pass bf16 planes [(sub*2 + g)*2 + kq] = four consecutive plane8 units per 32 channels.
+//   PREC = 2 / 4 (one_plane16): the one-pass bf16 / f16 planes [(sub*2 + g)*2 + kq] = four consecutive plane8 units per 32
+//   channels.
 //   AUX = 16: sc1 loads (COH bodies: X was written by other workgroups of the same launch).
 // ---------------------------------------------------------------------------------------------
 template <int KS, int PREC, int AUX, int RBN>
 DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw, const int lane, const int mt, const int b, const int t0,
                         const int halo, const int FW, const int c0, const int c1, const int code_x, const int code_r) {
-    constexpr int XP = (PREC == 2 ? 4 : PREC ? 12 : 8) * KS;            // 16-byte rows per X tile
+    constexpr int XP = x_tile_rows(PREC) * KS;            // 16-byte rows per X tile
     const int bx = a.x_bmod ? (b % a.x_bmod) : b;
     const float* Xg = a.X + (long)bx * a.x_bs;
     const int last_plane = a.x_planes - 1;
@@ -137,7 +139,7 @@ DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw,
             const int f = seg * 64 + lane;
             // planes beyond Cin (K padding) re-read the last valid plane: finite data x zero weights
             const float* src;
-            if constexpr (PREC == 2) {
+            if constexpr (one_plane16(PREC)) {
                 const int pc = min(chunk * (4 * KS) + pl, last_plane);                // plane8: rows are [(sub*2 + g)*2 + kq]
                 src = Xg + (long)pc * a.x_ps;
             } else if constexpr (PREC) {
@@ -211,6 +213,8 @@ DR_DEVINL void producer(const GemmArgs& a, float4* Xs, float4* Rs, const int pw,
 //   PREC = 2 ("bf16"): the X input and the weights are piece 0 of that split alone - each value rounded once to bf16 - in one
 //   plane set: X tile rows [(sub*2 + g)*2 + kq], ONE v_mfma_f32_32x32x16_bf16 per (group, row tile, frame tile) and K step;
 //   the EPI_GATE output and the second output Y2 are written in the same form (store_bf16_quad).
+//   PREC = 4 ("f16"): PREC = 2 with IEEE binary16 in place of bf16 - the same planes, tiles, slabs and K loop; only the
+//   conversion (store_f16_quad) and the MFMA (v_mfma_f32_32x32x16_f16) differ (device_common.h: store_quad_of, mma_of).
 //   COH = 1 (the fused residual-stack kernel only): the tensors this body exchanges with OTHER workgroups of the
 //   same launch - its X input (hd) and its EPI_GATE output (g) - are read with sc1 loads and written with sc1
 //   (write-through) stores, the placement-independent hand-off form of MI355X_MICROARCH.md "inter-workgroup
@@ -240,7 +244,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     constexpr int BN = 32 * NW;
     static_assert(NI == 1 || NI == 2 || ((NI == 3 || NI == 5) && EPI == EPI_GATE && PREC == 0 && KS == 1 && FOLDP == 1),
                   "block widths: 64, 128; 96, 160 (conv)");
-    constexpr int XP = (PREC == 2 ? 4 : PREC ? 12 : 8) * KS;      // 16-byte rows per X tile
+    constexpr int XP = x_tile_rows(PREC) * KS;      // 16-byte rows per X tile
     // Consumer wave arrangement: 4 (M) x 1 (N) - every wave owns 32 distinct rows x all 64*NI frames of the
     // block, so no two waves issue the same A-fragment loads (a CU's vector-memory path is the stressed
     // resource: with 2 x 2 the two N-waves fetched identical fragments); the X tile is shared through LDS.
@@ -318,7 +322,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // a branch + s_waitcnt vmcnt(0) per quad), the EPI_RES_SKIP read-modify-write tile waits in LDS (Rs).
     float4 eop[NW][4];
 
-    if constexpr (PREC == 2) {
+    if constexpr (one_plane16(PREC)) {
         // One-pass bf16: both operands rounded once to bf16 (piece 0 of the split), ONE v_mfma_f32_32x32x16_bf16 per
         // (group, row tile, frame tile) and K step.  A slab = 8 KiB, [g16 2][kq 2][row 128][8 bf16]; X tile rows
         // [(sub*2 + g)*2 + kq].  A K step is only 2*NW MFMAs of 32 cycles, shorter than an L2 round trip: the A fragments
@@ -357,7 +361,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         auto mma1 = [&](auto FIRST, const uint4 af, const BF1& bf) {
             constexpr bool kFirst = FOLD && decltype(FIRST)::value;      // the chunk's first products: C = 0 (a new chain)
 #pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_bf16(af, bf.v[ni], kFirst ? zero16 : acc[ni]);
+            for (int ni = 0; ni < NW; ++ni) acc[ni] = mma_of<PREC>(af, bf.v[ni], kFirst ? zero16 : acc[ni]);
         };
         auto step = [&](auto ROLE, auto FIRST, int slab, int chunk, int q) {
             constexpr bool kB = decltype(ROLE)::value;
@@ -775,8 +779,8 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] = v0[e] * v0[e] + v1[e] * v1[e];
                     }
-                    if constexpr (PREC == 2) {   // g for the one-pass bf16 1x1 kernel
-                        store_bf16_quad<COH>(a.Y + (long)be * a.y_bs, o, c0, t, a.T, a.wt_store);
+                    if constexpr (one_plane16(PREC)) {   // g for the one-pass bf16 / f16 1x1 kernel
+                        store_quad_of<PREC, COH>(a.Y + (long)be * a.y_bs, o, c0, t, a.T, a.wt_store);
                     } else if (a.out_s3 & 1) {   // g for the split-bf16 1x1 kernel
                         store_s3_quad<COH>(a.Y + (long)be * a.y_bs, o, c0, t, a.T, a.y_rows >> 3, a.wt_store);
                     } else {
@@ -795,7 +799,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                             float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
                             residual_quad(v, ebias[q], eop[ni][q], o);
                             *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-                            if (a.Y2) store_y2<COH, 0, PREC == 2>(a, be, o, ed2[q], p0, t);
+                            if (a.Y2) store_y2<COH, 0, one_plane16(PREC) ? PREC : 0>(a, be, o, ed2[q], p0, t);
                         } else {
                             float* dst = a.skip + (long)be * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
                             skip_quad(v, ebias[q], eop[ni][q], a.skip_init, o);

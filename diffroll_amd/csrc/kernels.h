@@ -130,7 +130,8 @@ hipError_t init_kernels();
 hipError_t read_bounds(unsigned long long* out4);
 hipError_t reset_bounds();
 // prec = 0: fp32 X / weights; 1: split-bf16 ("S3") X / weights (EPI_GATE and 1x1 EPI_RES_SKIP only); 2: one-pass bf16 X /
-// weights (the same two GEMMs; X, the EPI_GATE output and Y2 are [batch][channel/8][frame][8 bf16], out_s3 is not read)
+// weights (the same two GEMMs; X, the EPI_GATE output and Y2 are [batch][channel/8][frame][8 bf16], out_s3 is not read);
+// 4: one-pass f16 - as 2 with IEEE binary16 in place of bf16.  The codes are the DR_PRECISION_* values; 3 is refused.
 hipError_t launch_gemm(const GemmArgs& a, int epi, int NI, hipStream_t s, int prec = 0);
 // flexible-width variant (16x16x4 MFMA): block = 128 rows x 32*NJ frames, NJ in {3,5}; fp32, EPI_GATE / 1x1 EPI_RES_SKIP
 hipError_t launch_gemm16(const GemmArgs& a, int epi, int NJ, hipStream_t s);
@@ -140,6 +141,8 @@ hipError_t launch_pointwise(const GemmArgs& a, int NW, hipStream_t s);
 // precision "bf16": src = P4 fp32 [NB][Cp/4][T][4] -> dst = [NB][Cp/8][T][8 bf16], each value rounded to nearest even
 // (the first dilated conv's input, which the fp32 input projection leaves in P4)
 hipError_t launch_round_bf16(const float* src, float* dst, int NB, int Cp, int T, hipStream_t s);
+// precision "f16": the same with 8 IEEE binary16 per unit (round to nearest even, subnormals kept)
+hipError_t launch_round_f16(const float* src, float* dst, int NB, int Cp, int T, hipStream_t s);
 hipError_t launch_pointwise_ksplit(const GemmArgs& a, int NW, hipStream_t s);   // under-filled launches: 32-row tiles, K split over the block's waves
 
 // ---------------------------------------------------------------------------------------------
@@ -185,7 +188,7 @@ struct StackArgs {
 // FL = block flavour: 1 / 2 = 128 packed rows x 64 / 128 frames.  The caller guarantees
 // NB * stack_group_blocks(FL, Cp, T) <= #CUs and stack_lds_bytes(..) <= 160 KiB.
 // prec = 1: the split-bf16 flavour (s.hd / s.g = the S3 tensors; Cp % 128 == 0; LDS: stack3_lds_bytes)
-// prec = 2: the one-pass bf16 flavour (s.hd / s.g = the one-plane-set bf16 tensors; same restriction and LDS function)
+// prec = 2 / 4: the one-pass bf16 / f16 flavour (s.hd / s.g = the one-plane-set 16-bit tensors; same restriction and LDS function)
 hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st, int prec = 0);
 
 // Per-call scalars of the update that must not be baked into a captured graph: the chain graph reads them from

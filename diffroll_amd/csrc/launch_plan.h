@@ -35,6 +35,16 @@ struct PlanKnobs {
     int xcd_n = -1, xcd_model = 1, tail_t4 = 0, one_ks = 0;
 };
 
+// The precision codes are the DR_PRECISION_* values (3 is reserved and never reaches the planners or the kernels).
+// THE one-plane 16-bit modes: each operand of the two hot contractions rounded once to a 16-bit format - bf16 (2) or IEEE
+// binary16 (4) - and carried as ONE plane set [batch][channel/8][frame][8 x 16 bit].  The two share every layout, LDS
+// size and planner decision; they differ in the conversion and in the MFMA (device_common.h: Half16<PREC>).
+constexpr bool one_plane16(int prec) { return prec == DR_PRECISION_BF16 || prec == DR_PRECISION_F16; }
+// 16-byte rows of an X tile per 32 input channels: fp32 P4 planes, the three split-bf16 pieces, or one 16-bit plane set
+constexpr int x_tile_rows(int prec) { return one_plane16(prec) ? 4 : prec ? 12 : 8; }
+// bytes of one packed weight slab (128 rows x 32 channels of one tap)
+constexpr size_t weight_slab_bytes(int prec) { return one_plane16(prec) ? 8192 : prec ? 24576 : 16384; }
+
 // frames per block of gemm_kernel<NI, ...>: 64 / 128 (NI = 1 / 2), 96 / 160 (NI = 3 / 5: that many 32-frame MFMA tiles per
 // consumer wave, the gated conv only)
 inline int gemm_block_frames(int NI) { return (NI == 3 || NI == 5) ? 32 * NI : 64 * NI; }
@@ -42,7 +52,7 @@ inline size_t gemm_lds_bytes(int NI, int KS, int taps, int dil, int prec, int ep
     const int halo = ((taps - 1) / 2) * dil;
     const int BN = gemm_block_frames(NI);
     const int FW = BN + 2 * halo;
-    return (size_t)2 * (prec == 2 ? 4 : prec ? 12 : 8) * KS * FW * 16 + (epi == EPI_RES_SKIP ? (size_t)32 * BN * 16 : 0);
+    return (size_t)2 * x_tile_rows(prec) * KS * FW * 16 + (epi == EPI_RES_SKIP ? (size_t)32 * BN * 16 : 0);
 }
 
 // Block -> XCD mapping of a per-phase GEMM launch (gemm.hip: block_tile) of MT row tiles x NT frame tiles of BN frames:
@@ -124,7 +134,7 @@ inline KSplitPlan plan_ksplit(const PlanKnobs& k, long tiles, int nchunks, int k
 // 64 / 128 / 160 frames.
 inline int stack_tile_frames(int FL) { return FL == 5 ? 160 : 64 * FL; }
 // split-bf16 flavour: max over its two phase bodies (conv: S3 X tiles; 1x1: 128-channel S3 X tiles + the 64-frame h / skip tile)
-// (prec = 2: the one-pass bf16 flavour - the same two bodies on X tiles of a third the rows)
+// (the one-plane 16-bit flavours, prec = 2 / 4: the same two bodies on X tiles of a third the rows)
 inline size_t stack3_lds_bytes(int FL, int taps, int max_dil, int prec = 1) {
     return std::max(gemm_lds_bytes(FL, 1, taps, max_dil, prec, EPI_GATE), gemm_lds_bytes(1, 4, 1, 1, prec, EPI_RES_SKIP)) + 16;
 }
@@ -238,7 +248,7 @@ inline Tile pick_pointwise_tile(const PlanKnobs& k, int MT, int NB, int T, int p
 struct NetShape {
     int NB, n_cond, bmod, T;
     int Cp, L, K, max_dil;      // padded channels, residual layers, kernel size, largest dilation
-    int prec;                   // 0 exact fp32, 1 split-bf16, 2 one-pass bf16
+    int prec;                   // 0 exact fp32, 1 split-bf16, 2 one-pass bf16, 4 one-pass f16 (DR_PRECISION_*)
     int n_cus;                  // CUs of the device (0: unknown - never fused)
     int fuse;                   // FusedMode::active(): 0 one launch per phase, 1 fused where the cost model likes it, 2 fused regardless
     int opt_blocked, opt_tail;  // options "blocked_accumulation" and "fused_tail"
@@ -264,7 +274,7 @@ inline NetPlan plan_network(const NetShape& s, const PlanKnobs& k) {
     int stack_from = -1;                   // first phase run by the fused kernel (-1: none)
     int stack_ni = 0, stack_chunks = 1;    // flavour, and how many sample chunks the evaluation is launched in
     bool fused_step = false;
-    // (the split-bf16 and one-pass bf16 precisions have their own flavours of the kernel: 128-channel chunks in the 1x1 phases
+    // (the split-bf16 and one-pass bf16 / f16 precisions have their own flavours of the kernel: 128-channel chunks in the 1x1 phases
     // need Cp % 128 == 0)
     const int stack3 = k.stack3;
     const int fuse = s.fuse;

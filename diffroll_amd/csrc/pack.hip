@@ -1,6 +1,7 @@
 // Host side, part 1: weight packing into the kernels' fragment order, staged uploads, hoisted tables - dr_set_param,
 // dr_set_tables, dr_set_frontend_tables, dr_commit (and the split-bf16 packings built on first use).
 #include "engine_state.h"
+#include "f16_round.h"
 
 #include <mutex>
 
@@ -85,9 +86,10 @@ std::vector<uint16_t> pack_weights_s3(int MT, int kchunks, int taps, F get) {
     return out;
 }
 
-// one-pass bf16 packing (precision "bf16"): piece 0 of the split alone, [mtile][kchunk32][tap][g16 = 2][kq = 2][row = 128][8 bf16]
-template <class F>
-std::vector<uint16_t> pack_weights_bf16(int MT, int kchunks, int taps, F get) {
+// one-plane 16-bit packing, [mtile][kchunk32][tap][g16 = 2][kq = 2][row = 128][8 x 16 bit], each weight rounded once by `rnd`:
+// bf16_rne (precision "bf16": piece 0 of the split alone) or f16_rne (precision "f16": IEEE binary16, f16_round.h)
+template <class F, class R>
+std::vector<uint16_t> pack_weights_16(int MT, int kchunks, int taps, F get, R rnd) {
     std::vector<uint16_t> out((size_t)MT * kchunks * taps * 4096);
     size_t o = 0;
     for (int mt = 0; mt < MT; ++mt)
@@ -97,7 +99,7 @@ std::vector<uint16_t> pack_weights_bf16(int MT, int kchunks, int taps, F get) {
                     for (int kq = 0; kq < 2; ++kq)
                         for (int row = 0; row < 128; ++row)
                             for (int i = 0; i < 8; ++i)
-                                out[o++] = bf16_rne(get(mt * 128 + row, kc * 32 + g * 16 + kq * 8 + i, j));
+                                out[o++] = rnd(get(mt * 128 + row, kc * 32 + g * 16 + kq * 8 + i, j));
     return out;
 }
 
@@ -267,10 +269,12 @@ int ensure_s3(dr_engine* e) {
     return DR_OK;
 }
 
-// The one-pass bf16 packings of the same two GEMMs (precision "bf16"): a third of the split ones, built on first use in
-// the same way and independently of them - selecting one mode never builds or uploads the other's.
-int ensure_bf16(dr_engine* e) {
-    if (e->bf16_ready || !e->committed) return DR_OK;
+// The one-plane 16-bit packings of the same two GEMMs (precisions "bf16" and "f16"): a third of the split ones, built on
+// first use in the same way.  The three reduced-precision packings are independent: selecting one mode never builds or
+// uploads another's.
+template <class R>
+static int ensure_one_plane(dr_engine* e, bool& ready, float* LayerW::*conv_field, float* LayerW::*out_field, R rnd) {
+    if (ready || !e->committed) return DR_OK;
     const int C = e->C, Cp = e->Cp, L = e->L, K = e->K;
     std::vector<std::vector<uint16_t>> cb(L), ob(L);
     int prc = parallel_for(e, L, [&](int l) {
@@ -278,29 +282,34 @@ int ensure_bf16(dr_engine* e) {
         const auto& Wd = *find_param(e, pre + "dilated_conv.weight");
         const auto& Wo = *find_param(e, pre + "output_projection.weight");
         const int MTc = Cp / 64;
-        cb[l] = pack_weights_bf16(MTc, Cp / 32, K, [&](int pr, int ch, int j) {
+        cb[l] = pack_weights_16(MTc, Cp / 32, K, [&](int pr, int ch, int j) {
             int mi, c; paired_row(pr, mi, c);
             return (c < C && ch < C) ? Wd[((size_t)(mi * C + c) * C + ch) * K + j] : 0.f;
-        });
-        ob[l] = pack_weights_bf16(MTc, Cp / 32, 1, [&](int pr, int ch, int) {
+        }, rnd);
+        ob[l] = pack_weights_16(MTc, Cp / 32, 1, [&](int pr, int ch, int) {
             const int half = pr >= Cp, c = pr - half * Cp;
             return (c < C && ch < C) ? Wo[(size_t)(half * C + c) * C + ch] : 0.f;
-        });
+        }, rnd);
     });
     if (prc) return prc;
     for (int l = 0; l < L; ++l) {
         int rc;
-        if ((rc = upload_bytes(e, cb[l].data(), cb[l].size() * 2, &e->layers[l].conv_wb)) ||
-            (rc = upload_bytes(e, ob[l].data(), ob[l].size() * 2, &e->layers[l].out_wb)))
+        if ((rc = upload_bytes(e, cb[l].data(), cb[l].size() * 2, &(e->layers[l].*conv_field))) ||
+            (rc = upload_bytes(e, ob[l].data(), ob[l].size() * 2, &(e->layers[l].*out_field))))
             return rc;
         cb[l] = {}; ob[l] = {};
     }
     { StagerLock sl; HIPCHK(e, sl.s->drain()); }
-    e->bf16_ready = true;
+    ready = true;
     return DR_OK;
 }
+int ensure_bf16(dr_engine* e) { return ensure_one_plane(e, e->bf16_ready, &LayerW::conv_wb, &LayerW::out_wb, bf16_rne); }
+int ensure_f16(dr_engine* e) { return ensure_one_plane(e, e->f16_ready, &LayerW::conv_wh, &LayerW::out_wh, dr::f16_rne); }
 int ensure_packings(dr_engine* e, int prec) {
-    return prec == 2 ? ensure_bf16(e) : prec == 1 ? ensure_s3(e) : DR_OK;
+    return prec == DR_PRECISION_F16 ? ensure_f16(e) : prec == DR_PRECISION_BF16 ? ensure_bf16(e) : prec == DR_PRECISION_BF16X3 ? ensure_s3(e) : DR_OK;
+}
+bool packings_ready(const dr_engine* e, int prec) {
+    return prec == DR_PRECISION_F16 ? e->f16_ready : prec == DR_PRECISION_BF16 ? e->bf16_ready : prec == DR_PRECISION_BF16X3 ? e->s3_ready : true;
 }
 
 int commit(dr_engine* e, hipStream_t st) {
@@ -406,6 +415,7 @@ int commit(dr_engine* e, hipStream_t st) {
     e->t_upload_s = now_s() - tu0;
     e->s3_ready = false;      // the split-bf16 packings (opt-in precision) are built when that mode is first used
     e->bf16_ready = false;    // ... and so are the one-pass bf16 ones
+    e->f16_ready = false;     // ... and the one-pass f16 ones
     {   // skip projection (C,C,1) and output projection (88,C,1): natural rows
         const auto& Ws = P("skip_projection.weight");
         const auto& Bs = P("skip_projection.bias");
@@ -546,7 +556,7 @@ int commit(dr_engine* e, hipStream_t st) {
     e->fe_B = e->fe_T = 0;
     e->t_tables_s = now_s() - tu0 - e->t_upload_s;
     // (tune.s3_eager = 1: build the split-bf16 packings at every commit, as rounds 1-3 did - the "before" of the cold-start report)
-    if (e->prec == 2) return ensure_bf16(e);
+    if (one_plane16(e->prec)) return ensure_packings(e, e->prec);
     if (e->prec || tuning().s3_eager) return ensure_s3(e);
     return DR_OK;
 }

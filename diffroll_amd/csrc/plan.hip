@@ -94,12 +94,12 @@ struct Eval {
 };
 
 // per-sample size (4-byte units) of the reduced-precision form of an activation tensor with Cp channels: the three bf16
-// pieces of S3 (prec = 1) or the one bf16 plane set (prec = 2)
+// pieces of S3 (prec = 1) or the one 16-bit plane set (prec = 2 / 4: one_plane16)
 static long lowp_bs(int prec, int Cp, int T) {
     const long act_bs = (long)Cp * T;
-    return prec == 2 ? act_bs / 2 : act_bs + act_bs / 2;
+    return one_plane16(prec) ? act_bs / 2 : act_bs + act_bs / 2;
 }
-// S3 / one-pass bf16 input description of an activation tensor with Cp channels
+// S3 / one-plane 16-bit input description of an activation tensor with Cp channels
 static void s3_in(GemmArgs& a, const float* X, int Cp, int T, int prec) {
     a.X = X; a.x_bs = lowp_bs(prec, Cp, T); a.x_piece = (long)(Cp / 8) * T * 4; a.x_ps = (long)T * 4; a.x_fs = 4;
     a.x_planes = Cp / 8; a.kchunks = Cp / 32;
@@ -136,8 +136,9 @@ static int launch_inproj(const Eval& v, const PlanKnobs& k) {
     else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     allow_splitk(e, a);
     HIPCHK(e, launch_gemm(a, EPI_RELU, pick_ni(k, a.MT, v.NB, T, 1, 1), v.st));
-    // (one-pass bf16: this fp32 kernel leaves hd in P4; the first conv's operand is its rounding)
-    if (e->prec == 2) HIPCHK(e, launch_round_bf16(e->hd, e->hd3, v.NB, Cp, T, v.st));
+    // (one-pass bf16 / f16: this fp32 kernel leaves hd in P4; the first conv's operand is its rounding)
+    if (e->prec == DR_PRECISION_BF16) HIPCHK(e, launch_round_bf16(e->hd, e->hd3, v.NB, Cp, T, v.st));
+    if (e->prec == DR_PRECISION_F16) HIPCHK(e, launch_round_f16(e->hd, e->hd3, v.NB, Cp, T, v.st));
     e->inproj_launches += 1;
     return DR_OK;
 }
@@ -152,7 +153,7 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
         const int nb = v.NB / p.stack_chunks + (ck < v.NB % p.stack_chunks ? 1 : 0);      // balanced chunk sizes
         StackArgs sa{};
         sa.h = e->h + b0 * act_n; sa.hd = e->hd + b0 * act_n; sa.g = e->g + b0 * act_n; sa.skip = e->skip + b0 * act_n;
-        if (prec) { sa.hd = e->hd3 + b0 * lowp_bs(prec, Cp, T); sa.g = e->g3 + b0 * lowp_bs(prec, Cp, T); }      // the S3 / bf16 tensors
+        if (prec) { sa.hd = e->hd3 + b0 * lowp_bs(prec, Cp, T); sa.g = e->g3 + b0 * lowp_bs(prec, Cp, T); }      // the S3 / one-plane tensors
         sa.d2 = e->d_dtab + (v.tsel ? 0 : (size_t)v.t * L * Cp);
         sa.tsel = v.tsel ? v.tsel + b0 : nullptr; sa.d2_ts = (long)L * Cp;
         sa.zero = zero_vec();
@@ -194,7 +195,8 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
                            std::to_string(e->K) + " + conditioner + gate and 1x1 + residual/skip, phases " +
                            std::to_string(p0) + ".." + std::to_string(p1 - 1) + " of " + std::to_string(2 * L) +
                            (p.stack_chunks > 1 ? ", " + std::to_string(p.stack_chunks) + " sample chunks" : "") +
-                           (prec == 2 ? (p.fold ? ", bf16, blocked accumulation" : ", bf16, one chain per output")
+                           (prec == DR_PRECISION_F16 ? (p.fold ? ", f16, blocked accumulation" : ", f16, one chain per output")
+                            : prec == DR_PRECISION_BF16 ? (p.fold ? ", bf16, blocked accumulation" : ", bf16, one chain per output")
                             : prec ? (p.fold ? ", split-bf16, blocked accumulation" : ", split-bf16, one chain per output")
                                  : (p.fold ? ", blocked accumulation" : ", one fp32 chain per output")) + ")";
         });

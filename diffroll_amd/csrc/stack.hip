@@ -24,6 +24,7 @@ DR_BOUNDS_TU(stack)
 // of that precision: bit-identical to them.  Needs Cp % 128 == 0.
 // PREC = 2: the one-pass bf16 precision - the same phase structure on the one-plane-set bf16 tensors ([sample][channel/8][frame]
 // [8 bf16]: a third of an S3 tensor) and gemm_body<.., PREC = 2>.
+// PREC = 4: the one-pass f16 precision - PREC = 2 with IEEE binary16 in place of bf16 (gemm_body<.., PREC = 4>).
 template <int FL, int FOLDP = 1, int PREC = 0>
 __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
         a.x_bs = act_bs; a.x_ps = (long)s.T * 4; a.x_fs = 4; a.x_planes = P; a.kchunks = s.Cp >> 5;
         a.y_bs = act_bs; a.y_ps = (long)s.T * 4; a.y_fs = 4; a.y_rows = s.Cp;
         if constexpr (PREC) {
-            const long s3_bs = PREC == 2 ? act_bs / 2 : act_bs + act_bs / 2;      // per-sample size of an S3 / bf16 tensor (4-byte units)
+            const long s3_bs = one_plane16(PREC) ? act_bs / 2 : act_bs + act_bs / 2;      // per-sample size of an S3 / one-plane tensor (4-byte units)
             if ((p & 1) == 0) {
                 a.Wp = ly.conv_w; a.bias = ly.conv_b; a.bias2 = ly.conv_b2;
                 a.X = s.hd; a.x_bs = s3_bs; a.x_piece = (long)(s.Cp >> 3) * s.T * 4; a.x_planes = s.Cp >> 3;
@@ -277,6 +278,15 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
     }
 }
 
+// the three flavours of a reduced precision (split-bf16, one-pass bf16, one-pass f16)
+template <int PREC>
+static hipError_t launch_stack_lowp(const StackArgs& b, int FL, dim3 grid, size_t lds, hipStream_t st) {
+    if (FL == 1) hipLaunchKernelGGL((stack_kernel<1, 1, PREC>), grid, dim3(512), lds, st, b);
+    else if (b.fold128) hipLaunchKernelGGL((stack_kernel<2, 1, PREC>), grid, dim3(512), lds, st, b);
+    else hipLaunchKernelGGL((stack_kernel<2, 0, PREC>), grid, dim3(512), lds, st, b);
+    return hipGetLastError();
+}
+
 hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st, int prec) {
     if (FL != 1 && FL != 2 && FL != 5) return hipErrorInvalidValue;
     if (prec && ((s.Cp & 127) || FL == 5)) return hipErrorInvalidValue;
@@ -304,19 +314,10 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
 #endif
     (void)MT;
     const dim3 grid((unsigned)(gsize * NBp));
-    if (prec < 0 || prec > 2) return hipErrorInvalidValue;
-    if (prec == 2) {
-        if (FL == 1) hipLaunchKernelGGL((stack_kernel<1, 1, 2>), grid, dim3(512), lds, st, b);
-        else if (s.fold128) hipLaunchKernelGGL((stack_kernel<2, 1, 2>), grid, dim3(512), lds, st, b);
-        else hipLaunchKernelGGL((stack_kernel<2, 0, 2>), grid, dim3(512), lds, st, b);
-        return hipGetLastError();
-    }
-    if (prec) {
-        if (FL == 1) hipLaunchKernelGGL((stack_kernel<1, 1, 1>), grid, dim3(512), lds, st, b);
-        else if (s.fold128) hipLaunchKernelGGL((stack_kernel<2, 1, 1>), grid, dim3(512), lds, st, b);
-        else hipLaunchKernelGGL((stack_kernel<2, 0, 1>), grid, dim3(512), lds, st, b);
-        return hipGetLastError();
-    }
+    if (prec == DR_PRECISION_F16) return launch_stack_lowp<DR_PRECISION_F16>(b, FL, grid, lds, st);
+    if (prec == DR_PRECISION_BF16) return launch_stack_lowp<DR_PRECISION_BF16>(b, FL, grid, lds, st);
+    if (prec == DR_PRECISION_BF16X3) return launch_stack_lowp<DR_PRECISION_BF16X3>(b, FL, grid, lds, st);
+    if (prec != DR_PRECISION_F32) return hipErrorInvalidValue;
     if (FL == 1) hipLaunchKernelGGL((stack_kernel<1>), grid, dim3(512), lds, st, b);
     else if (FL == 5) hipLaunchKernelGGL((stack_kernel<5>), grid, dim3(512), lds, st, b);
     else if (FL == 2 && s.fold128) hipLaunchKernelGGL((stack_kernel<2, 1>), grid, dim3(512), lds, st, b);
@@ -327,7 +328,8 @@ hipError_t launch_stack(const StackArgs& s, int FL, int max_dil, hipStream_t st,
 hipError_t init_stack_kernels() {
     return allow_max_lds(&stack_kernel<1>, &stack_kernel<2, 0>, &stack_kernel<5>, &stack_kernel<2, 1>,
                          &stack_kernel<1, 1, 1>, &stack_kernel<2, 0, 1>, &stack_kernel<2, 1, 1>,
-                         &stack_kernel<1, 1, 2>, &stack_kernel<2, 0, 2>, &stack_kernel<2, 1, 2>);
+                         &stack_kernel<1, 1, 2>, &stack_kernel<2, 0, 2>, &stack_kernel<2, 1, 2>,
+                         &stack_kernel<1, 1, 4>, &stack_kernel<2, 0, 4>, &stack_kernel<2, 1, 4>);
 }
 
 }  // namespace dr

@@ -335,10 +335,12 @@ class Engine:
 
     def set_precision(self, mode: str):
         """'f32' (default, exact fp32 MFMA), 'bf16x3' (opt-in split-bf16: three bf16 pieces per operand,
-        six piece products, fp32 accumulation - fp32-level error at 2.67x the matrix rate) or 'bf16' (opt-in one-pass
+        six piece products, fp32 accumulation - fp32-level error at 2.67x the matrix rate), 'bf16' (opt-in one-pass
         bf16: the operands of the two hot contractions rounded once to bf16, round to nearest even, one product, fp32
         accumulation - an ordinary reduced-precision mode: about 1e-3 rms per evaluation on unit-scale activations,
-        include/diffroll_amd.h).  Each opt-in mode builds its own weight packing the first time it is selected."""
+        include/diffroll_amd.h) or 'f16' (opt-in one-pass fp16: the same four operands rounded once to IEEE binary16,
+        round to nearest even, subnormals kept, no saturation - bf16's cost, about 1e-4 rms per evaluation).  Each opt-in
+        mode builds its own weight packing the first time it is selected."""
         self._check(self.lib.dr_set_precision(self.h, _cabi.PRECISIONS[mode]))
         self.precision = mode
 

@@ -203,7 +203,7 @@ class ClassifierFreeDiffRoll(nn.Module):
         if int(sa.get("n_mels", n_mels)) != int(n_mels):
             raise ValueError(f"spec_args.n_mels={sa.get('n_mels')} differs from n_mels={n_mels} (the conditioner's input width)")
         self._device = device
-        self.precision = precision          # 'f32' (exact, default) | 'bf16x3' (opt-in split precision) | 'bf16' (opt-in, one pass)
+        self.precision = precision          # 'f32' (exact, default) | 'bf16x3' (opt-in split precision) | 'bf16' | 'f16' (opt-in, one pass)
         # accumulation order of the dilated conv (an extension): 'auto' = 'blocked' = one fp32 chain per
         # 32-channel chunk, chunk sums added up separately - like a CPU library's K-blocked GEMM - in every flavour;
         # 'single_chain' = 128-frame blocks (16 guided clips per GPU) and the 96 / 160-frame flavours (640-frame rolls) contract

@@ -86,7 +86,7 @@ enum {
                                  product is formed from the six piece products with i + j <= 2 on the bf16
                                  MFMA with fp32 accumulation (drops terms <= 2^-24 |ab|); fp32-level error
                                  at 2.67x the matrix rate                                                  */
-    DR_PRECISION_BF16 = 2     /* opt-in: ordinary one-pass bf16.  Rounding happens at exactly the operands
+    DR_PRECISION_BF16 = 2,    /* opt-in: ordinary one-pass bf16.  Rounding happens at exactly the operands
                                  BF16X3 splits - the input x + diffusion_projection and the weights of each
                                  layer's dilated conv, the gated activation sigmoid * tanh and the weights of
                                  each layer's output projection - each rounded ONCE to bf16, round to nearest
@@ -97,6 +97,21 @@ enum {
                                  truncated and no bf16 value is stored where BF16X3 stores fp32.  One sixth
                                  of BF16X3's matrix work, one third of its operand bytes; about 1e-3 rms
                                  error per evaluation on unit-scale activations (README.md)                */
+    /* 3 is reserved (a split-f16 near-exact mode would take it); dr_set_precision refuses it              */
+    DR_PRECISION_F16 = 4      /* opt-in: ordinary one-pass fp16.  Rounding happens at exactly the four operands
+                                 BF16 rounds - the input x + diffusion_projection and the weights of each
+                                 layer's dilated conv, the gated activation sigmoid * tanh and the weights of
+                                 each layer's output projection - each rounded ONCE to IEEE binary16, round to
+                                 nearest even.  Subnormal binary16 values are kept in the conversion, in the
+                                 packing and as MFMA operands (gradual underflow; verified on the MI355X by
+                                 tests/test_gpu_f16.py); a magnitude of 65520 or more becomes an infinity - the
+                                 mode does not saturate; NaN stays NaN; nothing is truncated.  Products of two
+                                 binary16 values are exact in fp32 (one v_mfma_f32_32x32x16_f16 per K step) and
+                                 accumulation is fp32, blocked as in BF16.  Biases, the conditioner term, the
+                                 residual stream, the skip sum, the input / skip / head projections and every
+                                 update, statistic and selection kernel stay fp32 as under BF16.  BF16's
+                                 layouts, operand bytes and matrix work; 11 significant bits instead of 8:
+                                 about 1e-4 rms error per evaluation on unit-scale activations (README.md) */
 };
 
 /* which spectrogram a dr_forward evaluation sees (model/diffwave.py:656-660) */
@@ -318,8 +333,9 @@ int dr_extract_x0(dr_engine* e, const float* d_x_t, const float* d_epsilon, cons
 int dr_set_spec_norm(dr_engine* e, int mode);
 
 /* Select DR_PRECISION_* for subsequent dr_forward / dr_step / dr_sample calls (default F32).
- * Drops a captured chain.  BF16X3 and BF16 each build their own weight packing the first time they are
- * selected (neither builds the other's); the mode changes only once that packing exists. */
+ * Drops a captured chain.  BF16X3, BF16 and F16 each build their own weight packing the first time they are
+ * selected (none builds another's); the mode changes only once that packing exists.  Any other value -
+ * the reserved 3 included - is DR_EINVAL and leaves the engine as it was. */
 int dr_set_precision(dr_engine* e, int mode);
 
 /*

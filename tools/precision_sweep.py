@@ -1,4 +1,4 @@
-"""Precision sweep (Engine.set_precision: f32 / bf16x3 / bf16): what each arithmetic of the two hot contractions costs per
+"""Precision sweep (Engine.set_precision: f32 / bf16x3 / bf16 / f16): what each arithmetic of the two hot contractions costs per
 chain, what its weight packing costs to build and to hold, and what it changes on the trained proxy.
 
     python tools/precision_sweep.py [--configs 2,6] [--chains 2] [--warmup 1] [--steps 200] [--no-proxy]
@@ -7,7 +7,8 @@ Chain time, per configuration of bench.py (2: 16 guided clips of 125 frames; 6: 
 640 frames; k = 9, 15 layers, C = 512, cfdg_ddpm_x0 w = 0.5, Philox noise) and precision: ms per chain from device events
 around --chains captured chains after --warmup, TWO runs of every cell in one process, the precisions in turn inside a run
 - so a cell's two figures are minutes apart and their ratio is the cell's own run-to-run spread.  A precision is faster
-than another only where the ratio of their times lies outside both spreads.  Beside the times: the launch mode from
+than another only where the ratio of their times lies outside both spreads (f16 is read against bf16 of the same run: the
+same MFMA count and operand bytes, so "not told apart" is the expectation).  Beside the times: the launch mode from
 dr_launch_state (a cell whose engine fell back or yielded prints no time), the wall time of the set_precision call that
 first selected the mode (packing + upload: the first-use cost; 0 for f32, whose packing the commit builds) and the device
 bytes that call took (hipMemGetInfo before / after: the mode's weight packings).
@@ -31,7 +32,7 @@ if ROOT not in sys.path:
 import numpy as np
 import torch
 
-PRECISIONS = ("f32", "bf16x3", "bf16")
+PRECISIONS = ("f32", "bf16x3", "bf16", "f16")
 
 
 def chain_times(args, config):
@@ -85,6 +86,9 @@ def chain_times(args, config):
                    first_use_s=first_use[p], packing_device_bytes=int(packing[p]))
         if ok and clean["bf16x3"]:
             rec["ratio_to_bf16x3"] = min(ms[p]) / min(ms["bf16x3"])
+        if ok and clean["bf16"]:
+            rec["ratio_to_bf16"] = min(ms[p]) / min(ms["bf16"])
+            rec["ratio_to_bf16_per_run"] = [a / b for a, b in zip(ms[p], ms["bf16"])]
         rows.append(rec)
         print(json.dumps(rec), flush=True)
     del m
@@ -136,14 +140,18 @@ def main():
     tables = [chain_times(args, int(c)) for c in args.configs.split(",")]
     print(f"\nk = 9, 15 layers, C = 512, cfdg_ddpm_x0, {args.steps} steps, two runs of {args.chains} chains per cell")
     print("config | clips x frames | precision | launch mode | ms per chain (run 1, run 2) | runs max / min | best / bf16x3's best | "
-          "first use [s] | packing [MiB]")
+          "best / bf16's best (run 1, run 2) | first use [s] | packing [MiB]")
     for rows in tables:
         for r in rows:
             if r["ms_runs"] is None:
-                print(f"{r['config']} | {r['clips']} x {r['frames']} | {r['precision']:6s} | {r['launch_mode']} | - | - | - | "
+                print(f"{r['config']} | {r['clips']} x {r['frames']} | {r['precision']:6s} | {r['launch_mode']} | - | - | - | - | "
                       f"{r['first_use_s']:.2f} | {r['packing_device_bytes'] / 2 ** 20:.0f}")
                 continue
             ratio = f"{r['ratio_to_bf16x3']:.3f}" if "ratio_to_bf16x3" in r else "-"
+            if "ratio_to_bf16" in r:
+                ratio += f" | {r['ratio_to_bf16']:.4f} ({r['ratio_to_bf16_per_run'][0]:.4f}, {r['ratio_to_bf16_per_run'][1]:.4f})"
+            else:
+                ratio += " | -"
             print(f"{r['config']} | {r['clips']} x {r['frames']} | {r['precision']:6s} | {r['launch_mode']} | "
                   f"{r['ms_runs'][0]:.2f}, {r['ms_runs'][1]:.2f} | {r['runs_max_over_min']:.4f} | {ratio} | "
                   f"{r['first_use_s']:.2f} | {r['packing_device_bytes'] / 2 ** 20:.0f}")
