@@ -164,6 +164,8 @@ int check_ready(dr_engine* e, int sampler, int B, int T) {
 // options "cfg_project" / "cfg_norm": refused beside "x0_threshold" (whose selection would have to rank the projected
 // prediction) and beside "cfg_rescale" (an alternative; a combined form would need the spread of the projected prediction)
 // option "cfg_momentum": refused while "cfg_project" and "cfg_norm" are both 0 (beside either, the two refusals above cover it)
+// option "guidance_stride": refused beside "x0_threshold", "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum" (a step
+// that reuses has no unconditional prediction for their statistics) and by a sampler that does not guide
 int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     const ChainOptions& o = e->opt;
     if (2 * o.win_O > T)
@@ -211,6 +213,19 @@ int check_options(dr_engine* e, int sampler, int B, int& NB, int T) {
     if (o.cfg_momentum != 0 && o.cfg_project == 0 && o.cfg_norm == 0)
         return fail(e, DR_EINVAL, "cfg_momentum = %d acts on the update that cfg_project / cfg_norm shape, and cfg_project = %d and "
                                   "cfg_norm = %d are both off; set one of them, or cfg_momentum 0", o.cfg_momentum, o.cfg_project, o.cfg_norm);
+    if (o.guid_stride > 1) {
+        // (the statistics of each of them need the unconditional prediction, which a step that reuses does not have)
+        const struct { const char* name; int value; } partners[] = {{"x0_threshold", o.x0_thresh}, {"cfg_rescale", o.cfg_rescale},
+            {"cfg_project", o.cfg_project}, {"cfg_norm", o.cfg_norm}, {"cfg_momentum", o.cfg_momentum}};
+        for (const auto& p : partners)
+            if (p.value != 0)
+                return fail(e, DR_EINVAL, "guidance_stride = %d does not combine with %s = %d: its statistics need the unconditional "
+                                          "prediction, which a step that reuses the guidance update does not evaluate; set one of "
+                                          "them 0", o.guid_stride, p.name, p.value);
+        if (NB != 2 * B)
+            return fail(e, DR_EINVAL, "sampler %d does not guide: guidance_stride = %d reuses the guidance update of a sampler that "
+                                      "guides (samplers 1, 3, 5); set guidance_stride 0 for this sampler", sampler, o.guid_stride);
+    }
     if (NB == 2 * B && o.guid.empty(e->S))
         return fail(e, DR_EINVAL, "guidance interval is empty: guidance_t_min = %d exceeds guidance_t_max = %d", o.guid.lo,
                     o.guid.hi_eff(e->S));
@@ -407,6 +422,8 @@ const ValueOption VALUE_OPTIONS[] = {
      "cfg_norm is 0 (off) or the rms bound r in units of 1 / 10000, 1 .. 100000 (500 = 0.05), got %d"},
     {"cfg_momentum", &ChainOptions::cfg_momentum, -9999, 9999, false, true,
      "cfg_momentum is 0 (off) or beta in units of 1 / 10000, -9999 .. 9999 (-5000 = -0.5), got %d"},
+    {"guidance_stride", &ChainOptions::guid_stride, 0, 64, false, true,
+     "guidance_stride is 0 or 1 (off) or the stride n, 2 .. 64 (2 = every second guided step runs both evaluations), got %d"},
 };
 
 // dr_set_option (lab = false: the product's options) / dr_debug_set_option (lab = true: the A/B and test knobs too)
@@ -550,6 +567,12 @@ int open_chain_call(dr_engine* e, int sampler, int B, int T, const int* step, in
         if (!e->momentum.fits(need)) e->mom_key.valid = false;
         if ((rc = grow_chain_buffer(e, e->momentum, need, st))) return rc;
     }
+    // option "guidance_stride": the state, one float per roll element (a buffer that grew holds nothing)
+    if (stage.stride) {
+        const size_t need = (size_t)B * T * 88;
+        if (!e->stride_d.fits(need)) e->stride_key.valid = false;
+        if ((rc = grow_chain_buffer(e, e->stride_d, need, st))) return rc;
+    }
     return DR_OK;
 }
 
@@ -596,6 +619,7 @@ GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     key.thresh_work = stage.thresh ? (const unsigned*)e->thresh_work : nullptr;
     key.stats_work = (stage.rescale || stage.project) ? (const unsigned*)e->stats_work : nullptr;
     key.momentum = stage.momentum ? (const float*)e->momentum : nullptr;
+    key.stride = stage.stride ? (const float*)e->stride_d : nullptr;
     return key;
 }
 
@@ -849,6 +873,17 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
                                       "(the chain's first guided step starts a new state; every other guided step follows the guided "
                                       "step before it)", e->opt.cfg_momentum, t, mv.expect);
     }
+    // option "guidance_stride": the stored guidance update, over the steps that guide (chain_tables.h: stride_step)
+    const bool strided = stages_of(e->opt, predicts_x0(sampler), NB == 2 * B && step_guided(e->opt.guid, e->S, w == 0.f, t)).stride;
+    StrideVerdict sv{StrideStep::REFRESHES, t, 0};
+    if (strided) {
+        sv = stride_step(e->stride_key, sampler, B, T, t, e->steps, e->opt.start, e->opt.guid, e->S, w == 0.f, e->opt.guid_stride);
+        if (sv.what == StrideStep::REFUSED)
+            return fail(e, DR_ESTATE, "guidance_stride = %d: dr_step at step %d reuses no stored guidance update - the step expected next "
+                                      "is %d (a step that refreshes - the chain's first guided step, every %d-th one behind it, step 0 - "
+                                      "needs nothing; every other guided step follows the guided step before it)", e->opt.guid_stride, t,
+                        sv.expect, e->opt.guid_stride);
+    }
     if (e->opt.solver == 2) {
         // the history is engine state: t starts one or continues the one the previous dr_step left (chain_tables.h: history_step)
         const HistoryVerdict v = history_step(e->hist_key, sampler, B, T, t, e->steps, e->opt.start);
@@ -862,6 +897,8 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
         e->mom_start = mv.what == MomentumStep::STARTS;
         e->mom_key.valid = false;       // (until the step has been issued)
     }
+    e->stride_reuse = strided && sv.what == StrideStep::REUSES;
+    if (strided) e->stride_key.valid = false;      // (until the step has been issued)
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
     if ((rc = write_windows(e, B, false, (hipStream_t)stream))) return rc;
@@ -871,6 +908,7 @@ int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, 
         HIPCHK(e, hipMemcpyAsync(d_x, res, (size_t)B * T * 88 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (e->opt.solver == 2 && t > 0) { auto& k = e->hist_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
     if (momentum) { auto& k = e->mom_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
+    if (strided) { auto& k = e->stride_key; k.valid = true; k.sampler = sampler; k.B = B; k.T = T; k.t = t; }
     return DR_OK;
 }
 
@@ -884,6 +922,7 @@ int dr_sample(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B
     if (rc) return rc;
     e->hist_key.valid = false;      // (a whole chain uses the history buffers: a dr_step sequence does not continue across it)
     e->mom_key.valid = false;       // (... and the momentum state)
+    e->stride_key.valid = false;    // (... and the stored guidance update)
     // (a yield is a precaution, not a verdict: the looks in front of later chains, >= 250 ms apart, may re-arm)
     if (e->fused.may_fuse()) fused_look(e, shared_with_another_process(e));
     FusedTurn turn(e, st);      // (released - event recorded on `st` - when this call returns, behind the chain's launches)

@@ -1,6 +1,6 @@
 // The tables of a reverse chain: the steps it visits (option "sampling_steps"), the coefficient rows derived for them
 // (respaced rows; options "solver_order" / "solver_noise"), the position option "start_step" names, the rule by which a
-// dr_step continues the history of solver order 2 or the state of option "cfg_momentum", and the per-window words of options "window_break" / "draws".  Every
+// dr_step continues the history of solver order 2 or the state of option "cfg_momentum" or "guidance_stride", and the per-window words of options "window_break" / "draws".  Every
 // one is a pure function of host values; abi.hip uploads what they return and words the refusals.  Host code; plain C++
 // (tests/test_chain_tables_cpu.py compiles it without HIP).
 #pragma once
@@ -182,6 +182,39 @@ inline MomentumVerdict momentum_step(const MomentumKey& k, int sampler, int B, i
     const int next = same && k.t > 0 ? guided_from(steps, k.t - 1, g, S, w_zero) : -1;
     const int expect = next >= 0 ? next : first;
     return {same && expect == t ? MomentumStep::CONTINUES : MomentumStep::REFUSED, expect};
+}
+
+// dr_step under option "guidance_stride": what the engine's stride state holds - d of the last refresh, as the guided step t
+// of a (sampler, B, T) chain left it (t: the last guided step run, a refresh or a reuse)
+struct StrideKey { bool valid = false; int sampler = -1, B = 0, T = 0, t = -1; };
+// The ordinal k of step t among the steps at or below `from` (from < 0: from the chain's first step) that the chain visits
+// and that guide, in chain order - guided_from's counting; -1: t is not one of them.
+inline int guided_ordinal(const ChainSteps& steps, int from, const GuidanceInterval& g, int S, bool w_zero, int t) {
+    for (int i = 0, k = 0, n = steps.count(); i < n; ++i) {
+        const int v = steps.at(i);
+        if ((from >= 0 && v > from) || !step_guided(g, S, w_zero, v)) continue;
+        if (v == t) return k;
+        ++k;
+    }
+    return -1;
+}
+// The state has the discipline of the momentum's, over the steps that guide alone: a step that refreshes (launch_plan.h:
+// stride_refreshes of its ordinal - the chain's first guided step, every n-th one behind it, step 0) needs nothing and
+// overwrites the state; a step that reuses must be the guided visited step behind the guided step the previous guided
+// dr_step ran, in a chain of the same (sampler, B, T) - or is refused, with the step expected next (the first guided step
+// where nothing continues, and for a step that is no guided step of this chain).  k: the step's ordinal.
+enum class StrideStep { REFRESHES, REUSES, REFUSED };
+struct StrideVerdict { StrideStep what; int expect; int k; };
+inline StrideVerdict stride_step(const StrideKey& key, int sampler, int B, int T, int t, const ChainSteps& steps, int start_step,
+                                 const GuidanceInterval& g, int S, bool w_zero, int n) {
+    const int first = guided_from(steps, start_step, g, S, w_zero);
+    const int k = guided_ordinal(steps, start_step, g, S, w_zero, t);
+    if (k < 0) return {StrideStep::REFUSED, first, k};
+    if (stride_refreshes(n, k, t)) return {StrideStep::REFRESHES, t, k};
+    const bool same = key.valid && key.sampler == sampler && key.B == B && key.T == T;
+    const int next = same && key.t > 0 ? guided_from(steps, key.t - 1, g, S, w_zero) : -1;
+    const int expect = next >= 0 ? next : first;
+    return {same && expect == t ? StrideStep::REUSES : StrideStep::REFUSED, expect, k};
 }
 
 // one word per window: Philox key offset of its recording (the ordinal in the batch; + draw x stride under option "draws":

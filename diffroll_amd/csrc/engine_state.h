@@ -101,30 +101,40 @@ struct ChainOptions {
     // a guided step under "cfg_project" / "cfg_norm" runs the statistics in their momentum form and update_momentum_kernel
     // (momentum.hip) over the engine's state (dr_engine::momentum).  Refused while both partners are 0 (abi.hip: check_options)
     int cfg_momentum = 0;
+    // option "guidance_stride": 0 / 1 = off; n = 2 .. 64: of the steps that guide, numbered in chain order from the chain's
+    // start position, every n-th one and step 0 refresh - both evaluations, and d = y - c stored per element into the engine's
+    // state (dr_engine::stride_d) - and the others reuse: the conditional evaluation alone, y = c + d (launch_plan.h:
+    // stride_refreshes; stride.hip: update_stride_kernel).  A guided step under it offers no tail plan.  Refused beside
+    // "x0_threshold", "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum", and by a sampler that does not guide
+    // (abi.hip: check_options)
+    int guid_stride = 0;
     bool operator==(const ChainOptions& o) const {
         return steps == o.steps && win_O == o.win_O && win_blend == o.win_blend && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
                guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
                start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && cfg_rescale == o.cfg_rescale &&
-               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm && cfg_momentum == o.cfg_momentum;
+               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm && cfg_momentum == o.cfg_momentum && guid_stride == o.guid_stride;
     }
 };
 // Which stages between the network and the update run - the one statement of it, for a step and for a chain: the threshold
 // launches of "x0_threshold" (the x0-prediction samplers, under the range "x0_clip" names), the statistics launch of
 // "cfg_rescale", that of "cfg_project" / "cfg_norm", and its momentum form under "cfg_momentum".  guides: asked about a step,
 // the step runs the unconditional evaluation; asked about a chain, a step of it can - a guiding sampler, w != 0.
-struct Stages { bool thresh, rescale, project, momentum; };
+// stride: the step guides under "guidance_stride" - a refresh or a reuse (`guides` then says that the step is one of those
+// that guide: a reuse runs no unconditional evaluation, and check_options has refused every other stage beside it).
+struct Stages { bool thresh, rescale, project, momentum, stride; };
 inline Stages stages_of(const ChainOptions& o, bool x0_sampler, bool guides) {
     Stages s{};
     s.thresh = o.x0_thresh != 0 && o.x0_clamp != 0 && x0_sampler;
     s.rescale = o.cfg_rescale != 0 && guides;
     s.project = (o.cfg_project != 0 || o.cfg_norm != 0) && guides;
     s.momentum = s.project && o.cfg_momentum != 0;
+    s.stride = o.guid_stride > 1 && guides;
     return s;
 }
 // The options as a chain sees them - what its captured graph bakes in, so what its key compares.  A value that is inert
 // under the others does not make another chain: "draw_stride" counts only under "draws" > 1, "solver_noise" only under
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
-// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum" count only for the stages a step of the
+// step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project", "cfg_norm", "cfg_momentum" and "guidance_stride" (whose 0 and 1 are one value) count only for the stages a step of the
 // chain can run (stages_of) - a sampler that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, bool w_zero) {
     if (o.draws <= 1) o.draw_G = 0;
@@ -135,6 +145,7 @@ inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, 
     if (!s.rescale) o.cfg_rescale = 0;
     if (!s.project) o.cfg_project = o.cfg_norm = 0;
     if (!s.momentum) o.cfg_momentum = 0;
+    if (!s.stride) o.guid_stride = 0;
     o.start = start_t;
     return o;
 }
@@ -165,10 +176,11 @@ struct GraphKey {
     const unsigned* thresh_work = nullptr;    // the work buffer the threshold launches point into - a buffer that grew since is another chain
     const unsigned* stats_work = nullptr;     // ... and the one the statistics launch of "cfg_rescale" or "cfg_project" / "cfg_norm" points into, likewise
     const float* momentum = nullptr;          // the state of "cfg_momentum" (null: off; "starts" is baked per node)
+    const float* stride = nullptr;            // the state of "guidance_stride" (null: off; refresh / reuse is baked per node)
     bool operator==(const GraphKey& o) const {
         return sampler == o.sampler && B == o.B && T == o.T && x == o.x && noise == o.noise && w_zero == o.w_zero &&
                opt == o.opt && baked == o.baked && tuning == o.tuning && fe_B == o.fe_B && hist == o.hist &&
-               thresh_work == o.thresh_work && stats_work == o.stats_work && momentum == o.momentum;
+               thresh_work == o.thresh_work && stats_work == o.stats_work && momentum == o.momentum && stride == o.stride;
     }
 };
 using Chain = CapturedChain<GraphKey>;      // the captured reverse chain and its owner (captured_chain.h)
@@ -337,6 +349,12 @@ struct dr_engine {
     drh::DevBuf<float> momentum;
     dr::MomentumKey mom_key;
     bool mom_start = true;
+    // option "guidance_stride": the state d, one float per roll element (B x T x 88), written by a refresh step's update and
+    // read by the reuse steps behind it.  stride_key: what it holds between dr_steps (chain_tables.h: stride_step);
+    // stride_reuse: the verdict for the dr_step under way - its guided step reuses (run_step reads it where no chain says)
+    drh::DevBuf<float> stride_d;
+    dr::StrideKey stride_key;
+    bool stride_reuse = false;
     int64_t inproj_launches = 0;        // standalone input-projection launches (dr_debug_launch_counts): steps no tail kernel primed
     int64_t conv0_launches = 0;         // ... and standalone shared first-layer conv launches in front of a fused stack
     unsigned win_epoch = 0;             // the last epoch handed to a tail launch (eager: one per launch; a chain graph: S per launch)
@@ -429,9 +447,10 @@ struct Range {
 
 // The captured chain is stale and a dr_step history has ended.  Says so and nothing more: the chain stays held - it may
 // still be running - until dr_sample replaces it (CapturedChain::capture waits for it first).
-inline void stale(dr_engine* e) { e->baked += 1; e->hist_key.valid = false; e->mom_key.valid = false; }
-// an option that shapes the prediction takes a new value: what dr_step left - the solver history, the momentum state - ends
-inline void end_step_states(dr_engine* e) { e->hist_key.valid = false; e->mom_key.valid = false; }
+inline void stale(dr_engine* e) { e->baked += 1; e->hist_key.valid = false; e->mom_key.valid = false; e->stride_key.valid = false; }
+// an option that shapes the prediction takes a new value: what dr_step left - the solver history, the momentum state, the
+// stored guidance update - ends
+inline void end_step_states(dr_engine* e) { e->hist_key.valid = false; e->mom_key.valid = false; e->stride_key.valid = false; }
 
 // ---- abi.hip
 int clear_stack_timeout(dr_engine* e);
@@ -493,12 +512,15 @@ RescaleArgs rescale_args(const dr_engine* e, const UpdateArgs& u);
 ProjectArgs project_args(const dr_engine* e, const UpdateArgs& u);
 // option "cfg_momentum": bf, the factor the kernels multiply m_prev by
 inline float momentum_bf(const dr_engine* e) { return (float)((double)e->opt.cfg_momentum / 10000.0); }
+// option "guidance_stride": the stride a step reads - n, or 0 for off (the values 0 and 1)
+inline int guidance_stride(const dr_engine* e) { return e->opt.guid_stride > 1 ? e->opt.guid_stride : 0; }
 struct ChainState {
     bool inproj_ready = false;
     StepEval ready{};          // the shape inproj_ready holds for (TailPlan::primed of the next step)
     int next_t = -1;
     float* x_out = nullptr;    // where a fused step writes x_{t-1} (null: e->xalt)
     bool guided = false;       // option "cfg_momentum": a guided step has run in this chain (the next one continues the state)
+    int guided_k = 0;          // option "guidance_stride": the guided steps this chain has run - the ordinal of the next one
 };
 int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int T, int t, float w, uint64_t seed,
              int first_sample, hipStream_t st, float** result = nullptr, ChainState* chain = nullptr);

@@ -404,6 +404,17 @@ hipError_t launch_update_momentum(const UpdateArgs& a, const MomentumUpd& mo, hi
 // (dr_debug_momentum) m_next = m of every element, by the device function the update uses; m_prev null: starts
 hipError_t launch_momentum_state(const UpdateArgs& a, const float* m_prev, float bf, float* m_next, hipStream_t s);
 
+// Option "guidance_stride" (include/diffroll_amd.h): the guidance update d = y - c of a step that REFRESHES - y the guided
+// prediction, c the conditional one, both after the shared-frame mean / blend, fp32, one rounding - is the engine's state, one
+// float per roll element (the layout of the roll, B x T x 88), stored by the element's own thread and left as it is by the
+// steps that REUSE it: those run the conditional evaluation alone and consume y = c + d.  Neighbouring windows read each
+// other's predictions, never each other's state (a frame two windows share holds the same d in both rows).  Refresh or reuse
+// is a fact of the step, baked per node in a captured chain (chain_tables.h: stride_step for dr_step).  What the update's
+// stride form needs beside UpdateArgs - its second kernel argument, StrideUpd - and its form_quad: stride_quad.h.
+struct StrideUpd;
+// update_kernel's stride form (stride.hip: update_stride_kernel); a refresh step has a.x0u set, a reuse step has it null
+hipError_t launch_update_stride(const UpdateArgs& a, const StrideUpd& su, hipStream_t s);
+
 // Tail of a reverse step as one persistent launch (tail_kernel in tail.hip): skip projection -> output projection ->
 // classifier-free combine + posterior update -> input projection of the next step.  Same grid / grouping as the
 // stack_kernel launch it follows: NB samples (first `dual` conditional, next `dual` unconditional when dual > 0) x

@@ -357,12 +357,19 @@ inline StepEval step_eval(int NB, int n_cond, int B, bool guided) {
     if (NB != 2 * B) return StepEval{NB, n_cond, false};
     return guided ? StepEval{NB, n_cond, true} : StepEval{B, B, false};
 }
-// this step's shape and its successor's in the chain (next_t < 0: the chain ends here, `next` is all zero)
+// Guidance stride (option "guidance_stride", include/diffroll_amd.h): of the steps that guide, numbered k = 0, 1, 2, ... in
+// the order the chain visits them from its start position, the one with k % n == 0 and step t == 0 REFRESH - both
+// evaluations, as without the option - and every other one REUSES the guidance update the last refresh stored: the
+// conditional evaluation alone, the shape of a step outside the interval.  n <= 1: off, every guided step refreshes.
+inline bool stride_refreshes(int n, int k, int t) { return n <= 1 || k % n == 0 || t == 0; }
+// this step's shape and its successor's in the chain (next_t < 0: the chain ends here, `next` is all zero); reuse_now /
+// reuse_next: the step guides and reuses under "guidance_stride" (the caller counts k: chain_tables.h, guided_ordinal)
 struct StepShapes { StepEval now, next; };
-inline StepShapes plan_step(int NB, int n_cond, int B, const GuidanceInterval& g, int S, bool w_zero, int t, int next_t) {
+inline StepShapes plan_step(int NB, int n_cond, int B, const GuidanceInterval& g, int S, bool w_zero, int t, int next_t,
+                            bool reuse_now = false, bool reuse_next = false) {
     StepShapes p;
-    p.now = step_eval(NB, n_cond, B, step_guided(g, S, w_zero, t));
-    if (next_t >= 0) p.next = step_eval(NB, n_cond, B, step_guided(g, S, w_zero, next_t));
+    p.now = step_eval(NB, n_cond, B, step_guided(g, S, w_zero, t) && !reuse_now);
+    if (next_t >= 0) p.next = step_eval(NB, n_cond, B, step_guided(g, S, w_zero, next_t) && !reuse_next);
     return p;
 }
 

@@ -1,6 +1,7 @@
 // Host side, part 2: the launch sequences of one network evaluation (run_network) and one reverse step (run_step).  What
 // they launch - tile flavours, split-K factors, the fused-stack shape - is decided in launch_plan.h.
 #include "engine_state.h"
+#include "stride_quad.h"      // StrideUpd
 
 namespace drh {
 
@@ -439,7 +440,19 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // outside the guidance interval (options "guidance_t_min" / "guidance_t_max") is that step, whatever the caller's w;
     // w == 0 is the empty interval (launch_plan.h: plan_step).
     const bool guiding = NB == 2 * B;
-    const StepShapes shapes = plan_step(NB, n_cond, B, e->opt.guid, e->S, w == 0.f, t, chain ? chain->next_t : -1);
+    // option "guidance_stride": a step that guides refreshes or reuses by its ordinal among the guided steps of the chain -
+    // counted along the chain, or dr_step's verdict; a captured chain bakes it into the node.  A reuse step is the
+    // conditional evaluation alone, and so is planned as a step outside the interval is (launch_plan.h: plan_step)
+    const int stride = guiding ? guidance_stride(e) : 0;
+    const bool strided = stride > 1 && step_guided(e->opt.guid, e->S, w == 0.f, t);
+    bool reuse = false, reuse_next = false;
+    if (strided) {
+        reuse = chain ? !stride_refreshes(stride, chain->guided_k, t) : e->stride_reuse;
+        if (chain) chain->guided_k += 1;
+    }
+    if (stride > 1 && chain && chain->next_t >= 0 && step_guided(e->opt.guid, e->S, w == 0.f, chain->next_t))
+        reuse_next = !stride_refreshes(stride, chain->guided_k, chain->next_t);
+    const StepShapes shapes = plan_step(NB, n_cond, B, e->opt.guid, e->S, w == 0.f, t, chain ? chain->next_t : -1, reuse, reuse_next);
     NB = shapes.now.NB; n_cond = shapes.now.n_cond;
     if (guiding && !shapes.now.dual) w = 0.f;
     UpdateArgs u = update_base(e, B, T);
@@ -476,8 +489,10 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     // option "cfg_rescale": likewise at a step that guides - the statistics sit between the network and everything that reads
     // the prediction; a step that runs no unconditional evaluation does not read the option and keeps its tail kernel
     // options "cfg_project" / "cfg_norm": likewise (check_options has refused them beside "x0_threshold" and "cfg_rescale")
-    const Stages stage = stages_of(e->opt, predicts_x0(sampler), u.x0u != nullptr);
-    TailPlan* offer = (result && x != xalt && !stage.thresh && !stage.rescale && !stage.project) ? &plan : nullptr;
+    // option "guidance_stride": likewise at a step that guides, a refresh or a reuse - the stride form of the update stands
+    // behind the head projections (check_options has refused the options above beside it)
+    const Stages stage = stages_of(e->opt, predicts_x0(sampler), u.x0u != nullptr || strided);
+    TailPlan* offer = (result && x != xalt && !stage.thresh && !stage.rescale && !stage.project && !stage.stride) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
     int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
@@ -487,6 +502,10 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
         return DR_OK;
     }
     if (result) *result = x;
+    if (stage.stride) {       // update that stores d = y - c, or consumes c + d
+        HIPCHK(e, launch_update_stride(u, StrideUpd{e->stride_d, reuse ? 1 : 0}, st));
+        return DR_OK;
+    }
     if (stage.project) {      // statistics, update on (a c) + (b y)
         const ProjectArgs pa = project_args(e, u);
         if (stage.momentum) {

@@ -137,7 +137,7 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise AttributeError(sampling.type)                               # getattr at task/diffusion.py:255
         # extensions, absent / None in the reference's configs (each key, its validator and the engine option it becomes:
         # schedule.sampling_options): steps, draws, guidance_interval, solver_order, solver_noise, start_step / strength,
-        # x0_clip, x0_threshold, cfg_rescale, cfg_project, cfg_norm, cfg_momentum
+        # x0_clip, x0_threshold, cfg_rescale, cfg_project, cfg_norm, cfg_momentum, guidance_stride
         sampling_options(sampling, timesteps, norm_args)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
@@ -306,6 +306,10 @@ class ClassifierFreeDiffRoll(nn.Module):
     def cfg_momentum(self) -> int:
         """hparams.sampling.cfg_momentum as the engine's option takes it (0: off, else the momentum beta in units of 1 / 10000)."""
         return self.sampling_options()["cfg_momentum"]
+
+    def guidance_stride(self) -> int:
+        """hparams.sampling.guidance_stride as the engine's option takes it (0: off, else the stride n of the steps that refresh)."""
+        return self.sampling_options()["guidance_stride"]
 
     def guidance_interval(self):
         """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain."""
@@ -556,6 +560,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         With hparams.sampling.cfg_momentum = beta beside either (option "cfg_momentum": the method's momentum, -0.5 in the paper)
         the update a guided step projects and bounds is d + beta m_prev, m_prev the previous guided step's; the chain's first
         guided step starts the state.
+        With hparams.sampling.guidance_stride = n (option "guidance_stride", 2 .. 64) only every n-th step that guides - and
+        step 0 - runs both evaluations; the others run the conditional one alone and reuse the stored guidance update, y = c + d.
+        Not beside x0_threshold, cfg_rescale, cfg_project, cfg_norm or cfg_momentum.
         check=True (default): the call returns with the FINISHED, verified roll, as task/diffusion.py:528-538 does
         (synchronous; a fused-kernel time-out caused by another tenant of the device is healed by re-running the chain
         on the per-phase kernels - Engine.sample).  check=False: asynchronous; call engine.finish() before use."""

@@ -300,6 +300,31 @@ def check_cfg_momentum(value, sampler: str = None, cfg_project=None, cfg_norm=No
     return int(round(float(value) * 10000))
 
 
+STRIDE_PARTNERS = ("x0_threshold", "cfg_rescale", "cfg_project", "cfg_norm", "cfg_momentum")
+
+
+def check_guidance_stride(value, sampler: str = None, **partners) -> int:
+    """Option "guidance_stride" (include/diffroll_amd.h) as hparams.sampling.guidance_stride: None / 0 / 1 = off, an integer n
+    in 2 .. 64 = of the steps that guide, every n-th one (and step 0) runs both evaluations and the others reuse its guidance
+    update beside the conditional evaluation alone.  partners: hparams.sampling's x0_threshold, cfg_rescale, cfg_project,
+    cfg_norm, cfg_momentum.  Returns the option's value, n or 0 for off; any other value, a set value with a sampler that does
+    not guide, or one beside a set partner (their statistics need the unconditional prediction) raises ValueError."""
+    if value is None or (not isinstance(value, bool) and isinstance(value, int) and value in (0, 1)):
+        return 0
+    if isinstance(value, bool) or not isinstance(value, int) or not 2 <= value <= 64:
+        raise ValueError(f"guidance_stride must be 0 / 1 / None (off) or an integer stride n with 2 <= n <= 64 (2 = every second "
+                         f"guided step runs both evaluations), got {value!r}")
+    if sampler is not None and sampler not in GUIDING_SAMPLERS:
+        raise ValueError(f"guidance_stride = {value!r} needs a sampler that guides ({', '.join(GUIDING_SAMPLERS)}), not '{sampler}'")
+    for other in STRIDE_PARTNERS:
+        theirs = partners.get(other)
+        if theirs is not None and theirs is not False and theirs != 0:
+            raise ValueError(f"guidance_stride = {value!r} does not combine with {other} = {theirs!r}: its statistics need the "
+                             f"unconditional prediction, which a step that reuses the guidance update does not evaluate; set one "
+                             f"of them None")
+    return int(value)
+
+
 def respaced_steps(timesteps: int, n: int) -> List[int]:
     """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
     integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""
@@ -332,6 +357,8 @@ def sampling_options(sampling, timesteps, norm_args=(0, 1)) -> Dict[str, object]
         ("cfg_project", "cfg_project", lambda: check_cfg_project(get("cfg_project"), sampler, get("x0_threshold"), get("cfg_rescale"))),
         ("cfg_norm", "cfg_norm", lambda: check_cfg_norm(get("cfg_norm"), sampler, get("x0_threshold"), get("cfg_rescale"))),
         ("cfg_momentum", "cfg_momentum", lambda: check_cfg_momentum(get("cfg_momentum"), sampler, get("cfg_project"), get("cfg_norm"))),
+        ("guidance_stride", "guidance_stride",
+         lambda: check_guidance_stride(get("guidance_stride"), sampler, **{k: get(k) for k in STRIDE_PARTNERS})),
     )
     options = {}
     for option, key, check in checks:

@@ -788,6 +788,52 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          combines with.  Stored like "cfg_project": the value is part of a captured chain's key where a
  *                          step can read it.  0 = off: every path is byte-identical to an engine that never set it.
  *                          Nothing is known about quality with real weights.
+ *   "guidance_stride"  [0] 0 or 1 (off), or 2 .. 64: THE GUIDANCE UPDATE COMPUTED EVERY n-th GUIDED STEP and reused in
+ *                          between - the CFG cache of FasterCache (Lv et al. 2024), the observation of "Adaptive Guidance"
+ *                          (Castillo et al. 2023): the difference between the guided and the conditional prediction changes
+ *                          slowly along the chain.  n = guidance_stride.  ORDINAL: the steps that guide - a sampler that
+ *                          guides, w != 0, inside "guidance_t_min" / "guidance_t_max" - are numbered k = 0, 1, 2, ... in the
+ *                          order the chain visits them from its start position ("start_step").  A guided step REFRESHES when
+ *                          k % n == 0 or when it is step t == 0; otherwise it REUSES.  The first guided step a chain runs
+ *                          is k = 0 and always refreshes: under an interval the first step inside it, under "start_step"
+ *                          the first guided step at or below the start.  Step 0 refreshes because the roll is the last
+ *                          step's prediction.  A REFRESH STEP evaluates both branches exactly as without the option.  With
+ *                          y the guided prediction and c the conditional one, both after the shared-frame mean / blend,
+ *                          per element, in fp32, no contraction, one rounding:
+ *                              d = y - c
+ *                          is stored into the engine's state - one float per roll element, written by the element's own
+ *                          thread - and y goes on unchanged: the roll a refresh step leaves is, bit for bit, the roll of
+ *                          the same step with the option off.  A REUSE STEP evaluates the conditional branch alone - B
+ *                          evaluations, the shape of a step outside the guidance interval - and its prediction is
+ *                              y = c + d
+ *                          in fp32 with one rounding, c behind the blend, d as the last refresh stored it.  Everything that
+ *                          read the guided prediction reads this y: the clamp of "x0_clip", the sampler's own update, the
+ *                          solver's extrapolation and its history ("solver_order"), the last step.  d CARRIES THE WEIGHT of
+ *                          the step that stored it: a dr_step sequence that changes w between a refresh and its reuses
+ *                          gets what it asked for - the stored update at the old weight.  WINDOWS: d is taken behind the
+ *                          blend, so a frame two windows share holds the same d in both rows; windows read each other's
+ *                          predictions as without the option and never each other's state, and shared frames stay
+ *                          bit-identical.  There is one state per roll: per draw under "draws", per window row, per rank's
+ *                          rows when sharded.  A CAPTURED CHAIN bakes refresh / reuse into the step's nodes; its first
+ *                          guided step refreshes and overwrites the state: no memset, no host help, every replay restarts
+ *                          by itself.  WHERE IT RUNS: a guided step under the option - refresh or reuse - runs the stack
+ *                          launch, the head projections and update_stride_kernel (csrc/stride.hip); dr_launch_state
+ *                          reports DR_MODE_FUSED_STACK where the stack is fused.  Steps that do not guide keep the tail
+ *                          kernel and every bit.  dr_step: the state is engine state with the discipline of "cfg_momentum" -
+ *                          a step that refreshes needs nothing; a step that reuses must be the guided visited step behind
+ *                          the guided step the previous guided dr_step ran, in a chain of the same (sampler, B, T);
+ *                          otherwise DR_ESTATE naming the step expected next.  The state ends on dr_sample, dr_frontend
+ *                          with another shape, growth of the state, every option change that ends a solver history, and a
+ *                          change of "guidance_stride" itself.  REFUSED: beside "x0_threshold", "cfg_rescale",
+ *                          "cfg_project", "cfg_norm" or "cfg_momentum" - their statistics need the unconditional
+ *                          prediction - and by a sampler that does not guide: DR_EINVAL from dr_sample / dr_step, naming
+ *                          the two options.  A value outside 0 .. 64 -> DR_EINVAL at the set, stating the range.  Combines
+ *                          with "sampling_steps", windows and "window_blend", "window_break", "draws", the guidance
+ *                          interval, "solver_order" / "solver_noise", "start_step" / "start_noise", "x0_clip", every
+ *                          precision and sharding.  The value is part of a captured chain's key where a step can read it -
+ *                          a sampler that guides, w != 0 - and 0 and 1 are one value there.  0 or 1 = off: every path is
+ *                          byte-identical to an engine that never set it and replays the same captured chain.  Nothing is
+ *                          known about quality with real weights.
  * Unknown names -> DR_ENAME. (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
