@@ -5,7 +5,9 @@ A deep bf16 network is not held element-wise to a restatement (tests/test_bf16_c
 used here discriminate): with e = got - float64 network and e_ref the error of the fp32-accumulated restatement
 (tests/bf16_ref.py), 0.5 rms(e_ref) <= rms(e) <= 1.15 rms(e_ref) and max|e| <= 2 max|e_ref|.  The lower bound proves that
 the mode is engaged (the exact path lies four orders of magnitude below), the upper ones refuse truncation (2.3 - 3.2 x
-in rms) and anything worse.  What IS held bit for bit: fused against per-phase launches, captured against plain chains,
+in rms) and anything worse.  That is true of the network, not of one contraction: SINGLE layers of the mode are held element
+by element in tests/test_gpu_layer_probe.py, which sees the one-element faults these bands let through
+(tests/test_layer_probe_cpu.py).  What IS held bit for bit here: fused against per-phase launches, captured against plain chains,
 run against run, shared window frames, and the other precisions after a visit to this one."""
 import json
 import os

@@ -6,7 +6,9 @@ bands used here discriminate): with e = got - float64 network and e_ref the erro
 (tests/f16_ref.py), 0.5 rms(e_ref) <= rms(e) <= 1.15 rms(e_ref) and max|e| <= 2 max|e_ref|.  The lower bound proves that
 the mode is engaged (the exact path lies three orders of magnitude below); the upper ones refuse rounding toward zero
 (2.5 - 3.6 x in rms), bf16 (7.4 - 8.5 x) and - on the subnormal-weight case - an MFMA that flushes subnormal operands
-(several hundred x).  What IS held bit for bit: fused against per-phase launches, captured against plain chains, run
+(several hundred x).  That is true of the network, not of one contraction: SINGLE layers of the mode are held element by
+element in tests/test_gpu_layer_probe.py, which sees the one-element faults these bands let through
+(tests/test_layer_probe_cpu.py).  What IS held bit for bit here: fused against per-phase launches, captured against plain chains, run
 against run, shared window frames, and the other precisions after a visit to this one."""
 import json
 import os
