@@ -48,7 +48,7 @@ DEBUG_EXPORTS = [
 # the options dr_set_option knows; every other name goes to dr_debug_set_option (Engine.set_option)
 PUBLIC_OPTIONS = ("blocked_accumulation", "fused_rearm", "fused_stack", "fused_tail", "window_overlap", "window_break", "window_blend", "sampling_steps", "draws", "draw_stride",
                   "guidance_t_min", "guidance_t_max", "solver_order", "start_step", "start_noise", "solver_noise", "x0_clip", "x0_threshold", "cfg_rescale",
-                  "cfg_project", "cfg_norm", "cfg_momentum", "guidance_stride")
+                  "cfg_project", "cfg_norm", "cfg_momentum", "guidance_stride", "exact_below")
 MODES = {0: "none", 1: "per_phase", 2: "fused_stack", 3: "fused_stack+tail"}
 
 

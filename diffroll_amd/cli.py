@@ -131,14 +131,14 @@ def build_config(argv: List[str], default_task: str = "generation") -> Dict[str,
         raise SystemExit(f"task.sampling.draws must be an integer >= 1 (or null: one roll per clip), got {draws!r}")
     # the other task.sampling keys - guidance_interval=[lo,hi], solver_order=N, solver_noise=1, strength=S / start_step=T,
     # x0_clip=1 (to the roll's range model.args.norm_args), x0_threshold=0.995, cfg_rescale=0.7,
-    # cfg_project=1.0, cfg_norm=0.05, cfg_momentum=-0.5, guidance_stride=2 - are read as the model reads them
+    # cfg_project=1.0, cfg_norm=0.05, cfg_momentum=-0.5, guidance_stride=2, exact_below=25 - are read as the model reads them
     # (schedule.sampling_options: each key's validator and the engine option it becomes); absent / null = off
     from .schedule import sampling_options
     samp = cfg["task"]["sampling"]
     start_key = next((k for k in ("strength", "start_step") if samp.get(k) is not None), None)
     try:
-        needs_S = next((k for k in ("guidance_interval", start_key) if k and samp.get(k) is not None), None)
-        if needs_S and not isinstance(S, int):      # (the two keys that are read against the schedule's length)
+        needs_S = next((k for k in ("guidance_interval", start_key, "exact_below") if k and samp.get(k) is not None), None)
+        if needs_S and not isinstance(S, int):      # (the keys that are read against the schedule's length)
             bad = ValueError(f"task.timesteps = {S!r}")
             bad.key = needs_S
             raise bad

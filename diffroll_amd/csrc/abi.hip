@@ -510,6 +510,15 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
         (is_max ? e->opt.guid.hi : e->opt.guid.lo) = value;
         return DR_OK;
     }
+    if (n == "exact_below") {
+        // (no captured chain is dropped by the set itself: the value is part of the chain's key - GraphKey - as "draws" is, so
+        // a chain captured under another value is not replayed and one captured under this value still is.  No state of a
+        // dr_step sequence depends on the mode: the roll, the history, the momentum and stride states are fp32)
+        if (!exact_below_ok(value, e->S))
+            return fail(e, DR_EINVAL, "exact_below is 0 (off) or v in [1, timesteps = %d]: the steps t < v run in exact fp32, got %d", e->S, value);
+        e->opt.exact_below = value;
+        return DR_OK;
+    }
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
     if (n == "fused_stack_xcd") { put(e, e->opt_stack_xcd, value); return DR_OK; }
     if (n == "fused_stack_warm") { put(e, e->opt_stack_warm, value); return DR_OK; }
@@ -611,6 +620,8 @@ GraphKey chain_key(const dr_engine* e, const ChainCall& c, int NB) {
     GraphKey key;
     key.sampler = c.sampler; key.B = c.B; key.T = c.T; key.x = e->xwork; key.noise = c.noise; key.w_zero = (c.w == 0.f);
     key.opt = effective(e->opt, NB == 2 * c.B, e->S, e->steps.at(c.i0), key.w_zero);
+    // option "exact_below": each node bakes its step's precision.  Under DR_PRECISION_F32 no step reads the value
+    if (e->prec == DR_PRECISION_F32) key.opt.exact_below = 0;
     key.baked = e->baked; key.tuning = tuning_epoch().load();
     key.fe_B = e->fe_B;
     key.hist = e->opt.solver == 2 ? (const float*)e->hist : nullptr;
@@ -833,7 +844,7 @@ int dr_forward(dr_engine* e, const float* d_x, int B, int T, int t, int cond, fl
     if ((rc = ensure_workspace(e, B, T))) return rc;
     FusedTurn turn(e, (hipStream_t)stream);
     if (turn.rc) return turn.rc;
-    return run_network(e, d_x, 0, B, cond == DR_COND_UNCOND ? 0 : B, T, t, d_x0_out, (hipStream_t)stream);
+    return run_network(e, d_x, 0, B, cond == DR_COND_UNCOND ? 0 : B, T, t, e->prec, d_x0_out, (hipStream_t)stream);
 }
 
 int dr_forward_steps(dr_engine* e, const float* d_x, int B, int T, const int32_t* host_t, int cond, float* d_x0_out,
@@ -852,7 +863,7 @@ int dr_forward_steps(dr_engine* e, const float* d_x, int B, int T, const int32_t
     HIPCHK(e, hipMemcpy(e->d_tsel, host_t, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
     FusedTurn turn(e, st);
     if (turn.rc) return turn.rc;
-    return run_network(e, d_x, 0, B, cond == DR_COND_UNCOND ? 0 : B, T, 0, d_x0_out, st, false, e->d_tsel);
+    return run_network(e, d_x, 0, B, cond == DR_COND_UNCOND ? 0 : B, T, 0, e->prec, d_x0_out, st, false, e->d_tsel);
 }
 
 int dr_step(dr_engine* e, int sampler, float* d_x, const float* d_noise, int B, int T, int t, float w, uint64_t seed,

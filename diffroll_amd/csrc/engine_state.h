@@ -108,11 +108,16 @@ struct ChainOptions {
     // "x0_threshold", "cfg_rescale", "cfg_project", "cfg_norm" and "cfg_momentum", and by a sampler that does not guide
     // (abi.hip: check_options)
     int guid_stride = 0;
+    // option "exact_below": 0 = off; v = 1 .. timesteps: a reverse step at diffusion step t < v runs in exact fp32 whatever
+    // dr_set_precision selected (launch_plan.h: step_precision; plan.hip: run_step asks once per step).  Inert under
+    // DR_PRECISION_F32 (abi.hip: chain_key takes it out of the key there)
+    int exact_below = 0;
     bool operator==(const ChainOptions& o) const {
         return steps == o.steps && win_O == o.win_O && win_blend == o.win_blend && draws == o.draws && draw_G == o.draw_G && guid.lo == o.guid.lo &&
                guid.hi == o.guid.hi && solver == o.solver && solver_noise == o.solver_noise && start == o.start &&
                start_noise == o.start_noise && x0_clamp == o.x0_clamp && x0_thresh == o.x0_thresh && cfg_rescale == o.cfg_rescale &&
-               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm && cfg_momentum == o.cfg_momentum && guid_stride == o.guid_stride;
+               cfg_project == o.cfg_project && cfg_norm == o.cfg_norm && cfg_momentum == o.cfg_momentum && guid_stride == o.guid_stride &&
+               exact_below == o.exact_below;
     }
 };
 // Which stages between the network and the update run - the one statement of it, for a step and for a chain: the threshold
@@ -136,6 +141,7 @@ inline Stages stages_of(const ChainOptions& o, bool x0_sampler, bool guides) {
 // a solver order, "window_blend" only under "window_overlap", the interval only for a sampler that guides (hi resolved); start_t is "start_step" resolved to the
 // step the chain visits first (chain_tables.h: start_position); "cfg_rescale", "cfg_project", "cfg_norm", "cfg_momentum" and "guidance_stride" (whose 0 and 1 are one value) count only for the stages a step of the
 // chain can run (stages_of) - a sampler that guides, at a weight that is not 0 (w_zero: GraphKey::w_zero, a chain of conditional evaluations alone).
+// ("exact_below" counts only under a reduced precision, which this function does not know: abi.hip, chain_key)
 inline ChainOptions effective(ChainOptions o, bool guiding, int S, int start_t, bool w_zero) {
     if (o.draws <= 1) o.draw_G = 0;
     if (o.solver == 0) o.solver_noise = 0;
@@ -493,12 +499,14 @@ struct TailPlan {
     int u_B = 0;               // rolls
     int next_t = -1;           // >= 0: the chain continues with step next_t (its input projection joins the tail)
     StepEval next{};           // ... whose evaluation has this shape (launch_plan.h: a guidance interval may begin or end here)
+    int next_prec = 0;         // ... and this precision (option "exact_below": launch_plan.h, step_precision)
     bool skip_inproj = false;  // h / hd (and, guided, layer 0's g) were written by the previous step's tail ...
     StepEval primed{};         // ... for an evaluation of this shape: honoured only when it is THIS step's shape
     bool done = false;         // out: the tail kernel ran (update included, result in x_out)
     bool inproj_done = false;  // out: ... and it wrote the next step's h / hd (and layer 0's g for a guided pair)
 };
-int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, int T, int t, float* x0_out,
+// prec: the precision of this evaluation - the engine's mode (dr_forward), or the step's (run_step: option "exact_below")
+int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, int T, int t, int prec, float* x0_out,
                 hipStream_t st, bool zero_spec = false, const int* tsel = nullptr, TailPlan* tail = nullptr);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond, int& family, bool& zero_spec);
 int sampler_shape(int sampler, int B, int& NB, int& n_cond);

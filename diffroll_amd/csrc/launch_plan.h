@@ -40,6 +40,14 @@ struct PlanKnobs {
 // binary16 (4) - and carried as ONE plane set [batch][channel/8][frame][8 x 16 bit].  The two share every layout, LDS
 // size and planner decision; they differ in the conversion and in the MFMA (device_common.h: Half16<PREC>).
 constexpr bool one_plane16(int prec) { return prec == DR_PRECISION_BF16 || prec == DR_PRECISION_F16; }
+// Option "exact_below" (include/diffroll_amd.h): THE rule of a reverse step's precision.  A step at diffusion step t <
+// exact_below runs in exact fp32 whatever mode the engine has selected (prec); every other step runs in that mode.  Keyed
+// by the real diffusion step, so it means the same under "sampling_steps"; 0 = off, timesteps = every step exact.  The
+// visited t decrease along a chain, so all exact steps lie behind all reduced ones.  Network evaluations that are not
+// chain steps (dr_forward, dr_forward_steps) do not ask: they keep the engine's mode.
+constexpr int step_precision(int prec, int exact_below, int t) { return t < exact_below ? (int)DR_PRECISION_F32 : prec; }
+// what dr_set_option accepts for the name (S = timesteps)
+constexpr bool exact_below_ok(int v, int S) { return v >= 0 && v <= S; }
 // 16-byte rows of an X tile per 32 input channels: fp32 P4 planes, the three split-bf16 pieces, or one 16-bit plane set
 constexpr int x_tile_rows(int prec) { return one_plane16(prec) ? 4 : prec ? 12 : 8; }
 // bytes of one packed weight slab (128 rows x 32 channels of one tap)

@@ -88,6 +88,7 @@ struct Eval {
     dr_engine* e;
     const float* xin;              // (B,T,88) rows used modulo bmod
     int bmod, NB, n_cond, T, t;
+    int prec;                      // the evaluation's precision (DR_PRECISION_*): the engine's mode, or the step's under "exact_below"
     float* x0_out;
     hipStream_t st;
     bool zero_spec;
@@ -133,13 +134,13 @@ static int launch_inproj(const Eval& v, const PlanKnobs& k) {
     // hd = h + d_0 (model/diffwave.py:138-139), fp32 P4 or split-bf16 for the first dilated conv
     a.d2 = e->d_dtab + (v.tsel ? 0 : (size_t)v.t * e->L * Cp);
     a.tsel = v.tsel; a.d2_ts = (long)e->L * Cp;
-    if (e->prec == 1) { a.Y2 = e->hd3; a.y2_bs = act_bs + act_bs / 2; a.out_s3 = 2; }
+    if (v.prec == 1) { a.Y2 = e->hd3; a.y2_bs = act_bs + act_bs / 2; a.out_s3 = 2; }
     else { a.Y2 = e->hd; a.y2_bs = act_bs; }
     allow_splitk(e, a);
     HIPCHK(e, launch_gemm(a, EPI_RELU, pick_ni(k, a.MT, v.NB, T, 1, 1), v.st));
     // (one-pass bf16 / f16: this fp32 kernel leaves hd in P4; the first conv's operand is its rounding)
-    if (e->prec == DR_PRECISION_BF16) HIPCHK(e, launch_round_bf16(e->hd, e->hd3, v.NB, Cp, T, v.st));
-    if (e->prec == DR_PRECISION_F16) HIPCHK(e, launch_round_f16(e->hd, e->hd3, v.NB, Cp, T, v.st));
+    if (v.prec == DR_PRECISION_BF16) HIPCHK(e, launch_round_bf16(e->hd, e->hd3, v.NB, Cp, T, v.st));
+    if (v.prec == DR_PRECISION_F16) HIPCHK(e, launch_round_f16(e->hd, e->hd3, v.NB, Cp, T, v.st));
     e->inproj_launches += 1;
     return DR_OK;
 }
@@ -147,7 +148,7 @@ static int launch_inproj(const Eval& v, const PlanKnobs& k) {
 // phases [p0, p1) of the residual layers as fused launches (stack_kernel), one per sample chunk
 static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
     dr_engine* e = v.e;
-    const int Cp = e->Cp, L = e->L, T = v.T, prec = e->prec;
+    const int Cp = e->Cp, L = e->L, T = v.T, prec = v.prec;
     const long act_n = (long)Cp * T, c_bs = (long)2 * Cp * T;
     int b0 = 0;
     for (int ck = 0; ck < p.stack_chunks; ++ck) {
@@ -210,7 +211,7 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
 // layer l's dilated conv of (h + d_l) + conditioner, gate (model/diffwave.py:138-147)
 static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int l) {
     dr_engine* e = v.e;
-    const int Cp = e->Cp, L = e->L, T = v.T, NB = v.NB, bmod = v.bmod, prec = e->prec;
+    const int Cp = e->Cp, L = e->L, T = v.T, NB = v.NB, bmod = v.bmod, prec = v.prec;
     const LayerW& w = e->layers[l];
     GemmArgs a = p4_gemm(w.conv_w_of(prec), w.conv_b, Cp / 64, e->hd, Cp / 4, NB, T);
     if (prec) s3_in(a, e->hd3, Cp, T, prec);
@@ -253,7 +254,7 @@ static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int 
 // layer l's 1x1 output projection, residual and skip (model/diffwave.py:149-151, :680)
 static int launch_res_skip(const Eval& v, const PlanKnobs& k, int l) {
     dr_engine* e = v.e;
-    const int Cp = e->Cp, L = e->L, T = v.T, NB = v.NB, prec = e->prec;
+    const int Cp = e->Cp, L = e->L, T = v.T, NB = v.NB, prec = v.prec;
     const long act_bs = (long)Cp * T;
     const LayerW& w = e->layers[l];
     GemmArgs a = p4_gemm(w.out_w_of(prec), w.out_b, Cp / 64, e->g, Cp / 4, NB, T);
@@ -293,7 +294,7 @@ static int launch_tail_step(const Eval& v, const NetPlan& p, const PlanKnobs& k,
     NetPlan np{};
     bool prime = false;
     if (tail->next_t >= 0) {
-        np = plan_network(NetShape{tail->next.NB, tail->next.n_cond, v.bmod, T, Cp, L, e->K, e->max_dil, e->prec, e->n_cus,
+        np = plan_network(NetShape{tail->next.NB, tail->next.n_cond, v.bmod, T, Cp, L, e->K, e->max_dil, tail->next_prec, e->n_cus,
                                    e->fused.active(), e->opt_blocked, e->opt_tail, false, true}, k);
         prime = np.use_tail;
     }
@@ -365,12 +366,12 @@ static int launch_head(const Eval& v) {
 //   xin (B,T,88) rows are used modulo bmod (classifier-free batching: 2B evaluations of B inputs).
 // It carries out the plan of launch_plan.h: the layers one launch per phase, or fused launches (stack_kernel) - and, when
 // run_step offered the fused step and the plan takes it, the tail kernel instead of the head projections and the update.
-int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, int T, int t, float* x0_out,
+int run_network(dr_engine* e, const float* xin, int bmod, int NB, int n_cond, int T, int t, int prec, float* x0_out,
                 hipStream_t st, bool zero_spec, const int* tsel, TailPlan* tail) {
     // tsel (device, NB ints): per-sample diffusion steps (forward() with a (B,) step tensor); else step t for all
-    const Eval v{e, xin, bmod, NB, n_cond, T, t, x0_out, st, zero_spec, tsel};
+    const Eval v{e, xin, bmod, NB, n_cond, T, t, prec, x0_out, st, zero_spec, tsel};
     const PlanKnobs k = plan_knobs();
-    const NetPlan p = plan_network(NetShape{NB, n_cond, bmod, T, e->Cp, e->L, e->K, e->max_dil, e->prec, e->n_cus, e->fused.active(),
+    const NetPlan p = plan_network(NetShape{NB, n_cond, bmod, T, e->Cp, e->L, e->K, e->max_dil, prec, e->n_cus, e->fused.active(),
                                             e->opt_blocked, e->opt_tail, tsel != nullptr, tail != nullptr}, k);
     e->last_mode = p.mode;      // dr_launch_state
     // h / hd of this step (and, guided, layer 0's g) were already written by the previous step's tail kernel - for an
@@ -481,6 +482,11 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     plan.u = u; plan.x_out = xalt; plan.u_B = B;
     plan.next_t = chain ? chain->next_t : -1;
     plan.next = shapes.next;
+    // option "exact_below": the precision is a property of the step.  The visited t decrease, so every exact step lies behind
+    // every reduced one: a reduced step takes no tail kernel and primes nothing, the first exact step computes its own input
+    // layer, and the tail kernel of an exact step primes an exact successor (launch_plan.h: step_precision)
+    const int prec = step_precision(e->prec, e->opt.exact_below, t);
+    plan.next_prec = plan.next_t >= 0 ? step_precision(e->prec, e->opt.exact_below, plan.next_t) : prec;
     plan.skip_inproj = chain && chain->inproj_ready;
     if (chain) plan.primed = chain->ready;
     // (x and the tail kernel's output buffer must differ: a caller that hands us xalt itself gets the unfused tail)
@@ -494,7 +500,7 @@ int run_step(dr_engine* e, int sampler, float* x, const float* noise, int B, int
     const Stages stage = stages_of(e->opt, predicts_x0(sampler), u.x0u != nullptr || strided);
     TailPlan* offer = (result && x != xalt && !stage.thresh && !stage.rescale && !stage.project && !stage.stride) ? &plan : nullptr;
     if (chain) chain->inproj_ready = false;
-    int rc = run_network(e, x, B, NB, n_cond, T, t, e->x0buf, st, zero_spec, nullptr, offer);
+    int rc = run_network(e, x, B, NB, n_cond, T, t, prec, e->x0buf, st, zero_spec, nullptr, offer);
     if (rc) return rc;
     if (offer && plan.done) {
         *result = xalt;

@@ -171,8 +171,8 @@ def sample_shard(model, x_T: torch.Tensor, waveform: Optional[torch.Tensor], noi
     """The part of sample_sharded one rank computes: the chain of its contiguous shard of the GLOBAL batch,
     returned as (b_local, 1, T', 88) on the engine's device (b_local may be 0).  Philox noise is keyed by the
     global sample index (first_sample = lo), so the rolls do not depend on the world size.
-    hparams.sampling.steps / guidance_interval travel with the model: model.sample sets them on this rank's engine, so
-    every rank that is handed the same hparams runs the same steps guided.
+    hparams.sampling.steps / guidance_interval / exact_below travel with the model, as its precision does: model.sample sets
+    them on this rank's engine, so every rank that is handed the same hparams runs the same steps guided, in the same arithmetic.
     draws = D > 1: x_T / noise hold D draws of the B global clips, draw-major; the rank runs its clip shard x all draws in
     one chain with "draw_stride" = B - draw d of global clip c is keyed c + d * B on any world size - and returns
     (D * b_local, 1, T', 88), draw-major over its shard.

@@ -57,6 +57,7 @@ _MIRRORED = {
     "cfg_norm": 0,               # 1 .. 100000 = r (1 / 10000): the bound on the rms of the guidance update c - u
     "cfg_momentum": 0,           # -9999 .. 9999 = beta (1 / 10000): the momentum of the guidance update, beside the two above
     "guidance_stride": 0,        # 2 .. 64 = n: every n-th guided step (and step 0) runs both evaluations, the others reuse its update
+    "exact_below": 0,            # v = 1 .. timesteps: the reverse steps at t < v run in exact fp32 whatever the precision
     "blocked_accumulation": 2,   # 2 = every fp32 flavour that has a blocked form, 1 = single chain on 128-frame blocks
 }
 
@@ -366,7 +367,7 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         """Integer options of the engine: 'fused_stack', 'fused_tail', 'fused_rearm', 'blocked_accumulation',
-        'window_overlap', 'window_break', 'window_blend', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'cfg_momentum', 'guidance_stride' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
+        'window_overlap', 'window_break', 'window_blend', 'sampling_steps', 'draws', 'draw_stride', 'guidance_t_min', 'guidance_t_max', 'solver_order', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'cfg_momentum', 'guidance_stride', 'exact_below' (dr_set_option, include/diffroll_amd.h); any other name - 'tune.*',
         'fused_stack_xcd', 'stack_ticks', ... - is a lab knob (dr_debug_set_option, include/diffroll_amd_debug.h).  Unknown
         names and values out of range raise ValueError."""
         fn = self.lib.dr_set_option if name in _cabi.PUBLIC_OPTIONS else self.lib.dr_debug_set_option
@@ -383,7 +384,7 @@ class Engine:
     def holding(self, **options):
         """Options held for one call and put back afterwards, also when the call raises: mirrored option names, and
         window_breaks = the marks.  An option that already has the value is not set at all - 'sampling_steps' would drop the
-        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'cfg_momentum', 'guidance_stride', 'window_blend' and the marks never do (they are part of its key or plain data), so a loop of
+        captured chain; 'draws', 'draw_stride', 'solver_noise', 'start_step', 'start_noise', 'x0_clip', 'x0_threshold', 'cfg_rescale', 'cfg_project', 'cfg_norm', 'cfg_momentum', 'guidance_stride', 'exact_below', 'window_blend' and the marks never do (they are part of its key or plain data), so a loop of
         such calls replays one graph, and putting them back behind an asynchronous call touches nothing in flight."""
         def put(name, value):
             if name == "window_breaks":

@@ -137,7 +137,7 @@ class ClassifierFreeDiffRoll(nn.Module):
             raise AttributeError(sampling.type)                               # getattr at task/diffusion.py:255
         # extensions, absent / None in the reference's configs (each key, its validator and the engine option it becomes:
         # schedule.sampling_options): steps, draws, guidance_interval, solver_order, solver_noise, start_step / strength,
-        # x0_clip, x0_threshold, cfg_rescale, cfg_project, cfg_norm, cfg_momentum, guidance_stride
+        # x0_clip, x0_threshold, cfg_rescale, cfg_project, cfg_norm, cfg_momentum, guidance_stride, exact_below
         sampling_options(sampling, timesteps, norm_args)
         self.hparams = AttrDict(
             residual_channels=residual_channels, unconditional=unconditional, condition=condition,
@@ -263,12 +263,13 @@ class ClassifierFreeDiffRoll(nn.Module):
     def sampling_options(self) -> Dict[str, Any]:
         """hparams.sampling as the engine's options take it, by option name (schedule.sampling_options).  Read at every use; a
         bad value raises ValueError before any GPU work.  While one of the reference's single-step methods runs, the options
-        that shape the chain's steps and updates read as off; which steps guide and how many rolls a clip gets stay."""
+        that shape the chain's steps and updates read as off; which steps guide, how many rolls a clip gets and which steps
+        run in exact fp32 stay."""
         hp = self.__dict__["hparams"]
         options = sampling_options(hp.sampling, hp.timesteps, hp.norm_args)
         if self.__dict__.get("_stride1"):
             off = sampling_options({}, hp.timesteps)
-            options = {k: v if k in ("guidance_interval", "draws") else off[k] for k, v in options.items()}
+            options = {k: v if k in ("guidance_interval", "draws", "exact_below") else off[k] for k, v in options.items()}
         return options
 
     def start_step(self) -> int:
@@ -310,6 +311,10 @@ class ClassifierFreeDiffRoll(nn.Module):
     def guidance_stride(self) -> int:
         """hparams.sampling.guidance_stride as the engine's option takes it (0: off, else the stride n of the steps that refresh)."""
         return self.sampling_options()["guidance_stride"]
+
+    def exact_below(self) -> int:
+        """hparams.sampling.exact_below as the engine's option takes it (0: off, else v: the steps t < v run in exact fp32)."""
+        return self.sampling_options()["exact_below"]
 
     def guidance_interval(self):
         """(lo, hi) of hparams.sampling.guidance_interval as the engine's options take them; (0, -1): the whole chain."""
@@ -563,6 +568,9 @@ class ClassifierFreeDiffRoll(nn.Module):
         With hparams.sampling.guidance_stride = n (option "guidance_stride", 2 .. 64) only every n-th step that guides - and
         step 0 - runs both evaluations; the others run the conditional one alone and reuse the stored guidance update, y = c + d.
         Not beside x0_threshold, cfg_rescale, cfg_project, cfg_norm or cfg_momentum.
+        With hparams.sampling.exact_below = v (option "exact_below", 0 .. timesteps) under a reduced precision ('bf16x3', 'bf16',
+        'f16') the steps at diffusion step t < v run in exact fp32 and the others in that precision; v = timesteps is the
+        'f32' roll bit for bit; inert under 'f32'.  It combines with every key above.
         check=True (default): the call returns with the FINISHED, verified roll, as task/diffusion.py:528-538 does
         (synchronous; a fused-kernel time-out caused by another tenant of the device is healed by re-running the chain
         on the per-phase kernels - Engine.sample).  check=False: asynchronous; call engine.finish() before use."""

@@ -325,6 +325,20 @@ def check_guidance_stride(value, sampler: str = None, **partners) -> int:
     return int(value)
 
 
+def check_exact_below(value, timesteps: int) -> int:
+    """Option "exact_below" (include/diffroll_amd.h) as hparams.sampling.exact_below: None / 0 = off, an integer v with
+    0 <= v <= timesteps = the reverse steps at diffusion step t < v run in exact fp32 whatever precision the model selected
+    (v = timesteps: every step).  Keyed by the real step, so it means the same under `steps`; inert under precision 'f32'.
+    Returns the option's value, v or 0 for off; anything else raises ValueError."""
+    if value is None:
+        return 0
+    S = int(timesteps)
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= S:
+        raise ValueError(f"exact_below must be 0 / None (off) or an integer v with 0 <= v <= timesteps = {S} (the steps t < v run "
+                         f"in exact fp32), got {value!r}")
+    return int(value)
+
+
 def respaced_steps(timesteps: int, n: int) -> List[int]:
     """The steps a chain of n network evaluations visits, in chain order: t_i = round-half-up(i (S - 1) / (n - 1)) in
     integer arithmetic for i = n-1 .. 0 - strictly decreasing from S - 1 to 0.  n = 0 or n = S: every step."""
@@ -359,6 +373,7 @@ def sampling_options(sampling, timesteps, norm_args=(0, 1)) -> Dict[str, object]
         ("cfg_momentum", "cfg_momentum", lambda: check_cfg_momentum(get("cfg_momentum"), sampler, get("cfg_project"), get("cfg_norm"))),
         ("guidance_stride", "guidance_stride",
          lambda: check_guidance_stride(get("guidance_stride"), sampler, **{k: get(k) for k in STRIDE_PARTNERS})),
+        ("exact_below", "exact_below", lambda: check_exact_below(get("exact_below"), timesteps)),
     )
     options = {}
     for option, key, check in checks:

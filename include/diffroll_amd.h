@@ -834,6 +834,33 @@ int dr_set_precision(dr_engine* e, int mode);
  *                          a sampler that guides, w != 0 - and 0 and 1 are one value there.  0 or 1 = off: every path is
  *                          byte-identical to an engine that never set it and replays the same captured chain.  Nothing is
  *                          known about quality with real weights.
+ *   "exact_below"      [0] 0 (off), or v in 1 .. timesteps: FINISH A REDUCED-PRECISION CHAIN IN FP32.  A reverse step at
+ *                          diffusion step t < v runs in DR_PRECISION_F32 whatever dr_set_precision selected; a step with
+ *                          t >= v runs in the selected mode.  The reverse chain forgets - each update takes most of its
+ *                          weight from the current prediction - so the rounding of the high-noise steps is mostly gone a
+ *                          few steps later and only the last steps decide the roll.  RANGE: 0 <= v <= timesteps; 0 = off,
+ *                          v = timesteps = every step exact (the roll of the DR_PRECISION_F32 engine, bit for bit); any
+ *                          other value -> DR_EINVAL at the set, stating the range, and the previous value stays in force.
+ *                          KEY: the real diffusion step t, as "guidance_t_min" / "guidance_t_max" are - the option means
+ *                          the same under "sampling_steps", where v may fall between two visited steps.  The visited t
+ *                          decrease along a chain, so every exact step lies behind every reduced one.  APPLIES TO the
+ *                          reverse steps of dr_step, dr_sample and dr_sample_checked, the per-phase recompute after a
+ *                          healed time-out included.  dr_forward and dr_forward_steps are network evaluations, not chain
+ *                          steps: they are EXEMPT and keep the engine's mode.  Under DR_PRECISION_F32 the option is
+ *                          accepted and changes nothing.  WHERE IT RUNS: an exact step is planned as a step of an fp32
+ *                          chain - fused stack + tail kernel (two launches, DR_MODE_FUSED_STACK_TAIL) where that chain
+ *                          would take them; the first exact step computes its own input layer, as a chain's first step
+ *                          does, and the last reduced step primes nothing.  The selected mode's packings stay resident
+ *                          beside the fp32 ones (which always are); no state depends on the mode - the roll, the history
+ *                          of "solver_order" 2, the states of "cfg_momentum" and "guidance_stride", the work words and
+ *                          the noise are fp32 - so a dr_step sequence continues across the boundary and the option
+ *                          combines with every sampling option, windows and their blend, "draws", every precision and
+ *                          sharding; it has no refusals.  dr_launch_state reports the last step that ran.  A CAPTURED
+ *                          CHAIN bakes each step's precision into its nodes: the value is part of the captured chain's
+ *                          key (not under DR_PRECISION_F32, where no step reads it) - a chain captured under another
+ *                          value is not replayed, one captured under this value still is.  0 = off: every path is
+ *                          byte-identical to an engine that never set it and replays the same captured chain.  Nothing is
+ *                          known about quality with real weights.
  * Unknown names -> DR_ENAME. (The A/B and test knobs - "tune.*", "fused_stack_xcd", "fused_stack_warm", "stack_ticks" -
  * are set with dr_debug_set_option, diffroll_amd_debug.h.)
  */
