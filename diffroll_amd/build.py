@@ -16,7 +16,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdiffroll_amd.so")
 # one translation unit per kernel family (a kernel edit rebuilds its unit only; the units compile in parallel)
 SOURCES = ["gemm.hip", "stack.hip", "tail.hip", "update.hip", "threshold.hip", "rescale.hip", "project.hip", "momentum.hip", "stride.hip", "frontend.hip", "pack.hip", "plan.hip", "abi.hip", "debug_abi.hip", "comm.hip"]
-HEADERS = [os.path.join(CSRC, h) for h in ("kernels.h", "chain_tables.h", "device_common.h", "gemm_body.h", "persistent.h", "update_quad.h", "threshold_quad.h", "rescale_quad.h", "project_quad.h", "momentum_quad.h", "stride_quad.h", "group_sums.h", "engine_state.h", "device_buffer.h", "captured_chain.h", "fused_mode.h", "launch_plan.h", "tenants.h", "f16_round.h")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("kernels.h", "chain_tables.h", "device_common.h", "gemm_body.h", "persistent.h", "update_quad.h", "threshold_quad.h", "rescale_quad.h", "project_quad.h", "momentum_quad.h", "stride_quad.h", "group_sums.h", "engine_state.h", "device_buffer.h", "captured_chain.h", "fused_mode.h", "launch_plan.h", "tenants.h", "f16_round.h", "zero_taps.h")] + \
           [os.path.join(os.path.dirname(HERE), "include", h) for h in ("diffroll_amd.h", "diffroll_amd_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -522,6 +522,7 @@ int set_option(dr_engine* e, const char* name, int value, bool lab) {
     if (!lab) return fail(e, DR_ENAME, "unknown option '%s'", name);
     if (n == "fused_stack_xcd") { put(e, e->opt_stack_xcd, value); return DR_OK; }
     if (n == "fused_stack_warm") { put(e, e->opt_stack_warm, value); return DR_OK; }
+    if (n == "zero_taps") { put(e, e->opt_zero_taps, value != 0); return DR_OK; }
 #ifdef DR_FAULT_HOOK
     if (n == "stack_fault_test") { put(e, e->opt_stack_fault, value); return DR_OK; }
 #endif

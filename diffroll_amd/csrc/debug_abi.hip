@@ -123,6 +123,7 @@ int dr_bench_layer(dr_engine* e, int layer, int NB, int T, int t, int n_cond, vo
     }
     a.bias2 = w.conv_b_u;
     a.taps = e->K; a.dil = w.dil;
+    a.zero_taps = e->opt_zero_taps;
     (void)t;
     a.cond = e->cond ? e->cond + (size_t)layer * e->fe_B * 2 * Cp * T : e->cond_dummy;
     a.c_bs = (long)2 * Cp * T;

@@ -319,6 +319,7 @@ struct dr_engine {
     int opt_stack_xcd = 1;              // group-per-XCD block mapping (0: weight-panel-per-XCD)
     int opt_stack_fault = 0;            // test hook (option "stack_fault_test")
     int opt_stack_warm = 0;             // idle waves of the fused kernel warm the L2 for the next phase (measured: +-0)
+    int opt_zero_taps = 1;              // lab option "zero_taps": fp32 128-frame conv blocks leave out their all-padding edge taps (GemmArgs::zero_taps)
     int n_cus = 0;
     drh::StackSync sync;                // group counters, XCC tags, time-out flags, window ready words
     int opt_tail = 1;                   // fused step: layer 0's shared conv inside the stack launch + the tail kernel
@@ -369,7 +370,7 @@ struct dr_engine {
     int last_mode = 0;                  // DR_MODE_* of the most recently planned evaluation (dr_launch_state)
     // The generation of everything a captured launch sequence bakes in that is neither an argument of the call nor a
     // ChainOptions value (both are GraphKey fields of their own): the launch mode (fused.active()), opt_tail, opt_blocked,
-    // opt_stack_xcd, opt_stack_warm, opt_stack_fault, stack_dbg_on and prec; the workspace and conditioner allocations and
+    // opt_stack_xcd, opt_stack_warm, opt_zero_taps, opt_stack_fault, stack_dbg_on and prec; the workspace and conditioner allocations and
     // fe_B / fe_T; the committed weights; the respaced coefficient table.  Whatever changes one of them calls stale().
     unsigned baked = 0;
     long kfd_gpu_id = -1;               // the driver's id of this GPU in /sys/class/kfd (tenants.h); -1: unknown, no scans

@@ -8,6 +8,7 @@
 // stack_kernel for its resident tile).  Where a result goes stays with the body that computed it.
 #pragma once
 #include "device_common.h"
+#include "zero_taps.h"
 
 namespace dr {
 
@@ -592,10 +593,118 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
     };
+    // Edge taps (zero_taps.h; option "zero_taps", fp32 128-frame blocks with blocked accumulation only - ZT): where the dilation
+    // is a whole MFMA tile (d = 8 at k = 9: the outer taps sit at -+32 frames), tap 0 of the block's first tile and the last
+    // tap of its last tile read nothing but zero padding, and their 16 MFMAs each add w * (+0) to a chain that starts from +0.
+    // stepx is stepi on the tiles [LO, HI) alone - FM: the tiles whose chain starts (C = 0) in this step - with the sched
+    // groups scaled to HI - LO tiles; the prefetch of the next step's group 0 stays NW wide.  The K loop is pure MFMA issue,
+    // so the MFMAs left out are cycles left out: 2 of 36 tile-taps of a chunk.  One tap per edge (the kernel clamps edge_taps
+    // to 1): the general form - counts, loops over them - spills in the merged kernel (256 VGPRs + 92 B of scratch; this one
+    // 224 and none), and so does either form at NW = 5.  Bit-identical; resources and timing: profiles/zero_taps_ab.txt.
+    constexpr bool ZT = NI == 2 && FOLD && EPI == EPI_GATE && KS == 1 && PREC == 0;
+    auto rdx = [&](auto LO_, auto HI_, const float4* Xb, int g, BF& o) {
+#pragma unroll
+        for (int ni = decltype(LO_)::value; ni < decltype(HI_)::value; ++ni) {
+            DR_CHECK_LDS(Xb + g * 2 * FW + ni * 32, xs0, xs1, 115);
+            o.v[ni] = Xb[g * 2 * FW + ni * 32];
+        }
+    };
+    auto mma4x = [&](auto FM_, auto LO_, auto HI_, const float4 af, const BF& bf) {
+        constexpr int FM = decltype(FM_)::value, LO = decltype(LO_)::value, HI = decltype(HI_)::value;
+#pragma unroll
+        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.v[ni].x, ((FM >> ni) & 1) ? zero16 : acc[ni], 0, 0, 0);
+#pragma unroll
+        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.v[ni].y, acc[ni], 0, 0, 0);
+#pragma unroll
+        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.v[ni].z, acc[ni], 0, 0, 0);
+#pragma unroll
+        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.v[ni].w, acc[ni], 0, 0, 0);
+    };
+    auto stepx = [&](auto FM_, auto LO_, auto HI_, int slab, int chunk, int q) {
+        constexpr int NX = decltype(HI_)::value - decltype(LO_)::value;
+        using Z_ = std::integral_constant<int, 0>;
+        const float4* Xb = xaddr(chunk, q);
+        const int nx = min(slab + 1, NS - 1);
+        rdx(LO_, HI_, Xb, 1, b1);
+        mma4x(FM_, LO_, HI_, wA.v[0], b0);
+        wA.v[0] = load_ag(nx, 0);
+        rdx(LO_, HI_, Xb, 2, b0);
+        mma4x(Z_{}, LO_, HI_, wA.v[1], b1);
+        wA.v[1] = load_ag(nx, 1);
+        rdx(LO_, HI_, Xb, 3, b1);
+        mma4x(Z_{}, LO_, HI_, wA.v[2], b0);
+        wA.v[2] = load_ag(nx, 2);
+        b0 = rd(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
+        mma4x(Z_{}, LO_, HI_, wA.v[3], b1);
+        wA.v[3] = load_ag(nx, 3);
+        sgb<0x100, NX>(); sgb<0x8, 4 * NX>(); sgb<0x20, 1>();
+        sgb<0x100, NX>(); sgb<0x8, 4 * NX>(); sgb<0x20, 1>();
+        sgb<0x100, NX>(); sgb<0x8, 4 * NX>(); sgb<0x20, 1>();
+        sgb<0x100, NW>(); sgb<0x8, 4 * NX>(); sgb<0x20, 1>();
+    };
+    bool zlo = false, zhi = false;              // block-uniform: one leading / trailing tap of this block is left out
+    if constexpr (ZT) {
+        if (a.zero_taps) {
+            const EdgeTaps et = edge_taps(a.T, t0, a.dil, a.taps, NW);
+            zlo = __builtin_amdgcn_readfirstlane(et.nlo) > 0;
+            zhi = __builtin_amdgcn_readfirstlane(et.nhi) > 0;
+        }
+    }
+
+    // The edge-tap K loop (ZT only; a generic lambda: no other instantiation compiles it), one copy per combination of edges.
+    // The WHOLE loop is specialised, not a chunk or a step: where the variants of a step meet again inside the loop the
+    // compiler reconciles their register assignments with copies of the A fragments just requested - a wait for the L2 per
+    // chunk, measured at +0.6 % per chain - while separate loops meet once, behind the last chunk.
+    auto edge_loop = [&](auto ZLO_, auto ZHI_) {
+        constexpr bool ZLO = decltype(ZLO_)::value, ZHI = decltype(ZHI_)::value;
+        using I0 = std::integral_constant<int, 0>;
+        using I1 = std::integral_constant<int, 1>;
+        using IN = std::integral_constant<int, NW>;
+        using IM = std::integral_constant<int, NW - 1>;
+        using FA = std::integral_constant<int, (1 << NW) - 2>;
+        for (int chunk = c0; chunk < c1; ++chunk) {
+            auto slab_of = [&](int q) { return chunk * a.taps + q; };      // (KS == 1)
+            __syncthreads();   // as below: the hand-over, the chunk mark, group 0 of step 0, the fold, the fence
+            if (a.dbg && blockIdx.x == 0 && tid == 0 && chunk < 14) a.dbg[2 + chunk] = clock64() - tick0;
+            b0 = rd(xaddr(chunk, 0), 0);
+            fold();
+            __builtin_amdgcn_sched_barrier(0);
+            const int qe = per_chunk - (ZHI ? 1 : 0);
+            int q = 1;
+            if constexpr (ZLO) {
+                stepx(FA{}, I1{}, IN{}, slab_of(0), chunk, 0);      // tiles 1 .. NW-1 start their chains; tile 0 has nothing yet
+                __builtin_amdgcn_sched_barrier(0);
+                stepx(I1{}, I0{}, IN{}, slab_of(1), chunk, 1);      // ... and starts here
+                __builtin_amdgcn_sched_barrier(0);
+                q = 2;
+            } else {
+                stepi(T_{}, slab_of(0), chunk, 0);
+            }
+            for (; q + 2 <= qe; q += 2) {
+                stepi(F_{}, slab_of(q), chunk, q);
+                stepi(F_{}, slab_of(q + 1), chunk, q + 1);
+            }
+            if (q < qe) { stepi(F_{}, slab_of(q), chunk, q); ++q; }
+            if constexpr (ZHI) {
+                __builtin_amdgcn_sched_barrier(0);
+                stepx(I0{}, I0{}, IM{}, slab_of(q), chunk, q);      // the last tap: tiles 0 .. NW-2
+            }
+        }
+    };
+    bool edge = false;          // the edge-tap loop ran in place of the one below (ZT only: everywhere else a constant)
+    if constexpr (ZT) {
+        if (zlo || zhi) {
+            if (zlo && zhi) edge_loop(T_{}, T_{});
+            else if (zlo) edge_loop(T_{}, F_{});
+            else edge_loop(F_{}, T_{});
+            edge = true;
+        }
+    }
 
     // Steps of a chunk, q = 0 .. per_chunk-1, in memory order of the slabs ([32-channel kchunk][tap]):
     // tap-major, sub-chunk minor.  Roles alternate A,B,A,...; a chunk always starts in role A (one
     // register copy per chunk when per_chunk is odd).
+    if (!edge)
     for (int chunk = c0; chunk < c1; ++chunk) {
         auto slab_of = [&](int q) {
             const int j = q / KS, sub = q - j * KS;

@@ -120,6 +120,9 @@ struct GemmArgs {
     int wt_store;            // fused residual stack only (COH bodies): 1 = the tensors handed to other workgroups are
                              // stored write-through (sc1), 0 = plain stores (every workgroup of the group shares one
                              // XCD's L2, verified at run time)
+    int zero_taps;           // EPI_GATE on 128-frame blocks (NI = 2, fp32, blocked accumulation): 1 = a block leaves out the edge tap
+                             // whose window of its first / last 32-frame tile is all zero padding (zero_taps.h; lab option
+                             // "zero_taps", default 1; 0 = every tap of every tile, the same bits)
 };
 
 // gemm_kernel: block tile = 128 packed rows x 64*NI frames (NI in {1, 2}), 512 threads (4 consumer + 4 producer
@@ -175,6 +178,7 @@ struct StackArgs {
     int fault;                                // test hook: barriers wait for one arrival too many (exercises the spin bound)
     int fold128;                              // FL = 2: 1 = the instantiation with blocked accumulation in its conv phases
     int warm;                                 // idle waves warm the L2 with the next phase's weights / conditioner tile
+    int zero_taps;                            // conv phases: GemmArgs::zero_taps
     unsigned* xid;                            // [grid] scratch: the XCC each block runs on (rewritten by every launch)
     unsigned* bar;                            // [groups][4] {arrivals, departures, generation, -}; the first two are zero
                                               // between launches, the generation advances by one per launch

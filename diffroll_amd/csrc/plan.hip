@@ -168,6 +168,7 @@ static int launch_stack_range(const Eval& v, const NetPlan& p, int p0, int p1) {
         sa.p0 = p0; sa.p1 = p1;
         sa.xcd_n = e->opt_stack_xcd;
         sa.warm = e->opt_stack_warm;
+        sa.zero_taps = e->opt_zero_taps;
         sa.fault = e->opt_stack_fault;
         sa.fold128 = e->opt_blocked >= 2;
         sa.bar = e->sync.bar(); sa.err = e->sync.err; sa.derr = e->sync.derr(); sa.xid = e->sync.xid();
@@ -222,6 +223,7 @@ static int launch_conv(const Eval& v, const NetPlan& p, const PlanKnobs& k, int 
     }
     a.taps = e->K; a.dil = w.dil;
     a.fold128 = e->opt_blocked >= 2;
+    a.zero_taps = e->opt_zero_taps;
     a.cond = e->cond ? e->cond + (size_t)l * e->fe_B * 2 * Cp * T : e->cond_dummy;
     a.c_bs = (long)2 * Cp * T;
     a.c_n = e->fe_B;        // (option "draws": conditional row b reads clip b % fe_B)

@@ -168,6 +168,7 @@ __global__ __launch_bounds__(512) void stack_kernel(const StackArgs s_by_value) 
         if ((p & 1) == 0) {
             a.Wp = ly.conv_w; a.bias = ly.conv_b; a.bias2 = ly.conv_b2;
             a.X = s.hd; a.taps = s.taps; a.dil = ly.dil;
+            a.zero_taps = s.zero_taps;
             a.cond = ly.cond; a.cond2 = ly.cond2; a.c_bs = s.c_bs; a.c_b0 = s.c_b0; a.c_n = s.c_n; a.n_cond = s.n_cond;
             a.Y = s.g;
             if (s.dbg && p + 2 >= s.p1) a.dbg = s.dbg + 64;       // last conv phase: body tick marks of block 0

@@ -43,6 +43,10 @@ int dr_debug_kfd_root(const char* kfd_root);
  *   "fused_stack_warm" [0] idle waves of the fused stack touch the next phase's weights / conditioner tile so that
  *                          they are L2-resident when needed.  Performance only (measured: 888.6 vs 889.3 ms per
  *                          config-2 chain, i.e. nothing, and 511.6 vs 486.3 ms at config 3).
+ *   "zero_taps"        [1] fp32 dilated conv on 128-frame blocks with blocked accumulation: a block issues no MFMAs for the
+ *                          edge tap whose window of its first / last 32-frame tile is all zero padding (csrc/zero_taps.h:
+ *                          d = 8 at k = 9).  0 = every tap of every tile.  The same bits either way; for the bitwise A/B and
+ *                          for timing (profiles/zero_taps_ab.txt), not a product option.
  *   "stack_ticks"      [0] block 0 records s_memtime at every phase start (dr_stack_status).
  *   "stack_fault_test" [0] ONLY in libraries built with -DDR_FAULT_HOOK (variant "hook" of diffroll_amd/build.py; the
  *                          production library answers DR_ENAME and contains no trace of it): the persistent kernels'
