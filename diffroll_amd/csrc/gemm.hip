@@ -129,17 +129,9 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
     int xvo[NW];
 #pragma unroll
     for (int ni = 0; ni < NW; ++ni) xvo[ni] = hi * xps + min(t0 + ni * 32 + r, a.T - 1) * 16;
-    struct BF { float4 v[4][NW]; };
+    using BF = BF4<NW>;
     auto load_a = [&](int slab) { return load_a4(wr, wvo, slab, NS, 140); };
-    auto load_b = [&](int slab) -> BF {
-        BF o;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni)
-                o.v[g][ni] = buffer_load_f4(xr, xvo[ni], (slab * 8 + g * 2) * xps);
-        return o;
-    };
+    auto load_b = [&](int slab) { return load_b4(xr, xvo, xps, slab); };
     // the epilogue operands of THIS wave's quad (q = wave): requested first, their latency hides behind the K loop
     const int p0 = mt * 128 + sr * 32 + 8 * wave + 4 * hi;     // first of the lane's 4 packed rows
     const bool res_rows = p0 < a.y_rows;                       // wave-uniform (y_rows is a multiple of 64)
@@ -163,16 +155,7 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
     BF bA = load_b(s0), bB;
     auto mma = [&](const AF4& af, const BF& bf) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.v[g].x, bf.v[g][ni].x, acc[ni], 0, 0, 0);
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.v[g].y, bf.v[g][ni].y, acc[ni], 0, 0, 0);
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.v[g].z, bf.v[g][ni].z, acc[ni], 0, 0, 0);
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.v[g].w, bf.v[g][ni].w, acc[ni], 0, 0, 0);
-        }
+        for (int g = 0; g < 4; ++g) mma_f32x4<0, 0, NW>(acc, af.v[g], bf.v[g]);
     };
     int slab = 0;
     for (; slab + 2 <= NSW; slab += 2) {          // two register sets, prefetch distance one slab
@@ -204,19 +187,19 @@ __global__ __launch_bounds__(256) void pwk_kernel(const GemmArgs a) {
             for (int e = 0; e < 4; ++e) v[e] += u[e];
         }
         if (res_rows) {          // h in place, hd = h + d_{l+1}
-            float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+            float* dst = y_quad_ptr(a, b, p0, t);
             residual_quad(v, ebias, eop[ni], o);
-            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+            store_quad(dst, o);
             if (a.Y2) {          // (fp32 only: launch_pointwise_ksplit)
                 float o2[4];
                 hd_quad(o, ed2, o2);
                 float* dst2 = a.Y2 + (long)b * a.y2_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                *reinterpret_cast<float4*>(dst2) = make_float4(o2[0], o2[1], o2[2], o2[3]);
+                store_quad(dst2, o2);
             }
         } else {
-            float* dst = a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
+            float* dst = skip_quad_ptr(a, b, p0, t);
             skip_quad(v, ebias, eop[ni], a.skip_init, o);
-            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+            store_quad(dst, o);
         }
     }
 }

@@ -3,9 +3,11 @@
 // 96 / 160-frame blocks).  Included by gemm.hip (one launch per phase), stack.hip and tail.hip (persistent kernels): the
 // same device code everywhere, which is what makes the fused kernels bit-identical to the per-phase launches.
 // What the bodies have in common is written once, in front of them: the epilogue arithmetic on register quads
-// (residual_quad, skip_quad, gate_quad, hd_quad / store_y2 - pwk_kernel uses them too), the A-fragment loader (load_a4) and the
-// producer waves of the two LDS-staged bodies (producer, with dma_tile for the read-modify-write tile - also used by
-// stack_kernel for its resident tile).  Where a result goes stays with the body that computed it.
+// (residual_quad, skip_quad, gate_quad, hd_quad / store_y2 - pwk_kernel uses them too), where an output / skip quad lives and
+// its plain store (y_quad_ptr, skip_quad_ptr, store_quad), the A-fragment loader (load_a4), the fp32 MFMA group (mma_f32x4),
+// the B-fragment loader of the two direct 1x1 kernels (load_b4) and the producer waves of the two LDS-staged bodies (producer,
+// with dma_tile for the read-modify-write tile - also used by stack_kernel for its resident tile).  Where a result goes stays
+// with the body that computed it.  What was tried beyond that and changed the machine code: profiles/kstep_once_isa.txt.
 #pragma once
 #include "device_common.h"
 #include "zero_taps.h"
@@ -51,6 +53,15 @@ DR_DEVINL void gate_quad(const float (&v0)[4], const float (&v1)[4], const float
         o[e] = gatef_(v0[e] + a0, v1[e] + a1);
     }
 }
+// Where the P4 quad of rows p0 .. p0+3, frame t of sample b lives: in the output Y (p0 = the output's own row) and in the
+// skip sum (p0 = the packed row of the residual / skip GEMM, >= y_rows: its skip half) - and its plain store
+DR_DEVINL float* y_quad_ptr(const GemmArgs& a, const int b, const int p0, const int t) {
+    return a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+}
+DR_DEVINL float* skip_quad_ptr(const GemmArgs& a, const int b, const int p0, const int t) {
+    return a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
+}
+DR_DEVINL void store_quad(float* dst, const float (&o)[4]) { *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]); }
 // the second output hd = h + d: the next dilated conv's input (model/diffwave.py:139)
 DR_DEVINL void hd_quad(const float (&h)[4], const float4 d, float (&o)[4]) {
     float dd[4];
@@ -85,6 +96,37 @@ DR_DEVINL AF4 load_a4(const __amdgpu_buffer_rsrc_t wrsrc, const int wvo, const i
         DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, code, slab, NS);
         o.v[g] = buffer_load_f4(wrsrc, wvo, slab * 16384 + g * 4096);
     }
+    return o;
+}
+
+// The fp32 MFMA group: 8 channels of K (one A fragment, one B fragment per tile) for the 32-frame tiles [LO, HI) of a
+// wave's N, as 4 x v_mfma_f32_32x32x2_f32 per tile with the tile index innermost - consecutive MFMAs go to different
+// accumulators (the pinned schedules keep program order inside their small groups: a chain of dependent back-to-back
+// MFMAs costs ~8 cycles each).  FM: bit ni = tile ni starts a new chain here (C = 0 in its first MFMA).
+template <int FM, int LO, int HI, int N>
+DR_DEVINL void mma_f32x4(f32x16 (&acc)[N], const float4 af, const float4 (&bf)[N]) {
+    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf[ni].x, ((FM >> ni) & 1) ? zero16 : acc[ni], 0, 0, 0);
+#pragma unroll
+    for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf[ni].y, acc[ni], 0, 0, 0);
+#pragma unroll
+    for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf[ni].z, acc[ni], 0, 0, 0);
+#pragma unroll
+    for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf[ni].w, acc[ni], 0, 0, 0);
+}
+// The B fragments of a K step of a 1x1 GEMM that reads them straight from L2 (pw_body, pwk_kernel), [8-channel group][32-frame
+// tile]: xr = the sample's X tensor, xvo = this lane's fixed byte offsets of its frames, xps = bytes per plane.  (The two
+// resources, wvo and xvo[] stay spelled out in both: as shared helpers they change pw_kernel's or pwk_kernel's digests.)
+template <int NW> struct BF4 { float4 v[4][NW]; };
+template <int NW>
+DR_DEVINL BF4<NW> load_b4(const __amdgpu_buffer_rsrc_t xr, const int (&xvo)[NW], const int xps, const int slab) {
+    BF4<NW> o;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int ni = 0; ni < NW; ++ni)
+            o.v[g][ni] = buffer_load_f4(xr, xvo[ni], (slab * 8 + g * 2) * xps);
     return o;
 }
 
@@ -509,27 +551,23 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         const int j = q / KS, sub = q - j * KS;
         return Xs + (((chunk - c0) & 1) * XP + sub * 8 + hi) * FW + halo + (j - cen) * a.dil + r;
     };
-    auto rd = [&](const float4* Xb, int g) -> BF {
-        BF o;
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    using I0 = std::integral_constant<int, 0>;
+    using IN = std::integral_constant<int, NW>;
+    using IA = std::integral_constant<int, (1 << NW) - 1>;       // chain-start mask: every tile
+    // group g of the step at Xb, tiles [LO, HI) (I0, IN: all)   (DR_BOUNDS: one code, 106; the edge-tap steps' 115 is retired)
+    auto rdx = [&](auto LO_, auto HI_, const float4* Xb, int g, BF& o) {
 #pragma unroll
-        for (int ni = 0; ni < NW; ++ni) {
+        for (int ni = decltype(LO_)::value; ni < decltype(HI_)::value; ++ni) {
             DR_CHECK_LDS(Xb + g * 2 * FW + ni * 32, xs0, xs1, 106);
             o.v[ni] = Xb[g * 2 * FW + ni * 32];
         }
-        return o;
     };
-    // 8 channels of K for every frame tile: consecutive MFMAs go to different accumulators (the pinned schedule
-    // keeps program order inside its small groups: a chain of dependent back-to-back MFMAs costs ~8 cycles each)
+    // mma_f32x4 on every tile; FIRST = the chunk's first MFMAs, which start a new chain where the accumulation is blocked (FOLD)
     auto mma4 = [&](auto FIRST, const float4 af, const BF& bf) {
-        constexpr bool kFirst = FOLD && decltype(FIRST)::value;  // the chunk's first MFMAs: C = 0 (a new chain)
-#pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.v[ni].x, kFirst ? zero16 : acc[ni], 0, 0, 0);
-#pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.v[ni].y, acc[ni], 0, 0, 0);
-#pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.v[ni].z, acc[ni], 0, 0, 0);
-#pragma unroll
-        for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.v[ni].w, acc[ni], 0, 0, 0);
+        constexpr bool kFirst = FOLD && decltype(FIRST)::value;
+        mma_f32x4<kFirst ? (1 << NW) - 1 : 0, 0, NW>(acc, af, bf.v);
     };
 
     // One K step (32 channels x 1 tap): 16*NW MFMAs per wave in 4 groups of 8 channels.  Software pipeline,
@@ -546,13 +584,13 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         const float4* Xb = xaddr(chunk, q);
         if constexpr (kB) wA = load_a(min(slab + 1, NS - 1));
         else wB = load_a(min(slab + 1, NS - 1));
-        b1 = rd(Xb, 1);
+        rdx(I0{}, IN{}, Xb, 1, b1);
         mma4(FIRST, kB ? wB.v[0] : wA.v[0], b0);
-        b0 = rd(Xb, 2);
+        rdx(I0{}, IN{}, Xb, 2, b0);
         mma4(std::false_type{}, kB ? wB.v[1] : wA.v[1], b1);
-        b1 = rd(Xb, 3);
+        rdx(I0{}, IN{}, Xb, 3, b1);
         mma4(std::false_type{}, kB ? wB.v[2] : wA.v[2], b0);
-        b0 = rd(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
+        rdx(I0{}, IN{}, xaddr(chunk, min(q + 1, per_chunk - 1)), 0, b0);
         mma4(std::false_type{}, kB ? wB.v[3] : wA.v[3], b1);
         // pinned schedule: the 4 A-fragment loads ride inside group 0's MFMAs (one per NW MFMAs: issued in the
         // shadow of a running MFMA instead of as a burst with the matrix pipe idle; hipcc on its own sinks them
@@ -562,80 +600,40 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>();
         sgb<0x100, NW>(); sgb<0x8, 4 * NW>();
     };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
     // 128-frame blocks (NI = 2) refresh the A fragments IN PLACE instead: group g's fragment register quad receives the
     // next step's group g right behind the group's last MFMA (one buffer load per group: prefetch distance three
     // groups = 48 MFMAs) - ONE fragment set instead of two, which is what lets the second accumulator set of the
     // blocked accumulation (64 registers at NW = 4) live in the K loop without spilling; no roles, no per-chunk copy.
+    // That step is stepx below on every tile: stepx(IA, I0, IN) starts the chunk's chains (C = 0), stepx(I0, I0, IN) goes on.
     constexpr bool AINP = (NI == 2 || NI == 5) && FOLD;
     auto load_ag = [&](int slab, int g) -> float4 {
         DR_CHECK(slab >= 0 && wvo + slab * 16384 + g * 4096 + 16 <= NS * 16384, 112, slab, NS);
         return buffer_load_f4(wrsrc, wvo, slab * 16384 + g * 4096);
     };
-    auto stepi = [&](auto FIRST, int slab, int chunk, int q) {
-        const float4* Xb = xaddr(chunk, q);
-        const int nx = min(slab + 1, NS - 1);
-        b1 = rd(Xb, 1);
-        mma4(FIRST, wA.v[0], b0);
-        wA.v[0] = load_ag(nx, 0);
-        b0 = rd(Xb, 2);
-        mma4(F_{}, wA.v[1], b1);
-        wA.v[1] = load_ag(nx, 1);
-        b1 = rd(Xb, 3);
-        mma4(F_{}, wA.v[2], b0);
-        wA.v[2] = load_ag(nx, 2);
-        b0 = rd(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
-        mma4(F_{}, wA.v[3], b1);
-        wA.v[3] = load_ag(nx, 3);
-        sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
-        sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
-        sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
-        sgb<0x100, NW>(); sgb<0x8, 4 * NW>(); sgb<0x20, 1>();
-    };
     // Edge taps (zero_taps.h; option "zero_taps", fp32 128-frame blocks with blocked accumulation only - ZT): where the dilation
     // is a whole MFMA tile (d = 8 at k = 9: the outer taps sit at -+32 frames), tap 0 of the block's first tile and the last
     // tap of its last tile read nothing but zero padding, and their 16 MFMAs each add w * (+0) to a chain that starts from +0.
-    // stepx is stepi on the tiles [LO, HI) alone - FM: the tiles whose chain starts (C = 0) in this step - with the sched
-    // groups scaled to HI - LO tiles; the prefetch of the next step's group 0 stays NW wide.  The K loop is pure MFMA issue,
+    // stepx is the in-place step on the tiles [LO, HI) alone - FM: the tiles whose chain starts (C = 0) in this step - with the
+    // sched groups scaled to HI - LO tiles; the prefetch of the next step's group 0 stays NW wide.  The K loop is pure MFMA issue,
     // so the MFMAs left out are cycles left out: 2 of 36 tile-taps of a chunk.  One tap per edge (the kernel clamps edge_taps
     // to 1): the general form - counts, loops over them - spills in the merged kernel (256 VGPRs + 92 B of scratch; this one
     // 224 and none), and so does either form at NW = 5.  Bit-identical; resources and timing: profiles/zero_taps_ab.txt.
     constexpr bool ZT = NI == 2 && FOLD && EPI == EPI_GATE && KS == 1 && PREC == 0;
-    auto rdx = [&](auto LO_, auto HI_, const float4* Xb, int g, BF& o) {
-#pragma unroll
-        for (int ni = decltype(LO_)::value; ni < decltype(HI_)::value; ++ni) {
-            DR_CHECK_LDS(Xb + g * 2 * FW + ni * 32, xs0, xs1, 115);
-            o.v[ni] = Xb[g * 2 * FW + ni * 32];
-        }
-    };
-    auto mma4x = [&](auto FM_, auto LO_, auto HI_, const float4 af, const BF& bf) {
-        constexpr int FM = decltype(FM_)::value, LO = decltype(LO_)::value, HI = decltype(HI_)::value;
-#pragma unroll
-        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.v[ni].x, ((FM >> ni) & 1) ? zero16 : acc[ni], 0, 0, 0);
-#pragma unroll
-        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.v[ni].y, acc[ni], 0, 0, 0);
-#pragma unroll
-        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.v[ni].z, acc[ni], 0, 0, 0);
-#pragma unroll
-        for (int ni = LO; ni < HI; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.v[ni].w, acc[ni], 0, 0, 0);
-    };
     auto stepx = [&](auto FM_, auto LO_, auto HI_, int slab, int chunk, int q) {
-        constexpr int NX = decltype(HI_)::value - decltype(LO_)::value;
-        using Z_ = std::integral_constant<int, 0>;
+        constexpr int FM = decltype(FM_)::value, LO = decltype(LO_)::value, HI = decltype(HI_)::value, NX = HI - LO;
         const float4* Xb = xaddr(chunk, q);
         const int nx = min(slab + 1, NS - 1);
         rdx(LO_, HI_, Xb, 1, b1);
-        mma4x(FM_, LO_, HI_, wA.v[0], b0);
+        mma_f32x4<FM, LO, HI>(acc, wA.v[0], b0.v);
         wA.v[0] = load_ag(nx, 0);
         rdx(LO_, HI_, Xb, 2, b0);
-        mma4x(Z_{}, LO_, HI_, wA.v[1], b1);
+        mma_f32x4<0, LO, HI>(acc, wA.v[1], b1.v);
         wA.v[1] = load_ag(nx, 1);
         rdx(LO_, HI_, Xb, 3, b1);
-        mma4x(Z_{}, LO_, HI_, wA.v[2], b0);
+        mma_f32x4<0, LO, HI>(acc, wA.v[2], b0.v);
         wA.v[2] = load_ag(nx, 2);
-        b0 = rd(xaddr(chunk, min(q + 1, per_chunk - 1)), 0);
-        mma4x(Z_{}, LO_, HI_, wA.v[3], b1);
+        rdx(I0{}, IN{}, xaddr(chunk, min(q + 1, per_chunk - 1)), 0, b0);
+        mma_f32x4<0, LO, HI>(acc, wA.v[3], b1.v);
         wA.v[3] = load_ag(nx, 3);
         sgb<0x100, NX>(); sgb<0x8, 4 * NX>(); sgb<0x20, 1>();
         sgb<0x100, NX>(); sgb<0x8, 4 * NX>(); sgb<0x20, 1>();
@@ -657,16 +655,14 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
     // chunk, measured at +0.6 % per chain - while separate loops meet once, behind the last chunk.
     auto edge_loop = [&](auto ZLO_, auto ZHI_) {
         constexpr bool ZLO = decltype(ZLO_)::value, ZHI = decltype(ZHI_)::value;
-        using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
-        using IN = std::integral_constant<int, NW>;
         using IM = std::integral_constant<int, NW - 1>;
         using FA = std::integral_constant<int, (1 << NW) - 2>;
         for (int chunk = c0; chunk < c1; ++chunk) {
             auto slab_of = [&](int q) { return chunk * a.taps + q; };      // (KS == 1)
             __syncthreads();   // as below: the hand-over, the chunk mark, group 0 of step 0, the fold, the fence
             if (a.dbg && blockIdx.x == 0 && tid == 0 && chunk < 14) a.dbg[2 + chunk] = clock64() - tick0;
-            b0 = rd(xaddr(chunk, 0), 0);
+            rdx(I0{}, IN{}, xaddr(chunk, 0), 0, b0);
             fold();
             __builtin_amdgcn_sched_barrier(0);
             const int qe = per_chunk - (ZHI ? 1 : 0);
@@ -678,13 +674,13 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                 __builtin_amdgcn_sched_barrier(0);
                 q = 2;
             } else {
-                stepi(T_{}, slab_of(0), chunk, 0);
+                stepx(IA{}, I0{}, IN{}, slab_of(0), chunk, 0);
             }
             for (; q + 2 <= qe; q += 2) {
-                stepi(F_{}, slab_of(q), chunk, q);
-                stepi(F_{}, slab_of(q + 1), chunk, q + 1);
+                stepx(I0{}, I0{}, IN{}, slab_of(q), chunk, q);
+                stepx(I0{}, I0{}, IN{}, slab_of(q + 1), chunk, q + 1);
             }
-            if (q < qe) { stepi(F_{}, slab_of(q), chunk, q); ++q; }
+            if (q < qe) { stepx(I0{}, I0{}, IN{}, slab_of(q), chunk, q); ++q; }
             if constexpr (ZHI) {
                 __builtin_amdgcn_sched_barrier(0);
                 stepx(I0{}, I0{}, IM{}, slab_of(q), chunk, q);      // the last tap: tiles 0 .. NW-2
@@ -713,19 +709,19 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
         auto at = [&](auto R, auto FIRST, int q) { step(R, FIRST, slab_of(q), chunk, q); };
         __syncthreads();   // X tile #chunk staged by the producers (matches their hand-over barrier)
         if (a.dbg && blockIdx.x == 0 && tid == 0 && chunk < 14) a.dbg[2 + chunk] = clock64() - tick0;
-        b0 = rd(xaddr(chunk, 0), 0);
+        rdx(I0{}, IN{}, xaddr(chunk, 0), 0, b0);
         fold();                           // the previous chunk's chain joins the outer sum (zeros the first time)
         // (the first step's pinned schedule starts HERE: without the fence its first sched group adopts the reads of b0
         // above, and every fragment read of the step is issued one group late - right in front of the MFMAs that wait for it)
         if constexpr (FOLD) __builtin_amdgcn_sched_barrier(0);
         if constexpr (AINP) {
-            stepi(T_{}, slab_of(0), chunk, 0);      // C = 0: a new chain
+            stepx(IA{}, I0{}, IN{}, slab_of(0), chunk, 0);      // C = 0: a new chain
             int q = 1;
             for (; q + 2 <= per_chunk; q += 2) {
-                stepi(F_{}, slab_of(q), chunk, q);
-                stepi(F_{}, slab_of(q + 1), chunk, q + 1);
+                stepx(I0{}, I0{}, IN{}, slab_of(q), chunk, q);
+                stepx(I0{}, I0{}, IN{}, slab_of(q + 1), chunk, q + 1);
             }
-            if (q < per_chunk) stepi(F_{}, slab_of(q), chunk, q);
+            if (q < per_chunk) stepx(I0{}, I0{}, IN{}, slab_of(q), chunk, q);
         } else {
             at(F_{}, T_{}, 0);                // C = 0: a new chain
             int q = 1;
@@ -893,7 +889,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                     } else if (a.out_s3 & 1) {   // g for the split-bf16 1x1 kernel
                         store_s3_quad<COH>(a.Y + (long)be * a.y_bs, o, c0, t, a.T, a.y_rows >> 3, a.wt_store);
                     } else {
-                        float* dst = a.Y + (long)be * a.y_bs + (long)(c0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                        float* dst = y_quad_ptr(a, be, c0, t);
                         store_f4<COH>(dst, make_float4(o[0], o[1], o[2], o[3]), a.wt_store);
                     }
                 } else {
@@ -905,14 +901,14 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                         // packed rows [0, y_rows) are the residual half, [y_rows, 2*y_rows) the skip half
                         // (y_rows is a multiple of 64, so the branch is wave-uniform)
                         if (p0 < a.y_rows) {   // h, in place
-                            float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                            float* dst = y_quad_ptr(a, be, p0, t);
                             residual_quad(v, ebias[q], eop[ni][q], o);
-                            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                            store_quad(dst, o);
                             if (a.Y2) store_y2<COH, 0, one_plane16(PREC) ? PREC : 0>(a, be, o, ed2[q], p0, t);
                         } else {
-                            float* dst = a.skip + (long)be * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
+                            float* dst = skip_quad_ptr(a, be, p0, t);
                             skip_quad(v, ebias[q], eop[ni][q], a.skip_init, o);
-                            *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                            store_quad(dst, o);
                         }
                     } else {
                         if (p0 >= a.y_rows) continue;
@@ -925,8 +921,7 @@ DR_DEVINL void gemm_body(const GemmArgs& a, char* smem, const int mt, const int 
                             else if constexpr (EPI == EPI_SILU) { const float z = v[e] + bb[e]; o[e] = z * sigmoidf_(z); }
                             else o[e] = logf(v[e] + 1e-6f);
                         }
-                        float* dst = a.Y + (long)be * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                        *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                        store_quad(y_quad_ptr(a, be, p0, t), o);
                         if constexpr (EPI == EPI_RELU) {
                             if (a.Y2) store_y2<COH, 0>(a, be, o, ed2[q], p0, t);    // hd = h + d_0 for the first dilated conv
                         }
@@ -999,18 +994,9 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
     int xvo[NW];
 #pragma unroll
     for (int ni = 0; ni < NW; ++ni) xvo[ni] = hi * xps + min(t0 + ni * 32 + r, a.T - 1) * 16;
-
-    struct BF { float4 v[4][NW]; };
+    using BF = BF4<NW>;
     auto load_a = [&](int slab) { return load_a4(wr, wvo, slab, NS, 120); };
-    auto load_b = [&](int slab) -> BF {
-        BF o;
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni)
-                o.v[g][ni] = buffer_load_f4(xr, xvo[ni], (slab * 8 + g * 2) * xps);
-        return o;
-    };
+    auto load_b = [&](int slab) { return load_b4(xr, xvo, xps, slab); };
 
     f32x16 acc[NW];
 #pragma unroll
@@ -1025,19 +1011,8 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
         const int nxt = min(slab + 1, NS - 1);
         if constexpr (kB) { aA = load_a(nxt); bA = load_b(nxt); }
         else { aB = load_a(nxt); bB = load_b(nxt); }
-        // consecutive MFMAs go to different accumulators (the pinned schedule keeps program order)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float4 af = kB ? aB.v[g] : aA.v[g];
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, (kB ? bB.v[g][ni] : bA.v[g][ni]).x, acc[ni], 0, 0, 0);
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, (kB ? bB.v[g][ni] : bA.v[g][ni]).y, acc[ni], 0, 0, 0);
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, (kB ? bB.v[g][ni] : bA.v[g][ni]).z, acc[ni], 0, 0, 0);
-#pragma unroll
-            for (int ni = 0; ni < NW; ++ni) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, (kB ? bB.v[g][ni] : bA.v[g][ni]).w, acc[ni], 0, 0, 0);
-        }
+        for (int g = 0; g < 4; ++g) mma_f32x4<0, 0, NW>(acc, kB ? aB.v[g] : aA.v[g], (kB ? bB : bA).v[g]);
         // pinned schedule: the 4 + 4*NW prefetch loads are spread through the MFMA stream (one per PER MFMAs),
         // so each is issued in the shadow of a running MFMA; issued as one burst at the top of the step they
         // cost 16 TA cycles each with the matrix pipe idle (71.8 vs 67.6 ticks per MFMA)
@@ -1109,7 +1084,7 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
                     o[e] = a.alpha * v[e] + bb[e];
                     if constexpr (EPI == EPI_RELU) o[e] = fmaxf(o[e], 0.f);
                 }
-                float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                float* dst = y_quad_ptr(a, b, p0, t);
                 store_f4<COH>(dst, make_float4(o[0], o[1], o[2], o[3]), a.wt_store);
                 continue;
             }
@@ -1122,16 +1097,16 @@ DR_DEVINL void pw_body(const GemmArgs& a, const int mt, const int nt, const int 
             if constexpr (RLDS) pv = *rs;
             else pv = eop[ni][q];
             if (res_rows) {
-                float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;       // (= y_quad_ptr; spelled out: profiles/kstep_once_isa.txt)
                 residual_quad(v, ebias[q], pv, o);
                 if constexpr (RLDS) *rs = make_float4(o[0], o[1], o[2], o[3]);
-                else *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                else store_quad(dst, o);
                 if (a.Y2) store_y2<0, COH>(a, b, o, ed2[q], p0, t);
             } else {
-                float* dst = a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
+                float* dst = skip_quad_ptr(a, b, p0, t);
                 skip_quad(v, ebias[q], pv, a.skip_init, o);
                 if constexpr (RLDS) *rs = make_float4(o[0], o[1], o[2], o[3]);
-                else *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                else store_quad(dst, o);
             }
         }
     }
@@ -1312,8 +1287,7 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
                 if (a.out_s3 & 1) {
                     store_s3_quad(a.Y + (long)b * a.y_bs, o, c0, t, a.T, a.y_rows >> 3);
                 } else {
-                    float* dst = a.Y + (long)b * a.y_bs + (long)(c0 >> 2) * a.y_ps + (long)t * a.y_fs;
-                    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                    store_quad(y_quad_ptr(a, b, c0, t), o);
                 }
             }
         } else {
@@ -1330,14 +1304,14 @@ DR_DEVINL void gemm16_body(const GemmArgs& a, char* smem, const int mt, const in
                 float v[4], o[4];
                 f4arr(acc[rt][ct], v);
                 if (p0 < a.y_rows) {
-                    float* dst = a.Y + (long)b * a.y_bs + (long)(p0 >> 2) * a.y_ps + (long)t * a.y_fs;
+                    float* dst = y_quad_ptr(a, b, p0, t);
                     residual_quad(v, ebias[rt], pv4[rt], o);
-                    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                    store_quad(dst, o);
                     if (a.Y2) store_y2<0, 0>(a, b, o, ed2[rt], p0, t);
                 } else {
-                    float* dst = a.skip + (long)b * a.s_bs + ((long)((p0 - a.y_rows) >> 2) * a.T + t) * 4;
+                    float* dst = skip_quad_ptr(a, b, p0, t);
                     skip_quad(v, ebias[rt], pv4[rt], a.skip_init, o);
-                    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+                    store_quad(dst, o);
                 }
             }
         }
